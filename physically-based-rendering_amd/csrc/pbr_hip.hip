@@ -20,6 +20,7 @@
 // are no longer part of this source; their kernels are kept for the record under lab/src/.
 #include "bvh_build.hpp"
 #include "pt_denoise.hpp"
+#include "pt_tuner.hpp"
 
 using ptk::DevParams;
 
@@ -30,7 +31,7 @@ typedef void ( *KernelFn )( const ptk::DevParams );
 // on every frame.
 struct Plan {
 	KernelFn kernel = nullptr;
-	int blocks = 0, blockThreads = 0, numHot = 0, park = 0, shade = 0, parkEighths = 4;
+	int blocks = 0, blockThreads = 0, numHot = 0, park = 0, shade = 0, parkEighths = 4, refillBatch = 0, drainMode = 1;
 	size_t ldsBytes = 0;
 	const char* name = "";
 	char kernelName[96] = "";   // the kernel's symbol as a profiler prints it (without "void " and the argument list)
@@ -119,28 +120,17 @@ struct pbr_ctx {
 	float focusDepth = 0.0f;
 	float4* dFrameBuf = nullptr;   // frame-parallel launches: {finalColor, focus} per frame and local pixel slot
 	size_t frameBufFrames = 0;
-	// schedule auto-tuning (launch()): per scene + configuration, the candidates are timed on the first
+	// schedule auto-tuning (launch(), pt_tuner.hpp): per scene + configuration, the candidates are timed on the first
 	// frames that are rendered anyway, then the fastest one is kept
-	int tunedPlan = -1;
-	Plan plans[7];                                  // the tuner's candidates; valid while plansBuilt (reset by pbr_upload_scene / pbr_configure / pbr_diag_set_knob)
-	Plan phongPlan;                                 // the Phong-tessellation build of the refill kernel (takes the place of plans[1])
+	ScheduleTuner tuner;
+	Plan plans[ScheduleTuner::kPlans];              // the tuner's candidates; valid while plansBuilt (reset by pbr_upload_scene / pbr_configure / pbr_diag_set_knob)
+	Plan phongPlan;                                 // the Phong-tessellation build of the refill kernel (renders every chunk with Phong tessellation)
 
 	bool plansBuilt = false, phongPlanBuilt = false;
-	int drainMode = 1;                              // pathTracingPhased, see launch()
 	bool workClean = false;                         // the queue heads are zero (foldFrames leaves them so)
 	float* hSeeds = nullptr;                        // pinned staging for the seeds of a launch
 	size_t hSeedCapacity = 0;
 	int pinnedPlan = -1;                            // pbr_diag_pin_plan: >= 0 renders with this plan, no tuning (ranks of a multi-GPU run: all the same)
-	uint32_t tuneRenderFrames = 0;                  // the longest render (frames per call) this context has been asked for
-	uint32_t tunedAtFrames = 0;                     // the render length tunedPlan was chosen for
-	double tuneMs[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };      // screening: kTuneFrames frames per plan
-	uint32_t tuneFrames[7] = { 0, 0, 0, 0, 0, 0, 0 };
-	uint32_t tuneLaunches[7] = { 0, 0, 0, 0, 0, 0, 0 };
-	int refineCount = 0;                            // refinement: the plans within 10 % of the fastest (at least two) again, on longer chunks
-	int refinePlan[7] = { -1, -1, -1, -1, -1, -1, -1 };
-	uint32_t refineChunks = 0;                      // chunks rendered so far in the refinement
-	uint32_t refineRounds = 1;                      // 1; 2 once a close call (best two within 5 %) has been given a second palindrome
-	double refineFit[7][5] = {};                    // per finalist, over its refinement launches: sums of 1, n, n^2, ms, n * ms (n = frames of the launch)
 	char lastPlan[48] = "";        // name of the plan that rendered the largest chunk of the last render
 	char lastKernel[96] = "";      // ... and its kernel
 	double lastTraceMs = 0.0;      // of the last render: time inside the path-tracing launches only ...
@@ -176,6 +166,15 @@ int fail( pbr_ctx* ctx, int code, const char* fmt, ... ) {
 		} \
 	} while( 0 )
 
+// a step of this library that failed has set the context's error: pass its code on
+#define PBR_TRY( call ) \
+	do { \
+		const int status__ = ( call ); \
+		if( status__ != PBR_OK ) { \
+			return status__; \
+		} \
+	} while( 0 )
+
 void freeScene( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dNodes );
 	(void) hipFree( ctx->dNodesWalk );
@@ -192,17 +191,12 @@ void freeScene( pbr_ctx* ctx ) {
 	ctx->hasScene = false;
 }
 
-// The schedule tuner starts over (a new scene, a new configuration, a changed knob).
-void resetTuning( pbr_ctx* ctx ) {
-	ctx->tunedPlan = -1;
-	ctx->tuneRenderFrames = ctx->tunedAtFrames = 0;
-	std::memset( ctx->tuneMs, 0, sizeof( ctx->tuneMs ) );
-	std::memset( ctx->tuneFrames, 0, sizeof( ctx->tuneFrames ) );
-	std::memset( ctx->tuneLaunches, 0, sizeof( ctx->tuneLaunches ) );
-	ctx->refineCount = 0;
-	ctx->refineChunks = 0;
-	ctx->refineRounds = 1;
-	std::memset( ctx->refineFit, 0, sizeof( ctx->refineFit ) );
+// Plans carry the scene's, the configuration's and the knobs' values: they are rebuilt on the next render, and the schedule
+// tuner starts over (a new scene, a new configuration, a changed knob).
+void replan( pbr_ctx* ctx ) {
+	ctx->plansBuilt = false;
+	ctx->phongPlanBuilt = false;
+	ctx->tuner.reset( ScheduleTuner::scaleOf( (size_t) ctx->numLocalTiles * 64 ) );
 }
 
 void freeImages( pbr_ctx* ctx ) {
@@ -326,7 +320,22 @@ void invariantDivisor( unsigned d, unsigned out[2] ) {
 	out[1] = ( l < 1u ? l : 1u ) | ( ( l > 0u ? l - 1u : 0u ) << 8 );
 }
 
-// The schedule tuner's chunk lengths are in 1080p-frame equivalents (launch()): how many of this context's frames make one.
+// The ray-ordered walk's streams of a layout (buildWalkStreams, below) to the device: 32 bytes of header, which the eight
+// first references are copied into, then the records; hotAvail: the ranked records at their head, in 32-byte slots.
+int uploadWalkStreams( pbr_ctx* ctx, std::vector<float4>* storage, uint32_t hotAvail, uint32_t layout ) {
+	std::memcpy( storage->data(), ctx->walkFirst, sizeof( ctx->walkFirst ) );
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	(void) hipFree( ctx->dNodesWalk );
+	ctx->dNodesWalk = nullptr;
+	ctx->walkBuilt = 0;
+	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( float4 ) * storage->size() ) );
+	HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, storage->data(), sizeof( float4 ) * storage->size(), hipMemcpyHostToDevice ) );
+	ctx->walkHotAvail = hotAvail;
+	ctx->walkBytes = sizeof( float4 ) * storage->size();
+	ctx->walkBuilt = layout;
+	return PBR_OK;
+}
+
 // ---- the ray-ordered walk's node streams (pbr_config.traversal, include/pbr_hip.h) --------------------------------
 // Not a reference structure: the reference walks its flat tree in one fixed order (a hit continues at index + 1,
 // pt_bvh.cl:102,112; the child with the bigger surface area sits there, accelstructures/BVH.cpp:335-343).  The records of
@@ -539,17 +548,7 @@ int buildWalkStreams( pbr_ctx* ctx, uint32_t layout ) {
 			ctx->walkFirst[k] = refOf( onHit[(size_t) k * N] );
 		}
 
-		std::memcpy( storage.data(), ctx->walkFirst, sizeof( ctx->walkFirst ) );
-		HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-		(void) hipFree( ctx->dNodesWalk );
-		ctx->dNodesWalk = nullptr;
-		ctx->walkBuilt = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( float4 ) * storage.size() ) );
-		HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, storage.data(), sizeof( float4 ) * storage.size(), hipMemcpyHostToDevice ) );
-		ctx->walkHotAvail = hot * 2u;      // in 32-byte slots, the unit of a plan's LDS share
-		ctx->walkBytes = sizeof( float4 ) * storage.size();
-		ctx->walkBuilt = layout;
-		return PBR_OK;
+		return uploadWalkStreams( ctx, &storage, hot * 2u, layout );      // 32-byte slots are the unit of a plan's LDS share
 	}
 
 	// records: the ranked nodes interleaved, then every order's remaining nodes along its own depth-first sequence
@@ -617,18 +616,7 @@ int buildWalkStreams( pbr_ctx* ctx, uint32_t layout ) {
 		ctx->walkFirst[k] = ctx->walkFirst[0];
 	}
 
-	std::memcpy( storage.data(), ctx->walkFirst, sizeof( ctx->walkFirst ) );
-
-	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	(void) hipFree( ctx->dNodesWalk );
-	ctx->dNodesWalk = nullptr;
-	ctx->walkBuilt = 0;
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( float4 ) * storage.size() ) );
-	HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, storage.data(), sizeof( float4 ) * storage.size(), hipMemcpyHostToDevice ) );
-	ctx->walkHotAvail = hotPerOrder * (uint32_t) K;
-	ctx->walkBytes = sizeof( float4 ) * storage.size();
-	ctx->walkBuilt = layout;
-	return PBR_OK;
+	return uploadWalkStreams( ctx, &storage, hotPerOrder * (uint32_t) K, layout );
 }
 
 // The node stream, its ranked prefix and the first record(s) for the configured traversal.
@@ -644,11 +632,7 @@ int applyWalk( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail ) {
 	}
 
 	if( ctx->walkBuilt != scheme ) {
-		const int built = buildWalkStreams( ctx, scheme );
-
-		if( built != PBR_OK ) {
-			return built;
-		}
+		PBR_TRY( buildWalkStreams( ctx, scheme ) );
 	}
 
 	P->nodes = ctx->dNodesWalk + 2;   // behind the 32-byte header ...
@@ -887,10 +871,315 @@ int learnTileCosts( pbr_ctx* ctx, const pbr_camera* cam, float pxDim ) {
 	return PBR_OK;
 }
 
-uint32_t tuneScaleOf( size_t localPixels ) {
-	const size_t reference = (size_t) 1920 * 1080;
-	const size_t scale = ( reference + localPixels / 2 ) / std::max<size_t>( localPixels, 1 );
-	return (uint32_t) std::min<size_t>( std::max<size_t>( scale, 1 ), 64 );
+// The scene for the path-tracing, diagnostic and denoise kernels, walked in the configured order (pbr_config.traversal);
+// hotAvail: the ranked prefix of that stream.  Returns PBR_OK, or why the configured walk's streams could not be built (the
+// caller fails with it — no silent walk in another order).
+int sceneParams( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail = nullptr ) {
+	std::memset( P, 0, sizeof( *P ) );
+	uint32_t hot = 0;
+	const int walk = applyWalk( ctx, P, &hot );
+
+	if( hotAvail != nullptr ) {
+		*hotAvail = hot;
+	}
+
+	P->parkEighths = 4;
+	P->tris = ctx->dTris;
+	P->faceN = ctx->dFaceN;
+	P->mats = ctx->dMats;
+	P->lights = ctx->dLights;
+	P->guard = ctx->dGuard;
+	P->numNodes = (int) ctx->numNodes;
+	P->numLights = (int) ctx->numLights;
+	return walk;
+}
+
+// The camera of a w x h image: its vectors, and the launch-invariant sub-expressions of initRay (pt_kernel.hpp) in the same
+// IEEE single operations as the kernel would do (this file is built with -ffp-contract=off like the kernels).
+void setCamera( DevParams* P, const pbr_camera* cam, int w, int h, float pxDim ) {
+	const float* src[4] = { &cam->eye.x, &cam->w.x, &cam->u.x, &cam->v.x };
+	float* dst[4] = { P->eye, P->cw, P->cu, P->cv };
+
+	for( int i = 0; i < 4; i++ ) {
+		for( int k = 0; k < 3; k++ ) {
+			dst[i][k] = src[i][k];
+		}
+	}
+
+	for( int k = 0; k < 3; k++ ) {
+		const float cuW = P->cu[k] * (float) w;
+		P->camA[k] = P->cu[k] - cuW;
+		P->cvH[k] = P->cv[k] * (float) h;
+	}
+
+	P->halfPx = pxDim * 0.5f;
+	P->pxDim = pxDim;
+	P->width = w;
+	P->height = h;
+}
+
+// A plan's recipe: kernel group, name, the state machine's thresholds, block size, and the per-lane path state that two
+// paths per lane keep in LDS behind the staged prefix.
+struct PlanSpec {
+	int group;
+	const char* name;
+	int park, shade;
+	int blockThreads = PBR_BLOCK;
+	size_t pathSlotBytes = 0;
+};
+
+// A plan = kernel + persistent grid + LDS split.  Grid: as many blocks as stay resident, never more
+// than there is work for.  LDS: each block stages a prefix of the node stream; the CU's 160 KB are
+// split between the blocks the register budget admits.  The experiment knobs (PBR_BLOCKS_PER_CU, PBR_LDS_SLOTS,
+// PBR_PH_PARK, PBR_PH_SHADE, PBR_PARK_EIGHTHS, PBR_DRAIN_MODE, PBR_REFILL_BATCH) are read when the plans are built — once per
+// scene + configuration — not per launch.
+int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan ) {
+	const Knobs& knobs = ctx->knobs;
+	const int flavour = flavourOf( ctx->cfg );
+	const bool lights = ( ctx->numLights > 0 );
+	const bool shadow = ( ctx->cfg.shadow_rays == 1 ) && lights;
+	const KernelFn kernel = pickKernel( flavour, spec.group, ctx->cfg.brdf, shadow, lights );
+
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "plan %s: this library was built without that kernel (flavour %d)", spec.name, flavour );
+	}
+
+	int blocksPerCU = 0;
+	HIP_TRY( ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor( &blocksPerCU, (const void*) kernel, spec.blockThreads, 0 ) );
+	blocksPerCU = ( blocksPerCU < 1 ) ? 1 : blocksPerCU;
+
+	if( knobs.blocksPerCU >= 1 && knobs.blocksPerCU < blocksPerCU ) {
+		blocksPerCU = knobs.blocksPerCU;
+	}
+
+	// a block's share of the CU's 160 KB, for the staged tree top
+	const size_t ldsPerCU = 160 * 1024;
+	const size_t share = ldsPerCU / (size_t) blocksPerCU - 256;
+	const size_t slotBytes = spec.pathSlotBytes;     // two paths per lane: 2 slots x 4 planes x 16 B of path state per lane behind the staged prefix
+
+	// (a toolchain that fitted such a kernel into fewer registers would report two blocks per CU, whose share
+	// is smaller than the path slots — the subtraction below is unsigned)
+	if( share < slotBytes + 32 ) {
+		return fail( ctx, PBR_ESTATE, "plan %s: %zu B of per-lane path state do not fit a block's %zu B share of LDS at %d blocks per CU", spec.name, slotBytes, share, blocksPerCU );
+	}
+
+	size_t slots = ( share - slotBytes ) / 32;
+	slots = std::min<size_t>( slots, hotAvail );
+
+	if( knobs.ldsSlots >= 0 ) {
+		slots = std::min<size_t>( slots, (size_t) knobs.ldsSlots );
+	}
+	if( flavour & 4 ) {
+		slots &= ~(size_t) 1;      // compact records are two slots each: a staged prefix ends on a record
+	}
+
+	// the limit is a property of the kernel function, shared by every context of the process: always the block's whole
+	// share, so that a context with a small scene never lowers it under another context's cached plan
+	HIP_TRY( ctx, hipFuncSetAttribute( (const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) share ) );
+
+	plan->kernel = kernel;
+	plan->blockThreads = spec.blockThreads;
+	plan->blocks = ctx->numCUs * blocksPerCU;   // all that are resident at once; runPlan() launches fewer when there is less work
+	plan->numHot = (int) slots;
+	plan->ldsBytes = slots * 32 + slotBytes;
+	plan->park = spec.park;
+	plan->shade = spec.shade;
+	plan->parkEighths = ( ctx->numNodes >= kWideMinNodes ) ? 4 : 6;   // see traverse(), pt_kernel.hpp
+	plan->refillBatch = ( knobs.refillBatch >= 1 ) ? std::min( 64, knobs.refillBatch ) : ( ( ctx->numNodes >= kWideMinNodes ) ? kRefillBatchLarge : kRefillBatchSmall );
+	// pathTracingPhased once lanes are DONE, 1: measured (single-frame 1080p launches): park share scaled, shade threshold as is:
+	// Dragon-class 2.99 -> 2.47 ms, hairball 4.26 -> 4.02 ms, Sponza- / Cornell-class unchanged; scaling the shade threshold too
+	// helps the first two further (2.26 / 3.56 ms) and costs the others 10 - 20 %
+	plan->drainMode = ( knobs.drainMode >= 0 ) ? knobs.drainMode : 1;
+
+	if( knobs.phPark >= 0 ) {
+		plan->park = std::max( 1, std::min( ( spec.pathSlotBytes != 0 ) ? 128 : 64, knobs.phPark ) );   // two paths per lane: walks of up to 128 per wave
+	}
+	if( knobs.phShade >= 0 ) {
+		plan->shade = std::max( 1, std::min( 64, knobs.phShade ) );
+	}
+	if( knobs.parkEighths >= 0 ) {
+		plan->parkEighths = std::min( 8, knobs.parkEighths );
+	}
+
+	plan->name = spec.name;
+	// the symbol as rocprofv3 prints it (pt_instance.hip instantiates exactly these; namespaces: pt_flavour.hpp)
+	const char* const tf[2] = { "false", "true" };
+	const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0 };
+
+	if( spec.group == PTI_DUAL ) {
+		std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingDual<%u, %s, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights] );
+	}
+	else if( spec.group >= PTI_PHASED_LEAN ) {
+		std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingPhased<%u, %s, %s, %d>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights], minw[spec.group] );
+	}
+	else {
+		std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracing<%u, %s, %s, %d, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights], minw[spec.group], tf[spec.group == PTI_REFILL_PHONG] );
+	}
+
+	return PBR_OK;
+}
+
+// The plans of this scene + configuration, built on the first render after replan(): the tuner's candidates, and with Phong
+// tessellation the one plan that renders it.
+int buildPlans( pbr_ctx* ctx, uint32_t hotAvail, bool phong ) {
+	if( !ctx->plansBuilt ) {
+		const int flavour = flavourOf( ctx->cfg );
+		// The state machine's thresholds (lanes that leave a node phase before it ends / lanes that wait before a shade phase):
+		// 16 / 40 in the reference's walk (profiles/r03/experiments/sweep_thresholds.txt).  A ray-ordered walk makes fewer visits per
+		// shading, and its 6-waves build does best at 12 / 48: Dragon-class +1.5 % (exact) / +2.5 % (native), hairball +0.1 … +0.3 %,
+		// Sponza-class -0.3 … -1.2 % — where the two-paths plan wins anyway (profiles/r05/experiments/sweep_thresholds_ordered_walk*.txt).
+		const bool orderedWalk = ( flavour & 1 ) != 0;
+		const PlanSpec specs[ScheduleTuner::kPlans] = {
+			{ PTI_REFILL_LEAN, "refill-lean", 0, 0 },
+			{ PTI_REFILL_WIDE, "refill-wide", 0, 0 },
+			{ PTI_PHASED_LEAN, "phased-lean", 16, 32 },
+			{ PTI_PHASED_WIDE, "phased-wide", 16, 48 },
+			{ PTI_PHASED_MID, "phased-mid", orderedWalk ? 12 : 16, orderedWalk ? 48 : 40, kMidBlockThreads },
+			{ PTI_REFILL_MID, "refill-mid", 0, 0, kMidBlockThreads },
+			// 28 of a wave's up to 128 walks leave a node phase before it ends; a shade phase waits for 48 lanes (measured:
+			// profiles/r04/experiments/two_paths_per_lane.txt).  Without the hand-scheduled node phase: phased-mid's kernel and thresholds.
+			dualIsDual( flavour ) ? PlanSpec{ PTI_DUAL, "phased-dual", 28, 48, PBR_BLOCK, (size_t) 2 * 4 * 16 * PBR_BLOCK }
+			                      : PlanSpec{ PTI_PHASED_MID, "phased-dual", 16, 40, kMidBlockThreads },
+		};
+
+		for( int k = 0; k < ScheduleTuner::kPlans; k++ ) {
+			PBR_TRY( makePlan( ctx, specs[k], hotAvail, &ctx->plans[k] ) );
+			ctx->tuner.names[k] = specs[k].name;
+		}
+
+		ctx->tuner.log = ( ctx->knobs.tuneLog > 0 ) ? stderr : nullptr;
+		ctx->plansBuilt = true;
+		ctx->phongPlanBuilt = false;
+	}
+
+	if( phong && !ctx->phongPlanBuilt ) {
+		// the Phong-tessellation build of the lock-step kernel (lean budget)
+		PBR_TRY( makePlan( ctx, PlanSpec{ PTI_REFILL_PHONG, "refill-lean-phong", 0, 0 }, hotAvail, &ctx->phongPlan ) );
+		ctx->phongPlanBuilt = true;
+	}
+
+	return PBR_OK;
+}
+
+// waveUnits: how many wave-sized pieces of work the launch has — tiles x frames (a rank of an 8-GPU run has 4050
+// tiles at 1080p: fewer than the 6144 - 8192 resident waves, but 256 frames of them)
+int runPlan( pbr_ctx* ctx, const Plan& plan, DevParams* P, size_t waveUnits ) {
+	const size_t wavesPerBlock = (size_t) plan.blockThreads / 64;
+	const size_t needed = std::max<size_t>( 1, ( waveUnits + wavesPerBlock - 1 ) / wavesPerBlock );
+	const unsigned blocks = (unsigned) std::min<size_t>( (size_t) plan.blocks, needed );
+	P->numHot = plan.numHot;
+	P->numHotBytes = plan.numHot * 32;
+	P->slotBase = plan.numHot * 32;
+	P->phPark = plan.park;
+	P->phShade = plan.shade;
+	P->refillBatch = plan.refillBatch;
+	P->drainMode = plan.drainMode;
+	P->parkEighths = plan.parkEighths;
+	hipLaunchKernelGGL( plan.kernel, dim3( blocks ), dim3( (unsigned) plan.blockThreads ), plan.ldsBytes, ctx->stream, *P );
+	HIP_TRY( ctx, hipGetLastError() );
+	return PBR_OK;
+}
+
+// The caller's seeds go to the device through a pinned staging buffer: a copy from pageable memory is staged synchronously
+// by the runtime.
+int stageSeeds( pbr_ctx* ctx, const float* seeds, uint32_t nFrames ) {
+	if( ctx->seedCapacity < nFrames ) {
+		(void) hipFree( ctx->dSeeds );
+		ctx->dSeeds = nullptr;
+		ctx->seedCapacity = 0;
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dSeeds, sizeof( float ) * nFrames ) );
+		ctx->seedCapacity = nFrames;
+	}
+
+	if( ctx->hSeedCapacity < nFrames ) {
+		(void) hipHostFree( ctx->hSeeds );
+		ctx->hSeeds = nullptr;
+		ctx->hSeedCapacity = 0;
+		HIP_TRY( ctx, hipHostMalloc( (void**) &ctx->hSeeds, sizeof( float ) * std::max<size_t>( nFrames, 64 ), hipHostMallocDefault ) );
+		ctx->hSeedCapacity = std::max<size_t>( nFrames, 64 );
+	}
+
+	std::memcpy( ctx->hSeeds, seeds, sizeof( float ) * nFrames );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->dSeeds, ctx->hSeeds, sizeof( float ) * nFrames, hipMemcpyHostToDevice, ctx->stream ) );
+	return PBR_OK;
+}
+
+// Frame-parallel schedules: every (pixel, frame) is its own unit of work — the frames of a pixel are
+// independent up to the running mean (pathtracing.cl:28,255,332) — so a launch ends with single
+// frames in flight, not with whole pixels; {finalColor, focus} of each go to dFrameBuf and
+// foldFrames applies setColors in frame order.  The buffer (16 B per pixel and frame) is capped,
+// longer renders run as several launch pairs.  *chunkCap: the frames of a render of nFrames per launch pair, at most;
+// dFrameBuf is grown to hold them.
+int growFrameBuf( pbr_ctx* ctx, uint32_t nFrames, size_t* chunkCap ) {
+	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
+	const size_t frameBytes = sizeof( float4 ) * pixelSlots;
+	const size_t capFrames = std::max<size_t>( 1, kFrameBufBytes / frameBytes );
+	size_t cap = std::min<size_t>( capFrames, nFrames );
+	// the queue heads count pixel slots x frames of a band in 32 bits
+	cap = std::min<size_t>( cap, std::max<size_t>( 1, 0x7FFFFFFFull / ( pixelSlots + 64 * (size_t) ctx->queueWidth ) ) );
+
+	if( ctx->knobs.chunkFrames >= 1 ) {    // tests: force several launch pairs
+		cap = std::min<size_t>( cap, (size_t) ctx->knobs.chunkFrames );
+	}
+
+	*chunkCap = cap;
+
+	if( ctx->frameBufFrames < cap ) {
+		// grown geometrically, never beyond the cap: at least 256 frames, then twice what is asked for.  A longer render
+		// after a shorter one must not pay for a multi-GB reallocation inside every call (measured: 432 -> 512 frames at
+		// 1080p, hipFree + hipMalloc of 16 GiB = 0.4 - 0.7 s when the pages have had other owners), and a small image must
+		// not take 16 GiB because one render was longer than 256 frames (64 x 64 pixels, 300 frames: 39 MB).
+		const size_t frames = std::min<size_t>( capFrames, std::max<size_t>( 256, ( cap <= 256 ) ? cap : 2 * cap ) );
+		(void) hipFree( ctx->dFrameBuf );
+		ctx->dFrameBuf = nullptr;
+		ctx->frameBufFrames = 0;
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFrameBuf, frameBytes * frames ) );
+		ctx->frameBufFrames = frames;
+	}
+
+	return PBR_OK;
+}
+
+// The dealing order of a render call of nFrames frames, by its size (costTileOrder / expensiveLastTileOrder): spatial, cost
+// classes or expensive last; P is pointed at it and lastDeal names it.  Until the schedule tuner has settled, everything is
+// dealt spatially: its chunks are short launches whatever the call's length, the cost orders are made for one length each
+// (expensive-last costs a 2-frame launch 6 %), and a plan's fitted fixed cost must not depend on which of them its chunks
+// happened to run in (seen: the 6-waves plan kept over the two-paths one, -3.6 %).
+void dealOrder( pbr_ctx* ctx, uint32_t nFrames, bool settled, DevParams* P ) {
+	const Knobs& knobs = ctx->knobs;
+	int dealt = 0;   // 0 spatial, 1 cost classes, 2 expensive last
+
+	if( !ctx->orderPinned && ctx->costLearnt && knobs.dealOrder != 0 && ( settled || knobs.dealOrder > 0 ) ) {
+		const size_t tileFrames = (size_t) ctx->numLocalTiles * nFrames;
+		const size_t costLimit = ( ctx->cfg.tile_world > 1u ) ? kCostOrderShardTileFrames : kCostOrderTileFrames;
+		dealt = ( knobs.dealOrder > 0 ) ? std::min( knobs.dealOrder, 2 ) : ( tileFrames <= costLimit ) ? 1 : ( tileFrames <= kSpatialOrderTileFrames ) ? 0 : 2;
+	}
+
+	std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", ctx->orderPinned ? "pinned" : ( dealt == 1 ) ? "cost-classes" : ( dealt == 2 ) ? "expensive-last" : "spatial" );
+	P->tileOrder = ( dealt == 1 ) ? ctx->dCostOrder : ( dealt == 2 ) ? ctx->dLastOrder : ctx->dTileOrder;
+	const unsigned* first = ( dealt != 0 ) ? ctx->costBandFirst : ctx->bandFirst;
+
+	for( int band = 0; band < PT_BANDS; band++ ) {
+		P->bandFirst[band] = first[band];
+		P->bandTiles[band] = first[band + 1] - first[band];
+	}
+}
+
+// [1] the path loop (or a record slot of the asynchronous node phase that never filled), [2] a traversal that took more
+// steps than the tree has nodes (PBR_GUARD builds): either way a walk was cut short and the image is wrong
+int checkGuard( pbr_ctx* ctx ) {
+	const volatile unsigned* guard = (const volatile unsigned*) ctx->dGuard;
+
+	if( guard[1] != 0u || guard[2] != 0u ) {
+		return fail( ctx, PBR_EDEVICE, "a bounded device loop of the path-tracing kernel gave up (path loop %u, traversal %u trips; pbr_diag_guard_trips): the image is incomplete",
+		             guard[1], guard[2] );
+	}
+
+	if( guard[3] != 0u ) {
+		return fail( ctx, PBR_EDEVICE, "the staged node prefix does not start at LDS address 0 (pt_kernel.hpp, stageHotNodes): this build of the kernels cannot be trusted" );
+	}
+
+	return PBR_OK;
 }
 
 int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* seeds,
@@ -921,25 +1210,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
 	}
 
-	if( ctx->seedCapacity < nFrames ) {
-		(void) hipFree( ctx->dSeeds );
-		ctx->dSeeds = nullptr;
-		ctx->seedCapacity = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dSeeds, sizeof( float ) * nFrames ) );
-		ctx->seedCapacity = nFrames;
-	}
-
-	// the caller's seeds go through a pinned staging buffer: a copy from pageable memory is staged synchronously by the runtime
-	if( ctx->hSeedCapacity < nFrames ) {
-		(void) hipHostFree( ctx->hSeeds );
-		ctx->hSeeds = nullptr;
-		ctx->hSeedCapacity = 0;
-		HIP_TRY( ctx, hipHostMalloc( (void**) &ctx->hSeeds, sizeof( float ) * std::max<size_t>( nFrames, 64 ), hipHostMallocDefault ) );
-		ctx->hSeedCapacity = std::max<size_t>( nFrames, 64 );
-	}
-
-	std::memcpy( ctx->hSeeds, seeds, sizeof( float ) * nFrames );
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dSeeds, ctx->hSeeds, sizeof( float ) * nFrames, hipMemcpyHostToDevice, ctx->stream ) );
+	PBR_TRY( stageSeeds( ctx, seeds, nFrames ) );
 
 	// the queue heads: foldFrames zeroes them behind every path-tracing launch, so only the first launch of a context
 	// (and any launch after one that did not end in foldFrames) has to
@@ -950,49 +1221,16 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	ctx->workClean = false;
 
 	DevParams P;
-	std::memset( &P, 0, sizeof( P ) );
-	P.parkEighths = 4;
 	uint32_t hotAvail = 0;
-	{
-		const int walk = applyWalk( ctx, &P, &hotAvail );   // P.nodes, P.firstRef / walkFirst for the configured traversal
-
-		if( walk != PBR_OK ) {
-			return walk;
-		}
-	}
-	P.tris = ctx->dTris;
+	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );   // P.nodes, P.firstRef / walkFirst for the configured traversal
 	P.triPN = ctx->dTriPN;
-	P.faceN = ctx->dFaceN;
 	P.phongAlpha = ctx->cfg.phong_tessellation;
-	P.mats = ctx->dMats;
-	P.lights = ctx->dLights;
 	P.imgIn = ctx->dImgIn;
 	P.imgOut = ctx->dImgOut;
 	P.imgDbg = ctx->dImgDbg;
-	P.seeds = ctx->dSeeds;
 	P.counters = ctx->dCounters;
 	P.workCounter = ctx->dWork;
-	P.guard = ctx->dGuard;
-
-	const float* src[4] = { &cam->eye.x, &cam->w.x, &cam->u.x, &cam->v.x };
-	float* dst[4] = { P.eye, P.cw, P.cu, P.cv };
-
-	for( int i = 0; i < 4; i++ ) {
-		for( int k = 0; k < 3; k++ ) {
-			dst[i][k] = src[i][k];
-		}
-	}
-
-	// launch-invariant sub-expressions of initRay (pt_kernel.hpp), same IEEE single operations as the kernel would do
-	// (this file is built with -ffp-contract=off like the kernels)
-	for( int k = 0; k < 3; k++ ) {
-		const float w = (float) ctx->cfg.width, h = (float) ctx->cfg.height;
-		const float cuW = P.cu[k] * w;
-		P.camA[k] = P.cu[k] - cuW;
-		P.cvH[k] = P.cv[k] * h;
-	}
-
-	P.halfPx = pxDim * 0.5f;
+	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
 	P.aperture = cam->lense[0] / cam->lense[1];
 	P.samplesF = (float) ctx->cfg.samples;
 	P.focusX = cam->focusPoint[0];
@@ -1002,413 +1240,56 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	ctx->focusGiven = false;   // one frame's worth: the next frame needs the next distance
 	P.lenseFocal = cam->lense[0];
 	P.lenseAperture = cam->lense[1];
-	P.width = (int) ctx->cfg.width;
-	P.height = (int) ctx->cfg.height;
 	P.tilesX = ctx->tilesX;
 	invariantDivisor( (unsigned) ctx->tilesX, P.tilesXDiv );
 	P.numLocalTiles = ctx->numLocalTiles;
-	P.tileOrder = ctx->dTileOrder;      // (and its band stretches: per launch, below)
-
-	invariantDivisor( 1u, P.framesDiv );   // nextSlot divides by the frames of the launch (set per chunk below)
 	P.tileWorld = (int) ctx->cfg.tile_world;
 	P.tileRank = (int) ctx->cfg.tile_rank;
-	P.numNodes = (int) ctx->numNodes;
-	P.numLights = (int) ctx->numLights;
 	P.maxDepth = (int) ctx->cfg.max_depth;
 	P.maxAddedDepth = (int) ctx->cfg.max_added_depth;
 	P.samples = (int) ctx->cfg.samples;
-	P.nFrames = (int) nFrames;
-	P.firstCount = (int) firstCount;
 	P.useExplicitWeight = explicitWeight ? 1 : 0;
 	P.explicitWeight = weight;
-	P.pxDim = pxDim;
 	P.antiAliasing = ctx->cfg.anti_aliasing;
 	P.sky[0] = ctx->cfg.sky_light[0];
 	P.sky[1] = ctx->cfg.sky_light[1];
 	P.sky[2] = ctx->cfg.sky_light[2];
 
-	const bool lights = ( ctx->numLights > 0 );
-	const bool shadow = ( ctx->cfg.shadow_rays == 1 ) && lights;
-	const Knobs& knobs = ctx->knobs;
 	const bool phong = ( ctx->cfg.phong_tessellation > 0.0f );
-	const int flavour = flavourOf( ctx->cfg );
 
 	if( phong && ctx->dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs a scene with usable vertex normals" );
 	}
 
-	// A plan = kernel + persistent grid + LDS split.  Grid: as many blocks as stay resident, never more
-	// than there is work for.  LDS: each block stages a prefix of the node stream; the CU's 160 KB are
-	// split between the blocks the register budget admits.  The experiment knobs (PBR_BLOCKS_PER_CU, PBR_LDS_SLOTS,
-	// PBR_PH_PARK, PBR_PH_SHADE, PBR_PARK_EIGHTHS, PBR_DRAIN_MODE) are read when the plans are built — once per
-	// scene + configuration — not per launch.
-	auto makePlan = [&]( int group, const char* name, int park, int shade, Plan* plan, int blockThreads = PBR_BLOCK, size_t pathSlotBytes = 0 ) -> int {
-		const KernelFn kernel = pickKernel( flavour, group, ctx->cfg.brdf, shadow, lights );
+	PBR_TRY( buildPlans( ctx, hotAvail, phong ) );
+	size_t chunkCap = 0;
+	PBR_TRY( growFrameBuf( ctx, nFrames, &chunkCap ) );
+	ctx->tuner.beginRender( nFrames );
 
-		if( kernel == nullptr ) {
-			return fail( ctx, PBR_ESTATE, "plan %s: this library was built without that kernel (flavour %d)", name, flavour );
-		}
-
-		int blocksPerCU = 0;
-		HIP_TRY( ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor( &blocksPerCU, (const void*) kernel, blockThreads, 0 ) );
-		blocksPerCU = ( blocksPerCU < 1 ) ? 1 : blocksPerCU;
-
-		if( knobs.blocksPerCU >= 1 && knobs.blocksPerCU < blocksPerCU ) {
-			blocksPerCU = knobs.blocksPerCU;
-		}
-
-		// a block's share of the CU's 160 KB, for the staged tree top
-		const size_t ldsPerCU = 160 * 1024;
-		const size_t share = ldsPerCU / (size_t) blocksPerCU - 256;
-		const size_t slotBytes = pathSlotBytes;     // two paths per lane: 2 slots x 4 planes x 16 B of path state per lane behind the staged prefix
-
-		// (a toolchain that fitted such a kernel into fewer registers would report two blocks per CU, whose share
-		// is smaller than the path slots — the subtraction below is unsigned)
-		if( share < slotBytes + 32 ) {
-			return fail( ctx, PBR_ESTATE, "plan %s: %zu B of per-lane path state do not fit a block's %zu B share of LDS at %d blocks per CU", name, slotBytes, share, blocksPerCU );
-		}
-
-		size_t slots = ( share - slotBytes ) / 32;
-		slots = std::min<size_t>( slots, hotAvail );
-
-		if( knobs.ldsSlots >= 0 ) {
-			slots = std::min<size_t>( slots, (size_t) knobs.ldsSlots );
-		}
-		if( flavour & 4 ) {
-			slots &= ~(size_t) 1;      // compact records are two slots each: a staged prefix ends on a record
-		}
-
-		// the limit is a property of the kernel function, shared by every context of the process: always the block's whole
-		// share, so that a context with a small scene never lowers it under another context's cached plan
-		HIP_TRY( ctx, hipFuncSetAttribute( (const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) share ) );
-
-		plan->kernel = kernel;
-		plan->blockThreads = blockThreads;
-		plan->blocks = ctx->numCUs * blocksPerCU;   // all that are resident at once; run() launches fewer when there is less work
-		plan->numHot = (int) slots;
-		plan->ldsBytes = slots * 32 + slotBytes;
-		plan->park = park;
-		plan->shade = shade;
-		plan->parkEighths = ( ctx->numNodes >= kWideMinNodes ) ? 4 : 6;   // see traverse(), pt_kernel.hpp
-
-		if( knobs.phPark >= 0 ) {
-			plan->park = std::max( 1, std::min( ( pathSlotBytes != 0 ) ? 128 : 64, knobs.phPark ) );   // two paths per lane: walks of up to 128 per wave
-		}
-		if( knobs.phShade >= 0 ) {
-			plan->shade = std::max( 1, std::min( 64, knobs.phShade ) );
-		}
-		if( knobs.parkEighths >= 0 ) {
-			plan->parkEighths = std::min( 8, knobs.parkEighths );
-		}
-
-		plan->name = name;
-		// the symbol as rocprofv3 prints it (pt_instance.hip instantiates exactly these; namespaces: pt_flavour.hpp)
-		const char* const tf[2] = { "false", "true" };
-		const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0 };
-
-		if( group == PTI_DUAL ) {
-			std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingDual<%u, %s, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights] );
-		}
-		else if( group >= PTI_PHASED_LEAN ) {
-			std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingPhased<%u, %s, %s, %d>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights], minw[group] );
-		}
-		else {
-			std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracing<%u, %s, %s, %d, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights], minw[group], tf[group == PTI_REFILL_PHONG] );
-		}
-
-		return PBR_OK;
-	};
-
-	// waveUnits: how many wave-sized pieces of work the launch has — tiles x frames (a rank of an 8-GPU run has 4050
-	// tiles at 1080p: fewer than the 6144 - 8192 resident waves, but 256 frames of them)
-	auto run = [&]( const Plan& plan, size_t waveUnits ) -> int {
-		const size_t wavesPerBlock = (size_t) plan.blockThreads / 64;
-		const size_t needed = std::max<size_t>( 1, ( waveUnits + wavesPerBlock - 1 ) / wavesPerBlock );
-		const unsigned blocks = (unsigned) std::min<size_t>( (size_t) plan.blocks, needed );
-		P.numHot = plan.numHot;
-		P.numHotBytes = plan.numHot * 32;
-		P.slotBase = plan.numHot * 32;
-
-		P.phPark = plan.park;
-		P.phShade = plan.shade;
-		P.refillBatch = ( knobs.refillBatch >= 1 ) ? std::min( 64, knobs.refillBatch ) : ( ( ctx->numNodes >= kWideMinNodes ) ? kRefillBatchLarge : kRefillBatchSmall );
-		P.drainMode = ctx->drainMode;   // 1: measured (single-frame 1080p launches): park share scaled, shade threshold as is: Dragon-class 2.99 -> 2.47 ms, hairball 4.26 -> 4.02 ms, Sponza- / Cornell-class unchanged; scaling the shade threshold too helps the first two further (2.26 / 3.56 ms) and costs the others 10 - 20 %
-		P.parkEighths = plan.parkEighths;
-		hipLaunchKernelGGL( plan.kernel, dim3( blocks ), dim3( (unsigned) plan.blockThreads ), plan.ldsBytes, ctx->stream, P );
-		HIP_TRY( ctx, hipGetLastError() );
-
-		return PBR_OK;
-	};
-
-
-	// Frame-parallel schedules: every (pixel, frame) is its own unit of work — the frames of a pixel are
-	// independent up to the running mean (pathtracing.cl:28,255,332) — so a launch ends with single
-	// frames in flight, not with whole pixels; {finalColor, focus} of each go to dFrameBuf and
-	// foldFrames applies setColors in frame order.  The buffer (16 B per pixel and frame) is capped,
-	// longer renders run as several launch pairs.
-	//
-	// Which kernel: the lock-step walk ("refill") or the lane state machine ("phased"), each with the lean
-	// (4 waves / SIMD, no spills), the mid (6) or the wide (8 waves / SIMD) register budget.  Which one wins
-	// depends on the scene (1080p: Cornell refill-mid 4250 vs phased-mid 3650 Msamples/s, dragon-class
-	// phased-mid 1900 vs refill-wide 1000), and all of them give the same bits — so the first frames
-	// of a scene + configuration, which have to be rendered anyway, are rendered in turn by each
-	// candidate (kTuneFrames each) and timed; short launches favour the plans with fewer, larger blocks,
-	// so the two or three fastest (the third only if within 10 % of the first) are timed again on short and long chunks,
-	// in the palindromic order A B C (short) C B A (long) A B C (long) C B A (short): two lengths separate a launch's
-	// fixed cost from its per-frame cost, and every plan's short launches and its long launches are centred on the same
-	// moment, so the drift of the clocks — the GPU ramps up from idle during exactly these launches, which biased a
-	// one-sided order by 5 % in the per-frame cost — cancels in both.  When the two best end within 5 % of each other the palindrome
-	// is run a second time before the decision (the fits accumulate): a fit over four launches carries 1 - 5 % of noise.
-	const int kPlans = 7;
-	// Lengths in 1080p-frame equivalents: a rank of an 8-GPU run (or a small image) has 1/8 of the pixels per frame, and
-	// launches of a few hundred microseconds say little about a long render (measured at 1/8 of the tiles: the tuner
-	// kept a plan 26 % slower than the best).  So the chunk lengths grow as the frame shrinks.
-	const uint32_t tuneScale = tuneScaleOf( (size_t) ctx->numLocalTiles * 64 );
-	const uint32_t kTuneFrames = 2 * tuneScale;     // screening, per plan (or two launches, whichever comes first)
-	const uint32_t kRefineShort = 4 * tuneScale, kRefineLong = 12 * tuneScale;     // refinement: two chunks of each length per plan
-	const uint32_t kRefinePasses = 4;
-	if( !ctx->plansBuilt ) {
-		Plan* plans = ctx->plans;
-		int status = makePlan( PTI_REFILL_LEAN, "refill-lean", 0, 0, &plans[0] );
-		status = ( status != PBR_OK ) ? status : makePlan( PTI_REFILL_WIDE, "refill-wide", 0, 0, &plans[1] );
-		status = ( status != PBR_OK ) ? status : makePlan( PTI_PHASED_LEAN, "phased-lean", 16, 32, &plans[2] );
-		status = ( status != PBR_OK ) ? status : makePlan( PTI_PHASED_WIDE, "phased-wide", 16, 48, &plans[3] );
-		// The state machine's thresholds (lanes that leave a node phase before it ends / lanes that wait before a shade phase):
-		// 16 / 40 in the reference's walk (profiles/r03/experiments/sweep_thresholds.txt).  A ray-ordered walk makes fewer visits per
-		// shading, and its 6-waves build does best at 12 / 48: Dragon-class +1.5 % (exact) / +2.5 % (native), hairball +0.1 … +0.3 %,
-		// Sponza-class -0.3 … -1.2 % — where the two-paths plan wins anyway (profiles/r05/experiments/sweep_thresholds_ordered_walk*.txt).
-		const bool orderedWalk = ( flavour & 1 ) != 0;
-		status = ( status != PBR_OK ) ? status : makePlan( PTI_PHASED_MID, "phased-mid", orderedWalk ? 12 : 16, orderedWalk ? 48 : 40, &plans[4], kMidBlockThreads );
-		status = ( status != PBR_OK ) ? status : makePlan( PTI_REFILL_MID, "refill-mid", 0, 0, &plans[5], kMidBlockThreads );
-		// 28 of a wave's up to 128 walks leave a node phase before it ends; a shade phase waits for 48 lanes (measured:
-		// profiles/r04/experiments/two_paths_per_lane.txt).  Without the hand-scheduled node phase: phased-mid's kernel and thresholds.
-		status = ( status != PBR_OK ) ? status : ( dualIsDual( flavour )
-			? makePlan( PTI_DUAL, "phased-dual", 28, 48, &plans[6], PBR_BLOCK, (size_t) 2 * 4 * 16 * PBR_BLOCK )
-			: makePlan( PTI_PHASED_MID, "phased-dual", 16, 40, &plans[6], kMidBlockThreads ) );
-
-		if( status != PBR_OK ) {
-			return status;
-		}
-
-
-		ctx->drainMode = 1;
-
-		if( knobs.drainMode >= 0 ) {
-			ctx->drainMode = knobs.drainMode;
-		}
-
-		ctx->plansBuilt = true;
-		ctx->phongPlanBuilt = false;
-	}
-
-	Plan plans[kPlans];
-
-	for( int k = 0; k < kPlans; k++ ) {
-		plans[k] = ctx->plans[k];
-	}
-
-	auto screened = [&]( int plan ) { return ctx->tuneFrames[plan] >= kTuneFrames || ctx->tuneLaunches[plan] >= 2u; };
-
-	int forcedPlan = -1;
-
-	if( ctx->pinnedPlan >= 0 ) {
-		forcedPlan = std::min( kPlans - 1, ctx->pinnedPlan );
-	}
-
-	if( phong ) {
-		// one plan: the Phong-tessellation build of the lock-step kernel (lean budget), in the slot of plan 1
-		if( !ctx->phongPlanBuilt ) {
-			const int made = makePlan( PTI_REFILL_PHONG, "refill-lean-phong", 0, 0, &ctx->phongPlan );
-
-			if( made != PBR_OK ) {
-				return made;
-			}
-
-			ctx->phongPlanBuilt = true;
-		}
-
-		plans[1] = ctx->phongPlan;
-		forcedPlan = 1;
-	}
-
-	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
-	const size_t frameBytes = sizeof( float4 ) * pixelSlots;
-	size_t chunkCap = std::max<size_t>( 1, kFrameBufBytes / frameBytes );
-	chunkCap = std::min<size_t>( chunkCap, nFrames );
-	// the queue heads count pixel slots x frames of a band in 32 bits
-	chunkCap = std::min<size_t>( chunkCap, std::max<size_t>( 1, 0x7FFFFFFFull / ( pixelSlots + 64 * (size_t) ctx->queueWidth ) ) );
-
-	if( knobs.chunkFrames >= 1 ) {    // tests: force several launch pairs
-		chunkCap = std::min<size_t>( chunkCap, (size_t) knobs.chunkFrames );
-	}
-
-	if( ctx->frameBufFrames < chunkCap ) {
-		// grown geometrically, never beyond the cap: at least 256 frames, then twice what is asked for.  A longer render
-		// after a shorter one must not pay for a multi-GB reallocation inside every call (measured: 432 -> 512 frames at
-		// 1080p, hipFree + hipMalloc of 16 GiB = 0.4 - 0.7 s when the pages have had other owners), and a small image must
-		// not take 16 GiB because one render was longer than 256 frames (64 x 64 pixels, 300 frames: 39 MB).
-		const size_t capFrames = std::max<size_t>( 1, kFrameBufBytes / frameBytes );
-		const size_t frames = std::min<size_t>( capFrames, std::max<size_t>( 256, ( chunkCap <= 256 ) ? chunkCap : 2 * chunkCap ) );
-		(void) hipFree( ctx->dFrameBuf );
-		ctx->dFrameBuf = nullptr;
-		ctx->frameBufFrames = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFrameBuf, frameBytes * frames ) );
-		ctx->frameBufFrames = frames;
-	}
-
-	ctx->tuneRenderFrames = std::max( ctx->tuneRenderFrames, nFrames );
-
-	// A launch costs a + b x frames (a: ramp-up and drain, 0.3 - 0.6 ms; b: the per-frame rate) and the plans differ in
-	// both: least squares over each finalist's refinement launches, then the cost of a render of `frames` frames.
-	// Launches of one length only (a caller rendering frame by frame) cannot separate the two: a = 0, `separable` false.
-	bool separable = true;
-	double runnerUp = 0.0;       // cost of the second-best finalist relative to the best's, as decide() last saw them
-	auto decide = [&]( uint32_t renderFrames ) -> int {
-		const double frames = (double) std::max<uint32_t>( renderFrames, 1u );
-		int best = -1;
-		double bestCost = 0.0, secondCost = 0.0;
-		separable = true;
-
-		for( int k = 0; k < ctx->refineCount; k++ ) {
-			const double* f = ctx->refineFit[k];
-			const double det = f[0] * f[2] - f[1] * f[1];
-			double a = 0.0, b = f[3] / f[1];
-
-			if( det > 1e-9 * f[2] * f[0] ) {
-				const double bFit = ( f[0] * f[4] - f[1] * f[3] ) / det;
-				const double aFit = ( f[3] - bFit * f[1] ) / f[0];
-
-				if( aFit >= 0.0 && bFit >= 0.0 ) {
-					a = aFit;
-					b = bFit;
-				}
-			}
-			else {
-				separable = false;
-			}
-
-			const double cost = ( a + b * frames ) / frames;
-
-			if( knobs.tuneLog > 0 ) {
-				std::fprintf( stderr, "[pbr tune] fit %-12s a %.3f ms  b %.3f ms/frame  -> %.4f ms/frame at %u frames\n", plans[ctx->refinePlan[k]].name, a, b, cost, (unsigned) frames );
-			}
-
-			if( best < 0 || cost < bestCost ) {
-				secondCost = ( best < 0 ) ? 0.0 : bestCost;
-				best = k;
-				bestCost = cost;
-			}
-			else if( secondCost == 0.0 || cost < secondCost ) {
-				secondCost = cost;
-			}
-		}
-
-		runnerUp = ( bestCost > 0.0 && secondCost > 0.0 ) ? secondCost / bestCost : 0.0;
-		return ctx->refinePlan[best];
-	};
-
-	if( ctx->tunedPlan >= 0 && ctx->refineCount > 0 && nFrames > 2u * ctx->tunedAtFrames ) {
-		// tuned for shorter renders than this one (a viewer's frame-by-frame calls, then a batch): the fixed cost
-		// weighs less now.  With fits from two launch lengths that is a new evaluation; with one length only, the
-		// finalists are timed again on this render's frames.
-		const int again = decide( nFrames );
-
-		if( separable ) {
-			ctx->tunedPlan = again;
-			ctx->tunedAtFrames = nFrames;
-		}
-		else if( nFrames >= 4u * kRefineLong ) {
-			ctx->tunedPlan = -1;
-			ctx->refineChunks = 0;
-			ctx->refineRounds = 1;
-			std::memset( ctx->refineFit, 0, sizeof( ctx->refineFit ) );
-		}
-	}
+	// Phong tessellation has one plan; a pinned plan renders without tuning
+	const Plan* forced = phong ? &ctx->phongPlan : ( ctx->pinnedPlan >= 0 ) ? &ctx->plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )] : nullptr;
+	dealOrder( ctx, nFrames, forced != nullptr || ctx->tuner.settled(), &P );
 	P.frameBuf = ctx->dFrameBuf;
+	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
 	P.frameStride = (unsigned) pixelSlots;
 	const unsigned foldBlocks = (unsigned) ( ( pixelSlots + 255 ) / 256 );
 	double traceMs = 0.0;
 	uint32_t launches = 0, largest = 0;
-
-	int dealt = 0;
-
-	// While the schedule tuner is still measuring, everything is dealt spatially: its chunks are short launches whatever the call's
-	// length, the cost orders are made for one length each (expensive-last costs a 2-frame launch 6 %), and a plan's fitted fixed cost
-	// must not depend on which of them its chunks happened to run in (seen: the 6-waves plan kept over the two-paths one, -3.6 %).
-	const bool stillTuning = ( forcedPlan < 0 && ctx->tunedPlan < 0 );
-
-	if( !ctx->orderPinned && ctx->costLearnt && knobs.dealOrder != 0 && ( !stillTuning || knobs.dealOrder > 0 ) ) {
-		const size_t tileFrames = (size_t) ctx->numLocalTiles * nFrames;
-		const size_t costLimit = ( ctx->cfg.tile_world > 1u ) ? kCostOrderShardTileFrames : kCostOrderTileFrames;
-		dealt = ( knobs.dealOrder > 0 ) ? std::min( knobs.dealOrder, 2 ) : ( tileFrames <= costLimit ) ? 1 : ( tileFrames <= kSpatialOrderTileFrames ) ? 0 : 2;
-	}
-
-	std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", ctx->orderPinned ? "pinned" : ( dealt == 1 ) ? "cost-classes" : ( dealt == 2 ) ? "expensive-last" : "spatial" );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 
 	for( uint32_t done = 0; done < nFrames; ) {
 		// which plan renders this chunk, and how many frames of it
-		int choice = forcedPlan;
-		bool tuning = false;
-
-		int refining = -1;   // index into refinePlan while the finalists are compared
-
-		if( choice < 0 ) {
-			choice = ctx->tunedPlan;
-
-			if( choice < 0 && ctx->refineCount > 0 ) {
-				// forward, then backward (A B C C B A): symmetric against a clock that is still ramping up or throttling
-				const uint32_t k = ctx->refineChunks % (uint32_t) ctx->refineCount;
-				const bool backward = ( ( ctx->refineChunks / (uint32_t) ctx->refineCount ) & 1u ) != 0u;
-				refining = backward ? ctx->refineCount - 1 - (int) k : (int) k;
-				choice = ctx->refinePlan[refining];
-			}
-			else if( choice < 0 ) {
-				tuning = true;
-				choice = 0;
-
-				while( choice < kPlans - 1 && screened( choice ) ) {
-					choice++;
-				}
-			}
-		}
-
-		const Plan& plan = plans[choice];
-		uint32_t n = std::min<uint32_t>( (uint32_t) chunkCap, nFrames - done );
-
-		if( tuning ) {
-			n = std::min<uint32_t>( n, kTuneFrames - ctx->tuneFrames[choice] );
-		}
-		if( refining >= 0 ) {
-			const uint32_t pass = ( ctx->refineChunks / (uint32_t) ctx->refineCount ) % kRefinePasses;
-			const bool longPass = ( pass == 1u || pass == 2u );
-			n = std::min<uint32_t>( n, longPass ? kRefineLong : kRefineShort );
-		}
-
+		const uint32_t most = std::min<uint32_t>( (uint32_t) chunkCap, nFrames - done );
+		const Chunk chunk = ( forced != nullptr ) ? Chunk{ -1, most, -1, false } : ctx->tuner.next( most );
+		const Plan& plan = ( forced != nullptr ) ? *forced : ctx->plans[chunk.plan];
+		const uint32_t n = chunk.frames;
 		P.nFrames = (int) n;
 		invariantDivisor( n, P.framesDiv );
 		P.firstCount = (int) ( firstCount + done );
 		P.seeds = ctx->dSeeds + done;
-		// the dealing order, by the launch's size (costTileOrder): short launches end sooner with the expensive tiles first,
-		// long ones are faster in the spatial order
-		// the dealing order, by the size of the render call (costTileOrder / expensiveLastTileOrder): 0 spatial, 1 cost classes, 2 expensive last
-		P.tileOrder = ( dealt == 1 ) ? ctx->dCostOrder : ( dealt == 2 ) ? ctx->dLastOrder : ctx->dTileOrder;
-
-		for( int band = 0; band < PT_BANDS; band++ ) {
-			const unsigned* first = ( dealt != 0 ) ? ctx->costBandFirst : ctx->bandFirst;
-			P.bandFirst[band] = first[band];
-			P.bandTiles[band] = first[band + 1] - first[band];
-		}
-
 
 		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStart, ctx->stream ) );
-
-		const int ran = run( plan, (size_t) ctx->numLocalTiles * n );
-
-		if( ran != PBR_OK ) {
-			return ran;
-		}
-
+		PBR_TRY( runPlan( ctx, plan, &P, (size_t) ctx->numLocalTiles * n ) );
 		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStop, ctx->stream ) );
 		// the running mean so far: the input image for the first chunk, imageOut after that
 		hipLaunchKernelGGL( ptk::foldFrames, dim3( foldBlocks ), dim3( 256 ), 0, ctx->stream, P,
@@ -1427,55 +1308,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 			std::snprintf( ctx->lastKernel, sizeof( ctx->lastKernel ), "%s", plan.kernelName );
 		}
 
-		if( ( tuning || refining >= 0 ) && knobs.tuneLog > 0 ) {
-			std::fprintf( stderr, "[pbr tune] %s %-12s %u frame(s) %.3f ms = %.3f ms/frame\n", tuning ? "screen" : "refine", plan.name, n, (double) ms, (double) ms / n );
-		}
-
-		if( tuning ) {
-			ctx->tuneMs[choice] += (double) ms;
-			ctx->tuneFrames[choice] += n;
-			ctx->tuneLaunches[choice]++;
-
-			if( screened( kPlans - 1 ) ) {
-				// screening done: every plan within 10 % of the fastest — at least the two fastest — goes on to the refinement
-				auto perFrame = [&]( int k ) { return ctx->tuneMs[k] / ctx->tuneFrames[k]; };
-				int order[kPlans] = { 0, 1, 2, 3, 4, 5, 6 };
-				std::sort( order, order + kPlans, [&]( int x, int y ) { return perFrame( x ) < perFrame( y ); } );
-				ctx->refineCount = 0;
-
-				for( int k = 0; k < kPlans; k++ ) {
-					if( k < 2 || ( k < 3 && perFrame( order[k] ) <= 1.10 * perFrame( order[0] ) ) ) {
-						ctx->refinePlan[ctx->refineCount++] = order[k];
-					}
-				}
-			}
-		}
-
-		if( refining >= 0 ) {
-			double* fit = ctx->refineFit[refining];
-			fit[0] += 1.0;
-			fit[1] += (double) n;
-			fit[2] += (double) n * (double) n;
-			fit[3] += (double) ms;
-			fit[4] += (double) n * (double) ms;
-			ctx->refineChunks++;
-
-			if( ctx->refineChunks >= ctx->refineRounds * kRefinePasses * (uint32_t) ctx->refineCount ) {
-				const int best = decide( ctx->tuneRenderFrames );
-
-				// A close call — the runner-up within 5 % (phased-mid and phased-dual on a Sponza-class scene are 3 % apart, and a
-				// fit over four launches per plan carries 1 - 5 % of noise in its per-frame cost: measured, one wrong pick in a dozen
-				// runs) — gets a second palindrome of launches before the decision; the fits accumulate.
-				if( runnerUp > 0.0 && runnerUp < 1.05 && ctx->refineRounds < 2u ) {
-					ctx->refineRounds = 2u;
-				}
-				else {
-					ctx->tunedPlan = best;
-					ctx->tunedAtFrames = ctx->tuneRenderFrames;
-				}
-			}
-		}
-
+		ctx->tuner.record( chunk, (double) ms );
 		done += n;
 	}
 
@@ -1489,18 +1322,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	ctx->lastTraceMs = traceMs;
 	ctx->lastTraceLaunches = launches;
 	ctx->launchesSinceLearn += launches;
-
-	// [1] the path loop (or a record slot of the asynchronous node phase that never filled), [2] a traversal that took more
-	// steps than the tree has nodes (PBR_GUARD builds): either way a walk was cut short and the image is wrong
-	if( ( (const volatile unsigned*) ctx->dGuard )[1] != 0u || ( (const volatile unsigned*) ctx->dGuard )[2] != 0u ) {
-		return fail( ctx, PBR_EDEVICE, "a bounded device loop of the path-tracing kernel gave up (path loop %u, traversal %u trips; pbr_diag_guard_trips): the image is incomplete",
-		             ( (const volatile unsigned*) ctx->dGuard )[1], ( (const volatile unsigned*) ctx->dGuard )[2] );
-	}
-
-	if( ( (const volatile unsigned*) ctx->dGuard )[3] != 0u ) {
-		return fail( ctx, PBR_EDEVICE, "the staged node prefix does not start at LDS address 0 (pt_kernel.hpp, stageHotNodes): this build of the kernels cannot be trusted" );
-	}
-
+	PBR_TRY( checkGuard( ctx ) );
 	return learnTileCosts( ctx, cam, pxDim );
 }
 
@@ -1725,13 +1547,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	}
 
 	std::vector<int> face0s, links;
-	{
-		const int checked = checkScene( ctx, s, &face0s, &links );
-
-		if( checked != PBR_OK ) {
-			return checked;
-		}
-	}
+	PBR_TRY( checkScene( ctx, s, &face0s, &links ) );
 
 	// ---- hot nodes: rank by expected visit frequency ----
 	// A node is visited when its parent's box was hit, i.e. (for rays without preferred
@@ -1958,8 +1774,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	ctx->numMaterials = s->num_materials;
 	ctx->numLights = s->num_lights;
 	ctx->sceneBrdf = s->brdf;
-	ctx->plansBuilt = false;
-	resetTuning( ctx );   // a new scene / configuration is tuned afresh
+	replan( ctx );   // a new scene / configuration is tuned afresh
 	ctx->hasScene = true;
 
 	return prepareWalk( ctx );   // a context that is already configured for a ray-ordered walk: its streams, now
@@ -2023,15 +1838,8 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileCost, sizeof( float ) * std::max<size_t>( 1, ctx->hTileOrder.size() ) ) );
 	ctx->costLearnt = false;
 	ctx->launchesSinceLearn = 0;
-	{
-		const int uploaded = uploadTileOrder( ctx );
-
-		if( uploaded != PBR_OK ) {
-			return uploaded;
-		}
-	}
-	ctx->plansBuilt = false;
-	resetTuning( ctx );   // a new scene / configuration is tuned afresh
+	PBR_TRY( uploadTileOrder( ctx ) );
+	replan( ctx );   // a new scene / configuration is tuned afresh
 	ctx->configured = true;
 
 	return prepareWalk( ctx );
@@ -2095,11 +1903,7 @@ int pbr_render( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, co
 		return fail( ctx, PBR_EINVAL, "pbr_render needs focusPoint < 0; with depth of field call pbr_render_frame + pbr_accumulate per frame" );
 	}
 
-	const int status = launch( ctx, first_sample_count, n_frames, seeds, false, 0.0f, pxDim, cam );
-
-	if( status != PBR_OK ) {
-		return status;
-	}
+	PBR_TRY( launch( ctx, first_sample_count, n_frames, seeds, false, 0.0f, pxDim, cam ) );
 
 	// result in imageOut AND imageIn
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
@@ -2268,31 +2072,6 @@ struct DevBuf {
 	hipError_t alloc( size_t bytes ) { return hipMalloc( &p, bytes ? bytes : 4 ); }
 };
 
-// The scene for the diagnostic and denoise kernels, walked in the configured order (pbr_config.traversal); hotAvail: the
-// ranked prefix of that stream.  *status: PBR_OK, or why the configured walk's streams could not be built (the caller fails
-// with it — no silent walk in another order).
-DevParams sceneParams( pbr_ctx* ctx, int* status, uint32_t* hotAvail = nullptr ) {
-	DevParams P;
-	std::memset( &P, 0, sizeof( P ) );
-	uint32_t hot = 0;
-	*status = applyWalk( ctx, &P, &hot );
-
-	if( hotAvail != nullptr ) {
-		*hotAvail = hot;
-	}
-
-	P.parkEighths = 4;
-	P.tris = ctx->dTris;
-	P.faceN = ctx->dFaceN;
-	P.mats = ctx->dMats;
-	P.lights = ctx->dLights;
-	P.guard = ctx->dGuard;
-	P.numNodes = (int) ctx->numNodes;
-	P.numLights = (int) ctx->numLights;
-	P.numHot = 0;
-	P.numHotBytes = 0;
-	return P;
-}
 
 }  // namespace
 
@@ -2336,31 +2115,9 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 	HIP_TRY( ctx, dPing.alloc( sizeof( float4 ) * pixels ) );
 	HIP_TRY( ctx, dPong.alloc( sizeof( float4 ) * pixels ) );
 
-	int walkStatus = PBR_OK;
-	DevParams P = sceneParams( ctx, &walkStatus );
-
-	if( walkStatus != PBR_OK ) {
-		return walkStatus;
-	}
-	const float* src[4] = { &cam->eye.x, &cam->w.x, &cam->u.x, &cam->v.x };
-	float* dst[4] = { P.eye, P.cw, P.cu, P.cv };
-
-	for( int i = 0; i < 4; i++ ) {
-		for( int k = 0; k < 3; k++ ) {
-			dst[i][k] = src[i][k];
-		}
-	}
-
-	for( int k = 0; k < 3; k++ ) {   // as launch() does for initRay
-		const float cuW = P.cu[k] * (float) w;
-		P.camA[k] = P.cu[k] - cuW;
-		P.cvH[k] = P.cv[k] * (float) h;
-	}
-
-	P.halfPx = pxDim * 0.5f;
-	P.pxDim = pxDim;
-	P.width = w;
-	P.height = h;
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
+	setCamera( &P, cam, w, h, pxDim );
 
 	const dim3 block( 64, 4 );
 	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
@@ -2626,11 +2383,7 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 	HIP_TRY( ctx, hipcub::DeviceRadixSort::SortKeys( dTemp.p, tempBytes, B.keys, B.keysSorted, (int) num_faces, 0, 64, ctx->stream ) );
 
 	uint32_t treeNodes = 0;
-	const int built = radix ? buildRadixTree( ctx, B, num_faces, &treeNodes ) : buildClustered( ctx, B, num_faces, &treeNodes );
-
-	if( built != PBR_OK ) {
-		return built;
-	}
+	PBR_TRY( radix ? buildRadixTree( ctx, B, num_faces, &treeNodes ) : buildClustered( ctx, B, num_faces, &treeNodes ) );
 
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 
@@ -2695,12 +2448,8 @@ int pbr_diag_trace( pbr_ctx* ctx, const float* rays, int n, float* out_t, int32_
 	HIP_TRY( ctx, dCounts.alloc( sizeof( unsigned ) * 2 * (size_t) n ) );
 	HIP_TRY( ctx, hipMemcpy( dRays.p, rays, sizeof( float ) * 6 * (size_t) n, hipMemcpyHostToDevice ) );
 
-	int walkStatus = PBR_OK;
-	const DevParams P = sceneParams( ctx, &walkStatus );
-
-	if( walkStatus != PBR_OK ) {
-		return walkStatus;
-	}
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
 	if( ctx->numLights > 0 ) {
@@ -2737,12 +2486,8 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * outWidth * (size_t) n ) );
 	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
 
-	int walkStatus = PBR_OK;
-	const DevParams P = sceneParams( ctx, &walkStatus );
-
-	if( walkStatus != PBR_OK ) {
-		return walkStatus;
-	}
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
 	if( newRay ) {
@@ -2792,12 +2537,8 @@ int pbr_diag_trace_stream( pbr_ctx* ctx, int mode, const float* rays8, uint32_t 
 	HIP_TRY( ctx, hipMemcpy( dRays.p, rays8, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
 
 	uint32_t hotAvail = 0;
-	int walkStatus = PBR_OK;
-	DevParams P = sceneParams( ctx, &walkStatus, &hotAvail );
-
-	if( walkStatus != PBR_OK ) {
-		return walkStatus;
-	}
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );
 	P.workCounter = ctx->dWork;
 	P.counters = ctx->dCounters;
 	ctx->workClean = false;   // this probe uses the queue heads its own way
@@ -2887,9 +2628,7 @@ int pbr_diag_tune_budget( pbr_ctx* ctx, uint32_t* frames ) {
 		return fail( ctx, PBR_ESTATE, "tune budget before pbr_configure" );
 	}
 
-	// screening: 7 plans x 2; refinement: up to 3 finalists x 2 x ( 4 + 12 ), twice when the best two are within 5 %; all in
-	// 1080p-frame equivalents
-	*frames = ( 7u * 2u + 2u * 3u * 2u * ( 4u + 12u ) ) * tuneScaleOf( (size_t) ctx->numLocalTiles * 64 );
+	*frames = ctx->tuner.budgetFrames();
 	return PBR_OK;
 }
 
@@ -2901,7 +2640,7 @@ int pbr_diag_last_plan( pbr_ctx* ctx, char* name, size_t capacity, int* tuned ) 
 	std::snprintf( name, capacity, "%s", ctx->lastPlan );
 
 	if( tuned != nullptr ) {
-		*tuned = ctx->tunedPlan;
+		*tuned = ctx->tuner.tunedPlan();
 	}
 
 	return PBR_OK;
@@ -2955,27 +2694,8 @@ int pbr_diag_launch_fit( pbr_ctx* ctx, double* fixed_ms, double* per_frame_ms ) 
 		return fail( ctx, PBR_EINVAL, "diag_launch_fit: null argument" );
 	}
 
-	const int plan = ( ctx->pinnedPlan >= 0 ) ? ctx->pinnedPlan : ctx->tunedPlan;
-
-	for( int k = 0; k < ctx->refineCount; k++ ) {
-		const double* f = ctx->refineFit[k];
-		const double det = f[0] * f[2] - f[1] * f[1];
-
-		if( ctx->refinePlan[k] != plan || !( det > 1e-9 * f[2] * f[0] ) ) {
-			continue;
-		}
-
-		const double b = ( f[0] * f[4] - f[1] * f[3] ) / det;
-		const double a = ( f[3] - b * f[1] ) / f[0];
-
-		if( a >= 0.0 && b >= 0.0 ) {
-			*fixed_ms = a;
-			*per_frame_ms = b;
-			return PBR_OK;
-		}
-	}
-
-	return fail( ctx, PBR_ESTATE, "diag_launch_fit: the tuner holds no two-length fit for the plan in use (pinned before it tuned, or launches of one length only)" );
+	const int plan = ( ctx->pinnedPlan >= 0 ) ? ctx->pinnedPlan : ctx->tuner.tunedPlan();
+	return ctx->tuner.fit( plan, fixed_ms, per_frame_ms ) ? PBR_OK : fail( ctx, PBR_ESTATE, "diag_launch_fit: the tuner holds no two-length fit for the plan in use (pinned before it tuned, or launches of one length only)" );
 }
 
 int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value ) {
@@ -2994,10 +2714,7 @@ int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value ) {
 	for( const auto& entry : table ) {
 		if( std::strcmp( entry.name, name ) == 0 ) {
 			*entry.slot = value;
-			// plans carry the knobs' values: rebuild them, and let the tuner start over
-			ctx->plansBuilt = false;
-			ctx->phongPlanBuilt = false;
-			resetTuning( ctx );
+			replan( ctx );
 			return PBR_OK;
 		}
 	}
