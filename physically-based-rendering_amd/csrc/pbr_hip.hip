@@ -20,6 +20,7 @@
 // are no longer part of this source; their kernels are kept for the record under lab/src/.
 #include "bvh_build.hpp"
 #include "pt_denoise.hpp"
+#include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 
 using ptk::DevParams;
@@ -73,10 +74,8 @@ struct pbr_ctx {
 	float4* dLights = nullptr;
 	uint32_t numHotAvail = 0;      // records at the head of the node stream that are ranked for LDS staging
 	int firstRef = 0;              // record of node 1
-	// ray-ordered walk (pbr_config.traversal != 0): one stream of records per order, built on first use from a host copy of the flat tree
-	std::vector<pbr_bvh_node> hostNodes;
-	std::vector<int> hostFace0s, hostLinks;   // per node: first face or -1; second face / miss link (checkScene)
-	std::vector<uint32_t> hostRanked;         // the nodes ranked for LDS staging, most visited first
+	// ray-ordered walk (pbr_config.traversal != 0): the records of the configured layout, packed from a host copy of the flat tree
+	SceneTree tree;
 	float4* dNodesWalk = nullptr;
 	uint32_t walkBuilt = 0;        // the scheme dNodesWalk holds (0: none)
 	uint32_t walkHotAvail = 0;     // records at the head of dNodesWalk that are ranked for LDS staging (all orders interleaved)
@@ -175,11 +174,16 @@ int fail( pbr_ctx* ctx, int code, const char* fmt, ... ) {
 		} \
 	} while( 0 )
 
-void freeScene( pbr_ctx* ctx ) {
-	(void) hipFree( ctx->dNodes );
+void freeWalkStreams( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dNodesWalk );
 	ctx->dNodesWalk = nullptr;
 	ctx->walkBuilt = 0;
+	ctx->walkBytes = 0;
+}
+
+void freeScene( pbr_ctx* ctx ) {
+	(void) hipFree( ctx->dNodes );
+	freeWalkStreams( ctx );
 	(void) hipFree( ctx->dTris );
 	(void) hipFree( ctx->dTriPN );
 	ctx->dTriPN = nullptr;
@@ -222,11 +226,6 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->orderPinned = false;
 	ctx->dImgIn = ctx->dImgOut = ctx->dImgDbg = ctx->dRows = ctx->dFull = nullptr;
 	ctx->configured = false;
-}
-
-// Is w an integer-valued float in [lo, hi]?
-bool integral( float w, double lo, double hi ) {
-	return ( w == std::floor( w ) ) && ( (double) w >= lo ) && ( (double) w <= hi );
 }
 
 // queue heads of the pixel-slot queue, one 128-B line each, PT_SUB per band, + the line of the word of heads seen empty (pt_kernel.hpp, nextSlot)
@@ -320,303 +319,23 @@ void invariantDivisor( unsigned d, unsigned out[2] ) {
 	out[1] = ( l < 1u ? l : 1u ) | ( ( l > 0u ? l - 1u : 0u ) << 8 );
 }
 
-// The ray-ordered walk's streams of a layout (buildWalkStreams, below) to the device: 32 bytes of header, which the eight
-// first references are copied into, then the records; hotAvail: the ranked records at their head, in 32-byte slots.
-int uploadWalkStreams( pbr_ctx* ctx, std::vector<float4>* storage, uint32_t hotAvail, uint32_t layout ) {
-	std::memcpy( storage->data(), ctx->walkFirst, sizeof( ctx->walkFirst ) );
+// The ray-ordered walk's records of a layout (pt_scene_pack.hpp, packWalk) to the device, in place of the ones there were.
+int uploadWalkStreams( pbr_ctx* ctx, const PackedWalk& walk, uint32_t layout ) {
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	(void) hipFree( ctx->dNodesWalk );
-	ctx->dNodesWalk = nullptr;
-	ctx->walkBuilt = 0;
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( float4 ) * storage->size() ) );
-	HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, storage->data(), sizeof( float4 ) * storage->size(), hipMemcpyHostToDevice ) );
-	ctx->walkHotAvail = hotAvail;
-	ctx->walkBytes = sizeof( float4 ) * storage->size();
+	freeWalkStreams( ctx );
+	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( Quad ) * walk.storage.size() ) );
+	HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, walk.storage.data(), sizeof( Quad ) * walk.storage.size(), hipMemcpyHostToDevice ) );
+	std::memcpy( ctx->walkFirst, walk.first, sizeof( ctx->walkFirst ) );
+	ctx->walkHotAvail = walk.hotSlots;
+	ctx->walkBytes = sizeof( Quad ) * walk.storage.size();
 	ctx->walkBuilt = layout;
 	return PBR_OK;
 }
 
-// ---- the ray-ordered walk's node streams (pbr_config.traversal, include/pbr_hip.h) --------------------------------
-// Not a reference structure: the reference walks its flat tree in one fixed order (a hit continues at index + 1,
-// pt_bvh.cl:102,112; the child with the bigger surface area sits there, accelstructures/BVH.cpp:335-343).  The records of
-// the node stream name their successors explicitly (pt_kernel.hpp, decodeNode), so another visiting order is another set
-// of successor words over the same boxes and leaf words — the kernels do not change, a walk only starts somewhere else.
-//
-// The tree behind the flat array: a leaf ends at index + 1, a container i at its miss link when that is > i, else where
-// its parent ends (the root: N); its children are c0 = i + 1, c1 = end( c0 ), ... below end( i ) — the flattening drops
-// nodes (PathTracer.cpp:250-256), so there can be more than two.
-// A child's key on an axis: bbMin[axis] + bbMax[axis] (binary32).  A container's children in an order = the DFS child
-// list insertion-sorted — a child moves in front of its predecessor while its key is smaller (ascending) / greater
-// (descending); as an algorithm, so that ties and NaN keys have one outcome.
-//   scheme 1, six orders   order 2 * a + neg sorts EVERY container on axis a, descending when neg; a ray takes the order of
-//                          its direction's dominant axis and that component's sign (walkOrderOf, pt_kernel.hpp)
-//   scheme 2, eight orders order k = sign bits of the direction; a container sorts on ITS axis — the one its children's keys
-//                          spread furthest on (max - min, x before y before z on ties) — descending when that bit of k is set
-// Successors in an order: a hit container continues at its first child; child j's next is child j + 1, the last child's
-// is its parent's next, the root's is "end"; a missed container and every leaf continue at next.
-//
-// Layout: [ the ranked nodes, rank by rank, all orders of a rank next to each other (any prefix a block stages in LDS
-// serves every order alike) ][ order 0's other nodes in that order's depth-first sequence ][ order 1's ] ...
 int buildWalkStreams( pbr_ctx* ctx, uint32_t layout ) {
-	// layout 3 = scheme 2's eight orders in the compact record (pt_kernel.hpp, "the compact record"): the successors are the same
-	const bool compact = ( layout == PBR_WALK_EIGHT_ORDERS_COMPACT );
-	const uint32_t scheme = compact ? 2u : layout;
-	const int K = ( scheme == 1 ) ? 6 : 8;
-	const uint32_t N = ctx->numNodes;
-	const std::vector<pbr_bvh_node>& bvh = ctx->hostNodes;
-	const std::vector<int>& face0s = ctx->hostFace0s;
-
-	if( bvh.size() != N || N < 2 ) {
-		return fail( ctx, PBR_ESTATE, "ray-ordered walk: no host copy of the scene's tree" );
-	}
-	if( !compact && (size_t) K * N * 32 >= ( (size_t) 1 << 31 ) ) {
-		return fail( ctx, PBR_EINVAL, "ray-ordered walk: %d streams of %u records exceed 2 GiB (record references are 31-bit byte offsets); traversal = PBR_WALK_EIGHT_ORDERS_COMPACT holds 2^24 nodes", K, N );
-	}
-	if( compact && (size_t) N * 64 >= ( (size_t) 1 << 31 ) ) {
-		return fail( ctx, PBR_EINVAL, "ray-ordered walk: %u compact records exceed 2 GiB (record references are 31-bit byte offsets)", N );
-	}
-
-	// where every subtree ends
-	std::vector<uint32_t> end( N );
-	{
-		std::vector<uint32_t> open;
-
-		for( uint32_t i = 0; i < N; i++ ) {
-			while( !open.empty() && i >= end[open.back()] ) {
-				open.pop_back();
-			}
-
-			if( face0s[i] >= 0 ) {
-				end[i] = i + 1;
-			}
-			else {
-				end[i] = ( ctx->hostLinks[i] > (int) i ) ? (uint32_t) ctx->hostLinks[i] : ( open.empty() ? N : end[open.back()] );
-				open.push_back( i );
-			}
-		}
-	}
-
-	auto key = [&]( uint32_t node, int axis ) {
-		const pbr_bvh_node& n = bvh[node];
-		return ( axis == 0 ) ? n.bbMin.x + n.bbMax.x : ( axis == 1 ) ? n.bbMin.y + n.bbMax.y : n.bbMin.z + n.bbMax.z;
-	};
-
-	// per order and node: the node to go to when it is a hit container, and the node to go to otherwise (-1: end)
-	std::vector<int> onHit( (size_t) K * N, -1 ), onNext( (size_t) K * N, -1 );
-	std::vector<uint32_t> children, inOrder;
-	std::vector<unsigned char> axisOf( compact ? N : 0, 0 );   // compact: the axis a container sorts its children on
-
-	for( uint32_t i = 0; i < N; i++ ) {
-		if( face0s[i] >= 0 ) {
-			continue;
-		}
-
-		children.clear();
-
-		for( uint32_t c = i + 1; c < end[i]; c = end[c] ) {
-			children.push_back( c );
-		}
-
-		int ownAxis = 0;
-
-		if( scheme == 2 ) {
-			float widest = -1.0f;
-
-			for( int axis = 0; axis < 3; axis++ ) {
-				float lo = INFINITY, hi = -INFINITY;
-
-				for( uint32_t c : children ) {
-					const float k = key( c, axis );
-					lo = ( k < lo ) ? k : lo;
-					hi = ( k > hi ) ? k : hi;
-				}
-
-				if( hi - lo > widest ) {
-					widest = hi - lo;
-					ownAxis = axis;
-				}
-			}
-		}
-
-		if( compact ) {
-			axisOf[i] = (unsigned char) ownAxis;
-
-			if( children.empty() ) {
-				return fail( ctx, PBR_EINVAL, "ray-ordered walk, compact records: container %u has no child (a record names its two first children)", i );
-			}
-		}
-
-		for( int k = 0; k < K; k++ ) {
-			const int axis = ( scheme == 1 ) ? k / 2 : ownAxis;
-			const bool descending = ( scheme == 1 ) ? ( k & 1 ) != 0 : ( ( k >> ownAxis ) & 1 ) != 0;
-			inOrder.clear();
-
-			for( uint32_t c : children ) {
-				const float mine = key( c, axis );
-				size_t at = inOrder.size();
-				inOrder.push_back( c );
-
-				while( at > 0 ) {
-					const float before = key( inOrder[at - 1], axis );
-
-					if( !( descending ? ( mine > before ) : ( mine < before ) ) ) {
-						break;
-					}
-
-					inOrder[at] = inOrder[at - 1];
-					at--;
-				}
-
-				inOrder[at] = c;
-			}
-
-			const size_t base = (size_t) k * N;
-			const int next = ( i == 0 ) ? -1 : onNext[base + i];   // written when i's parent was handled (parents come first)
-			onHit[base + i] = inOrder.empty() ? next : (int) inOrder[0];
-
-			for( size_t j = 0; j < inOrder.size(); j++ ) {
-				onNext[base + inOrder[j]] = ( j + 1 < inOrder.size() ) ? (int) inOrder[j + 1] : next;
-			}
-		}
-	}
-
-	if( compact ) {
-		// ONE record per node: the ranked nodes first (any prefix a block stages in LDS serves every order), the rest along
-		// order 0's depth-first sequence (all-ascending: a hit container's ascending first child is then the adjacent record)
-		const uint32_t maxHotRecords = ( 160 * 1024 - 256 ) / 64;
-		const uint32_t hot = (uint32_t) std::min<size_t>( ctx->hostRanked.size(), maxHotRecords );
-		std::vector<int> recordOf( N, -1 );
-		size_t nextRecord = 0;
-
-		for( uint32_t r = 0; r < hot; r++ ) {
-			recordOf[ctx->hostRanked[r]] = (int) nextRecord++;
-		}
-
-		for( int k = 0; k < K; k++ ) {      // every order must reach every node (a tree that is not properly nested fails here)
-			const size_t base = (size_t) k * N;
-			size_t seen = 0;
-
-			for( int node = onHit[base]; node > 0; node = ( face0s[node] < 0 ) ? onHit[base + node] : onNext[base + node] ) {
-				if( ++seen >= N ) {
-					return fail( ctx, PBR_ESTATE, "ray-ordered walk: order %d does not visit every node once", k );
-				}
-				if( k == 0 && recordOf[(size_t) node] < 0 ) {
-					recordOf[(size_t) node] = (int) nextRecord++;
-				}
-			}
-
-			if( seen != N - 1 ) {
-				return fail( ctx, PBR_ESTATE, "ray-ordered walk: order %d reaches %zu of %u nodes", k, seen, N - 1 );
-			}
-		}
-
-		// 32 bytes of header (the eight first references), then 64-byte records: 4 x float4 each; one record of padding
-		const size_t numRecords = nextRecord + 1;
-		std::vector<float4> storage( 2 + numRecords * 4, make_float4( 0.0f, 0.0f, 0.0f, 0.0f ) );
-		float4* const nodes = storage.data() + 2;
-		auto refOf = [&]( int node ) { return ( node > 0 ) ? recordOf[(size_t) node] * 64 : -1; };
-		auto asFloat = []( int v ) { return __builtin_bit_cast( float, v ); };
-
-		for( uint32_t i = 1; i < N; i++ ) {
-			const pbr_bvh_node& n = bvh[i];
-			int h0, h1;
-
-			if( face0s[i] < 0 ) {
-				// order 0 sorts every container ascending, order 7 every container descending
-				h0 = refOf( onHit[(size_t) 0 * N + i] );
-				h1 = refOf( onHit[(size_t) 7 * N + i] ) | ( 4 << axisOf[i] );
-			}
-			else {
-				h0 = (int) ( 0x80000000u | ( ( ctx->hostLinks[i] >= 0 ) ? 0x40000000u : 0u ) | (uint32_t) face0s[i] );
-				h1 = 0;
-			}
-
-			int next[8];
-
-			for( int k = 0; k < 8; k++ ) {
-				next[k] = refOf( onNext[(size_t) k * N + i] );
-			}
-
-			float4* rec = nodes + (size_t) recordOf[i] * 4;
-			rec[0] = make_float4( n.bbMin.x, n.bbMin.y, n.bbMax.x, n.bbMax.y );
-			rec[1] = make_float4( n.bbMin.z, n.bbMax.z, asFloat( h0 ), asFloat( h1 ) );
-			rec[2] = make_float4( asFloat( next[0] ), asFloat( next[1] ), asFloat( next[2] ), asFloat( next[3] ) );
-			rec[3] = make_float4( asFloat( next[4] ), asFloat( next[5] ), asFloat( next[6] ), asFloat( next[7] ) );
-		}
-
-		for( int k = 0; k < 8; k++ ) {
-			ctx->walkFirst[k] = refOf( onHit[(size_t) k * N] );
-		}
-
-		return uploadWalkStreams( ctx, &storage, hot * 2u, layout );      // 32-byte slots are the unit of a plan's LDS share
-	}
-
-	// records: the ranked nodes interleaved, then every order's remaining nodes along its own depth-first sequence
-	const uint32_t maxHot = ( 160 * 1024 - 256 ) / 32;
-	const uint32_t hotPerOrder = (uint32_t) std::min<size_t>( ctx->hostRanked.size(), maxHot / (uint32_t) K );
-	std::vector<int> recordOf( (size_t) K * N, -1 );
-	size_t nextRecord = 0;
-
-	for( uint32_t r = 0; r < hotPerOrder; r++ ) {
-		for( int k = 0; k < K; k++ ) {
-			recordOf[(size_t) k * N + ctx->hostRanked[r]] = (int) nextRecord++;
-		}
-	}
-
-	for( int k = 0; k < K; k++ ) {
-		const size_t base = (size_t) k * N;
-		size_t seen = 0;
-
-		for( int node = onHit[base]; node > 0; node = ( face0s[node] < 0 ) ? onHit[base + node] : onNext[base + node] ) {
-			if( ++seen >= N ) {
-				return fail( ctx, PBR_ESTATE, "ray-ordered walk: order %d does not visit every node once", k );
-			}
-			if( recordOf[base + node] < 0 ) {
-				recordOf[base + node] = (int) nextRecord++;
-			}
-		}
-
-		if( seen != N - 1 ) {
-			return fail( ctx, PBR_ESTATE, "ray-ordered walk: order %d reaches %zu of %u nodes", k, seen, N - 1 );
-		}
-	}
-
-	// 32 bytes of header — the eight first references, where firstNode() reads them — then the records; the last one is
-	// padding, as in the reference-order stream
-	const size_t numRecords = nextRecord + 1;
-	std::vector<float4> storage( ( numRecords + 1 ) * 2, make_float4( 0.0f, 0.0f, 0.0f, 0.0f ) );
-	float4* const nodes = storage.data() + 2;
-
-	for( int k = 0; k < K; k++ ) {
-		const size_t base = (size_t) k * N;
-		auto refOf = [&]( int node ) { return ( node > 0 ) ? recordOf[base + (size_t) node] * 32 : -1; };
-
-		for( uint32_t i = 1; i < N; i++ ) {
-			const pbr_bvh_node& n = bvh[i];
-			int w0, w1;
-
-			if( face0s[i] < 0 ) {
-				w0 = refOf( onHit[base + i] );
-				w1 = refOf( onNext[base + i] );
-			}
-			else {
-				w0 = (int) ( 0x80000000u | ( ( ctx->hostLinks[i] >= 0 ) ? 0x40000000u : 0u ) | (uint32_t) face0s[i] );
-				w1 = refOf( onNext[base + i] );
-			}
-
-			const size_t r = (size_t) recordOf[base + i];
-			nodes[r * 2 + 0] = make_float4( n.bbMin.x, n.bbMin.y, n.bbMax.x, n.bbMax.y );
-			nodes[r * 2 + 1] = make_float4( n.bbMin.z, n.bbMax.z, __builtin_bit_cast( float, w0 ), __builtin_bit_cast( float, w1 ) );
-		}
-
-		ctx->walkFirst[k] = refOf( onHit[base] );
-	}
-
-	for( int k = K; k < 8; k++ ) {
-		ctx->walkFirst[k] = ctx->walkFirst[0];
-	}
-
-	return uploadWalkStreams( ctx, &storage, hotPerOrder * (uint32_t) K, layout );
+	PackedWalk walk;
+	PBR_TRY( packWalk( ctx->tree, layout, &walk, &ctx->error ) );
+	return uploadWalkStreams( ctx, walk, layout );
 }
 
 // The node stream, its ranked prefix and the first record(s) for the configured traversal.
@@ -645,27 +364,18 @@ int applyWalk( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail ) {
 
 // What a mode needs beyond valid numbers, checked where the mode is CHOSEN (pbr_configure, and pbr_upload_scene of a
 // configured context) instead of in the middle of a viewer's render loop: the mode's kernels are linked in, and —
-// with a scene present — its node streams can be built (they are, here: a tree that is not properly nested, or too many nodes
-// for 31-bit record references, fails now).  Streams of a traversal that is no longer configured are freed.
-int prepareWalk( pbr_ctx* ctx ) {
-	if( !ctx->configured ) {
+// for a tree (null: none to walk) — its records can be built.  They are packed here, before the caller changes the context
+// (ADVICE r06): a mode or a scene the walk cannot take (a tree that is not properly nested, too many nodes for 31-bit record
+// references) leaves the context as it was.
+int packConfiguredWalk( pbr_ctx* ctx, const pbr_config& cfg, const SceneTree* tree, PackedWalk* walk ) {
+	if( pbr_mode_built( cfg.traversal, cfg.arith ) != 1 ) {
+		return fail( ctx, PBR_ESTATE, "this library was built without the kernels of traversal %u / arith %u (pbr_mode_built)", cfg.traversal, cfg.arith );
+	}
+	if( tree == nullptr || cfg.traversal == 0 ) {
 		return PBR_OK;
 	}
-	if( pbr_mode_built( ctx->cfg.traversal, ctx->cfg.arith ) != 1 ) {
-		return fail( ctx, PBR_ESTATE, "this library was built without the kernels of traversal %u / arith %u (pbr_mode_built)", ctx->cfg.traversal, ctx->cfg.arith );
-	}
-	if( ctx->walkBuilt != ctx->cfg.traversal && ctx->dNodesWalk != nullptr ) {
-		HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-		(void) hipFree( ctx->dNodesWalk );
-		ctx->dNodesWalk = nullptr;
-		ctx->walkBuilt = 0;
-		ctx->walkBytes = 0;
-	}
-	if( ctx->hasScene && ctx->cfg.traversal != 0 && ctx->walkBuilt != ctx->cfg.traversal ) {
-		return buildWalkStreams( ctx, ctx->cfg.traversal );
-	}
 
-	return PBR_OK;
+	return packWalk( *tree, cfg.traversal, walk, &ctx->error );
 }
 
 // ---- the dealing order of the banded queue (pt_kernel.hpp, nextSlot) -------------------------------------------------
@@ -1441,101 +1151,12 @@ const char* pbr_last_error( const pbr_ctx* ctx ) {
 	return ( ctx != nullptr ) ? ctx->error.c_str() : "null context";
 }
 
-}  // extern "C"
-
-namespace {
-
-// Everything pbr_upload_scene checks before it touches the device: every index the kernels will follow.
-// face0s / links (optional): per node, first face or -1 (container) and second face / miss link.
-int checkScene( pbr_ctx* ctx, const pbr_scene_desc* s, std::vector<int>* face0sOut, std::vector<int>* linksOut ) {
-	if( s == nullptr || s->bvh == nullptr || s->facesV == nullptr || s->vertices == nullptr || s->materials == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "scene: null array" );
-	}
-	if( s->num_nodes < 2 || s->num_faces == 0 || s->num_vertices == 0 || s->num_materials == 0 ) {
-		return fail( ctx, PBR_EINVAL, "scene: needs >= 2 BVH nodes (the root is never tested, pt_bvh.cl:84), faces, vertices and materials" );
-	}
-	if( s->brdf > 1 ) {
-		return fail( ctx, PBR_EINVAL, "scene: brdf must be 0 or 1" );
-	}
-	if( s->num_lights > 0 && s->lights == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "scene: num_lights > 0 but lights is null" );
-	}
-	if( s->num_nodes > ( 1u << 24 ) || s->num_faces > ( 1u << 24 ) ) {
-		return fail( ctx, PBR_EINVAL, "scene: node / face indices are stored as floats and must stay below 2^24" );
-	}
-
-	// ---- nodes: validate every link the walk can follow ----
-	std::vector<int> face0s( s->num_nodes ), links( s->num_nodes );
-
-	for( uint32_t i = 0; i < s->num_nodes; i++ ) {
-		const pbr_bvh_node& n = s->bvh[i];
-
-		if( n.bbMin.w == -1.0f ) {
-			// container node: miss link in [-1, N) (the walk stops outside (0, N), pt_bvh.cl:122)
-			if( !integral( n.bbMax.w, -1.0, (double) s->num_nodes - 1.0 ) ) {
-				return fail( ctx, PBR_EINVAL, "node %u: miss link %g is not an index", i, (double) n.bbMax.w );
-			}
-
-			// ... and FORWARD: the stackless walk has no visited set, so a ray that keeps missing a box whose link
-			// points at or before it would circle forever (the reference's flattening only emits links behind the
-			// subtree, PathTracer.cpp:300-330; -1 and 0 end the walk)
-			if( i > 0 && n.bbMax.w > 0.0f && n.bbMax.w <= (float) i ) {
-				return fail( ctx, PBR_EINVAL, "node %u: miss link %g must point forward (or be -1 / 0 = end of the walk)", i, (double) n.bbMax.w );
-			}
-
-			face0s[i] = -1;
-			links[i] = (int) n.bbMax.w;
-		}
-		else if( integral( n.bbMin.w, 0.0, (double) s->num_faces - 1.0 ) ) {
-			// leaf: the second face, if any, is the next one in leaf order (PathTracer.cpp:267-268)
-			if( !( n.bbMax.w == -1.0f || n.bbMax.w == n.bbMin.w + 1.0f ) || n.bbMax.w > (float) ( s->num_faces - 1 ) ) {
-				return fail( ctx, PBR_EINVAL, "node %u: second face %g is neither -1 nor first face + 1", i, (double) n.bbMax.w );
-			}
-
-			face0s[i] = (int) n.bbMin.w;
-			links[i] = (int) n.bbMax.w;
-		}
-		else {
-			return fail( ctx, PBR_EINVAL, "node %u: bbMin.w = %g is neither -1 nor a face index", i, (double) n.bbMin.w );
-		}
-	}
-
-	if( face0s[s->num_nodes - 1] < 0 ) {
-		return fail( ctx, PBR_EINVAL, "node %u: the last node is a container (its children would lie outside the array)", s->num_nodes - 1 );
-	}
-
-	// ---- faces ----
-	for( uint32_t f = 0; f < s->num_faces; f++ ) {
-		const pbr_uint4& fv = s->facesV[f];
-
-		if( fv.x >= s->num_vertices || fv.y >= s->num_vertices || fv.z >= s->num_vertices ) {
-			return fail( ctx, PBR_EINVAL, "face %u: vertex index out of range", f );
-		}
-		if( fv.w >= s->num_materials ) {
-			return fail( ctx, PBR_EINVAL, "face %u: material index %u out of range (faces without usemtl carry -1)", f, fv.w );
-		}
-	}
-
-	if( face0sOut != nullptr ) {
-		face0sOut->swap( face0s );
-	}
-	if( linksOut != nullptr ) {
-		linksOut->swap( links );
-	}
-
-	return PBR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int pbr_validate_scene( const pbr_scene_desc* s, char* message, size_t capacity ) {
-	pbr_ctx scratch;   // no device behind it: only its error string is used
-	const int status = checkScene( &scratch, s, nullptr, nullptr );
+	std::string why;
+	const int status = checkScene( s, nullptr, &why );
 
 	if( message != nullptr && capacity > 0 ) {
-		std::snprintf( message, capacity, "%s", scratch.error.c_str() );
+		std::snprintf( message, capacity, "%s", why.c_str() );
 	}
 
 	return status;
@@ -1546,229 +1167,53 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 		return fail( ctx, PBR_ESTATE, "context is not usable" );
 	}
 
-	std::vector<int> face0s, links;
-	PBR_TRY( checkScene( ctx, s, &face0s, &links ) );
+	// everything on the host first — the scene, and the records of a ray-ordered walk the context is configured for — so
+	// that a scene the walk cannot take leaves the context as it was
+	SceneTree tree;
+	PackedScene packed;
+	PackedWalk walk;
+	PBR_TRY( checkScene( s, &tree, &ctx->error ) );
+	PBR_TRY( packScene( s, tree, &packed, &ctx->error ) );
 
-	// ---- hot nodes: rank by expected visit frequency ----
-	// A node is visited when its parent's box was hit, i.e. (for rays without preferred
-	// position) in proportion to the parent's surface area.  In the DFS array a container's
-	// subtree is [i + 1, escape) with escape = its miss link (or N), so parents fall out of one
-	// stack walk.  Measured against real visit histograms this ranking captures 56 % / 40 % /
-	// 18 % of all node visits with 1024 slots (Sponza- / Dragon-class / hairball), within 4
-	// points of the best possible choice.
-	const uint32_t N = s->num_nodes;
-	std::vector<double> weight( N, 0.0 );
-	{
-		auto area = [&]( uint32_t i ) {
-			const pbr_bvh_node& n = s->bvh[i];
-			const double dx = std::fabs( (double) n.bbMax.x - n.bbMin.x );
-			const double dy = std::fabs( (double) n.bbMax.y - n.bbMin.y );
-			const double dz = std::fabs( (double) n.bbMax.z - n.bbMin.z );
-			return 2.0 * ( dx * dy + dz * dy + dx * dz );
-		};
-		std::vector<std::pair<uint32_t, double>> stack;   // (escape, area)
-		const double rootArea = area( 0 );
-
-		for( uint32_t i = 0; i < N; i++ ) {
-			while( !stack.empty() && i >= stack.back().first ) {
-				stack.pop_back();
-			}
-
-			weight[i] = stack.empty() ? rootArea : stack.back().second;
-
-			if( face0s[i] < 0 ) {
-				const uint32_t escape = ( links[i] > (int) i ) ? (uint32_t) links[i] : N;
-				stack.push_back( std::make_pair( escape, area( i ) ) );
-			}
-		}
-	}
-
-	// at most what one block can stage with a CU's 160 KB of LDS to itself
-	const uint32_t maxHot = ( 160 * 1024 - 256 ) / 32;
-	std::vector<uint32_t> ranked;
-	ranked.reserve( N );
-
-	for( uint32_t i = 1; i < N; i++ ) {   // node 0 (the root) is never fetched
-		ranked.push_back( i );
-	}
-
-	const uint32_t numHot = (uint32_t) std::min<size_t>( ranked.size(), maxHot );
-	std::partial_sort( ranked.begin(), ranked.begin() + numHot, ranked.end(), [&]( uint32_t a, uint32_t b ) {
-		return ( weight[a] != weight[b] ) ? ( weight[a] > weight[b] ) : ( a < b );
-	} );
-
-	// ---- the node stream (pt_kernel.hpp decodeNode): hot nodes by rank, then the rest ----
-	std::vector<int> recordOf( (size_t) N, -1 );   // node index -> record; the root has none
-
-	for( uint32_t r = 0; r < numHot; r++ ) {
-		recordOf[ranked[r]] = (int) r;
-	}
-
-	const size_t numRecords = N;   // records the stream holds (the last one is padding)
-
-	{
-		// the rest in DFS order: a cold node's hit successor is the adjacent 32 B.  (Any order is legal — every record names
-		// its successors.  Treelets, a connected piece of the tree per 128-byte line, were built and measured in round 3:
-		// -13 ... -19 % distinct lines per ray offline, +0.0 / +0.2 / +0.7 % on the GPU; lab/src/node_stream_treelets.txt.)
-		int next = (int) numHot;
-
-		for( uint32_t i = 1; i < N; i++ ) {
-			if( recordOf[i] < 0 ) {
-				recordOf[i] = next++;
-			}
-		}
-	}
-
-	// the walk stops outside (0, N), pt_bvh.cl:122
-	// a reference is the record's byte offset in the stream (pt_kernel.hpp, Cursor): record * 32 < 2^29 for N <= 2^24
-	auto refOf = [&]( long long node ) {
-		return ( node > 0 && node < (long long) N ) ? recordOf[(size_t) node] * 32 : -1;
-	};
-
-	if( numRecords * 32 >= ( (size_t) 1 << 31 ) ) {
-		return fail( ctx, PBR_EINVAL, "upload_scene: the node stream would exceed 2 GiB (record references are 31-bit byte offsets)" );
-	}
-
-	std::vector<float4> nodes( numRecords * 2, make_float4( 0.0f, 0.0f, 0.0f, 0.0f ) );
-
-	for( uint32_t i = 1; i < N; i++ ) {
-		const pbr_bvh_node& n = s->bvh[i];
-		int w0, w1;
-
-		if( face0s[i] < 0 ) {
-			w0 = refOf( (long long) i + 1 );
-			w1 = refOf( links[i] );
-		}
-		else {
-			w0 = (int) ( 0x80000000u | ( ( links[i] >= 0 ) ? 0x40000000u : 0u ) | (uint32_t) face0s[i] );
-			w1 = refOf( (long long) i + 1 );
-		}
-
-		auto boxWord = []( float x ) { return x; };
-		const size_t r = (size_t) recordOf[i];
-		nodes[r * 2 + 0] = make_float4( boxWord( n.bbMin.x ), boxWord( n.bbMin.y ), boxWord( n.bbMax.x ), boxWord( n.bbMax.y ) );
-		nodes[r * 2 + 1] = make_float4( boxWord( n.bbMin.z ), boxWord( n.bbMax.z ), __builtin_bit_cast( float, w0 ), __builtin_bit_cast( float, w1 ) );
-	}
-
-	// ---- faces: gather the corners; store a, b - a, c - a (what pt_intersect.cl:98-99 computes) ----
-	std::vector<float4> tris( (size_t) ( s->num_faces + 1 ) * 3, make_float4( 0.0f, 0.0f, 0.0f, 0.0f ) );   // + 1: testLeaf reads face + 1 ahead
-
-	for( uint32_t f = 0; f < s->num_faces; f++ ) {
-		const pbr_uint4& fv = s->facesV[f];
-
-		const pbr_float4& a = s->vertices[fv.x];
-		const pbr_float4& b = s->vertices[fv.y];
-		const pbr_float4& c = s->vertices[fv.z];
-		const float e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z;
-		const float e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;
-		const int material = (int) fv.w;
-
-		tris[(size_t) f * 3 + 0] = make_float4( a.x, a.y, a.z, e1x );
-		tris[(size_t) f * 3 + 1] = make_float4( e1y, e1z, e2x, e2y );
-		tris[(size_t) f * 3 + 2] = make_float4( e2z, __builtin_bit_cast( float, material ), 0.0f, 0.0f );
-	}
-
-	// ---- Phong tessellation input: the exact corners and their vertex normals, gathered per face ----
-	// (pt_intersect.cl:146-157 gathers them through facesV / facesN per test).  The default flat test never reads
-	// facesN, so scenes whose normal indices are unusable stay valid; they just cannot be configured with PHONGTESS.
-	std::vector<float4> triPN;
-	{
-		bool usable = ( s->facesN != nullptr && s->normals != nullptr && s->num_normals > 0 );
-
-		for( uint32_t f = 0; usable && f < s->num_faces; f++ ) {
-			const pbr_uint4& fn = s->facesN[f];
-			usable = ( fn.x < s->num_normals && fn.y < s->num_normals && fn.z < s->num_normals );
-		}
-
-		if( usable ) {
-			triPN.resize( (size_t) s->num_faces * 6 );
-
-			for( uint32_t f = 0; f < s->num_faces; f++ ) {
-				const pbr_uint4& fv = s->facesV[f];
-				const pbr_uint4& fn = s->facesN[f];
-				const uint32_t vi[3] = { fv.x, fv.y, fv.z }, ni[3] = { fn.x, fn.y, fn.z };
-
-				for( int k = 0; k < 3; k++ ) {
-					const pbr_float4& v = s->vertices[vi[k]];
-					const pbr_float4& n = s->normals[ni[k]];
-					triPN[(size_t) f * 6 + k] = make_float4( v.x, v.y, v.z, 0.0f );
-					triPN[(size_t) f * 6 + 3 + k] = make_float4( n.x, n.y, n.z, 0.0f );
-				}
-			}
-		}
-	}
-
-	// ---- materials: one 64-byte shape for both BRDFs ----
-	std::vector<float4> mats( (size_t) s->num_materials * 4 );
-
-	for( uint32_t i = 0; i < s->num_materials; i++ ) {
-		if( s->brdf == 0 ) {
-			const pbr_material_schlick& m = ( (const pbr_material_schlick*) s->materials )[i];
-			mats[(size_t) i * 4 + 0] = make_float4( m.data[0], m.data[1], m.data[2], m.data[3] );
-			mats[(size_t) i * 4 + 1] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
-			mats[(size_t) i * 4 + 2] = make_float4( m.rgbDiff.x, m.rgbDiff.y, m.rgbDiff.z, 0.0f );
-			mats[(size_t) i * 4 + 3] = make_float4( m.rgbSpec.x, m.rgbSpec.y, m.rgbSpec.z, 0.0f );
-		}
-		else {
-			const pbr_material_sa& m = ( (const pbr_material_sa*) s->materials )[i];
-			mats[(size_t) i * 4 + 0] = make_float4( m.data[0], m.data[1], m.data[2], m.data[3] );
-			mats[(size_t) i * 4 + 1] = make_float4( m.data[4], m.data[5], 0.0f, 0.0f );
-			mats[(size_t) i * 4 + 2] = make_float4( m.rgbDiff.x, m.rgbDiff.y, m.rgbDiff.z, 0.0f );
-			mats[(size_t) i * 4 + 3] = make_float4( m.rgbSpec.x, m.rgbSpec.y, m.rgbSpec.z, 0.0f );
-		}
-	}
-
-	const uint32_t lightSlots = ( s->num_lights > 0 ) ? s->num_lights : 1;
-	std::vector<float4> lights( (size_t) lightSlots * 3, make_float4( 0.0f, 0.0f, 0.0f, 0.0f ) );
-
-	for( uint32_t i = 0; i < s->num_lights; i++ ) {
-		const pbr_light& l = s->lights[i];
-		lights[(size_t) i * 3 + 0] = make_float4( l.pos.x, l.pos.y, l.pos.z, l.pos.w );
-		lights[(size_t) i * 3 + 1] = make_float4( l.rgb.x, l.rgb.y, l.rgb.z, l.rgb.w );
-		lights[(size_t) i * 3 + 2] = make_float4( l.data.x, l.data.y, l.data.z, l.data.w );
+	if( ctx->configured ) {
+		PBR_TRY( packConfiguredWalk( ctx, ctx->cfg, &tree, &walk ) );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeScene( ctx );
 
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodes, sizeof( float4 ) * nodes.size() ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTris, sizeof( float4 ) * tris.size() ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dMats, sizeof( float4 ) * mats.size() ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dLights, sizeof( float4 ) * lights.size() ) );
-	HIP_TRY( ctx, hipMemcpy( ctx->dNodes, nodes.data(), sizeof( float4 ) * nodes.size(), hipMemcpyHostToDevice ) );
-	ctx->nodeBytes = sizeof( float4 ) * nodes.size();
-	ctx->triBytes = sizeof( float4 ) * tris.size();
-	ctx->walkBytes = 0;
+	auto toDevice = [ctx]( float4** dst, const std::vector<Quad>& src ) {
+		HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( Quad ) * src.size() ) );
+		HIP_TRY( ctx, hipMemcpy( *dst, src.data(), sizeof( Quad ) * src.size(), hipMemcpyHostToDevice ) );
+		return PBR_OK;
+	};
 
-	HIP_TRY( ctx, hipMemcpy( ctx->dTris, tris.data(), sizeof( float4 ) * tris.size(), hipMemcpyHostToDevice ) );
+	PBR_TRY( toDevice( &ctx->dNodes, packed.nodes.storage ) );
+	PBR_TRY( toDevice( &ctx->dTris, packed.tris ) );
 
-	if( !triPN.empty() ) {
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTriPN, sizeof( float4 ) * triPN.size() ) );
-		HIP_TRY( ctx, hipMemcpy( ctx->dTriPN, triPN.data(), sizeof( float4 ) * triPN.size(), hipMemcpyHostToDevice ) );
+	if( !packed.triPN.empty() ) {
+		PBR_TRY( toDevice( &ctx->dTriPN, packed.triPN ) );
 	}
-	HIP_TRY( ctx, hipMemcpy( ctx->dMats, mats.data(), sizeof( float4 ) * mats.size(), hipMemcpyHostToDevice ) );
-	HIP_TRY( ctx, hipMemcpy( ctx->dLights, lights.data(), sizeof( float4 ) * lights.size(), hipMemcpyHostToDevice ) );
+
+	PBR_TRY( toDevice( &ctx->dMats, packed.mats ) );
+	PBR_TRY( toDevice( &ctx->dLights, packed.lights ) );
+	ctx->nodeBytes = sizeof( Quad ) * packed.nodes.storage.size();
+	ctx->triBytes = sizeof( Quad ) * packed.tris.size();
 
 	// the face normals the shading would recompute on every hit, evaluated once by the shading's own device function
-	{
-		if( s->num_faces > 0 && ctx->knobs.faceNormals != 0 ) {
-			HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFaceN, sizeof( float4 ) * s->num_faces ) );
-			DevParams P;
-			std::memset( &P, 0, sizeof( P ) );
-			P.tris = ctx->dTris;
-			hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( s->num_faces + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->dFaceN, (int) s->num_faces );
-			HIP_TRY( ctx, hipGetLastError() );
-		}
-
-		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	if( s->num_faces > 0 && ctx->knobs.faceNormals != 0 ) {
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFaceN, sizeof( float4 ) * s->num_faces ) );
+		DevParams P;
+		std::memset( &P, 0, sizeof( P ) );
+		P.tris = ctx->dTris;
+		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( s->num_faces + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->dFaceN, (int) s->num_faces );
+		HIP_TRY( ctx, hipGetLastError() );
 	}
 
-	ctx->numHotAvail = numHot;
-	ctx->firstRef = recordOf[1] * 32;
-	ctx->hostNodes.assign( s->bvh, s->bvh + N );
-	ctx->hostFace0s.swap( face0s );
-	ctx->hostLinks.swap( links );
-	ctx->hostRanked.assign( ranked.begin(), ranked.begin() + numHot );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	ctx->numHotAvail = packed.nodes.hotSlots;
+	ctx->firstRef = packed.nodes.first[0];
+	ctx->tree = std::move( tree );
 	ctx->numNodes = s->num_nodes;
 	ctx->numFaces = s->num_faces;
 	ctx->numMaterials = s->num_materials;
@@ -1777,7 +1222,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	replan( ctx );   // a new scene / configuration is tuned afresh
 	ctx->hasScene = true;
 
-	return prepareWalk( ctx );   // a context that is already configured for a ray-ordered walk: its streams, now
+	return walk.storage.empty() ? PBR_OK : uploadWalkStreams( ctx, walk, ctx->cfg.traversal );
 }
 
 int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
@@ -1805,6 +1250,10 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( cfg->tile_world == 0 || cfg->tile_rank >= cfg->tile_world ) {
 		return fail( ctx, PBR_EINVAL, "tile_rank must be < tile_world, tile_world >= 1" );
 	}
+
+	// the records of the configured walk for the scene there is, unless they are there already: packed before anything changes
+	PackedWalk walk;
+	PBR_TRY( packConfiguredWalk( ctx, *cfg, ( ctx->hasScene && ctx->walkBuilt != cfg->traversal ) ? &ctx->tree : nullptr, &walk ) );
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeImages( ctx );
@@ -1842,7 +1291,14 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	replan( ctx );   // a new scene / configuration is tuned afresh
 	ctx->configured = true;
 
-	return prepareWalk( ctx );
+	if( !walk.storage.empty() ) {
+		return uploadWalkStreams( ctx, walk, cfg->traversal );
+	}
+	if( ctx->walkBuilt != cfg->traversal ) {
+		freeWalkStreams( ctx );   // the records of a traversal that is no longer configured
+	}
+
+	return PBR_OK;
 }
 
 int pbr_write_input( pbr_ctx* ctx, const float* rgba ) {

@@ -836,8 +836,8 @@ PT_DEV NodeLinks decodeNode( const float4 n1 ) {
 	return n;
 }
 
-// Which of the successor sets a ray walks (pbr_config.traversal; the statement both ends follow is in pbr_upload's
-// buildWalkStreams and in the oracle's "Ray-ordered walk").  Scheme 1: 2 * dominant axis (x before y before z on ties)
+// Which of the successor sets a ray walks (pbr_config.traversal; the statement both ends follow is in pt_scene_pack.hpp's
+// walkTables and in the oracle's "Ray-ordered walk").  Scheme 1: 2 * dominant axis (x before y before z on ties)
 // + ( dir[axis] < 0 ).  Scheme 2: the sign bits x | y << 1 | z << 2.
 PT_DEV int walkOrderOf( int scheme, const f3 d ) {
 	// both formulas, then a select on the (wave-uniform) scheme: as a branch around one of them this cost the 80-register

@@ -227,6 +227,38 @@ def test_a_modes_streams_live_and_die_with_its_configuration(pbr, device):
     assert device.scene_bytes()["walk_streams"] == 2 * nodes + 32
 
 
+def test_a_call_the_walk_refuses_leaves_the_context_as_it_was(pbr, oracle, device):
+    """a scene or a mode whose ray-ordered walk cannot be built is refused before the call changes anything, so
+    the old scene, or the old configuration, still renders."""
+    from test_scene_pack_cpu import NOT_NESTED, hand_tree
+    sc = make_scene(pbr, **{"render.max_depth": 3})
+    bad, keep = hand_tree(pbr, NOT_NESTED)          # the reference order walks it, no ordered walk does
+    w, h = 32, 24
+    cfg, cam, px, seeds = sc.config(w, h), sc.camera(), pbr.pixel_dimension(w, h), pbr.frame_seeds(0, 2)
+    walked = pbr.Config.from_buffer_copy(cfg)
+    walked.traversal = 1
+
+    def renders(desc, c):
+        device.reset_accum()
+        device.render(0, seeds, px, cam)
+        got, want = device.read_output(), oracle.Renderer(desc, c, threads=8).render(0, seeds, px, cam)
+        assert same_values(got, want), describe_mismatch(got, want)
+
+    device.upload_scene(sc.desc)
+    device.configure(cfg)
+    renders(sc.desc, cfg)
+    device.configure(walked)
+    with pytest.raises(pbr.PbrError, match="does not visit every node once"):
+        device.upload_scene(bad)
+    renders(sc.desc, walked)                         # the old scene
+    device.configure(cfg)
+    device.upload_scene(bad)
+    renders(bad, cfg)
+    with pytest.raises(pbr.PbrError, match="does not visit every node once"):
+        device.configure(walked)
+    renders(bad, cfg)                                # the old configuration
+
+
 def test_the_device_builder_says_which_radius_it_used(pbr, device):
     """pbr_build_bvh clusters with radius 3 for a tree that will be walked in ray order and 32 for the reference's
     walk — by the traversal the context is configured with AT THE TIME OF THE CALL; pbr_diag_bvh_build_info shows which."""
