@@ -6,6 +6,11 @@
  * sampling — so the parity tests can compare each stage with the oracle's hook of the same
  * shape (oracle/pt_oracle.h: orc_math, orc_trace_rays, orc_brdf_eval, orc_new_ray) instead of
  * only whole images.  Host pointers in, host pointers out; synchronous.
+ *
+ * pbr_diag_math, pbr_diag_brdf and pbr_diag_new_ray compute in the arithmetic of the context's last successful
+ * pbr_configure: the native one (v_sin / v_rcp / v_log / ... , csrc/pt_math.hpp) when it set arith = PBR_ARITH_NATIVE,
+ * the exact one — the oracle's definitions, bit for bit — with no configuration or arith = exact.  A library built
+ * without the native diagnostics answers PBR_ESTATE in the native case.
  */
 #ifndef PBR_HIP_DIAG_H
 #define PBR_HIP_DIAG_H

@@ -169,6 +169,10 @@ def hip_commands(target, guard=False, objdir=None):
         obj = os.path.join(objdir, "inst_f%d_g%d.o" % (f, g))
         objects.append(obj)
         compiles.append(common + (NATIVE_FLAGS if f & 2 else []) + ["-DPT_FLAVOUR=%d" % f, "-DPT_GROUP=%d" % g, "-c", os.path.join(CSRC, "pt_instance.hip"), "-o", obj])
+    # the stage diagnostics once more in the native arithmetic (csrc/pt_diag_native.hip): pbr_diag_* of a context configured
+    # with arith = native
+    objects.append(os.path.join(objdir, "diag_f2.o"))
+    compiles.append(common + NATIVE_FLAGS + ["-DPT_FLAVOUR=2", "-c", os.path.join(CSRC, "pt_diag_native.hip"), "-o", objects[-1]])
     link = [_hipcc(), "--offload-arch=gfx950:xnack-", "-shared", "-fPIC", *objects, "-o"]
     return compiles, link, objdir
 

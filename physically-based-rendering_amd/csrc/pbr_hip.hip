@@ -1866,9 +1866,38 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 	return PBR_OK;
 }
 
+// The stage diagnostics in the native arithmetic (pt_diag_native.hip); null where that unit was not linked in (lab builds
+// without flavour 2).
+extern "C" const void* pt_diag_native_pick( int stage, uint32_t brdf ) __attribute__( ( weak ) );
+
+namespace {
+
+typedef void ( *DiagMathFn )( int, const float*, const float*, int, float* );
+typedef void ( *DiagItemFn )( const ptk::DevParams, const float*, int, float* );
+
+// The kernel of a diagnostic stage (0 math, 1 BRDF, 2 new ray) in the arithmetic of the configuration in force: the native
+// flavour's after a successful pbr_configure with arith = PBR_ARITH_NATIVE, else (no configuration, or arith = exact) the
+// exact one of this translation unit.  Null: the native unit is not linked in.
+const void* diagKernel( const pbr_ctx* ctx, int stage, uint32_t brdf ) {
+	if( ctx->configured && ctx->cfg.arith != 0 ) {
+		return ( pt_diag_native_pick != nullptr ) ? pt_diag_native_pick( stage, brdf ) : nullptr;
+	}
+	switch( stage ) {
+		case 0: return (const void*) ptk::diagMath;
+		case 1: return ( brdf == 0 ) ? (const void*) ptk::diagBrdf<0> : (const void*) ptk::diagBrdf<1>;
+		default: return ( brdf == 0 ) ? (const void*) ptk::diagNewRay<0> : (const void*) ptk::diagNewRay<1>;
+	}
+}
+
+}  // namespace
+
 int pbr_diag_math( pbr_ctx* ctx, int op, const float* x, const float* y, int n, float* out ) {
 	if( ctx == nullptr || ctx->stream == nullptr || x == nullptr || out == nullptr || n <= 0 ) {
 		return fail( ctx, PBR_EINVAL, "diag_math: bad argument" );
+	}
+	const DiagMathFn kernel = (DiagMathFn) diagKernel( ctx, 0, 0u );
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag_math: this library was built without the native-arithmetic diagnostics" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
@@ -1879,7 +1908,7 @@ int pbr_diag_math( pbr_ctx* ctx, int op, const float* x, const float* y, int n, 
 	HIP_TRY( ctx, dout.alloc( bytes ) );
 	HIP_TRY( ctx, hipMemcpy( dx.p, x, bytes, hipMemcpyHostToDevice ) );
 	HIP_TRY( ctx, hipMemcpy( dy.p, ( y != nullptr ) ? y : x, bytes, hipMemcpyHostToDevice ) );
-	hipLaunchKernelGGL( ptk::diagMath, dim3( (unsigned) ( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream,
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream,
 		op, (const float*) dx.p, (const float*) dy.p, n, (float*) dout.p );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
@@ -1935,6 +1964,10 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	if( in == nullptr || out == nullptr || n <= 0 ) {
 		return fail( ctx, PBR_EINVAL, "diag: bad argument" );
 	}
+	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, newRay ? 2 : 1, ctx->sceneBrdf );
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag: this library was built without the native-arithmetic diagnostics" );
+	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	DevBuf dIn, dOut;
@@ -1946,22 +1979,7 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
-	if( newRay ) {
-		if( ctx->sceneBrdf == 0 ) {
-			hipLaunchKernelGGL( ptk::diagNewRay<0>, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
-		}
-		else {
-			hipLaunchKernelGGL( ptk::diagNewRay<1>, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
-		}
-	}
-	else {
-		if( ctx->sceneBrdf == 0 ) {
-			hipLaunchKernelGGL( ptk::diagBrdf<0>, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
-		}
-		else {
-			hipLaunchKernelGGL( ptk::diagBrdf<1>, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
-		}
-	}
+	hipLaunchKernelGGL( kernel, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
 
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "pt_kernel.hpp"
+#include "pt_diag.hpp"
 
 namespace ptk {
 
@@ -173,28 +174,8 @@ __global__ void scatterGathered( const float4* all, float4* tiles, int numTiles,
 
 // ---------------------------------------------------------------------------------------
 // Diagnostic kernels (include/pbr_hip_diag.h): one thread per item, for stage-by-stage parity
+// (diagMath, diagBrdf and diagNewRay: pt_diag.hpp)
 // ---------------------------------------------------------------------------------------
-
-__global__ void diagMath( int op, const float* x, const float* y, int n, float* out ) {
-	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
-
-	if( i >= n ) {
-		return;
-	}
-
-	float s, c;
-
-	switch( op ) {
-		case 0: sincos( x[i], &s, &c ); out[i] = s; break;
-		case 1: sincos( x[i], &s, &c ); out[i] = c; break;
-		case 2: out[i] = tan1( x[i] ); break;
-		case 3: out[i] = acos1( x[i] ); break;
-		case 4: out[i] = atan1( x[i] ); break;
-		case 5: out[i] = pow1( x[i], y[i] ); break;
-		case 6: out[i] = fract( sin1( x[i] ) * 43758.5453123f ); break;
-		default: out[i] = 0.0f; break;
-	}
-}
 
 // rays: n x {origin, dir}; outputs as orc_trace_rays
 template<bool LIGHTS>
@@ -303,59 +284,6 @@ __global__ __launch_bounds__( 256 ) void diagCalibrate( const float4* table, uns
 	if( acc == 123456.789f ) {
 		sink[0] = acc;   // never true for the zero-filled table; keeps the loads alive
 	}
-}
-
-// in: n x 16 {out_dir, in_dir, normal, pad}; out: n x 4 (as orc_brdf_eval); material 0 of P.mats
-template<int BRDF>
-__global__ void diagBrdf( const DevParams P, const float* in, int n, float* out ) {
-	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
-
-	if( i >= n ) {
-		return;
-	}
-
-	const float* p = in + (size_t) i * 16;
-	const Material mtl = loadMaterial( P, 0 );
-	const f3 outDir = mk3( p[0], p[1], p[2] );
-	const f3 inDir = mk3( p[3], p[4], p[5] );
-	const f3 normal = mk3( p[6], p[7], p[8] );
-	float* o = out + (size_t) i * 4;
-
-	if( BRDF == 0 ) {
-		float u, pdf;
-		const float b = brdfSchlick( mtl, outDir, inDir, normal, &u, &pdf );
-		o[0] = b; o[1] = u; o[2] = pdf; o[3] = 0.0f;
-	}
-	else {
-		float spec, diff, dotHK1, pdf;
-		brdfSA( mtl, outDir, inDir, normal, &spec, &diff, &dotHK1, &pdf );
-		o[0] = spec; o[1] = diff; o[2] = dotHK1; o[3] = pdf;
-	}
-}
-
-// in: n x 12 {origin, dir, normal, t, seed, pad}; out: n x 8 (as orc_new_ray); material 0
-template<int BRDF>
-__global__ void diagNewRay( const DevParams P, const float* in, int n, float* out ) {
-	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
-
-	if( i >= n ) {
-		return;
-	}
-
-	const float* p = in + (size_t) i * 12;
-	const Material mtl = loadMaterial( P, 0 );
-	const f3 origin = mk3( p[0], p[1], p[2] );
-	const f3 dir = mk3( p[3], p[4], p[5] );
-	const f3 normal = mk3( p[6], p[7], p[8] );
-	float seed = p[10];
-	bool addDepth = false;
-	const f3 newOrigin = fma3( p[9], dir, origin );
-	const f3 newDir = newRayDir<BRDF>( dir, normal, mtl, seed, addDepth );
-	float* o = out + (size_t) i * 8;
-	o[0] = newOrigin.x; o[1] = newOrigin.y; o[2] = newOrigin.z;
-	o[3] = newDir.x; o[4] = newDir.y; o[5] = newDir.z;
-	o[6] = seed;
-	o[7] = addDepth ? 1.0f : 0.0f;
 }
 
 }  // namespace ptk

@@ -269,8 +269,12 @@ PT_DEV float pow1( float x, float y ) {
 	}
 
 #if PT_ARITH_NATIVE
-	// v_log_f32 / v_exp_f32 ( log2( 0 ) = -inf, exp2( -inf ) = 0, log2( inf ) = inf )
-	return sign * __builtin_amdgcn_exp2f( y * __builtin_amdgcn_logf( ax ) );
+	// v_log_f32 / v_exp_f32 ( log2( 0 ) = -inf, exp2( -inf ) = 0, log2( inf ) = inf ).  v_log_f32 does not take a subnormal
+	// input (pow( 1.1e-38, 0.001 ) came out 1e24 instead of 0.92): such a base is moved 2^32 up into the normal range first
+	// and the 32 taken off its logarithm.  v_exp_f32 flushes a subnormal result to 0.
+	const bool subnormal = ax < 0x1p-126f;
+	const float lg = __builtin_amdgcn_logf( subnormal ? ax * 0x1p32f : ax ) - ( subnormal ? 32.0f : 0.0f );
+	return sign * __builtin_amdgcn_exp2f( y * lg );
 #endif
 	double l;
 

@@ -1,0 +1,212 @@
+"""The HIP kernels' math layer, BRDF evaluation and new-ray sampling (pbr_diag_math / pbr_diag_brdf / pbr_diag_new_ray)
+against float64, with no oracle in the loop, in both arithmetics.
+
+Exact arithmetic: the random batches, the edge set and the threshold seeds of test_shading_ref_cpu.py against the
+float64 restatement of the reference's formulas (tests/shading_ref.py), at the same error bounds (K_EXACT).
+
+Native arithmetic (pbr_config.arith = PBR_ARITH_NATIVE: the diagnostics follow the context's configuration): the math
+ops against numpy float64, and the same shading cases at native bounds, with one hard invariant — no NaN or Inf where
+the float64 reference is finite and its sensitivity bounded.  The draws are always the device's own (pbr_diag_math
+"randhash" in the arithmetic under test); the threshold seeds are found in the exact hash on the host.
+
+The native bounds were fixed before the first GPU run, from what the instructions are documented to deliver (the ISA
+guides give v_rcp_f32, v_sqrt_f32, v_rsq_f32, v_log_f32 and v_exp_f32 as about 1 ulp and do not bound v_sin_f32 /
+v_cos_f32 beyond "approximate"; 2^-19 absolute is assumed for those, on an input reduced to [0, 1) turns):
+  sin, cos   |err| <= |x| 2^-23 + 2^-19      (x * 1/(2 pi) rounded twice in binary32, ulp of the turns, + the instruction)
+  tan        |err| <= 2 E / cos^2 + 2^-22 |tan|, E the sin / cos bound   (sin * v_rcp( cos ))
+  pow        |err| <= |ref| ( ln2 ( |y| 2^-21 + |y log2 x| 2^-22 ) + 2^-21 ) + 2^-126   (v_exp( y * v_log( x ) ); a
+             subnormal result may be flushed)
+  shading    K_NATIVE = 32 K_EXACT: v_sin / v_cos at 2^-19 are 32 roundings of a result near 1, the worst native
+             operation against the one rounding per operation K_EXACT is a multiple of; the median ratio and the share
+             of ambiguous samples of a random batch scale with it.  The reference's rounding trials let a subnormal
+             intermediate flush to 0, as v_exp_f32's results do.
+One bound was set after the first GPU run, and says so: the randhash histogram (test_native_randhash_range_and_histogram)."""
+import numpy as np
+import pytest
+
+from test_gpu_parity import make_scene, single_material_desc
+from test_shading_ref_cpu import (AMBIGUOUS_MAX, K_EXACT, MEDIAN_MAX, Stages, run_edges, run_random,
+                                  run_threshold_seeds)
+
+NATIVE_SCALE = 32
+K_NATIVE = NATIVE_SCALE * K_EXACT
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture()
+def device(pbr, gpu_device):
+    dev = pbr.Device(gpu_device)
+    yield dev
+    dev.close()
+
+
+def configure(pbr, dev, brdf, arith, mtl=None):
+    """Upload a one-material scene (material 0 is what the diag kernels read) and configure the arithmetic."""
+    sc = make_scene(pbr, **{"render.brdf": brdf})
+    desc, keep = single_material_desc(pbr, sc, brdf, mtl if mtl is not None else [1, 1.5, 1, 0.5] + [0.5] * 12)
+    dev.upload_scene(desc)
+    cfg = sc.config(64, 64)
+    cfg.arith = arith
+    dev.configure(cfg)
+    return sc, desc, keep
+
+
+def device_stages(pbr, dev, arith=0):
+    """The device as the stage under test, in the arithmetic `arith`."""
+    state = {"key": None}
+
+    def use(brdf, mtl):
+        key = (brdf, mtl.tobytes())
+        if state["key"] != key:
+            state["key"], state["keep"] = key, configure(pbr, dev, brdf, arith, mtl)
+
+    def brdf_fn(brdf, mtl, ev):
+        use(brdf, mtl)
+        return dev.diag_brdf(ev)
+
+    def ray_fn(brdf, mtl, nr):
+        use(brdf, mtl)
+        return dev.diag_new_ray(nr)
+
+    def randhash(x):                      # called after brdf_fn / ray_fn: the context is configured by then
+        return dev.diag_math("randhash", x)
+
+    if arith == 0:
+        return Stages(brdf_fn, ray_fn, randhash)
+    return Stages(brdf_fn, ray_fn, randhash, NATIVE_SCALE * MEDIAN_MAX, NATIVE_SCALE * AMBIGUOUS_MAX, flush=True)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_random_batches_match_float64(pbr, device, brdf):
+    stats = run_random(device_stages(pbr, device), brdf, K_EXACT, seed=1)
+    print("brdf %d: median error / bound per material (eval, new ray): %s" % (brdf, [(round(a, 3), round(b, 3)) for a, b in stats]))
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_edge_set_matches_float64(pbr, device, brdf):
+    run_edges(device_stages(pbr, device), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_threshold_draws_match_float64(pbr, oracle, device, brdf):
+    run_threshold_seeds(device_stages(pbr, device), brdf, K_EXACT, lambda x: oracle.math("randhash", x))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# native arithmetic
+# ---------------------------------------------------------------------------------------------------------------------
+
+def native_device(pbr, dev):
+    configure(pbr, dev, 1, 1)
+    return dev
+
+
+def report(op, err, bound, x, y=None):
+    """Print the measured maximum error and its ratio to the bound (and where); return that largest ratio."""
+    k = int(np.argmax(err / bound))
+    at = "x = %r" % float(x[k]) if y is None else "x = %r, y = %r" % (float(x[k]), float(y[k]))
+    print("native %s: max |err| %.3g, max |err| / bound %.3g at %s" % (op, float(err.max()), float((err / bound)[k]), at))
+    return float((err / bound)[k])
+
+
+def test_diagnostics_follow_the_configured_arithmetic(pbr, oracle, device):
+    """No configuration and arith = exact: the oracle's bits.  arith = native: something else."""
+    x = np.random.default_rng(3).uniform(-1e4, 1e4, 1 << 16).astype(np.float32)
+    want = oracle.math("sin", x)
+    assert np.array_equal(device.diag_math("sin", x), want)
+    configure(pbr, device, 1, 1)
+    assert not np.array_equal(device.diag_math("sin", x), want)
+    configure(pbr, device, 1, 0)
+    assert np.array_equal(device.diag_math("sin", x), want)
+
+
+def test_native_sin_cos_against_float64(pbr, device):
+    dev = native_device(pbr, device)
+    rng = np.random.default_rng(41)
+    x = np.concatenate([rng.uniform(-1e4, 1e4, 1 << 20), rng.uniform(-8, 8, 1 << 18),
+                        [0, -0.0, 1e4, -1e4, np.pi / 2, np.pi, 2 * np.pi, 1e-30]]).astype(np.float32)
+    x64 = x.astype(np.float64)
+    bound = np.abs(x64) * 2.0 ** -23 + 2.0 ** -19
+    for op, f in (("sin", np.sin), ("cos", np.cos)):
+        got = dev.diag_math(op, x).astype(np.float64)
+        assert np.isfinite(got).all(), op
+        assert report(op, np.abs(got - f(x64)), bound, x) <= 1.0
+
+
+def test_native_tan_against_float64(pbr, device):
+    dev = native_device(pbr, device)
+    rng = np.random.default_rng(42)
+    top = np.float32(np.pi / 2)
+    if float(top) >= np.pi / 2:
+        top = np.nextafter(top, np.float32(0))
+    near = (top.view(np.uint32) - np.arange(64, dtype=np.uint32)).view(np.float32)
+    x = np.concatenate([rng.uniform(0, np.pi / 2, 1 << 20).astype(np.float32), near, np.float32([0, 1e-30, 0.7853982])])
+    x = x[x < np.pi / 2]
+    x64 = x.astype(np.float64)
+    got = dev.diag_math("tan", x).astype(np.float64)
+    assert np.isfinite(got).all()
+    e = np.abs(x64) * 2.0 ** -23 + 2.0 ** -19
+    c = np.cos(x64)
+    bound = 2 * e / (c * c) + 2.0 ** -22 * np.abs(np.tan(x64))
+    assert report("tan", np.abs(got - np.tan(x64)), bound, x) <= 1.0
+
+
+def test_native_pow_against_float64(pbr, device):
+    """pow on the BRDFs' domain: bases in [0, 1] and a little above, subnormal and zero bases, exponents up to 1e5."""
+    dev = native_device(pbr, device)
+    rng = np.random.default_rng(43)
+    n = 1 << 20
+    base = np.concatenate([rng.uniform(0, 1, n), rng.uniform(0.999, 1, n // 4), rng.uniform(1, 30, n // 8),
+                           (rng.integers(1, 1 << 23, n // 8).astype(np.uint32)).view(np.float32), np.zeros(1024)]).astype(np.float32)
+    expo = (10 ** rng.uniform(-3, 5, base.size)).astype(np.float32)
+    expo[: 64] = 1e5
+    above = base > 1
+    expo[above] = rng.uniform(0, 20, int(above.sum())).astype(np.float32)   # no overflow: the BRDFs' bases are <= 1
+    x64, y64 = base.astype(np.float64), expo.astype(np.float64)
+    got = dev.diag_math("pow", base, expo).astype(np.float64)
+    ref = np.power(x64, y64)
+    assert np.isfinite(got).all()
+    with np.errstate(divide="ignore"):
+        t = np.where(x64 > 0, y64 * np.log2(np.where(x64 > 0, x64, 1.0)), 0.0)
+    bound = ref * (np.log(2) * (y64 * 2.0 ** -21 + np.abs(t) * 2.0 ** -22) + 2.0 ** -21) + 2.0 ** -126
+    assert report("pow", np.abs(got - ref), bound, base, expo) <= 1.0
+
+
+def test_native_randhash_range_and_histogram(pbr, oracle, device):
+    """Every draw in [0, 1); over 2^22 seeds from the range seeds reach (|s| <= 1e4) a 16-bin histogram that is flat.
+
+    FINDING, and a bound set after the first GPU run: the native hash is NOT flat to 1 %.  Its largest bin is 5.19 % off
+    the mean over these seeds (the exact hash: 0.79 %, held here to 1 %): fract( v_sin( s ) * 43758.5453 ) magnifies the
+    instruction's error 4.4e4 times, and what it leaves is not uniform.  That is the arithmetic the reference asks for
+    (native_sin, pt_utils.cl:43) on this hardware, so it is recorded, not changed; 8 % holds it where it was measured."""
+    dev = native_device(pbr, device)
+    s = np.random.default_rng(44).uniform(0, 1e4, 1 << 22).astype(np.float32)
+    h = dev.diag_math("randhash", s)
+    assert ((h >= 0) & (h < 1)).all()
+
+    def spread(v):
+        counts = np.histogram(v, bins=16, range=(0.0, 1.0))[0]
+        return np.abs(counts / (s.size / 16.0) - 1.0), counts
+
+    flat, counts = spread(h)
+    flat_exact, _ = spread(oracle.math("randhash", s))
+    print("native randhash: largest bin deviation %.4f (exact hash %.4f); bins %s" % (flat.max(), flat_exact.max(), counts.tolist()))
+    assert flat_exact.max() <= 0.01
+    assert flat.max() <= 0.08
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_random_batches_match_float64(pbr, device, brdf):
+    stats = run_random(device_stages(pbr, device, 1), brdf, K_NATIVE, seed=2)
+    print("native brdf %d: median error / bound per material (eval, new ray): %s" % (brdf, [(round(a, 3), round(b, 3)) for a, b in stats]))
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_edge_set_matches_float64(pbr, device, brdf):
+    run_edges(device_stages(pbr, device, 1), brdf, K_NATIVE)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_threshold_draws_match_float64(pbr, oracle, device, brdf):
+    run_threshold_seeds(device_stages(pbr, device, 1), brdf, K_NATIVE, lambda x: oracle.math("randhash", x))
