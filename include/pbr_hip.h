@@ -31,10 +31,10 @@ extern "C" {
 #endif
 
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
- * entry point changes (round 5 grew pbr_config from 60 to 68 bytes).  A caller that loads the library at run time — or
+ * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 6
+#define PBR_ABI_VERSION 7
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -191,6 +191,18 @@ int pbr_accumulate( pbr_ctx* ctx );
  * left in imageOut AND imageIn (ready to continue). */
 int pbr_render( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, const float* seeds, float pxDim, const pbr_camera* cam );
 
+/* pbr_render for a camera WITH a focus point (cam->focusPoint >= 0; without one it is pbr_render): bit-identical to
+ * n_frames x { pbr_render_frame ; pbr_accumulate } with pixelWeight = n/(n+1), .w included, result in imageOut AND imageIn.
+ * What frame k reads of frame k - 1 — the first-hit distance of its own pixel and of the focus pixel — is a chain of
+ * camera-ray first hits per pixel; a pre-pass (the focus chain, csrc/pt_chain.hpp) walks it for every local pixel and every
+ * frame of a launch, and the frames then go through pbr_render's launch: same tuner, plans, dealing orders and chunking.
+ * The pre-pass is not counted (pbr_get_counters, the debug image); pbr_last_kernel_ms includes it.
+ * With tile sharding the focus pixel's distance is handed over ONCE PER CALL (pbr_get_focus_depth / pbr_set_focus_depth
+ * below; PBR_EINVAL without it): every rank walks the focus pixel's chain itself from there.
+ * Phong tessellation (phong_tessellation > 0) with a focus point is refused with PBR_EINVAL: render it with
+ * pbr_render_frame + pbr_accumulate per frame. */
+int pbr_render_dof( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, const float* seeds, float pxDim, const pbr_camera* cam );
+
 /* CL::readImageOutput( imageOut ) / ( imageDebug ) (PathTracer.cpp:66-67).  With tile sharding
  * only this rank's tiles are meaningful (others read 0). */
 int pbr_read_output( pbr_ctx* ctx, float* rgba );
@@ -243,7 +255,8 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
  * pixel's tile lives on one rank only.  Per frame: every rank calls pbr_get_focus_depth( x, y ); the rank with
  * *owned = 1 broadcasts *t (one float: ncclBroadcast / MPI_Bcast); every rank passes it to pbr_set_focus_depth and
  * then calls pbr_render_frame with the same camera.  The value is consumed by that frame.  With tile_world = 1 none of
- * this is needed (the kernel reads the pixel itself). */
+ * this is needed (the kernel reads the pixel itself).  pbr_render_dof needs the same hand-over once per call, whatever
+ * its number of frames; the value is consumed by that call. */
 int pbr_get_focus_depth( pbr_ctx* ctx, int x, int y, float* t, int* owned );
 int pbr_set_focus_depth( pbr_ctx* ctx, float t );
 

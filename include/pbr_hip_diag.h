@@ -79,11 +79,12 @@ int pbr_diag_launch_fit( pbr_ctx* ctx, double* fixed_ms, double* per_frame_ms );
  *   "drain_mode"    bit 0 / 1: scale ph_park / ph_shade with the lanes still at work once the queue is empty
  *   "refill_batch"  lock-step kernels: lanes of a wave that wait with a finished unit before they take their next units
  *                   together (1 = every lane at once, as up to round 2)
- *   "chunk_frames"  cap of the frames per launch pair of pbr_render (tests: several launch pairs)
+ *   "chunk_frames"  cap of the frames per launch pair of pbr_render / pbr_render_dof (tests: several launch pairs)
  *   "face_normals"  0 = recompute the face normal on every hit (takes effect at the next pbr_upload_scene)
  *   "bvh_builder"   pbr_build_bvh: 0 clustering (default), 1 round 1's radix tree; "ploc_radius": its search radius
  *   "tune_log"      1 = the schedule tuner logs its launches to stderr
  *   "deal_order"    the queue's dealing order: 0 always spatial, 1 always cost classes, 2 always expensive last (once learnt), -1 by the render call's size
+ *   "chain_layout"  the focus chain's table (pbr_render_dof): 0 frame-major planes (default), 1 a pixel slot's frames side by side
  * Setting a knob rebuilds the plans and restarts the schedule tuner. */
 int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value );
 
@@ -125,6 +126,10 @@ int pbr_diag_tune_budget( pbr_ctx* ctx, uint32_t* frames );
  * and their number.  A multi-frame render is one launch unless its per-frame result buffer would
  * exceed 16 GiB; pbr_last_kernel_ms covers the whole render, foldFrames launches included. */
 int pbr_diag_last_trace( pbr_ctx* ctx, double* trace_ms, uint32_t* launches );
+
+/* The focus chain of the last render (pbr_render_dof with a focus point: the pre-pass ahead of every path-tracing launch,
+ * csrc/pt_chain.hpp): its summed duration, 0 for every other render.  pbr_diag_last_trace keeps meaning the path launches. */
+int pbr_diag_last_focus_chain( pbr_ctx* ctx, double* ms );
 
 /* All 16 device counter slots: [0..3] = pbr_counters; [4..15] are written only by experiment
  * builds (-DPBR_LAB_HOOKS, lab/src/pt_lab_hooks.hpp) and stay 0 otherwise. */

@@ -55,7 +55,8 @@ int pbr_multi_tune( pbr_multi* m, uint32_t frames_per_call, float pxDim, const p
 
 /* pbr_render on every context at the same time (each its own tiles, all n_frames), then the all-gather: afterwards every
  * device holds the full frame (pbr_multi_read_full).  `gather` = 0 leaves the exchange out (a caller that accumulates
- * several renders before it looks at the frame: pbr_multi_gather). */
+ * several renders before it looks at the frame: pbr_multi_gather).  With a focus point set (cam->focusPoint >= 0) the
+ * owner of the focus pixel's tile hands its distance to every context ONCE, then pbr_render_dof runs everywhere. */
 int pbr_multi_render( pbr_multi* m, uint32_t first_sample_count, uint32_t n_frames, const float* seeds, float pxDim, const pbr_camera* cam, int gather );
 /* The reference's per-frame sequence (PathTracer.cpp:59-71) on N devices: with a focus point set, the owner of the focus
  * pixel's tile hands its previous-frame distance to every context first (pbr_get_focus_depth / pbr_set_focus_depth);

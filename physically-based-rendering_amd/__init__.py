@@ -96,7 +96,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 6
+ABI_VERSION = 7
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -155,7 +155,9 @@ for _name, _args in (
         ("pbr_diag_get_tile_order", [_vp, ctypes.c_int, _up, ctypes.c_uint32, _up, _up]),          # round 6
         ("pbr_diag_set_tile_order", [_vp, _up, ctypes.c_uint32, _up]),
         ("pbr_diag_last_deal", [_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
-        ("pbr_diag_bvh_build_info", [_vp, ctypes.POINTER(ctypes.c_int)])):
+        ("pbr_diag_bvh_build_info", [_vp, ctypes.POINTER(ctypes.c_int)]),
+        ("pbr_render_dof", [_vp, ctypes.c_uint32, ctypes.c_uint32, _fp, ctypes.c_float, ctypes.POINTER(Camera)]),       # ABI version 7
+        ("pbr_diag_last_focus_chain", [_vp, ctypes.POINTER(ctypes.c_double)])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -402,6 +404,12 @@ class Device:
         seeds = np.ascontiguousarray(seeds, np.float32)
         self._check(hip.pbr_render(self._ctx, first_sample_count, len(seeds), _as_fp(seeds), px_dim, ctypes.byref(cam)))
 
+    def render_dof(self, first_sample_count, seeds, px_dim, cam):
+        """pbr_render_dof: `render` for a camera with a focus point — the frames of a depth-of-field render in one call, bit-identical
+        to render_frame + accumulate per frame.  With tile sharding: one set_focus_depth before the call."""
+        seeds = np.ascontiguousarray(seeds, np.float32)
+        self._check(hip.pbr_render_dof(self._ctx, first_sample_count, len(seeds), _as_fp(seeds), px_dim, ctypes.byref(cam)))
+
     def _read(self, fn):
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(fn(self._ctx, _as_fp(out)))
@@ -511,6 +519,12 @@ class Device:
         ms, n = ctypes.c_double(), ctypes.c_uint32()
         self._check(hip.pbr_diag_last_trace(self._ctx, ctypes.byref(ms), ctypes.byref(n)))
         return float(ms.value), int(n.value)
+
+    def last_focus_chain_ms(self):
+        """Duration in ms of the focus chain (the pre-pass of render_dof) of the last render; 0 for any other render."""
+        ms = ctypes.c_double()
+        self._check(hip.pbr_diag_last_focus_chain(self._ctx, ctypes.byref(ms)))
+        return float(ms.value)
 
     def last_plan(self):
         """(name of the schedule that rendered the last render, auto-tuner's choice or -1 while measuring)."""

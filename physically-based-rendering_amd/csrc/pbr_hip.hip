@@ -53,13 +53,14 @@ struct Knobs {
 	int plocRadius = -1;    // pbr_build_bvh: search radius of the clustering builder
 	int tuneLog = -1;       // 1 = the schedule tuner logs its launches to stderr
 	int dealOrder = -1;     // the queue's dealing order: 0 always spatial, 1 always cost-ordered (once learnt), -1 by the launch's size
+	int chainLayout = -1;   // the focus chain's table (pbr_render_dof): 0 frame-major planes (the built-in choice), 1 a pixel slot's frames side by side
 };
 
 struct pbr_ctx {
 	int device = -1;
 	Knobs knobs;
 	hipStream_t stream = nullptr;
-	hipEvent_t evStart = nullptr, evStop = nullptr, evTraceStart = nullptr, evTraceStop = nullptr;
+	hipEvent_t evStart = nullptr, evStop = nullptr, evTraceStart = nullptr, evTraceStop = nullptr, evChainStart = nullptr;
 	std::string error;
 	double lastKernelMs = 0.0;
 	int numCUs = 0;
@@ -119,13 +120,20 @@ struct pbr_ctx {
 	float focusDepth = 0.0f;
 	float4* dFrameBuf = nullptr;   // frame-parallel launches: {finalColor, focus} per frame and local pixel slot
 	size_t frameBufFrames = 0;
+	// pbr_render_dof: the focus chain's table (pt_chain.hpp) — per frame of a launch and local pixel slot the previous
+	// first-hit distance, behind them the focus pixel's per frame — and the focus pixel's distance after the last launch
+	float* dChain = nullptr;
+	size_t chainFloats = 0;
+	float* dChainCarry = nullptr;
+	double lastChainMs = 0.0;      // of the last render: time inside the focus chain's launches
 	// schedule auto-tuning (launch(), pt_tuner.hpp): per scene + configuration, the candidates are timed on the first
 	// frames that are rendered anyway, then the fastest one is kept
 	ScheduleTuner tuner;
 	Plan plans[ScheduleTuner::kPlans];              // the tuner's candidates; valid while plansBuilt (reset by pbr_upload_scene / pbr_configure / pbr_diag_set_knob)
 	Plan phongPlan;                                 // the Phong-tessellation build of the refill kernel (renders every chunk with Phong tessellation)
 
-	bool plansBuilt = false, phongPlanBuilt = false;
+	Plan chainPlans[ScheduleTuner::kPlans];         // the same candidates in the chained build of their kernels (pbr_render_dof; pt_flavour.hpp)
+	bool plansBuilt = false, phongPlanBuilt = false, chainPlansBuilt = false;
 	bool workClean = false;                         // the queue heads are zero (foldFrames leaves them so)
 	float* hSeeds = nullptr;                        // pinned staging for the seeds of a launch
 	size_t hSeedCapacity = 0;
@@ -199,6 +207,7 @@ void freeScene( pbr_ctx* ctx ) {
 // tuner starts over (a new scene, a new configuration, a changed knob).
 void replan( pbr_ctx* ctx ) {
 	ctx->plansBuilt = false;
+	ctx->chainPlansBuilt = false;
 	ctx->phongPlanBuilt = false;
 	ctx->tuner.reset( ScheduleTuner::scaleOf( (size_t) ctx->numLocalTiles * 64 ) );
 }
@@ -212,6 +221,9 @@ void freeImages( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dFrameBuf );
 	ctx->dFrameBuf = nullptr;
 	ctx->frameBufFrames = 0;
+	(void) hipFree( ctx->dChain );
+	ctx->dChain = nullptr;
+	ctx->chainFloats = 0;
 	(void) hipFree( ctx->dTileOrder );
 	(void) hipFree( ctx->dCostOrder );
 	(void) hipFree( ctx->dLastOrder );
@@ -244,16 +256,24 @@ const size_t kCounterSlots = 16;
 // flavours have no two-paths-per-lane kernels) leaves its picker null.
 #define PTI_DECLARE( f, g ) extern "C" const void* PTI_NAME( f, g )( uint32_t, int, int ) __attribute__( ( weak ) );
 #define PTI_DECLARE_FLAVOUR( f ) \
-	PTI_DECLARE( f, 0 ) PTI_DECLARE( f, 1 ) PTI_DECLARE( f, 2 ) PTI_DECLARE( f, 3 ) PTI_DECLARE( f, 4 ) PTI_DECLARE( f, 5 ) PTI_DECLARE( f, 6 ) PTI_DECLARE( f, 7 )
+	PTI_DECLARE( f, 0 ) PTI_DECLARE( f, 1 ) PTI_DECLARE( f, 2 ) PTI_DECLARE( f, 3 ) PTI_DECLARE( f, 4 ) PTI_DECLARE( f, 5 ) PTI_DECLARE( f, 6 ) PTI_DECLARE( f, 7 ) \
+	PTI_DECLARE( f, 8 )
 PTI_DECLARE_FLAVOUR( 0 )
 PTI_DECLARE_FLAVOUR( 1 )
 PTI_DECLARE_FLAVOUR( 2 )
 PTI_DECLARE_FLAVOUR( 3 )
 PTI_DECLARE_FLAVOUR( 5 )     // the compact record of the eight-order walk (flavour bit 2; only together with bit 0)
 PTI_DECLARE_FLAVOUR( 7 )
-#define PTI_ROW( f ) { PTI_NAME( f, 0 ), PTI_NAME( f, 1 ), PTI_NAME( f, 2 ), PTI_NAME( f, 3 ), PTI_NAME( f, 4 ), PTI_NAME( f, 5 ), PTI_NAME( f, 6 ), PTI_NAME( f, 7 ) }
-#define PTI_NO_ROW { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }
-const pti_picker kPickers[PTI_FLAVOURS][PTI_GROUPS] = { PTI_ROW( 0 ), PTI_ROW( 1 ), PTI_ROW( 2 ), PTI_ROW( 3 ), PTI_NO_ROW, PTI_ROW( 5 ), PTI_NO_ROW, PTI_ROW( 7 ) };
+PTI_DECLARE_FLAVOUR( 8 )     // the chained builds (flavour bit 3, pbr_render_dof): groups 3 and 8 stay null
+PTI_DECLARE_FLAVOUR( 9 )
+PTI_DECLARE_FLAVOUR( 10 )
+PTI_DECLARE_FLAVOUR( 11 )
+PTI_DECLARE_FLAVOUR( 13 )
+PTI_DECLARE_FLAVOUR( 15 )
+#define PTI_ROW( f ) { PTI_NAME( f, 0 ), PTI_NAME( f, 1 ), PTI_NAME( f, 2 ), PTI_NAME( f, 3 ), PTI_NAME( f, 4 ), PTI_NAME( f, 5 ), PTI_NAME( f, 6 ), PTI_NAME( f, 7 ), PTI_NAME( f, 8 ) }
+#define PTI_NO_ROW { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }
+const pti_picker kPickers[PTI_FLAVOURS][PTI_GROUPS] = { PTI_ROW( 0 ), PTI_ROW( 1 ), PTI_ROW( 2 ), PTI_ROW( 3 ), PTI_NO_ROW, PTI_ROW( 5 ), PTI_NO_ROW, PTI_ROW( 7 ),
+                                                       PTI_ROW( 8 ), PTI_ROW( 9 ), PTI_ROW( 10 ), PTI_ROW( 11 ), PTI_NO_ROW, PTI_ROW( 13 ), PTI_NO_ROW, PTI_ROW( 15 ) };
 
 KernelFn pickKernel( int flavour, int group, uint32_t brdf, bool shadow, bool lights ) {
 	const pti_picker pick = kPickers[flavour][group];
@@ -643,9 +663,9 @@ struct PlanSpec {
 // split between the blocks the register budget admits.  The experiment knobs (PBR_BLOCKS_PER_CU, PBR_LDS_SLOTS,
 // PBR_PH_PARK, PBR_PH_SHADE, PBR_PARK_EIGHTHS, PBR_DRAIN_MODE, PBR_REFILL_BATCH) are read when the plans are built — once per
 // scene + configuration — not per launch.
-int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan ) {
+int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan, bool chained = false ) {
 	const Knobs& knobs = ctx->knobs;
-	const int flavour = flavourOf( ctx->cfg );
+	const int flavour = flavourOf( ctx->cfg ) | ( chained ? PTI_CHAINED : 0 );
 	const bool lights = ( ctx->numLights > 0 );
 	const bool shadow = ( ctx->cfg.shadow_rays == 1 ) && lights;
 	const KernelFn kernel = pickKernel( flavour, spec.group, ctx->cfg.brdf, shadow, lights );
@@ -714,7 +734,7 @@ int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan 
 	plan->name = spec.name;
 	// the symbol as rocprofv3 prints it (pt_instance.hip instantiates exactly these; namespaces: pt_flavour.hpp)
 	const char* const tf[2] = { "false", "true" };
-	const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0 };
+	const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0, 0 };
 
 	if( spec.group == PTI_DUAL ) {
 		std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingDual<%u, %s, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights] );
@@ -731,8 +751,8 @@ int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan 
 
 // The plans of this scene + configuration, built on the first render after replan(): the tuner's candidates, and with Phong
 // tessellation the one plan that renders it.
-int buildPlans( pbr_ctx* ctx, uint32_t hotAvail, bool phong ) {
-	if( !ctx->plansBuilt ) {
+int buildPlans( pbr_ctx* ctx, uint32_t hotAvail, bool phong, bool chained ) {
+	if( !ctx->plansBuilt || ( chained && !ctx->chainPlansBuilt ) ) {
 		const int flavour = flavourOf( ctx->cfg );
 		// The state machine's thresholds (lanes that leave a node phase before it ends / lanes that wait before a shade phase):
 		// 16 / 40 in the reference's walk (profiles/r03/experiments/sweep_thresholds.txt).  A ray-ordered walk makes fewer visits per
@@ -753,13 +773,20 @@ int buildPlans( pbr_ctx* ctx, uint32_t hotAvail, bool phong ) {
 		};
 
 		for( int k = 0; k < ScheduleTuner::kPlans; k++ ) {
-			PBR_TRY( makePlan( ctx, specs[k], hotAvail, &ctx->plans[k] ) );
-			ctx->tuner.names[k] = specs[k].name;
+			if( !ctx->plansBuilt ) {
+				PBR_TRY( makePlan( ctx, specs[k], hotAvail, &ctx->plans[k] ) );
+				ctx->tuner.names[k] = specs[k].name;
+			}
+			if( chained && !ctx->chainPlansBuilt ) {
+				PBR_TRY( makePlan( ctx, specs[k], hotAvail, &ctx->chainPlans[k], true ) );
+			}
 		}
 
+		ctx->chainPlansBuilt = ctx->chainPlansBuilt || chained;
+
 		ctx->tuner.log = ( ctx->knobs.tuneLog > 0 ) ? stderr : nullptr;
+		ctx->phongPlanBuilt = ctx->plansBuilt && ctx->phongPlanBuilt;
 		ctx->plansBuilt = true;
-		ctx->phongPlanBuilt = false;
 	}
 
 	if( phong && !ctx->phongPlanBuilt ) {
@@ -892,8 +919,65 @@ int checkGuard( pbr_ctx* ctx ) {
 	return PBR_OK;
 }
 
+// The focus chain of one launch of a chained render (pt_chain.hpp): the table is grown to the launch's frames, P is pointed at
+// it, and the two kernels of the context's build flavour run ahead of the path-tracing launch.  prev: the image before the
+// launch's first frame; first: the first launch of the render (tile sharding: the caller's distance starts the chain, the
+// chain's own last value every launch after it).
+typedef void ( *ChainPixelFn )( const ptk::DevParams, const float4*, float*, float*, int );
+typedef void ( *ChainSlotsFn )( const ptk::DevParams, const float4*, float* );
+
+int runFocusChain( pbr_ctx* ctx, DevParams* P, const float4* prev, bool first ) {
+	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
+	const size_t n = (size_t) P->nFrames;
+	const size_t floats = pixelSlots * n + n;
+
+	if( floats > 0xFFFFFFFFull ) {
+		return fail( ctx, PBR_EINVAL, "focus chain: %zu pixel slots x %zu frames do not fit a 32-bit table index", pixelSlots, n );
+	}
+
+	if( ctx->chainFloats < floats ) {
+		// grown like the frame buffer whose quarter it is: at least 64 frames' worth, then twice what is asked for
+		const size_t want = std::max<size_t>( ( pixelSlots + 1 ) * 64, ( n <= 64 ) ? floats : 2 * floats );
+		(void) hipFree( ctx->dChain );
+		ctx->dChain = nullptr;
+		ctx->chainFloats = 0;
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChain, sizeof( float ) * want ) );
+		ctx->chainFloats = want;
+	}
+
+	// The main launch reads a pixel's 64 frames per wave (nextSlot), the chain writes a frame's 64 pixels per wave: layout 1
+	// keeps a slot's frames side by side (one stretch per wave of the main launch), layout 0 a frame's slots (coalesced stores
+	// here).  Measured at 1080p (profiles/r07/experiments/dof_render.txt): frame-major planes render the Cornell box's 256
+	// frames in 116.8 ms against 121.1 ms (the chain alone 11.3 against 13.3 ms), the Sponza-class scene's 64 frames within
+	// the spread of each other (chain 17.1 against 18.0 ms) — layout 0 it is.
+	const bool slotMajor = ( ctx->knobs.chainLayout == 1 );
+	P->chain = ctx->dChain;
+	P->chainSlotStride = slotMajor ? (unsigned) n : 1u;
+	P->chainFrameStride = slotMajor ? 1u : (unsigned) pixelSlots;
+	P->chainFocusAt = (unsigned) ( pixelSlots * n );
+
+	const int flavour = flavourOf( ctx->cfg );
+	const pti_picker pick = kPickers[flavour][PTI_CHAIN];
+
+	if( pick == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "this library was built without the focus chain of flavour %d", flavour );
+	}
+
+	const int lights = ( ctx->numLights > 0 ) ? 1 : 0;
+	const ChainPixelFn pixelKernel = (ChainPixelFn) pick( 0, 0, lights );
+	const ChainSlotsFn slotsKernel = (ChainSlotsFn) pick( 1, 0, lights );
+	DevParams C = *P;
+	C.parkEighths = ( ctx->numNodes >= kWideMinNodes ) ? 4 : 6;
+	hipLaunchKernelGGL( pixelKernel, dim3( 1 ), dim3( 64 ), 0, ctx->stream, C, prev, ctx->dChain, ctx->dChainCarry, first ? 0 : 1 );
+	HIP_TRY( ctx, hipGetLastError() );
+	hipLaunchKernelGGL( slotsKernel, dim3( (unsigned) ( ( pixelSlots + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream, C, prev, ctx->dChain );
+	HIP_TRY( ctx, hipGetLastError() );
+	return PBR_OK;
+}
+
+// chained: pbr_render_dof — many frames with depth of field in one call, the focus chain ahead of every launch
 int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* seeds,
-            bool explicitWeight, float weight, float pxDim, const pbr_camera* cam ) {
+            bool explicitWeight, float weight, float pxDim, const pbr_camera* cam, bool chained = false ) {
 	if( !ctx->hasScene || !ctx->configured ) {
 		return fail( ctx, PBR_ESTATE, "render before pbr_upload_scene / pbr_configure" );
 	}
@@ -906,12 +990,15 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 
 	const bool dof = ( cam->focusPoint[0] >= 0 && cam->focusPoint[1] >= 0 );
 
-	if( dof && nFrames > 1 ) {
+	if( dof && nFrames > 1 && !chained ) {
 		return fail( ctx, PBR_EINVAL, "depth of field reads the previous frame of another pixel: render one frame per call" );
 	}
 	if( dof && ctx->cfg.tile_world > 1 && !ctx->focusGiven ) {
-		return fail( ctx, PBR_EINVAL, "depth of field with tile sharding: the focus pixel's tile may live on another rank — pass its previous-frame distance with pbr_set_focus_depth (owner: pbr_get_focus_depth) before every frame" );
+		return fail( ctx, PBR_EINVAL, "depth of field with tile sharding: the focus pixel's tile may live on another rank — pass its previous-frame distance with pbr_set_focus_depth (owner: pbr_get_focus_depth) before every %s", chained ? "pbr_render_dof call" : "frame" );
 	}
+
+	const bool chain = dof && chained;
+	ctx->lastChainMs = 0.0;
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
@@ -967,23 +1054,27 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 
 	const bool phong = ( ctx->cfg.phong_tessellation > 0.0f );
 
+	if( phong && chain ) {
+		return fail( ctx, PBR_EINVAL, "pbr_render_dof does not render Phong tessellation with a focus point (its plan has an intersection of its own); call pbr_render_frame + pbr_accumulate per frame" );
+	}
 	if( phong && ctx->dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs a scene with usable vertex normals" );
 	}
 
-	PBR_TRY( buildPlans( ctx, hotAvail, phong ) );
+	PBR_TRY( buildPlans( ctx, hotAvail, phong, chain ) );
 	size_t chunkCap = 0;
 	PBR_TRY( growFrameBuf( ctx, nFrames, &chunkCap ) );
 	ctx->tuner.beginRender( nFrames );
 
 	// Phong tessellation has one plan; a pinned plan renders without tuning
-	const Plan* forced = phong ? &ctx->phongPlan : ( ctx->pinnedPlan >= 0 ) ? &ctx->plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )] : nullptr;
+	const Plan* plans = chain ? ctx->chainPlans : ctx->plans;   // the tuner's choice holds for both builds of a plan's kernel
+	const Plan* forced = phong ? &ctx->phongPlan : ( ctx->pinnedPlan >= 0 ) ? &plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )] : nullptr;
 	dealOrder( ctx, nFrames, forced != nullptr || ctx->tuner.settled(), &P );
 	P.frameBuf = ctx->dFrameBuf;
 	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
 	P.frameStride = (unsigned) pixelSlots;
 	const unsigned foldBlocks = (unsigned) ( ( pixelSlots + 255 ) / 256 );
-	double traceMs = 0.0;
+	double traceMs = 0.0, chainMs = 0.0;
 	uint32_t launches = 0, largest = 0;
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 
@@ -991,12 +1082,18 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		// which plan renders this chunk, and how many frames of it
 		const uint32_t most = std::min<uint32_t>( (uint32_t) chunkCap, nFrames - done );
 		const Chunk chunk = ( forced != nullptr ) ? Chunk{ -1, most, -1, false } : ctx->tuner.next( most );
-		const Plan& plan = ( forced != nullptr ) ? *forced : ctx->plans[chunk.plan];
+		const Plan& plan = ( forced != nullptr ) ? *forced : plans[chunk.plan];
 		const uint32_t n = chunk.frames;
 		P.nFrames = (int) n;
 		invariantDivisor( n, P.framesDiv );
 		P.firstCount = (int) ( firstCount + done );
 		P.seeds = ctx->dSeeds + done;
+
+		if( chain ) {
+			// imageIn.w before the first launch, the last fold's .w — the previous launch's last first-hit distances — after it
+			HIP_TRY( ctx, hipEventRecord( ctx->evChainStart, ctx->stream ) );
+			PBR_TRY( runFocusChain( ctx, &P, done == 0 ? ctx->dImgIn : ctx->dImgOut, done == 0 ) );
+		}
 
 		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStart, ctx->stream ) );
 		PBR_TRY( runPlan( ctx, plan, &P, (size_t) ctx->numLocalTiles * n ) );
@@ -1011,6 +1108,12 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evTraceStart, ctx->evTraceStop ) );
 		traceMs += (double) ms;
 		launches++;
+
+		if( chain ) {
+			float chainPart = 0.0f;
+			HIP_TRY( ctx, hipEventElapsedTime( &chainPart, ctx->evChainStart, ctx->evTraceStart ) );
+			chainMs += (double) chainPart;
+		}
 
 		if( n > largest ) {
 			largest = n;
@@ -1030,6 +1133,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
 	ctx->lastKernelMs = (double) ms;
 	ctx->lastTraceMs = traceMs;
+	ctx->lastChainMs = chainMs;
 	ctx->lastTraceLaunches = launches;
 	ctx->launchesSinceLearn += launches;
 	PBR_TRY( checkGuard( ctx ) );
@@ -1079,6 +1183,9 @@ int pbr_mode_built( uint32_t traversal, uint32_t arith ) {
 		if( kPickers[flavour][group] == nullptr ) {
 			return 0;
 		}
+		if( group != PTI_REFILL_PHONG && group != PTI_CHAIN && kPickers[flavour | PTI_CHAINED][group] == nullptr ) {
+			return 0;
+		}
 	}
 
 	return 1;
@@ -1112,6 +1219,8 @@ int pbr_create( int device, pbr_ctx** out ) {
 	HIP_TRY( ctx, hipEventCreate( &ctx->evTraceStart ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evTraceStop ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evStop ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evChainStart ) );
+	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChainCarry, sizeof( float ) ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCounters, sizeof( unsigned long long ) * kCounterSlots ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dWork, kWorkBytes ) );
 	// host-visible so that it can be read while a kernel is still running
@@ -1141,6 +1250,8 @@ void pbr_destroy( pbr_ctx* ctx ) {
 		(void) hipEventDestroy( ctx->evTraceStart );
 		(void) hipEventDestroy( ctx->evTraceStop );
 		(void) hipEventDestroy( ctx->evStop );
+		(void) hipEventDestroy( ctx->evChainStart );
+		(void) hipFree( ctx->dChainCarry );
 		(void) hipStreamDestroy( ctx->stream );
 	}
 
@@ -1360,6 +1471,20 @@ int pbr_render( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, co
 	}
 
 	PBR_TRY( launch( ctx, first_sample_count, n_frames, seeds, false, 0.0f, pxDim, cam ) );
+
+	// result in imageOut AND imageIn
+	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	return PBR_OK;
+}
+
+int pbr_render_dof( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, const float* seeds, float pxDim, const pbr_camera* cam ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+
+	PBR_TRY( launch( ctx, first_sample_count, n_frames, seeds, false, 0.0f, pxDim, cam, true ) );
 
 	// result in imageOut AND imageIn
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
@@ -2182,7 +2307,7 @@ int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value ) {
 		{ "lds_slots", &k.ldsSlots }, { "blocks_per_cu", &k.blocksPerCU }, { "ph_park", &k.phPark }, { "ph_shade", &k.phShade },
 		{ "park_eighths", &k.parkEighths }, { "drain_mode", &k.drainMode }, { "refill_batch", &k.refillBatch },
 		{ "chunk_frames", &k.chunkFrames }, { "face_normals", &k.faceNormals }, { "bvh_builder", &k.bvhBuilder },
-		{ "ploc_radius", &k.plocRadius }, { "tune_log", &k.tuneLog }, { "deal_order", &k.dealOrder },
+		{ "ploc_radius", &k.plocRadius }, { "tune_log", &k.tuneLog }, { "deal_order", &k.dealOrder }, { "chain_layout", &k.chainLayout },
 	};
 
 	for( const auto& entry : table ) {
@@ -2308,6 +2433,15 @@ int pbr_diag_last_trace( pbr_ctx* ctx, double* trace_ms, uint32_t* launches ) {
 
 	*trace_ms = ctx->lastTraceMs;
 	*launches = ctx->lastTraceLaunches;
+	return PBR_OK;
+}
+
+int pbr_diag_last_focus_chain( pbr_ctx* ctx, double* ms ) {
+	if( ctx == nullptr || ms == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_last_focus_chain: null argument" );
+	}
+
+	*ms = ctx->lastChainMs;
 	return PBR_OK;
 }
 

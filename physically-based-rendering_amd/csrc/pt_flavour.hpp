@@ -13,6 +13,8 @@
 //               bit 1  native arithmetic: v_rcp / v_sqrt / v_sin / v_cos / v_log / v_exp instead of the exact definitions
 //               bit 2  (with bit 0, round 6) the COMPACT record of the eight-order walk: one 64-byte record per node shared by
 //                      the eight orders instead of eight streams of 32-byte records (pt_kernel.hpp, "the compact record")
+//               bit 3  (round 7) the CHAINED build: focusInputs takes a frame's depth-of-field inputs from the focus chain's table
+//                      (pt_chain.hpp) instead of the input image — the kernels pbr_render_dof launches.  Flavours 8 + f.
 //   undefined          the translation unit of pbr_hip.hip: no path-tracing kernel is instantiated there; its diagnostic and
 //                      denoise kernels take the walk from DevParams.walkScheme at run time and compute exactly
 #pragma once
@@ -26,8 +28,10 @@
 #define PT_WALK_MODE ( PT_FLAVOUR & 1 )           // 0: the reference's order only; 1: a ray-ordered walk only
 #define PT_ARITH_NATIVE ( ( PT_FLAVOUR >> 1 ) & 1 )
 #define PT_WALK_COMPACT ( ( PT_FLAVOUR >> 2 ) & 1 )   // 1: the node stream holds compact 64-byte records (walkScheme 3)
+#define PT_CHAINED ( ( PT_FLAVOUR >> 3 ) & 1 )        // 1: depth-of-field inputs per frame from DevParams.chain
 #else
 #define PT_WALK_MODE 2                             // decided per launch (DevParams.walkScheme)
 #define PT_ARITH_NATIVE 0
 #define PT_WALK_COMPACT 2                          // decided per launch (DevParams.walkScheme == 3)
+#define PT_CHAINED 0
 #endif

@@ -1,11 +1,28 @@
 // One group of path-tracing kernels in one build flavour (pt_instances.hpp, pt_flavour.hpp):
-//   hipcc -c -DPT_FLAVOUR=<0..3 | 5 | 7> -DPT_GROUP=<0..7> pt_instance.hip
+//   hipcc -c -DPT_FLAVOUR=<0..3 | 5 | 7, + 8: chained> -DPT_GROUP=<0..8> pt_instance.hip
 #if !defined( PT_FLAVOUR ) || !defined( PT_GROUP )
 #error "pt_instance.hip is compiled once per (PT_FLAVOUR, PT_GROUP) pair: see build.py"
 #endif
 
 #include "pt_kernel.hpp"
 #include "pt_instances.hpp"
+
+#if PT_CHAINED && ( PT_GROUP == PTI_CHAIN || PT_GROUP == PTI_REFILL_PHONG )
+#error "the chained flavours hold the seven plans' kernels only"
+#endif
+
+#if PT_GROUP == PTI_CHAIN
+// the focus chain of this flavour: two kernels, with or without orb lights
+#include "pt_chain.hpp"
+
+extern "C" const void* PTI_NAME( PT_FLAVOUR, PT_GROUP )( uint32_t stage, int, int lights ) {
+	if( stage == 0 ) {
+		return lights ? (const void*) ptk::focusChainPixel<true> : (const void*) ptk::focusChainPixel<false>;
+	}
+
+	return lights ? (const void*) ptk::focusChainSlots<true> : (const void*) ptk::focusChainSlots<false>;
+}
+#else
 
 #if PT_GROUP == PTI_DUAL && PT_WALK_COMPACT == 1
 #error "pathTracingDual has no node phase for the compact record: the compact flavours render plan 6 with the 6-waves state machine"
@@ -52,3 +69,5 @@ extern "C" const void* PTI_NAME( PT_FLAVOUR, PT_GROUP )( uint32_t brdf, int shad
 
 	return (const void*) k;
 }
+
+#endif   // PT_GROUP != PTI_CHAIN

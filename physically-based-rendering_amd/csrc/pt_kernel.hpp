@@ -158,6 +158,12 @@ struct DevParams {
 	// prepareFaceNormals with the same code.  The lock-step kernels read it (Cornell +1.3 %); in the lane state
 	// machine the extra pointer costs more in registers than the 40 instructions per hit are worth (measured -2 %).
 	const float4* faceN;
+	// behind everything the kernels of the parent layout read — chained depth-of-field launches (pbr_render_dof): the two
+	// inputs of focusInputs for every frame of the launch, filled by the focus chain (pt_chain.hpp) before it.  Read by the
+	// CHAINED builds of the kernels only (pt_flavour.hpp, PT_CHAINED).
+	const float* chain;
+	unsigned chainSlotStride, chainFrameStride;   // a pixel slot's previous first-hit distance for frame k: chain[slot * chainSlotStride + k * chainFrameStride]
+	unsigned chainFocusAt;                        // the focus pixel's for frame k: chain[chainFocusAt + k]
 };
 
 // ---- which rank owns which tile (multi-GPU sharding) -----------------------------------------
@@ -1825,14 +1831,24 @@ PT_DEV size_t frameBufIndex( const DevParams& P, unsigned slot, unsigned k ) {
 	return ( (size_t) ( slot >> 3 ) * (size_t) P.nFrames + (size_t) k ) * 8u + (size_t) ( slot & 7u );
 }
 
-// getPreviousFocus, pathtracing.cl:58-65 (single-frame launches only; CLAMP_TO_EDGE): the previous frame's first-hit
+// getPreviousFocus, pathtracing.cl:58-65 (CLAMP_TO_EDGE): the previous frame's first-hit
 // distance at the focus pixel and at this pixel, -1 = depth of field off.  imageIn does not change during a launch, so
 // the two values are re-read where a camera ray starts instead of living in two registers for the whole path.
-PT_DEV void focusInputs( const DevParams& P, unsigned slot, float* tFocus, float* tObject ) {
+// A chained launch (pbr_render_dof) renders many frames with depth of field: frame k's two values are frame k - 1's, and the
+// focus chain (pt_chain.hpp) has put them into P.chain before the launch.  That is a BUILD of the kernels (PT_CHAINED,
+// pt_flavour.hpp), not a branch: as a run-time test on P.chain it changed registers, spills or scratch of 85 of the 641
+// kernels and cost pathTracingPhased<0, false, true, 4> of the compact flavour its sixth wave.
+PT_DEV void focusInputs( const DevParams& P, unsigned slot, unsigned frame, float* tFocus, float* tObject ) {
 	*tFocus = -1.0f;
 	*tObject = -1.0f;
 
 	if( P.focusX >= 0 && P.focusY >= 0 ) {
+#if PT_CHAINED
+		*tObject = P.chain[slot * P.chainSlotStride + frame * P.chainFrameStride];
+		*tFocus = P.chain[P.chainFocusAt + frame];
+		return;
+#endif
+		(void) frame;
 		const int fx = ( P.focusX > P.width - 1 ) ? P.width - 1 : P.focusX;
 		const int fy = ( P.focusY > P.height - 1 ) ? P.height - 1 : P.focusY;
 		const int ft = ( fy >> 3 ) * P.tilesX + ( fx >> 3 );
@@ -1856,7 +1872,7 @@ PT_DEV void beginPixel( const DevParams& P, PixelState& st, unsigned slot, LaneC
 	st.depth = 0;
 	st.depthAdded = 0;
 	float tFocus, tObject;
-	focusInputs( P, slot, &tFocus, &tObject );
+	focusInputs( P, slot, frame, &tFocus, &tObject );
 	int px, py;
 	pixelOfSlot( P, slot, &px, &py );
 	st.ray = initRay( P, px, py, st.seed, tFocus, tObject );
@@ -2053,7 +2069,7 @@ PT_DEV bool shadeStep( const DevParams& P, const float4* lds, PixelState& st, La
 	depth = 0;
 	depthAdded = 0;
 	float tFocus, tObject;
-	focusInputs( P, st.slot, &tFocus, &tObject );
+	focusInputs( P, st.slot, (unsigned) st.frame, &tFocus, &tObject );
 	int px, py;
 	pixelOfSlot( P, st.slot, &px, &py );
 	ray = initRay( P, px, py, seed, tFocus, tObject );

@@ -450,10 +450,22 @@ int MultiPathTracer::render( uint32_t firstSampleCount, uint32_t nFrames, const 
 		return PBR_ESTATE;
 	}
 
+	// a focus point: the frames go through pbr_render_dof, which wants the focus pixel's distance once per call
+	const bool dof = ( cam != nullptr && cam->focusPoint[0] >= 0 && cam->focusPoint[1] >= 0 );
+
+	if( dof ) {
+		const int status = handOverFocusDepth( cam );
+
+		if( status != PBR_OK ) {
+			return status;
+		}
+	}
+
 	return onEveryRank( [&]( int r ) {
 		Rank& rank = mRanks[(size_t) r];
 		const double t0 = nowMs();
-		const int status = pbr_render( rank.ctx, firstSampleCount, nFrames, seeds, pxDim, cam );
+		const int status = dof ? pbr_render_dof( rank.ctx, firstSampleCount, nFrames, seeds, pxDim, cam )
+		                       : pbr_render( rank.ctx, firstSampleCount, nFrames, seeds, pxDim, cam );
 		rank.renderMs = nowMs() - t0;
 		rank.gatherMs = 0.0;
 
@@ -469,14 +481,10 @@ int MultiPathTracer::render( uint32_t firstSampleCount, uint32_t nFrames, const 
 	} );
 }
 
-int MultiPathTracer::renderFrame( float seed, float pixelWeight, float pxDim, const pbr_camera* cam, bool accumulate, bool withGather ) {
-	if( !mConfigured || cam == nullptr ) {
-		mError = "pbr_multi_render_frame: configure first; the camera must be given";
-		return PBR_ESTATE;
-	}
-
-	// depth of field: every pixel reads the previous-frame distance of the focus pixel (pathtracing.cl:58-65), whose tile
-	// lives on ONE rank.  In one process the hand-over is a host float, not an ncclBroadcast.
+// depth of field: every pixel reads the previous-frame distance of the focus pixel (pathtracing.cl:58-65), whose tile
+// lives on ONE rank.  In one process the hand-over is a host float, not an ncclBroadcast.  Once per frame of the
+// frame-by-frame sequence, once per pbr_multi_render call.
+int MultiPathTracer::handOverFocusDepth( const pbr_camera* cam ) {
 	if( cam->focusPoint[0] >= 0 && cam->focusPoint[1] >= 0 && mRanks.size() > 1 ) {
 		float depth = 0.0f;
 		bool found = false;
@@ -509,6 +517,21 @@ int MultiPathTracer::renderFrame( float seed, float pixelWeight, float pxDim, co
 				return status;
 			}
 		}
+	}
+
+	return PBR_OK;
+}
+
+int MultiPathTracer::renderFrame( float seed, float pixelWeight, float pxDim, const pbr_camera* cam, bool accumulate, bool withGather ) {
+	if( !mConfigured || cam == nullptr ) {
+		mError = "pbr_multi_render_frame: configure first; the camera must be given";
+		return PBR_ESTATE;
+	}
+
+	const int handed = handOverFocusDepth( cam );
+
+	if( handed != PBR_OK ) {
+		return handed;
 	}
 
 	return onEveryRank( [&]( int r ) {

@@ -99,6 +99,7 @@ class MultiPathTracer {
 		int onEveryRank( const std::function<int( int )>& job );
 		int exchange( int rank );
 		void skipExchange();
+		int handOverFocusDepth( const pbr_camera* cam );
 		int failed( int rank, int status, const std::string& what );
 		void freeBuffers();
 		void release();

@@ -416,7 +416,15 @@ std::vector<float> PathTracer::generateImages( uint32_t frames ) {
 	}
 
 	const float pxDim = pixelDimension( mWidth, mHeight, mFOV );
-	this->check( pbr_render( mCtx, mSampleCount, frames, seeds.data(), pxDim, &mStructCam ), "pbr_render" );
+
+	// after setFocus: the same launch behind the focus chain (pbr_render_dof); pbr_render refuses a focus point
+	if( mStructCam.focusPoint[0] >= 0 && mStructCam.focusPoint[1] >= 0 ) {
+		this->check( pbr_render_dof( mCtx, mSampleCount, frames, seeds.data(), pxDim, &mStructCam ), "pbr_render_dof" );
+	}
+	else {
+		this->check( pbr_render( mCtx, mSampleCount, frames, seeds.data(), pxDim, &mStructCam ), "pbr_render" );
+	}
+
 	mSampleCount += frames;
 
 	std::vector<float> image( (size_t) mWidth * mHeight * 4 );

@@ -92,6 +92,7 @@ class MultiDevice:
         return int(plan.value), [int(v) for v in votes]
 
     def render(self, first_sample_count, seeds, px_dim, cam, gather=True):
+        """pbr_multi_render; a camera with a focus point renders through pbr_render_dof (one focus hand-over per call)."""
         seeds = np.ascontiguousarray(seeds, np.float32)
         self._check(lib().pbr_multi_render(self._m, first_sample_count, len(seeds), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                            px_dim, ctypes.byref(cam), 1 if gather else 0))
