@@ -31,10 +31,10 @@ extern "C" {
 #endif
 
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
- * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof).  A caller that loads the library at run time — or
+ * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 7
+#define PBR_ABI_VERSION 8
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -202,6 +202,45 @@ int pbr_render( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, co
  * Phong tessellation (phong_tessellation > 0) with a focus point is refused with PBR_EINVAL: render it with
  * pbr_render_frame + pbr_accumulate per frame. */
 int pbr_render_dof( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, const float* seeds, float pxDim, const pbr_camera* cam );
+
+/* Adaptive sampling: pbr_render that stops rendering the 8x8 tiles whose mean has converged (not in the reference, which
+ * spends the same frames on every pixel).  The call runs in rounds: round 0 renders frames 0 .. min_frames - 1 of every local
+ * tile, every later round the next min( round_frames, max_frames - done ) frames of the tiles that are still active; after
+ * every round each active tile's error estimate is tested, and a tile that stops never becomes active again.  The k-th frame
+ * a pixel renders in this call uses seeds[k] and the weight n/(n+1), n = first_sample_count + k — so a tile that stopped after
+ * c frames holds, .w included, bit for bit what pbr_render( first_sample_count, c, seeds ) leaves there; its part of the debug
+ * image holds the counts of the last frame it rendered, and pbr_get_counters counts exactly what was traced.  Result in
+ * imageOut AND imageIn.
+ * The error estimate of a tile with c frames (csrc/pt_adaptive.hpp states it operation by operation, in binary32; it is
+ * reproducible to the bit): the relative standard error of the tile's mean luminance,
+ *     sqrt( mean over the 64 pixels of var( Y ) / c ) / ( mean over the 64 pixels of mean( Y ) + 0.01 ),
+ * Y = 0.2126 r + 0.7152 g + 0.0722 b of a frame's colour, var the sample variance over the c frames of this call.  A tile
+ * stops when it is <= threshold; a tile with a frame that is not finite (estimate NaN) stays active.
+ * PBR_EINVAL, the context unchanged: a camera with a focus point (every pixel reads the focus pixel's previous frame, and that
+ * pixel's tile may stop: pbr_render_dof is the call for depth of field), min_frames < 2, max_frames < min_frames,
+ * round_frames = 0, a negative or NaN threshold, null arguments.  Tile sharding and Phong tessellation work as in pbr_render;
+ * a rank decides on its own tiles, there is no collective.
+ * Schedule: the pinned plan (pbr_diag_pin_plan), else the plan the schedule tuner has kept, else "phased-mid".  An adaptive
+ * call does not tune: a caller who wants the tuned plan renders once with pbr_render first.  It leaves the tuner, the learnt
+ * tile costs and the dealing orders as they were.
+ * AFTER the call the accumulated image has a sample count PER TILE (pbr_read_tile_stats).  Continuing it with a uniform
+ * first_sample_count — pbr_render, pbr_render_frame with a weight n/(n+1), another pbr_render_adaptive — is the caller's
+ * error: start the next accumulation with pbr_reset_accum / first_sample_count 0. */
+typedef struct pbr_adaptive_params {
+	uint32_t min_frames;     /* every tile renders at least this many frames; the first test comes after them (>= 2) */
+	uint32_t round_frames;   /* frames per further round, a test after every round (>= 1).  A round costs 0.4 - 0.6 ms at 1080p
+	                          * (the end of one more launch, the fold, the host's table building: DESIGN.md 5.1i), about what
+	                          * one frame costs — 16 frames per round are +4 ... +6 % when nothing stops, 32 half of that */
+	uint32_t max_frames;     /* no tile renders more (>= min_frames); seeds[] has max_frames entries */
+	float threshold;         /* a tile stops when its error estimate is <= threshold.  0: only tiles whose frames are all the
+	                          * same colour stop; +inf: all stop after min_frames */
+} pbr_adaptive_params;
+int pbr_render_adaptive( pbr_ctx* ctx, uint32_t first_sample_count, const float* seeds, float pxDim, const pbr_camera* cam, const pbr_adaptive_params* params );
+/* Of the last pbr_render_adaptive, per LOCAL tile in local-tile order (local tile j = the tile at dealing position
+ * j * tile_world + tile_rank, see pbr_config): the frames it rendered, and its error estimate at its last test.  *count =
+ * the number of local tiles; frames / error may be NULL (both NULL: *count only), else capacity >= *count entries each.
+ * PBR_ESTATE before the first adaptive call after pbr_configure. */
+int pbr_read_tile_stats( pbr_ctx* ctx, uint32_t* frames, float* error, uint32_t capacity, uint32_t* count );
 
 /* CL::readImageOutput( imageOut ) / ( imageDebug ) (PathTracer.cpp:66-67).  With tile sharding
  * only this rank's tiles are meaningful (others read 0). */

@@ -79,7 +79,7 @@ int pbr_diag_launch_fit( pbr_ctx* ctx, double* fixed_ms, double* per_frame_ms );
  *   "drain_mode"    bit 0 / 1: scale ph_park / ph_shade with the lanes still at work once the queue is empty
  *   "refill_batch"  lock-step kernels: lanes of a wave that wait with a finished unit before they take their next units
  *                   together (1 = every lane at once, as up to round 2)
- *   "chunk_frames"  cap of the frames per launch pair of pbr_render / pbr_render_dof (tests: several launch pairs)
+ *   "chunk_frames"  cap of the frames per launch pair of pbr_render / pbr_render_dof / pbr_render_adaptive (tests: several launch pairs)
  *   "face_normals"  0 = recompute the face normal on every hit (takes effect at the next pbr_upload_scene)
  *   "bvh_builder"   pbr_build_bvh: 0 clustering (default), 1 round 1's radix tree; "ploc_radius": its search radius
  *   "tune_log"      1 = the schedule tuner logs its launches to stderr
@@ -130,6 +130,13 @@ int pbr_diag_last_trace( pbr_ctx* ctx, double* trace_ms, uint32_t* launches );
 /* The focus chain of the last render (pbr_render_dof with a focus point: the pre-pass ahead of every path-tracing launch,
  * csrc/pt_chain.hpp): its summed duration, 0 for every other render.  pbr_diag_last_trace keeps meaning the path launches. */
 int pbr_diag_last_focus_chain( pbr_ctx* ctx, double* ms );
+
+/* The last pbr_render_adaptive: how many rounds it ran (= convergence tests of a tile that never stopped), the (pixel, frame)
+ * units it traced — the sum over the local tiles of 64 x frames rendered; against 64 x tiles x max_frames that is the saving —
+ * and the summed duration of its folds (foldFramesAdaptive, csrc/pt_adaptive.hpp).  pbr_diag_last_trace and pbr_last_kernel_ms
+ * report its path-tracing launches and the whole call (the host's table building between rounds included).
+ * PBR_ESTATE before the first adaptive call. */
+int pbr_diag_last_adaptive( pbr_ctx* ctx, uint32_t* rounds, uint64_t* units_traced, double* fold_ms );
 
 /* All 16 device counter slots: [0..3] = pbr_counters; [4..15] are written only by experiment
  * builds (-DPBR_LAB_HOOKS, lab/src/pt_lab_hooks.hpp) and stay 0 otherwise. */

@@ -66,6 +66,12 @@ class Config(ctypes.Structure):
     ]
 
 
+class AdaptiveParams(ctypes.Structure):
+    """pbr_adaptive_params"""
+    _fields_ = [("min_frames", ctypes.c_uint32), ("round_frames", ctypes.c_uint32), ("max_frames", ctypes.c_uint32),
+                ("threshold", ctypes.c_float)]
+
+
 class Counters(ctypes.Structure):
     _fields_ = [("nodes", ctypes.c_uint64), ("tris", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("paths", ctypes.c_uint64)]
 
@@ -96,7 +102,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 7
+ABI_VERSION = 8
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -157,7 +163,10 @@ for _name, _args in (
         ("pbr_diag_last_deal", [_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
         ("pbr_diag_bvh_build_info", [_vp, ctypes.POINTER(ctypes.c_int)]),
         ("pbr_render_dof", [_vp, ctypes.c_uint32, ctypes.c_uint32, _fp, ctypes.c_float, ctypes.POINTER(Camera)]),       # ABI version 7
-        ("pbr_diag_last_focus_chain", [_vp, ctypes.POINTER(ctypes.c_double)])):
+        ("pbr_diag_last_focus_chain", [_vp, ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_render_adaptive", [_vp, ctypes.c_uint32, _fp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(AdaptiveParams)]),   # ABI version 8
+        ("pbr_read_tile_stats", [_vp, _up, _fp, ctypes.c_uint32, _up]),
+        ("pbr_diag_last_adaptive", [_vp, _up, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -186,6 +195,8 @@ host.pbrh_pt_destroy.restype = None
 host.pbrh_pt_init.argtypes = [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_pt_generate_image.argtypes = [_vp, _fp, _fp]
 host.pbrh_pt_generate_images.argtypes = [_vp, ctypes.c_uint32, _fp]
+if hasattr(host, "pbrh_pt_generate_images_adaptive"):
+    host.pbrh_pt_generate_images_adaptive.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, _fp]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -345,6 +356,7 @@ class Device:
                 self._ctx = None
             raise PbrError(msg)
         self.width = self.height = 0
+        self._shard = (1, 0)
         if os.environ.get("PBR_LAB_ENV") == "1":
             self._apply_lab_environment()
 
@@ -385,6 +397,7 @@ class Device:
     def configure(self, cfg):
         self._check(hip.pbr_configure(self._ctx, ctypes.byref(cfg)))
         self.width, self.height = int(cfg.width), int(cfg.height)
+        self._shard = (int(cfg.tile_world), int(cfg.tile_rank))
 
     def write_input(self, rgba):
         rgba = np.ascontiguousarray(rgba, np.float32)
@@ -409,6 +422,37 @@ class Device:
         to render_frame + accumulate per frame.  With tile sharding: one set_focus_depth before the call."""
         seeds = np.ascontiguousarray(seeds, np.float32)
         self._check(hip.pbr_render_dof(self._ctx, first_sample_count, len(seeds), _as_fp(seeds), px_dim, ctypes.byref(cam)))
+
+    def render_adaptive(self, first_sample_count, seeds, px_dim, cam, min_frames, round_frames, max_frames, threshold):
+        """pbr_render_adaptive: `render` in rounds — min_frames for every tile, then round_frames at a time for the tiles whose
+        error estimate (the relative standard error of the tile's mean luminance) is still above `threshold`, max_frames =
+        len(seeds) at most.  A tile that stopped after c frames holds what render(first_sample_count, seeds[:c]) leaves there."""
+        seeds = np.ascontiguousarray(seeds, np.float32)
+        if len(seeds) != max_frames:
+            raise PbrError("render_adaptive: %d seeds for max_frames = %d" % (len(seeds), max_frames))
+        params = AdaptiveParams(min_frames, round_frames, max_frames, threshold)
+        self._check(hip.pbr_render_adaptive(self._ctx, first_sample_count, _as_fp(seeds), px_dim, ctypes.byref(cam), ctypes.byref(params)))
+
+    def tile_stats(self):
+        """pbr_read_tile_stats: (frames, error) of the last render_adaptive per tile — frames rendered, and the error estimate
+        at the tile's last test.  Unsharded context: two (tiles_y, tiles_x) arrays, row 0 = the bottom tile row like
+        read_output.  A shard (tile_world > 1): (frames, error, tile_ids) in local-tile order, tile_ids = the tiles' global
+        indices ty * tiles_x + tx (tiles.local_tile_ids)."""
+        n = ctypes.c_uint32()
+        self._check(hip.pbr_read_tile_stats(self._ctx, None, None, 0, ctypes.byref(n)))
+        frames, error = np.empty(n.value, np.uint32), np.empty(n.value, np.float32)
+        self._check(hip.pbr_read_tile_stats(self._ctx, frames.ctypes.data_as(_up), _as_fp(error), n.value, ctypes.byref(n)))
+        world, rank = self._shard
+        if world <= 1:
+            shape = (self.height // tiles.TILE, self.width // tiles.TILE)
+            return frames.reshape(shape), error.reshape(shape)
+        return frames, error, tiles.local_tile_ids(self.width, self.height, world, rank)
+
+    def last_adaptive(self):
+        """pbr_diag_last_adaptive: (rounds, (pixel, frame) units traced, ms inside the folds) of the last render_adaptive."""
+        rounds, units, ms = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        self._check(hip.pbr_diag_last_adaptive(self._ctx, ctypes.byref(rounds), ctypes.byref(units), ctypes.byref(ms)))
+        return int(rounds.value), int(units.value), float(ms.value)
 
     def _read(self, fn):
         out = np.empty((self.height, self.width, 4), np.float32)
@@ -671,6 +715,14 @@ class PathTracer:
     def generateImages(self, frames):
         img = np.empty((self.height, self.width, 4), np.float32)
         if host.pbrh_pt_generate_images(self._h, frames, _as_fp(img)) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+        return img
+
+    def generateImagesAdaptive(self, min_frames, round_frames, max_frames, threshold):
+        """PathTracer::generateImagesAdaptive: up to max_frames frames, tiles stop once converged (Device.render_adaptive).
+        Starts a new accumulation and leaves the sample count at 0: the image has a sample count per tile."""
+        img = np.empty((self.height, self.width, 4), np.float32)
+        if host.pbrh_pt_generate_images_adaptive(self._h, min_frames, round_frames, max_frames, threshold, _as_fp(img)) != 0:
             raise PbrError(host.pbrh_last_error().decode())
         return img
 

@@ -15,6 +15,7 @@
 #include "pbr_hip.h"
 #include "pbr_hip_diag.h"
 #include "pt_aux.hpp"
+#include "pt_adaptive.hpp"
 #include "pt_instances.hpp"
 // The schedules that were measured and rejected in rounds 1 - 2 (tile, batched, wavefront, pooled: DESIGN.md 5.1b / 5.1d)
 // are no longer part of this source; their kernels are kept for the record under lab/src/.
@@ -22,6 +23,7 @@
 #include "pt_denoise.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
+#include "pt_adaptive_host.hpp"
 
 using ptk::DevParams;
 
@@ -147,6 +149,19 @@ struct pbr_ctx {
 	unsigned long long* dCounters = nullptr;
 	unsigned int* dWork = nullptr;
 	unsigned int* dGuard = nullptr;
+	// pbr_render_adaptive (launchAdaptive, pt_adaptive.hpp): allocated by the first adaptive call after pbr_configure.  Per local
+	// tile the frames it rendered, its error estimate at its last test and whether it is still active; per pixel slot the
+	// luminance's {mean, M2}; the dealing table of the round (the active tiles only) — the context's own tables stay as they are
+	unsigned* dTileFrames = nullptr;
+	float* dTileError = nullptr;
+	unsigned* dTileActive = nullptr;
+	float2* dMoments = nullptr;
+	unsigned* dAdaptiveOrder = nullptr;
+	hipEvent_t evFoldStart = nullptr, evFoldStop = nullptr;
+	bool adaptiveStats = false;          // dTileFrames / dTileError hold the last adaptive call's
+	uint32_t lastAdaptiveRounds = 0;     // of the last adaptive call: rounds (= convergence tests per tile that reached the end),
+	uint64_t lastAdaptiveUnits = 0;      // (pixel, frame) units traced,
+	double lastAdaptiveFoldMs = 0.0;     // time inside foldFramesAdaptive
 };
 
 namespace {
@@ -230,6 +245,15 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->dLastOrder = nullptr;
 	ctx->hLastOrder.clear();
 	(void) hipFree( ctx->dTileCost );
+	(void) hipFree( ctx->dTileFrames );
+	(void) hipFree( ctx->dTileError );
+	(void) hipFree( ctx->dTileActive );
+	(void) hipFree( ctx->dMoments );
+	(void) hipFree( ctx->dAdaptiveOrder );
+	ctx->dTileFrames = ctx->dTileActive = ctx->dAdaptiveOrder = nullptr;
+	ctx->dTileError = nullptr;
+	ctx->dMoments = nullptr;
+	ctx->adaptiveStats = false;
 	ctx->dTileOrder = ctx->dCostOrder = nullptr;
 	ctx->dTileCost = nullptr;
 	ctx->hTileOrder.clear();
@@ -1140,6 +1164,236 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	return learnTileCosts( ctx, cam, pxDim );
 }
 
+// ---- pbr_render_adaptive: rounds of frames over the tiles that have not converged (pt_adaptive_host.hpp, pt_adaptive.hpp) ----
+// The path-tracing kernels are launch()'s, untouched: a round is runPlan over a dealing table that names the active tiles only
+// (nextSlot takes a band without tiles as exhausted; frameBufIndex, pixelOfSlot and the debug image work on the slot the
+// table names), and foldFramesAdaptive folds and tests exactly those tiles.  numLocalTiles / frameStride stay the full values:
+// they size the frame buffer.  The call neither feeds the schedule tuner nor the tile-cost learner, and the context's dealing
+// tables stay as they are — the renders before and after it behave as if it had not been.
+
+// Which of the context's tables a round of `tiles` active tiles x `frames` frames is filtered from: dealOrder()'s rule by size
+// (a short round: falling cost classes if they have been learnt), for a plan that is fixed.  0 spatial (or pinned), 1 cost
+// classes, 2 expensive last.
+int adaptiveDealTable( const pbr_ctx* ctx, size_t tiles, uint32_t frames ) {
+	const Knobs& knobs = ctx->knobs;
+
+	if( ctx->orderPinned || !ctx->costLearnt || knobs.dealOrder == 0 ) {
+		return 0;
+	}
+
+	const size_t tileFrames = tiles * frames;
+	const size_t costLimit = ( ctx->cfg.tile_world > 1u ) ? kCostOrderShardTileFrames : kCostOrderTileFrames;
+	return ( knobs.dealOrder > 0 ) ? std::min( knobs.dealOrder, 2 ) : ( tileFrames <= costLimit ) ? 1 : ( tileFrames <= kSpatialOrderTileFrames ) ? 0 : 2;
+}
+
+int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float pxDim, const pbr_camera* cam, const pbr_adaptive_params& A ) {
+	if( !ctx->hasScene || !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "render before pbr_upload_scene / pbr_configure" );
+	}
+	if( ctx->cfg.brdf != ctx->sceneBrdf ) {
+		return fail( ctx, PBR_EINVAL, "configured BRDF %u does not match the uploaded materials (BRDF %u)", ctx->cfg.brdf, ctx->sceneBrdf );
+	}
+
+	const bool phong = ( ctx->cfg.phong_tessellation > 0.0f );
+
+	if( phong && ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "Phong tessellation needs a scene with usable vertex normals" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const size_t tiles = (size_t) ctx->numLocalTiles;
+	const size_t pixelSlots = tiles * 64;
+
+	if( ctx->dMoments == nullptr ) {
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileFrames, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileError, sizeof( float ) * std::max<size_t>( 1, tiles ) ) );
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileActive, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dAdaptiveOrder, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dMoments, sizeof( float2 ) * std::max<size_t>( 1, pixelSlots ) ) );
+	}
+
+	ctx->adaptiveStats = false;
+	ctx->lastChainMs = 0.0;
+
+	// the kernels' error flags are of THIS render (host-mapped memory; no launch of this context is in flight here)
+	for( int k = 0; k < 4; k++ ) {
+		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
+	}
+
+	PBR_TRY( stageSeeds( ctx, seeds, A.max_frames ) );
+
+	if( !ctx->workClean ) {
+		HIP_TRY( ctx, hipMemsetAsync( ctx->dWork, 0, kWorkBytes, ctx->stream ) );
+	}
+
+	ctx->workClean = false;
+
+	// the launch's parameters, as launch() sets them for a render without a focus point
+	DevParams P;
+	uint32_t hotAvail = 0;
+	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );
+	P.triPN = ctx->dTriPN;
+	P.phongAlpha = ctx->cfg.phong_tessellation;
+	P.imgIn = ctx->dImgIn;
+	P.imgOut = ctx->dImgOut;
+	P.imgDbg = ctx->dImgDbg;
+	P.counters = ctx->dCounters;
+	P.workCounter = ctx->dWork;
+	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
+	P.aperture = cam->lense[0] / cam->lense[1];
+	P.samplesF = (float) ctx->cfg.samples;
+	P.focusX = cam->focusPoint[0];
+	P.focusY = cam->focusPoint[1];
+	P.focusGiven = 0;
+	P.focusDepth = ctx->focusDepth;
+	P.lenseFocal = cam->lense[0];
+	P.lenseAperture = cam->lense[1];
+	P.tilesX = ctx->tilesX;
+	invariantDivisor( (unsigned) ctx->tilesX, P.tilesXDiv );
+	P.numLocalTiles = ctx->numLocalTiles;
+	P.tileWorld = (int) ctx->cfg.tile_world;
+	P.tileRank = (int) ctx->cfg.tile_rank;
+	P.maxDepth = (int) ctx->cfg.max_depth;
+	P.maxAddedDepth = (int) ctx->cfg.max_added_depth;
+	P.samples = (int) ctx->cfg.samples;
+	P.useExplicitWeight = 0;
+	P.explicitWeight = 0.0f;
+	P.antiAliasing = ctx->cfg.anti_aliasing;
+	P.sky[0] = ctx->cfg.sky_light[0];
+	P.sky[1] = ctx->cfg.sky_light[1];
+	P.sky[2] = ctx->cfg.sky_light[2];
+
+	PBR_TRY( buildPlans( ctx, hotAvail, phong, false ) );
+	size_t chunkCap = 0;
+	PBR_TRY( growFrameBuf( ctx, std::max( A.min_frames, std::min( A.round_frames, A.max_frames ) ), &chunkCap ) );
+
+	// Phong tessellation has one plan; else the pinned plan, else what the tuner has kept, else phased-mid.  No tuning here: a
+	// caller who wants the tuned plan renders with pbr_render first.
+	const int kPhasedMid = 4;
+	const Plan& plan = phong ? ctx->phongPlan
+	                   : ( ctx->pinnedPlan >= 0 ) ? ctx->plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )]
+	                   : ctx->plans[ctx->tuner.settled() ? ctx->tuner.tunedPlan() : kPhasedMid];
+	std::snprintf( ctx->lastPlan, sizeof( ctx->lastPlan ), "%s", plan.name );
+	std::snprintf( ctx->lastKernel, sizeof( ctx->lastKernel ), "%s", plan.kernelName );
+
+	P.frameBuf = ctx->dFrameBuf;
+	P.frameStride = (unsigned) pixelSlots;
+
+	const std::vector<AdaptivePair> pairs = adaptiveSchedule( A.min_frames, A.round_frames, A.max_frames, (uint32_t) chunkCap );
+	std::vector<unsigned> active( tiles, 1u ), order;
+	unsigned first[PT_BANDS + 1];
+	size_t activeTiles = tiles;
+	const unsigned* dTable = nullptr;   // the round's dealing table = the list of its tiles
+	double traceMs = 0.0, foldMs = 0.0;
+	uint32_t launches = 0, rounds = 0;
+	uint64_t units = 0;
+	bool roundStart = true;
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+
+	for( size_t at = 0; at < pairs.size() && activeTiles > 0; at++ ) {
+		const AdaptivePair& pair = pairs[at];
+
+		if( roundStart ) {
+			// the round's frames (its pairs up to the one that ends it) decide the table, the active tiles are filtered from it
+			uint32_t roundFrames = 0;
+
+			for( size_t k = at; k < pairs.size(); k++ ) {
+				roundFrames += pairs[k].frames;
+
+				if( pairs[k].endsRound ) {
+					break;
+				}
+			}
+
+			const int dealt = adaptiveDealTable( ctx, activeTiles, roundFrames );
+			std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", ctx->orderPinned ? "pinned" : ( dealt == 1 ) ? "cost-classes" : ( dealt == 2 ) ? "expensive-last" : "spatial" );
+			const std::vector<unsigned>& table = ( dealt == 1 ) ? ctx->hCostOrder : ( dealt == 2 ) ? ctx->hLastOrder : ctx->hTileOrder;
+			const unsigned* tableFirst = ( dealt != 0 ) ? ctx->costBandFirst : ctx->bandFirst;
+
+			if( activeTiles == tiles ) {
+				dTable = ( dealt == 1 ) ? ctx->dCostOrder : ( dealt == 2 ) ? ctx->dLastOrder : ctx->dTileOrder;
+				std::copy( tableFirst, tableFirst + PT_BANDS + 1, first );
+			}
+			else {
+				filterOrder( table, tableFirst, active.data(), PT_BANDS, &order, first );
+				HIP_TRY( ctx, hipMemcpyAsync( ctx->dAdaptiveOrder, order.data(), sizeof( unsigned ) * order.size(), hipMemcpyHostToDevice, ctx->stream ) );
+				HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // the source is pageable
+				dTable = ctx->dAdaptiveOrder;
+			}
+
+			if( (size_t) first[PT_BANDS] != activeTiles ) {
+				return fail( ctx, PBR_ESTATE, "pbr_render_adaptive: the dealing table names %u of %zu active tiles", first[PT_BANDS], activeTiles );
+			}
+
+			P.tileOrder = dTable;
+
+			for( int band = 0; band < PT_BANDS; band++ ) {
+				P.bandFirst[band] = first[band];
+				P.bandTiles[band] = first[band + 1] - first[band];
+			}
+
+			roundStart = false;
+		}
+
+		const uint32_t n = pair.frames;
+		P.nFrames = (int) n;
+		invariantDivisor( n, P.framesDiv );
+		P.firstCount = (int) ( firstCount + pair.first );
+		P.seeds = ctx->dSeeds + pair.first;
+
+		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStart, ctx->stream ) );
+		PBR_TRY( runPlan( ctx, plan, &P, activeTiles * n ) );
+		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStop, ctx->stream ) );
+		// the running mean so far: the input image for the first pair (every tile is in it), imageOut after that
+		HIP_TRY( ctx, hipEventRecord( ctx->evFoldStart, ctx->stream ) );
+		hipLaunchKernelGGL( ptk::foldFramesAdaptive, dim3( (unsigned) ( ( activeTiles + 3 ) / 4 ) ), dim3( 256 ), 0, ctx->stream, P,
+			(const float4*) ( pair.first == 0 ? ctx->dImgIn : ctx->dImgOut ), ctx->dImgOut, dTable, (unsigned) activeTiles,
+			ctx->dMoments, pair.first, pair.endsRound ? 1 : 0, A.threshold, ctx->dTileFrames, ctx->dTileError, ctx->dTileActive );
+		HIP_TRY( ctx, hipGetLastError() );
+		HIP_TRY( ctx, hipEventRecord( ctx->evFoldStop, ctx->stream ) );
+
+		if( pair.endsRound ) {
+			HIP_TRY( ctx, hipMemcpyAsync( active.data(), ctx->dTileActive, sizeof( unsigned ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
+		}
+
+		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+
+		float ms = 0.0f;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evTraceStart, ctx->evTraceStop ) );
+		traceMs += (double) ms;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evFoldStart, ctx->evFoldStop ) );
+		foldMs += (double) ms;
+		launches++;
+		units += (uint64_t) activeTiles * 64u * n;
+
+		if( pair.endsRound ) {
+			rounds++;
+			activeTiles = 0;
+
+			for( size_t t = 0; t < tiles; t++ ) {
+				activeTiles += ( active[t] != 0u ) ? 1u : 0u;
+			}
+
+			roundStart = true;
+		}
+	}
+
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	ctx->workClean = true;   // the last fold left the queue heads at zero
+
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	ctx->lastTraceMs = traceMs;
+	ctx->lastTraceLaunches = launches;
+	ctx->lastAdaptiveRounds = rounds;
+	ctx->lastAdaptiveUnits = units;
+	ctx->lastAdaptiveFoldMs = foldMs;
+	ctx->adaptiveStats = true;
+	return checkGuard( ctx );
+}
+
 int readTiled( pbr_ctx* ctx, const float4* tiles, float* rgba, int tileWorld, int tileRank ) {
 	if( !ctx->configured || tiles == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "read before pbr_configure (or before pbr_import_tiles)" );
@@ -1220,6 +1474,8 @@ int pbr_create( int device, pbr_ctx** out ) {
 	HIP_TRY( ctx, hipEventCreate( &ctx->evTraceStop ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evStop ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evChainStart ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStart ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStop ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChainCarry, sizeof( float ) ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCounters, sizeof( unsigned long long ) * kCounterSlots ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dWork, kWorkBytes ) );
@@ -1251,6 +1507,8 @@ void pbr_destroy( pbr_ctx* ctx ) {
 		(void) hipEventDestroy( ctx->evTraceStop );
 		(void) hipEventDestroy( ctx->evStop );
 		(void) hipEventDestroy( ctx->evChainStart );
+		(void) hipEventDestroy( ctx->evFoldStart );
+		(void) hipEventDestroy( ctx->evFoldStop );
 		(void) hipFree( ctx->dChainCarry );
 		(void) hipStreamDestroy( ctx->stream );
 	}
@@ -1489,6 +1747,56 @@ int pbr_render_dof( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames
 	// result in imageOut AND imageIn
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
 	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	return PBR_OK;
+}
+
+int pbr_render_adaptive( pbr_ctx* ctx, uint32_t first_sample_count, const float* seeds, float pxDim, const pbr_camera* cam, const pbr_adaptive_params* params ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+
+	std::string why;
+
+	if( adaptiveCheck( params, seeds, cam, &why ) != PBR_OK ) {
+		return fail( ctx, PBR_EINVAL, "%s", why.c_str() );
+	}
+
+	PBR_TRY( launchAdaptive( ctx, first_sample_count, seeds, pxDim, cam, *params ) );
+
+	// result in imageOut AND imageIn, as pbr_render leaves it
+	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	return PBR_OK;
+}
+
+int pbr_read_tile_stats( pbr_ctx* ctx, uint32_t* frames, float* error, uint32_t capacity, uint32_t* count ) {
+	if( ctx == nullptr || count == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "read_tile_stats: null argument" );
+	}
+	if( !ctx->configured || !ctx->adaptiveStats ) {
+		return fail( ctx, PBR_ESTATE, "read_tile_stats before pbr_render_adaptive" );
+	}
+
+	*count = (uint32_t) ctx->numLocalTiles;
+
+	if( frames == nullptr && error == nullptr ) {
+		return PBR_OK;
+	}
+	if( capacity < *count ) {
+		return fail( ctx, PBR_EINVAL, "read_tile_stats: %u entries for %u local tiles", capacity, *count );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( frames != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( frames, ctx->dTileFrames, sizeof( uint32_t ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+	if( error != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( error, ctx->dTileError, sizeof( float ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -2442,6 +2750,20 @@ int pbr_diag_last_focus_chain( pbr_ctx* ctx, double* ms ) {
 	}
 
 	*ms = ctx->lastChainMs;
+	return PBR_OK;
+}
+
+int pbr_diag_last_adaptive( pbr_ctx* ctx, uint32_t* rounds, uint64_t* units_traced, double* fold_ms ) {
+	if( ctx == nullptr || rounds == nullptr || units_traced == nullptr || fold_ms == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_last_adaptive: null argument" );
+	}
+	if( !ctx->adaptiveStats ) {
+		return fail( ctx, PBR_ESTATE, "diag_last_adaptive before pbr_render_adaptive" );
+	}
+
+	*rounds = ctx->lastAdaptiveRounds;
+	*units_traced = ctx->lastAdaptiveUnits;
+	*fold_ms = ctx->lastAdaptiveFoldMs;
 	return PBR_OK;
 }
 

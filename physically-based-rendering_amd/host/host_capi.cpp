@@ -256,6 +256,20 @@ int pbrh_pt_generate_images( void* tracer, uint32_t frames, float* image ) {
 	}
 }
 
+int pbrh_pt_generate_images_adaptive( void* tracer, uint32_t min_frames, uint32_t round_frames, uint32_t max_frames, float threshold, float* image ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		const std::vector<float> img = t->pt.generateImagesAdaptive( min_frames, round_frames, max_frames, threshold );
+		std::memcpy( image, img.data(), img.size() * sizeof( float ) );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 void pbrh_pt_set_focus( void* tracer, int x, int y ) {
 	static_cast<HostTracer*>( tracer )->pt.setFocus( x, y );
 }

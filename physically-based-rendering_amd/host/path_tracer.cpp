@@ -433,6 +433,29 @@ std::vector<float> PathTracer::generateImages( uint32_t frames ) {
 	return image;
 }
 
+std::vector<float> PathTracer::generateImagesAdaptive( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, float threshold ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] generateImagesAdaptive before initOpenCLBuffers" );
+	}
+
+	this->updateEyeBuffer();
+	mSampleCount = 0;
+
+	std::vector<float> seeds( maxFrames );
+
+	for( uint32_t k = 0; k < maxFrames; k++ ) {
+		seeds[k] = mSeedStep * (float) ( k + 1 );
+	}
+
+	const pbr_adaptive_params params = { minFrames, roundFrames, maxFrames, threshold };
+	this->check( pbr_render_adaptive( mCtx, 0, seeds.data(), pixelDimension( mWidth, mHeight, mFOV ), &mStructCam, &params ), "pbr_render_adaptive" );
+
+	std::vector<float> image( (size_t) mWidth * mHeight * 4 );
+	this->check( pbr_read_output( mCtx, image.data() ), "pbr_read_output" );
+
+	return image;
+}
+
 // PathTracer::resetSampleCount, PathTracer.cpp:576-578.  The image is NOT cleared: the next
 // frame's pixelWeight is 0, which overwrites the colour, and depth of field still needs the
 // previous frame's hit distances in .w (pathtracing.cl:58-65).

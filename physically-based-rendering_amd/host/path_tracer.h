@@ -74,6 +74,11 @@ class PathTracer {
 		std::vector<float> generateImage( std::vector<float>* textureDebug );
 		// `frames` x generateImage in one device launch (no per-frame host round trip).
 		std::vector<float> generateImages( uint32_t frames );
+		// generateImages with adaptive sampling (pbr_render_adaptive): minFrames for every 8x8 tile, then roundFrames at a time
+		// for the tiles whose error estimate is above `threshold`, maxFrames at most.  A NEW accumulation (sample count 0), and
+		// the sample count is 0 again afterwards: the image then has a count per tile, which no later frame can continue.
+		// Needs a camera without a focus point (setFocus): depth of field reads the focus pixel's every frame.
+		std::vector<float> generateImagesAdaptive( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, float threshold );
 
 		void resetSampleCount();
 		void setCamera( Camera* camera ) { mCamera = camera; }

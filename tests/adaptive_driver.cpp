@@ -1,0 +1,44 @@
+// Exposes the host-only unit of pbr_render_adaptive (physically-based-rendering_amd/csrc/pt_adaptive_host.hpp) to ctypes
+// (tests/test_adaptive_cpu.py): built with a plain C++17 compiler, no HIP.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "pt_adaptive_host.hpp"
+
+extern "C" {
+
+// -> entries written to out (the surviving tiles); outFirst[bands + 1]
+unsigned adp_filter_order( const unsigned* order, unsigned count, const unsigned* bandFirst, const unsigned* active, int bands, unsigned* out, unsigned* outFirst ) {
+	const std::vector<unsigned> table( order, order + count );
+	std::vector<unsigned> kept;
+	filterOrder( table, bandFirst, active, bands, &kept, outFirst );
+	std::memcpy( out, kept.data(), sizeof( unsigned ) * kept.size() );
+	return (unsigned) kept.size();
+}
+
+// -> launch pairs (capacity entries of {first, frames, endsRound} at most are written); *rounds
+unsigned adp_schedule( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, uint32_t chunkCap, uint32_t* out, unsigned capacity, uint32_t* rounds ) {
+	const std::vector<AdaptivePair> pairs = adaptiveSchedule( minFrames, roundFrames, maxFrames, chunkCap );
+
+	for( size_t k = 0; k < pairs.size() && k < capacity; k++ ) {
+		out[3 * k + 0] = pairs[k].first;
+		out[3 * k + 1] = pairs[k].frames;
+		out[3 * k + 2] = pairs[k].endsRound ? 1u : 0u;
+	}
+
+	*rounds = adaptiveRounds( pairs );
+	return (unsigned) pairs.size();
+}
+
+// what pbr_render_adaptive answers to these arguments, before it touches the context
+int adp_check( const pbr_adaptive_params* params, int haveSeeds, const pbr_camera* cam, char* message, size_t capacity ) {
+	const float seed = 0.0f;
+	std::string why;
+	const int status = adaptiveCheck( params, haveSeeds ? &seed : nullptr, cam, &why );
+	std::strncpy( message, why.c_str(), capacity - 1 );
+	message[capacity - 1] = 0;
+	return status;
+}
+
+}
