@@ -31,10 +31,11 @@ extern "C" {
 #endif
 
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
- * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive).  A caller that loads the library at run time — or
+ * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
+ * version 9 pbr_update_vertices and pbr_read_bvh).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 8
+#define PBR_ABI_VERSION 9
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -163,6 +164,42 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* scene );
  * it circle forever) — leaf pairs k, k + 1, the last node a leaf, vertex and material indices of every face.
  * Returns PBR_OK or PBR_EINVAL with the reason in message[capacity]. */
 int pbr_validate_scene( const pbr_scene_desc* scene, char* message, size_t capacity );
+
+/* Moving geometry (not in the reference, whose scene is static): replaces the vertex positions of the uploaded scene and
+ * rebuilds ON THE DEVICE everything that was derived from them — the face records {a, b - a, c - a, material}, the per-face
+ * normals (unless the "face_normals" knob was 0 at the upload) and every node's box (a REFIT: the tree's links, the faces,
+ * materials and lights are kept).  `vertices` is host memory, borrowed for the call; num_vertices must be the upload's.
+ * pbr_last_kernel_ms then reports the device time of the update's kernels; the copy of the vertices to the device is NOT in
+ * it (pbr_diag_refit_info, pbr_hip_diag.h, reports it next to it).
+ * The boxes, operation by operation, per component in binary32 — reproducible to the bit:
+ *   leaf       start from corner a of its first face; fold in b, c, then the second face's a, b, c if there is one, with
+ *              lo = ( v < lo ) ? v : lo and hi = ( v > hi ) ? v : hi;
+ *   container  (node 0 included) the same fold over its children's boxes in depth-first child order, starting from the first
+ *              child's box; the children of i are c0 = i + 1, c1 = end( c0 ), ... below end( i ) (there can be more than two);
+ *   the .w words are unchanged.
+ * These are tight boxes of the flat triangles, NOT the reference builder's (MathHelp.cpp:260-309 thickens a triangle's box
+ * for Phong tessellation): an update with the very vertices that were uploaded may change boxes, and — through tNear,
+ * pt_intersect.cl:96-97 — bits of t.  THE CONTRACT is equality with a fresh upload, not with the state before: after
+ * pbr_upload_scene( S ) and pbr_update_vertices( V' ) every call (pbr_render*, pbr_render_frame, pbr_diag_trace,
+ * pbr_denoise, the counters, the debug image) gives bit for bit what it gives after pbr_upload_scene( S' ), S' = S with the
+ * vertices V' and the nodes pbr_read_bvh returns.  Only speed may differ: the ranking of the nodes staged in LDS, the schedule
+ * tuner's kept plan, the learnt tile costs and the dealing orders stay from before the update (pbr_diag_set_knob or a new
+ * upload re-tunes).  The accumulated image is not touched: resetting it is the caller's business, as after a camera move.
+ * Refusals, each leaving the context unchanged:
+ *   PBR_ESTATE  no scene; a tree that is not properly nested (pbr_validate_scene accepts any forward link, a refit needs the
+ *               children of every container to tile [i + 1, end( i )) exactly, and no container without a child — decided at
+ *               the upload, the reason is in the message); a ray-ordered traversal (traversal != 0) is configured (its streams
+ *               carry child orders built from the old box centres: configure traversal 0, update, configure the ordered walk
+ *               again — it is then built from the refitted boxes, bit-identical to a fresh upload of S' + the same
+ *               pbr_configure); phong_tessellation > 0 is configured.
+ *   PBR_EINVAL  a null pointer, num_vertices other than the upload's, a coordinate that is not finite (checked on the host).
+ * After an update pbr_configure refuses phong_tessellation > 0 (PBR_ESTATE) until the next pbr_upload_scene: tight boxes
+ * would clip the patches, and the patches' corners are not updated. */
+int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices );
+/* The current tree in the wire format: the uploaded nodes, after pbr_update_vertices with the refitted boxes (copied back
+ * from the device by this call, not by the update).  *num_nodes = the node count; nodes_out = NULL returns the count only,
+ * else capacity >= *num_nodes entries.  A caller's rebuild heuristic (e.g. the growth of the boxes' surface area) reads this. */
+int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint32_t* num_nodes );
 
 /* CL::loadProgram + createKernel + initKernelArgs (PathTracer.cpp:225-229, :88-125) and
  * initOpenCLBuffers_Textures (:525-533): selects the kernel variant, allocates the three

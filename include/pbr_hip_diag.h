@@ -58,8 +58,19 @@ int pbr_diag_last_plan( pbr_ctx* ctx, char* name, size_t capacity, int* tuned );
 int pbr_diag_bvh_build_info( pbr_ctx* ctx, int* radius );
 
 /* Device memory of the uploaded scene's arrays, bytes: [0] the node stream in the reference's order, [1] the streams of
- * the ray-ordered walk (0 unless such a mode is configured: six or eight times [0], compact records twice [0]), [2] the face records. */
+ * the ray-ordered walk (0 unless such a mode is configured: six or eight times [0], compact records twice [0]), [2] the face records.
+ * Not in these figures: what the upload keeps for pbr_update_vertices — 16 bytes per face and per vertex, 10 per node, 4 per
+ * thread slot of the refit's workgroups; pbr_diag_refit_info below reports it. */
 int pbr_diag_scene_bytes( pbr_ctx* ctx, uint64_t out[3] );
+
+/* What pbr_upload_scene keeps for pbr_update_vertices (csrc/pt_refit_host.hpp), beyond pbr_diag_scene_bytes' three figures:
+ * out[0] 1 if the tree can be refitted (properly nested; else `why` holds the reason), [1] the cap S of a subtree's nodes,
+ * [2] the workgroups of the subtree kernel, [3] the maximal subtrees of at most S nodes they share, [4] the nodes above the
+ * cut and [5] their levels (one more launch), [6] the device bytes kept for updates — 16 per face (its vertex indices), 16 per
+ * vertex, 10 per node (a word, a height, its record) and 4 per thread slot of [2] x S, nothing for a tree that cannot be
+ * refitted —, [7] the updates since the upload.  *upload_ms: the host's time inside the copy of the last update's vertices to
+ * the device (pbr_last_kernel_ms excludes it).  upload_ms and why may be NULL. */
+int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char* why, size_t capacity );
 
 /* The kernel behind pbr_diag_last_plan's schedule, as a profiler prints its symbol (without "void " and the argument
  * list): "ptk_f0::pathTracingDual<1, false, false>" — namespace ptk_f<flavour> (bit 0: ray-ordered walk, bit 1: native

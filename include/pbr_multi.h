@@ -42,6 +42,9 @@ pbr_ctx* pbr_multi_context( pbr_multi* m, int rank );
 
 /* pbr_upload_scene on every context, concurrently (the scene is replicated). */
 int pbr_multi_upload_scene( pbr_multi* m, const pbr_scene_desc* scene );
+/* pbr_update_vertices on every context, concurrently: every context refits its own copy of the scene, no collective.  A
+ * refusal (pbr_hip.h) is the same on every rank and leaves all of them unchanged. */
+int pbr_multi_update_vertices( pbr_multi* m, const pbr_float4* vertices, uint32_t num_vertices );
 /* pbr_configure on every context with tile_world = count, tile_rank = its rank (the caller's values are ignored);
  * allocates the exchange buffers. */
 int pbr_multi_configure( pbr_multi* m, const pbr_config* cfg );

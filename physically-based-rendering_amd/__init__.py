@@ -102,7 +102,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 8
+ABI_VERSION = 9
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -166,7 +166,10 @@ for _name, _args in (
         ("pbr_diag_last_focus_chain", [_vp, ctypes.POINTER(ctypes.c_double)]),
         ("pbr_render_adaptive", [_vp, ctypes.c_uint32, _fp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(AdaptiveParams)]),   # ABI version 8
         ("pbr_read_tile_stats", [_vp, _up, _fp, ctypes.c_uint32, _up]),
-        ("pbr_diag_last_adaptive", [_vp, _up, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)])):
+        ("pbr_diag_last_adaptive", [_vp, _up, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_update_vertices", [_vp, ctypes.c_void_p, ctypes.c_uint32]),                                                # ABI version 9
+        ("pbr_read_bvh", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up]),
+        ("pbr_diag_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -197,6 +200,8 @@ host.pbrh_pt_generate_image.argtypes = [_vp, _fp, _fp]
 host.pbrh_pt_generate_images.argtypes = [_vp, ctypes.c_uint32, _fp]
 if hasattr(host, "pbrh_pt_generate_images_adaptive"):
     host.pbrh_pt_generate_images_adaptive.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, _fp]
+if hasattr(host, "pbrh_pt_update_vertices"):
+    host.pbrh_pt_update_vertices.argtypes = [_vp, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -393,6 +398,31 @@ class Device:
 
     def upload_scene(self, desc):
         self._check(hip.pbr_upload_scene(self._ctx, ctypes.byref(desc)))
+
+    def update_vertices(self, vertices):
+        """pbr_update_vertices: new positions, (n, 4) float32 with n as uploaded, for the uploaded scene; face records, face
+        normals and every node's box are rebuilt on the device (a refit: the tree's links stay).  Afterwards every call gives
+        bit for bit what it gives after a fresh upload of the scene with these vertices and the nodes read_bvh() returns."""
+        vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        self._check(hip.pbr_update_vertices(self._ctx, vertices.ctypes.data, vertices.shape[0]))
+
+    def read_bvh(self):
+        """pbr_read_bvh: the current tree, (nodes, 8) float32 in the wire format — the uploaded nodes, after update_vertices
+        with the refitted boxes."""
+        n = ctypes.c_uint32()
+        self._check(hip.pbr_read_bvh(self._ctx, None, 0, ctypes.byref(n)))
+        nodes = np.empty((n.value, 8), np.float32)
+        self._check(hip.pbr_read_bvh(self._ctx, nodes.ctypes.data, n.value, ctypes.byref(n)))
+        return nodes
+
+    def refit_info(self):
+        """pbr_diag_refit_info: what the upload keeps for update_vertices, and the last update's vertex copy time."""
+        out, ms, why = (ctypes.c_uint64 * 8)(), ctypes.c_double(), ctypes.create_string_buffer(256)
+        self._check(hip.pbr_diag_refit_info(self._ctx, out, ctypes.byref(ms), why, 256))
+        keys = ("nested", "subtree_cap", "workgroups", "subtrees", "top_nodes", "top_levels", "device_bytes", "updates")
+        info = dict(zip(keys, [int(v) for v in out]))
+        info["nested"], info["upload_ms"], info["why"] = bool(info["nested"]), float(ms.value), why.value.decode()
+        return info
 
     def configure(self, cfg):
         self._check(hip.pbr_configure(self._ctx, ctypes.byref(cfg)))
@@ -725,6 +755,12 @@ class PathTracer:
         if host.pbrh_pt_generate_images_adaptive(self._h, min_frames, round_frames, max_frames, threshold, _as_fp(img)) != 0:
             raise PbrError(host.pbrh_last_error().decode())
         return img
+
+    def updateVertices(self, vertices):
+        """PathTracer::updateVertices: Device.update_vertices on the tracer's context; starts a new accumulation."""
+        vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        if host.pbrh_pt_update_vertices(self._h, _as_fp(vertices), vertices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
 
     def setFocus(self, x, y):
         host.pbrh_pt_set_focus(self._h, x, y)

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <chrono>
 #include <cstring>
 #include <string>
 #include <algorithm>
@@ -24,6 +25,8 @@
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 #include "pt_adaptive_host.hpp"
+#include "pt_refit_host.hpp"
+#include "pt_refit.hpp"
 
 using ptk::DevParams;
 
@@ -86,6 +89,24 @@ struct pbr_ctx {
 	uint64_t nodeBytes = 0, walkBytes = 0, triBytes = 0;   // device bytes of the reference-order stream, the ordered streams, the face records
 	uint32_t numNodes = 0, numFaces = 0, numMaterials = 0, numLights = 0;
 	uint32_t sceneBrdf = 1;
+	// pbr_update_vertices (pt_refit_host.hpp, pt_refit.hpp): kept from the upload — the faces' vertex indices, a buffer for the
+	// vertices, node 0's box (it has no record), and the refit's tables: thread slots, per-node words and heights, node ->
+	// record, the nodes above the cut by level.  refit keeps the verdict, recordOf and the partition's sizes on the host
+	RefitPlan refit;
+	uint4* dFacesV = nullptr;
+	float4* dVertices = nullptr;
+	float4* dRootBox = nullptr;
+	unsigned* dRefitSlots = nullptr;
+	unsigned* dRefitInfo = nullptr;
+	unsigned short* dRefitHeights = nullptr;
+	int* dRefitRecordOf = nullptr;
+	unsigned* dRefitTop = nullptr;
+	unsigned* dRefitLevelFirst = nullptr;
+	uint32_t numVertices = 0, refitGroups = 0, refitLevels = 0, refitTopNodes = 0, refitSubtrees = 0;
+	uint64_t refitBytes = 0;       // device bytes of all of the above
+	uint32_t refitUpdates = 0;     // pbr_update_vertices calls since the upload: > 0 = the boxes are refitted ones, dTriPN is stale
+	bool treeStale = false;        // tree.bvh's boxes are older than the device's (refreshTree)
+	double lastRefitUploadMs = 0.0;
 
 	// configuration + images
 	bool configured = false;
@@ -215,6 +236,23 @@ void freeScene( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dMats );
 	(void) hipFree( ctx->dLights );
 	ctx->dNodes = ctx->dTris = ctx->dMats = ctx->dLights = nullptr;
+	(void) hipFree( ctx->dFacesV );
+	(void) hipFree( ctx->dVertices );
+	(void) hipFree( ctx->dRootBox );
+	(void) hipFree( ctx->dRefitSlots );
+	(void) hipFree( ctx->dRefitInfo );
+	(void) hipFree( ctx->dRefitHeights );
+	(void) hipFree( ctx->dRefitRecordOf );
+	(void) hipFree( ctx->dRefitTop );
+	(void) hipFree( ctx->dRefitLevelFirst );
+	ctx->dFacesV = nullptr;
+	ctx->dVertices = ctx->dRootBox = nullptr;
+	ctx->dRefitSlots = ctx->dRefitInfo = ctx->dRefitTop = ctx->dRefitLevelFirst = nullptr;
+	ctx->dRefitHeights = nullptr;
+	ctx->dRefitRecordOf = nullptr;
+	ctx->refitBytes = 0;
+	ctx->refitUpdates = 0;
+	ctx->treeStale = false;
 	ctx->hasScene = false;
 }
 
@@ -376,7 +414,34 @@ int uploadWalkStreams( pbr_ctx* ctx, const PackedWalk& walk, uint32_t layout ) {
 	return PBR_OK;
 }
 
+// The host copy of the tree after pbr_update_vertices: the boxes come back from the device when somebody asks for them
+// (pbr_read_bvh, a ray-ordered walk to build) — an update itself copies nothing back.
+int refreshTree( pbr_ctx* ctx ) {
+	if( !ctx->treeStale ) {
+		return PBR_OK;
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	std::vector<Quad> records( ctx->nodeBytes / sizeof( Quad ) );
+	Quad root[2];
+	HIP_TRY( ctx, hipMemcpy( records.data(), ctx->dNodes, ctx->nodeBytes, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( root, ctx->dRootBox, sizeof( root ), hipMemcpyDeviceToHost ) );
+	std::vector<pbr_bvh_node>& bvh = ctx->tree.bvh;
+	bvh[0].bbMin = pbr_float4 { root[0].x, root[0].y, root[0].z, bvh[0].bbMin.w };
+	bvh[0].bbMax = pbr_float4 { root[1].x, root[1].y, root[1].z, bvh[0].bbMax.w };
+
+	for( uint32_t i = 1; i < ctx->tree.size(); i++ ) {
+		const Quad* rec = records.data() + (size_t) ctx->refit.recordOf[i] * 2;
+		bvh[i].bbMin = pbr_float4 { rec[0].x, rec[0].y, rec[1].x, bvh[i].bbMin.w };
+		bvh[i].bbMax = pbr_float4 { rec[0].z, rec[0].w, rec[1].y, bvh[i].bbMax.w };
+	}
+
+	ctx->treeStale = false;
+	return PBR_OK;
+}
+
 int buildWalkStreams( pbr_ctx* ctx, uint32_t layout ) {
+	PBR_TRY( refreshTree( ctx ) );
 	PackedWalk walk;
 	PBR_TRY( packWalk( ctx->tree, layout, &walk, &ctx->error ) );
 	return uploadWalkStreams( ctx, walk, layout );
@@ -1543,6 +1608,8 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	PackedWalk walk;
 	PBR_TRY( checkScene( s, &tree, &ctx->error ) );
 	PBR_TRY( packScene( s, tree, &packed, &ctx->error ) );
+	RefitPlan refit;
+	planRefit( tree, packed.nodes.recordOf, kRefitSubtree, &refit );   // a tree that cannot be refitted uploads all the same: refit.why
 
 	if( ctx->configured ) {
 		PBR_TRY( packConfiguredWalk( ctx, ctx->cfg, &tree, &walk ) );
@@ -1579,6 +1646,44 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
+	// what pbr_update_vertices needs on the device
+	ctx->refitBytes = 0;
+
+	if( refit.nested ) {
+		auto keep = [ctx]( void** dst, const void* src, size_t bytes ) {
+			HIP_TRY( ctx, hipMalloc( dst, std::max<size_t>( bytes, 16 ) ) );
+
+			if( src != nullptr && bytes > 0 ) {
+				HIP_TRY( ctx, hipMemcpy( *dst, src, bytes, hipMemcpyHostToDevice ) );
+			}
+
+			ctx->refitBytes += bytes;
+			return PBR_OK;
+		};
+		const Quad rootBox[2] = { { s->bvh[0].bbMin.x, s->bvh[0].bbMin.y, s->bvh[0].bbMin.z, -1.0f }, { s->bvh[0].bbMax.x, s->bvh[0].bbMax.y, s->bvh[0].bbMax.z, -1.0f } };
+		PBR_TRY( keep( (void**) &ctx->dFacesV, s->facesV, sizeof( pbr_uint4 ) * s->num_faces ) );
+		PBR_TRY( keep( (void**) &ctx->dVertices, nullptr, sizeof( pbr_float4 ) * s->num_vertices ) );
+		PBR_TRY( keep( (void**) &ctx->dRootBox, rootBox, sizeof( rootBox ) ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitSlots, refit.slots.data(), sizeof( uint32_t ) * refit.slots.size() ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitInfo, refit.info.data(), sizeof( uint32_t ) * refit.info.size() ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitHeights, refit.height16.data(), sizeof( uint16_t ) * refit.height16.size() ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitRecordOf, refit.recordOf.data(), sizeof( int ) * refit.recordOf.size() ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitTop, refit.topNodes.data(), sizeof( uint32_t ) * refit.topNodes.size() ) );
+		PBR_TRY( keep( (void**) &ctx->dRefitLevelFirst, refit.topLevelFirst.data(), sizeof( uint32_t ) * refit.topLevelFirst.size() ) );
+	}
+
+	ctx->refitGroups = refit.numGroups();
+	ctx->refitLevels = refit.numLevels();
+	ctx->refitTopNodes = (uint32_t) refit.topNodes.size();
+	ctx->refitSubtrees = (uint32_t) refit.subtreeRoots.size();
+	ctx->numVertices = s->num_vertices;
+	// the host keeps the verdict and node -> record; the rest is on the device now
+	for( std::vector<uint32_t>* v : { &refit.parent, &refit.end, &refit.height, &refit.subtreeRoots, &refit.groupFirst, &refit.slots, &refit.topNodes, &refit.topLevelFirst, &refit.info } ) {
+		std::vector<uint32_t>().swap( *v );
+	}
+	std::vector<uint16_t>().swap( refit.height16 );
+	ctx->refit = std::move( refit );
+
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	ctx->numHotAvail = packed.nodes.hotSlots;
 	ctx->firstRef = packed.nodes.first[0];
@@ -1592,6 +1697,87 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	ctx->hasScene = true;
 
 	return walk.storage.empty() ? PBR_OK : uploadWalkStreams( ctx, walk, ctx->cfg.traversal );
+}
+
+int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices before pbr_upload_scene" );
+	}
+
+	PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error ) );
+
+	if( !ctx->refit.nested ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", ctx->refit.why.c_str() );
+	}
+	if( ctx->configured && ctx->cfg.traversal != 0 ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while a ray-ordered traversal (%u) is configured: its streams carry child orders built from the old boxes — configure traversal 0, update, then configure the ordered walk again", ctx->cfg.traversal );
+	}
+	if( ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while Phong tessellation is configured: tight boxes of the flat triangles would clip the patches" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const auto uploadStart = std::chrono::steady_clock::now();
+	HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
+	ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+
+	const uint32_t F = ctx->numFaces;
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dVertices, ctx->dTris, (int) F );
+	HIP_TRY( ctx, hipGetLastError() );
+
+	if( ctx->dFaceN != nullptr ) {
+		DevParams P;
+		std::memset( &P, 0, sizeof( P ) );
+		P.tris = ctx->dTris;
+		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->dFaceN, (int) F );
+		HIP_TRY( ctx, hipGetLastError() );
+	}
+
+	hipLaunchKernelGGL( ptr::refitSubtrees, dim3( ctx->refitGroups ), dim3( REFIT_SUBTREE ), 0, ctx->stream, ctx->dRefitSlots, ctx->dRefitInfo,
+	                    ctx->dRefitHeights, ctx->dRefitRecordOf, ctx->dFacesV, ctx->dVertices, ctx->dNodes, ctx->dRootBox );
+	HIP_TRY( ctx, hipGetLastError() );
+
+	if( ctx->refitLevels > 0 ) {
+		hipLaunchKernelGGL( ptr::refitTop, dim3( 1 ), dim3( REFIT_TOP_THREADS ), 0, ctx->stream, ctx->dRefitTop, ctx->dRefitLevelFirst, (int) ctx->refitLevels,
+		                    ctx->dRefitInfo, ctx->dRefitRecordOf, ctx->dNodes, ctx->dRootBox );
+		HIP_TRY( ctx, hipGetLastError() );
+	}
+
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = ms;
+	ctx->treeStale = true;
+	ctx->refitUpdates++;
+	freeWalkStreams( ctx );   // none while traversal 0 is configured; an unconfigured context may hold a previous mode's
+	return PBR_OK;
+}
+
+int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint32_t* num_nodes ) {
+	if( ctx == nullptr || !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_read_bvh before pbr_upload_scene" );
+	}
+	if( num_nodes == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_bvh: null num_nodes" );
+	}
+
+	*num_nodes = ctx->tree.size();
+
+	if( nodes_out == nullptr ) {
+		return PBR_OK;
+	}
+	if( capacity < ctx->tree.size() ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_bvh: room for %u nodes, the tree has %u", capacity, ctx->tree.size() );
+	}
+
+	PBR_TRY( refreshTree( ctx ) );
+	std::memcpy( nodes_out, ctx->tree.bvh.data(), sizeof( pbr_bvh_node ) * ctx->tree.size() );
+	return PBR_OK;
 }
 
 int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
@@ -1613,6 +1799,9 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs vertex normals: the uploaded scene's facesN / normals are missing or out of range" );
 	}
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 ) {
+		return fail( ctx, PBR_ESTATE, "Phong tessellation after pbr_update_vertices: the refitted boxes are tight boxes of the flat triangles and would clip the patches, and the patches' corners were not updated — upload the scene again" );
+	}
 	if( cfg->traversal > 3 || cfg->arith > 1 ) {
 		return fail( ctx, PBR_EINVAL, "traversal must be 0 (the reference's walk), 1 (six orders), 2 (eight orders) or 3 (eight orders, compact records); arith 0 (exact) or 1 (native)" );
 	}
@@ -1622,7 +1811,13 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 
 	// the records of the configured walk for the scene there is, unless they are there already: packed before anything changes
 	PackedWalk walk;
-	PBR_TRY( packConfiguredWalk( ctx, *cfg, ( ctx->hasScene && ctx->walkBuilt != cfg->traversal ) ? &ctx->tree : nullptr, &walk ) );
+	const bool packsWalk = ( ctx->hasScene && ctx->walkBuilt != cfg->traversal );
+
+	if( packsWalk && cfg->traversal != 0 ) {
+		PBR_TRY( refreshTree( ctx ) );   // after pbr_update_vertices: the orders are built from the refitted boxes
+	}
+
+	PBR_TRY( packConfiguredWalk( ctx, *cfg, packsWalk ? &ctx->tree : nullptr, &walk ) );
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeImages( ctx );
@@ -2584,6 +2779,30 @@ int pbr_diag_scene_bytes( pbr_ctx* ctx, uint64_t out[3] ) {
 	out[0] = ctx->nodeBytes;
 	out[1] = ctx->walkBytes;
 	out[2] = ctx->triBytes;
+	return PBR_OK;
+}
+
+int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char* why, size_t capacity ) {
+	if( ctx == nullptr || out == nullptr || !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "diag_refit_info: no scene" );
+	}
+
+	out[0] = ctx->refit.nested ? 1 : 0;
+	out[1] = ctx->refit.subtreeCap;
+	out[2] = ctx->refitGroups;
+	out[3] = ctx->refitSubtrees;
+	out[4] = ctx->refitTopNodes;
+	out[5] = ctx->refitLevels;
+	out[6] = ctx->refitBytes;
+	out[7] = ctx->refitUpdates;
+
+	if( upload_ms != nullptr ) {
+		*upload_ms = ctx->lastRefitUploadMs;
+	}
+	if( why != nullptr && capacity > 0 ) {
+		std::snprintf( why, capacity, "%s", ctx->refit.why.c_str() );
+	}
+
 	return PBR_OK;
 }
 

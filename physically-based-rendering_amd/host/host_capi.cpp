@@ -270,6 +270,19 @@ int pbrh_pt_generate_images_adaptive( void* tracer, uint32_t min_frames, uint32_
 	}
 }
 
+int pbrh_pt_update_vertices( void* tracer, const float* vertices, uint32_t num_vertices ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateVertices( reinterpret_cast<const pbr_float4*>( vertices ), num_vertices );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 void pbrh_pt_set_focus( void* tracer, int x, int y ) {
 	static_cast<HostTracer*>( tracer )->pt.setFocus( x, y );
 }

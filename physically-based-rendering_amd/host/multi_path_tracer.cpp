@@ -245,6 +245,11 @@ int MultiPathTracer::uploadScene( const pbr_scene_desc* scene ) {
 	return onEveryRank( [&]( int r ) { return pbr_upload_scene( mRanks[(size_t) r].ctx, scene ); } );
 }
 
+// the scene is replicated: every context refits its own copy, on its own thread; no collective
+int MultiPathTracer::updateVertices( const pbr_float4* vertices, uint32_t numVertices ) {
+	return onEveryRank( [&]( int r ) { return pbr_update_vertices( mRanks[(size_t) r].ctx, vertices, numVertices ); } );
+}
+
 int MultiPathTracer::configure( const pbr_config* cfg ) {
 	if( cfg == nullptr ) {
 		mError = "pbr_multi_configure: null config";
@@ -656,6 +661,10 @@ pbr_ctx* pbr_multi_context( pbr_multi* m, int rank ) {
 
 int pbr_multi_upload_scene( pbr_multi* m, const pbr_scene_desc* scene ) {
 	return ( m == nullptr ) ? PBR_EINVAL : done( m, m->impl->uploadScene( scene ) );
+}
+
+int pbr_multi_update_vertices( pbr_multi* m, const pbr_float4* vertices, uint32_t num_vertices ) {
+	return ( m == nullptr ) ? PBR_EINVAL : done( m, m->impl->updateVertices( vertices, num_vertices ) );
 }
 
 int pbr_multi_configure( pbr_multi* m, const pbr_config* cfg ) {

@@ -69,6 +69,7 @@ class MultiPathTracer {
 		const std::string& lastError() const { return mError; }
 
 		int uploadScene( const pbr_scene_desc* scene );
+		int updateVertices( const pbr_float4* vertices, uint32_t numVertices );
 		int configure( const pbr_config* cfg );
 		int resetAccum();
 		int tune( uint32_t framesPerCall, float pxDim, const pbr_camera* cam, int* plan, int* votes );

@@ -433,6 +433,15 @@ std::vector<float> PathTracer::generateImages( uint32_t frames ) {
 	return image;
 }
 
+void PathTracer::updateVertices( const pbr_float4* vertices, uint32_t numVertices ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateVertices before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_vertices( mCtx, vertices, numVertices ), "pbr_update_vertices" );
+	this->resetSampleCount();
+}
+
 std::vector<float> PathTracer::generateImagesAdaptive( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, float threshold ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] generateImagesAdaptive before initOpenCLBuffers" );

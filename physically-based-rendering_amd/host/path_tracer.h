@@ -80,6 +80,10 @@ class PathTracer {
 		// Needs a camera without a focus point (setFocus): depth of field reads the focus pixel's every frame.
 		std::vector<float> generateImagesAdaptive( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, float threshold );
 
+		// pbr_update_vertices: new positions for the scene's vertices (count as uploaded), the BVH refitted on the device; starts
+		// a new accumulation.  The host copy of the scene (buffers()) keeps the uploaded vertices and boxes.
+		void updateVertices( const pbr_float4* vertices, uint32_t numVertices );
+
 		void resetSampleCount();
 		void setCamera( Camera* camera ) { mCamera = camera; }
 		void setFocus( int x, int y );

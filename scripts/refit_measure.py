@@ -1,0 +1,125 @@
+"""pbr_update_vertices timed on one GPU against the alternatives, for one scene per process.
+
+  python scripts/refit_measure.py --scene sponza|dragon|hairball [--reps 7] [--frames 16] [--out FILE]
+
+The BASELINE scenes as bench.py generates them (Sponza-class 260k, Dragon-class 870k, hairball 2M triangles), 1920 x 1080.  The
+vertices are moved with tests/refit_ref.py's seeded deformation at its two amplitudes.  Reported, medians over --reps with the
+spread (min .. max), wall times around the synchronous calls:
+  (a) pbr_update_vertices: device time of its kernels (pbr_last_kernel_ms), the copy of the vertices (pbr_diag_refit_info) and
+      the wall time of the call
+  (b) the alternatives on the same machine and build: pbr_upload_scene( S' ) alone (S' = the moved vertices + the refitted
+      nodes), and pbr_build_bvh + pbr_upload_scene
+  (c) the refit's device time against its traffic floor: 16 B per vertex and per face index read, 48 B per face record, 24 B per
+      node and, where face normals are kept, 16 B per face written (and the 48 B read back for them) — bytes, GB/s, and the
+      fraction of 8 TB/s
+  (d) the cost of a stale tree: Msamples/s of pbr_render( --frames ) on the refitted tree against the tree pbr_build_bvh
+      builds for the moved vertices, at both amplitudes, the same pinned plan.  (The tree host/bvh_builder.cpp builds for moved
+      vertices needs a loader path for arrays that the host library does not have; that leg is not in this script.)
+Append the output of the three scenes to profiles/r09/experiments/refit.txt."""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import pbr_loader  # noqa: E402
+
+W, H = 1920, 1080
+SCENES = {"dragon": ("dragon", 1, 870000), "sponza": ("sponza", 2, 260000), "hairball": ("hairball", 3, 2000000)}
+HBM_BYTES_PER_S = 8.0e12
+
+
+def arg(name, default):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
+def spread(values):
+    return "%9.3f (%.3f .. %.3f)" % (float(np.median(values)), min(values), max(values))
+
+
+def wall(call):
+    start = time.perf_counter()
+    call()
+    return (time.perf_counter() - start) * 1e3
+
+
+def main():
+    import refit_ref
+    pbr = pbr_loader.load()
+    name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = sc.arrays()
+    cfg, cam, px = sc.config(W, H), sc.camera(), pbr.pixel_dimension(W, H)
+    seeds = pbr.frame_seeds(0, frames)
+    faces, vertices, nodes = a["facesV"].shape[0], a["vertices"].shape[0], a["bvh"].shape[0]
+    lines = ["== %s: %d faces, %d vertices, %d nodes, %d x %d" % (name, faces, vertices, nodes, W, H)]
+
+    dev = pbr.Device(0)
+    dev.upload_scene(sc.desc)
+    dev.configure(cfg)
+    dev.render(0, pbr.frame_seeds(0, max(frames, dev.tune_budget())), px, cam)
+    plan = dev.last_plan()[1]
+    plan = plan if plan >= 0 else 4
+    dev.pin_plan(plan)
+    info = dev.refit_info()
+    lines.append("partition: %(workgroups)d workgroups, %(subtrees)d subtrees, %(top_nodes)d nodes above the cut in %(top_levels)d levels; %(device_bytes)d bytes kept" % info)
+    moved = {amp: refit_ref.deform(a["facesV"], a["vertices"], amp, seed=3) for amp in refit_ref.AMPLITUDES}
+
+    def desc_with(v, bvh, facesV=None, facesN=None):
+        d = pbr.SceneDesc.from_buffer_copy(sc.desc)
+        d.vertices, d.bvh, d.num_nodes = v.ctypes.data, bvh.ctypes.data, bvh.shape[0]
+        if facesV is not None:
+            d.facesV, d.facesN = facesV.ctypes.data, facesN.ctypes.data
+        return d
+
+    for amp, v in moved.items():
+        device_ms, copy_ms, wall_ms = [], [], []
+        for _ in range(reps):
+            dev.update_vertices(a["vertices"])
+            wall_ms.append(wall(lambda: dev.update_vertices(v)))
+            device_ms.append(dev.last_kernel_ms())
+            copy_ms.append(dev.refit_info()["upload_ms"])
+        lines.append("(a) %-5s update_vertices: device %s ms | vertex copy %s ms | wall %s ms" % (amp, spread(device_ms), spread(copy_ms), spread(wall_ms)))
+        normals = 1 if dev.scene_bytes()["faces"] else 0
+        floor = 16 * vertices + 16 * faces + 48 * faces + 24 * nodes + normals * (48 + 16) * faces
+        rate = floor / (float(np.median(device_ms)) * 1e-3)
+        lines.append("(c) %-5s traffic floor %d bytes -> %.1f GB/s = %.1f %% of 8 TB/s" % (amp, floor, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S))
+        refitted = dev.read_bvh()
+        dev.reset_accum()
+        stale = [wall(lambda: dev.render(0, seeds, px, cam)) for _ in range(reps)]
+
+        other = pbr.Device(0)
+        other.configure(cfg)
+        other.pin_plan(plan)
+        d1 = desc_with(v, refitted)
+        upload = [wall(lambda: other.upload_scene(d1)) for _ in range(reps)]
+        lines.append("(b) %-5s upload_scene( S' ): wall %s ms" % (amp, spread(upload)))
+        build = []
+        for _ in range(max(1, reps // 2)):
+            start = time.perf_counter()
+            built, outV, outN = other.build_bvh(v, a["facesV"], a["facesN"])
+            d2 = desc_with(v, built, outV, outN)
+            other.upload_scene(d2)
+            build.append((time.perf_counter() - start) * 1e3)
+        lines.append("(b) %-5s build_bvh + upload_scene: wall %s ms" % (amp, spread(build)))
+        other.render(0, seeds, px, cam)
+        fresh = [wall(lambda: other.render(0, seeds, px, cam)) for _ in range(reps)]
+        samples = W * H * frames * cfg.samples / 1e6
+        lines.append("(d) %-5s render( %d ) plan %d: refitted tree %.1f Msamples/s | tree built for V' by pbr_build_bvh %.1f Msamples/s (wall, medians)"
+                     % (amp, frames, plan, samples / (np.median(stale) * 1e-3), samples / (np.median(fresh) * 1e-3)))
+        other.close()
+    dev.close()
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if "--out" in sys.argv:
+        with open(arg("--out", ""), "a") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
