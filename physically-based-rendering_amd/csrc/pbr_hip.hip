@@ -24,6 +24,7 @@
 #include "pt_denoise.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
+#include "pt_deal.hpp"
 #include "pt_adaptive_host.hpp"
 #include "pt_refit_host.hpp"
 #include "pt_refit.hpp"
@@ -59,6 +60,13 @@ struct Knobs {
 	int tuneLog = -1;       // 1 = the schedule tuner logs its launches to stderr
 	int dealOrder = -1;     // the queue's dealing order: 0 always spatial, 1 always cost-ordered (once learnt), -1 by the launch's size
 	int chainLayout = -1;   // the focus chain's table (pbr_render_dof): 0 frame-major planes (the built-in choice), 1 a pixel slot's frames side by side
+};
+
+// One dealing order's table: band b's stretch is [ first[b], first[b + 1] ) of host / dev.
+struct DealTable {
+	std::vector<unsigned> host;
+	unsigned first[PT_BANDS + 1] = {};
+	unsigned* dev = nullptr;
 };
 
 struct pbr_ctx {
@@ -117,23 +125,16 @@ struct pbr_ctx {
 	float4* dImgDbg = nullptr;
 	float4* dRows = nullptr;       // W x H row-major staging for read-back / write_input
 	float4* dFull = nullptr;       // all tiles of the frame, filled by pbr_import_tiles
-	// the banded queue's dealing order (pt_kernel.hpp, nextSlot): the local tiles as a queueRows x queueWidth grid cut into
-	// PT_BANDS bands of rows; hTileOrder / dTileOrder name, per band, its tiles in the order they are dealt
-	int queueWidth = 1, queueRows = 1;
-	unsigned bandFirst[PT_BANDS + 1] = {};       // of hTileOrder / dTileOrder (the spatial table, or a pinned one)
-	unsigned costBandFirst[PT_BANDS + 1] = {};   // of hCostOrder / dCostOrder
-	std::vector<unsigned> hTileOrder;
-	unsigned* dTileOrder = nullptr;
+	// the banded queue's dealing orders (pt_deal.hpp; pt_kernel.hpp, nextSlot): the local tiles as a grid cut into PT_BANDS bands
+	// of rows, and per order (DealOrder) a table that names, per band, its tiles in the order they are dealt.  deal[kDealSpatial]
+	// is the spatial table, or a pinned one; the two cost orders are learnt from the debug image (node visits per pixel of a
+	// launch's last frame, learnTileCosts) and keep the spatial bands
+	DealGrid queueGrid;
+	DealTable deal[kDealOrders];
 	bool orderPinned = false;      // pbr_diag_set_tile_order: the caller's order stays (tests, A/B runs)
-	// cost-ordered dealing for SHORT launches (round 6, learnTileCosts): per band the tiles in kCostClasses classes of
-	// falling cost, spatial order inside a class; learnt from the debug image (node visits per pixel of a launch's last frame)
-	std::vector<unsigned> hCostOrder;
-	unsigned* dCostOrder = nullptr;
-	std::vector<unsigned> hLastOrder;   // LONG launches: per band its most expensive quarter last, spatial inside both parts (the spatial bands)
-	unsigned* dLastOrder = nullptr;
 	float* dTileCost = nullptr;    // node visits per local tile
 	std::vector<float> hTileCost;
-	bool costLearnt = false;       // dCostOrder holds an order learnt for costCam
+	bool costLearnt = false;       // the two cost tables hold orders learnt for costCam
 	pbr_camera costCam = {};       // the camera (and pixel size) the costs were measured with
 	float costPxDim = 0.0f;
 	uint32_t launchesSinceLearn = 0;
@@ -277,11 +278,13 @@ void freeImages( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dChain );
 	ctx->dChain = nullptr;
 	ctx->chainFloats = 0;
-	(void) hipFree( ctx->dTileOrder );
-	(void) hipFree( ctx->dCostOrder );
-	(void) hipFree( ctx->dLastOrder );
-	ctx->dLastOrder = nullptr;
-	ctx->hLastOrder.clear();
+
+	for( DealTable& table : ctx->deal ) {
+		(void) hipFree( table.dev );
+		table.dev = nullptr;
+		table.host.clear();
+	}
+
 	(void) hipFree( ctx->dTileCost );
 	(void) hipFree( ctx->dTileFrames );
 	(void) hipFree( ctx->dTileError );
@@ -292,10 +295,7 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->dTileError = nullptr;
 	ctx->dMoments = nullptr;
 	ctx->adaptiveStats = false;
-	ctx->dTileOrder = ctx->dCostOrder = nullptr;
 	ctx->dTileCost = nullptr;
-	ctx->hTileOrder.clear();
-	ctx->hCostOrder.clear();
 	ctx->costLearnt = false;
 	ctx->orderPinned = false;
 	ctx->dImgIn = ctx->dImgOut = ctx->dImgDbg = ctx->dRows = ctx->dFull = nullptr;
@@ -487,180 +487,19 @@ int packConfiguredWalk( pbr_ctx* ctx, const pbr_config& cfg, const SceneTree* tr
 	return packWalk( *tree, cfg.traversal, walk, &ctx->error );
 }
 
-// ---- the dealing order of the banded queue (pt_kernel.hpp, nextSlot) -------------------------------------------------
-// The local tiles form a queueRows x queueWidth grid (row-major local tile index; its true shape when unsharded, about that
-// when sharded).  Band b holds the rows [ b * queueRows / PT_BANDS, ( b + 1 ) * queueRows / PT_BANDS ); its stretch of the order
-// table is [ bandFirst[b], bandFirst[b + 1] ) and names exactly the band's tiles (the ragged end of the grid is left out).
-//
-// The spatial order (rounds 1 - 5's only one): inside a band column by column, so that the tiles the waves of one XCD hold
-// at a time form a compact block of the image, not a strip as wide as the frame.
-void spatialTileOrder( const pbr_ctx* ctx, std::vector<unsigned>* order, unsigned first[PT_BANDS + 1] ) {
-	order->clear();
-	order->reserve( (size_t) ctx->numLocalTiles );
-
-	for( int band = 0; band < PT_BANDS; band++ ) {
-		const unsigned row0 = ( (unsigned) band * (unsigned) ctx->queueRows ) / PT_BANDS;
-		const unsigned rows = ( (unsigned) ( band + 1 ) * (unsigned) ctx->queueRows ) / PT_BANDS - row0;
-		first[band] = (unsigned) order->size();
-
-		for( unsigned col = 0; col < (unsigned) ctx->queueWidth; col++ ) {
-			for( unsigned row = 0; row < rows; row++ ) {
-				const unsigned tile = ( row0 + row ) * (unsigned) ctx->queueWidth + col;
-
-				if( tile < (unsigned) ctx->numLocalTiles ) {
-					order->push_back( tile );
-				}
-			}
-		}
-	}
-
-	first[PT_BANDS] = (unsigned) order->size();
-}
-
+// ---- the dealing orders of the banded queue: the device side (the orders themselves, and which one a call gets: pt_deal.hpp) ----
 int uploadTileOrder( pbr_ctx* ctx ) {
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dTileOrder, ctx->hTileOrder.data(), sizeof( unsigned ) * ctx->hTileOrder.size(), hipMemcpyHostToDevice, ctx->stream ) );
+	const DealTable& table = ctx->deal[kDealSpatial];
+	HIP_TRY( ctx, hipMemcpyAsync( table.dev, table.host.data(), sizeof( unsigned ) * table.host.size(), hipMemcpyHostToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // the source is pageable: do not let it change under the copy
 	return PBR_OK;
-}
-
-// Cost-ordered dealing.  A launch ends at the pace of its longest paths ("How a launch ends"): when the queue runs
-// dry every lane holds a path, and the machine empties while the longest of them finish — 0.5 ms on a Sponza-class scene,
-// whatever the launch's length.  Dealt expensive tiles first, the paths that start last are short ones.  Measured (round 6,
-// profiles/r06/experiments/deal_order*.txt; round 4 had measured the unsharded half of it, profiles/r04/experiments/
-// heaviest_tiles_first.txt): rank 0's share of a 20-frame render split 8 ways -3.5 ... -8 % (Sponza-class 3.14 -> 3.00 ms,
-// Dragon-class 3.85 -> 3.72, hairball 6.97 -> 6.72, Cornell 1.50 -> 1.42), its single frame -2 ... -10 %; but a long launch
-// LOSES 1 - 8 % because the tiles an XCD holds at one time are no longer neighbours (Sponza-class 64 frames 60.5 -> 61.1 ms,
-// hairball 127.9 -> 131.5) and a single full frame neither gains nor loses.  So falling classes only up to kCostOrderTileFrames
-// tiles x frames (what is dealt above that: next paragraph).  Eight classes by the band's own cost octiles — the finer the
-// classes the less locality is left, a full sort is the worst on long launches and no better on short.
-//
-// LONG launches (found late in round 6, profiles/r06/experiments/deal_order_ascending*.txt, band_balance*.txt): the same cost
-// map, the other way round.  A band that deals its most EXPENSIVE quarter LAST — spatial order inside both parts — renders a long
-// launch 1 - 7 % faster than the spatial order: Sponza-class 20 frames 19.37 -> 19.10 ms (two-paths plan), 20.13 -> 19.60 (6 waves);
-// Dragon-class 19.85 -> 18.60 ms, 64 frames 61.1 -> 57.0; hairball 127.7 -> 125.2; Cornell 27.2 -> 26.1; the eight-order walk alike
-// (Dragon-class 49.96 -> 47.14 ms); rank 0 of 8 from ~40 frames on.  The gain is proportional to the launch's length, the opposite
-// direction (expensive first) loses as much, the split point hardly matters (15 / 25 / 40 %), ascending classes do the same and
-// interleaving the classes does not: what counts is that a band's heavy tiles come when the XCDs whose own bands are cheap have
-// run out of them and join in (bands differ by up to 10 x in cost, and an XCD works on its own band until it is empty) — the
-// heavy part of every band is then shared by all eight XCDs, their L2s and their fabric links, instead of being its owner's alone.
-// Equalising the bands' costs by moving their row boundaries gives a fifth of that; and the heavy tiles have to be the VERY last a
-// band deals: a coda of its cheapest 10 % behind them gives the whole gain back (band_balance_cheap_coda.txt).  That was the clue:
-// most of it was the QUEUE HEADS.  The XCDs that have run dry all draw from the one head of the band they help, a head hands out
-// ~90 draws / us, and cheap tiles are drawn the fastest — expensive-last merely made sure that the shared part of a launch draws
-// slowly.  With four heads per band and the helpers spread over them (pt_kernel.hpp, nextSlot; experiments/queue_heads_*.txt,
-// queue_subheads_*.txt) the SPATIAL order is as fast as expensive-last was (Sponza-class 64 frames 2165 -> 2211 Msamples/s against
-// 2196; Dragon-class 2132 -> 2317 against 2290; Cornell 4832 -> 5148 against 5053) and expensive-last still adds 1.3 % on the
-// Dragon-class scene and Cornell, nothing on the other two.  Below ~192 Ki tiles x frames it loses to the
-// spatial order (the long paths start last), hence three orders by the size of the RENDER CALL (all launches of a call alike;
-// while the schedule tuner is still measuring, everything is dealt spatially: launch()):
-//   tiles x frames <= 128 Ki  eight classes of falling cost     <= 192 Ki  spatial     above  expensive quarter last
-// A SHARD (tile_world > 1) deals falling classes up to 1 Mi tiles x frames: its tiles are every N-th of the image, the spatial order
-// has little locality to lose there, and with the heads out of the way the shorter end is what is left to gain — rank 0's share at
-// 20 frames, N = 2 / 4: Sponza-class 10.24 -> 10.07 ms, 5.54 -> 5.40; Dragon-class 10.67 -> 10.58, 6.23 -> 6.09; N = 8 at 64 frames
-// 8.29 -> 8.13, 8.97 -> 8.80 (queue_subheads_orders_by_launch_length.txt).  Small UNSHARDED images do not share that: 1280x720 ...
-// 640x360 behave like 1080p (queue_subheads_orders_small_and_4k_images.txt).
-const unsigned kCostClasses = 8;
-const size_t kCostOrderTileFrames = 128 * 1024;
-const size_t kCostOrderShardTileFrames = 1024 * 1024;
-const size_t kSpatialOrderTileFrames = 192 * 1024;
-
-// per band: the spatial order, stably partitioned into [ the cheaper three quarters ][ the most expensive quarter ]
-void expensiveLastTileOrder( const unsigned bandFirst[PT_BANDS + 1], const std::vector<unsigned>& spatial, const std::vector<float>& cost, std::vector<unsigned>* order ) {
-	order->assign( spatial.size(), 0u );
-	std::vector<float> sorted;
-
-	for( int band = 0; band < PT_BANDS; band++ ) {
-		const unsigned first = bandFirst[band], n = bandFirst[band + 1] - first;
-
-		if( n == 0 ) {
-			continue;
-		}
-
-		sorted.resize( n );
-
-		for( unsigned k = 0; k < n; k++ ) {
-			sorted[k] = cost[spatial[first + k]];
-		}
-
-		std::sort( sorted.begin(), sorted.end() );
-		const float edge = sorted[std::min<size_t>( n - 1, ( (size_t) 3 * n ) / 4 )];
-		unsigned at = first;
-
-		for( int pass = 0; pass < 2; pass++ ) {
-			for( unsigned k = 0; k < n; k++ ) {
-				const unsigned tile = spatial[first + k];
-
-				if( ( cost[tile] > edge ) == ( pass == 1 ) ) {
-					( *order )[at++] = tile;
-				}
-			}
-		}
-	}
-}
-
-// per band: the spatial order, stably partitioned into kCostClasses classes of falling cost (class edges = the band's octiles)
-void costTileOrder( const unsigned bandFirst[PT_BANDS + 1], const std::vector<unsigned>& spatial, const std::vector<float>& cost, std::vector<unsigned>* order ) {
-	order->assign( spatial.size(), 0u );
-	std::vector<float> sorted;
-	std::vector<unsigned> fill( kCostClasses );
-
-	for( int band = 0; band < PT_BANDS; band++ ) {
-		const unsigned first = bandFirst[band], n = bandFirst[band + 1] - first;
-
-		if( n == 0 ) {
-			continue;
-		}
-
-		sorted.resize( n );
-
-		for( unsigned k = 0; k < n; k++ ) {
-			sorted[k] = cost[spatial[first + k]];
-		}
-
-		std::sort( sorted.begin(), sorted.end() );
-		float edge[kCostClasses - 1];
-
-		for( unsigned c = 0; c + 1 < kCostClasses; c++ ) {
-			edge[c] = sorted[std::min<size_t>( n - 1, ( (size_t) ( c + 1 ) * n ) / kCostClasses )];
-		}
-
-		// class 0 = the most expensive: a tile's class counts the edges its cost stays below
-		auto classOf = [&]( float v ) {
-			unsigned below = 0;
-
-			for( unsigned c = 0; c + 1 < kCostClasses; c++ ) {
-				below += ( v < edge[c] ) ? 1u : 0u;
-			}
-
-			return below;
-		};
-
-		std::fill( fill.begin(), fill.end(), 0u );
-
-		for( unsigned k = 0; k < n; k++ ) {
-			fill[classOf( cost[spatial[first + k]] )]++;
-		}
-
-		unsigned at = 0;
-
-		for( unsigned c = 0; c < kCostClasses; c++ ) {
-			const unsigned size = fill[c];
-			fill[c] = at;
-			at += size;
-		}
-
-		for( unsigned k = 0; k < n; k++ ) {
-			const unsigned tile = spatial[first + k];
-			( *order )[first + fill[classOf( cost[tile] )]++] = tile;
-		}
-	}
 }
 
 // After a launch: node visits per local tile from the debug image (the launch's last frame), then the cost order.  Runs when
 // there is no order yet or the camera has moved since it was learnt (then at most every 16th launch: an order learnt a few
 // frames ago is nearly as good, and the read-back is a synchronisation a frame-by-frame caller should not pay per frame).
 int learnTileCosts( pbr_ctx* ctx, const pbr_camera* cam, float pxDim ) {
-	if( ctx->orderPinned || ctx->knobs.dealOrder == 0 || ctx->dCostOrder == nullptr ) {
+	if( ctx->orderPinned || ctx->knobs.dealOrder == 0 || ctx->deal[kDealCostClasses].dev == nullptr ) {
 		return PBR_OK;
 	}
 
@@ -677,11 +516,14 @@ int learnTileCosts( pbr_ctx* ctx, const pbr_camera* cam, float pxDim ) {
 	HIP_TRY( ctx, hipMemcpyAsync( ctx->hTileCost.data(), ctx->dTileCost, sizeof( float ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	std::vector<unsigned> spatial;
-	spatialTileOrder( ctx, &spatial, ctx->costBandFirst );
-	costTileOrder( ctx->costBandFirst, spatial, ctx->hTileCost, &ctx->hCostOrder );
-	expensiveLastTileOrder( ctx->costBandFirst, spatial, ctx->hTileCost, &ctx->hLastOrder );
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dCostOrder, ctx->hCostOrder.data(), sizeof( unsigned ) * ctx->hCostOrder.size(), hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dLastOrder, ctx->hLastOrder.data(), sizeof( unsigned ) * ctx->hLastOrder.size(), hipMemcpyHostToDevice, ctx->stream ) );
+	DealTable& classes = ctx->deal[kDealCostClasses];
+	DealTable& last = ctx->deal[kDealExpensiveLast];
+	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &spatial, classes.first );
+	std::copy( classes.first, classes.first + PT_BANDS + 1, last.first );
+	costTileOrder( classes.first, PT_BANDS, spatial, ctx->hTileCost, &classes.host );
+	expensiveLastTileOrder( last.first, PT_BANDS, spatial, ctx->hTileCost, &last.host );
+	HIP_TRY( ctx, hipMemcpyAsync( classes.dev, classes.host.data(), sizeof( unsigned ) * classes.host.size(), hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( last.dev, last.host.data(), sizeof( unsigned ) * last.host.size(), hipMemcpyHostToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	ctx->costLearnt = true;
 	ctx->costCam = *cam;
@@ -942,7 +784,7 @@ int growFrameBuf( pbr_ctx* ctx, uint32_t nFrames, size_t* chunkCap ) {
 	const size_t capFrames = std::max<size_t>( 1, kFrameBufBytes / frameBytes );
 	size_t cap = std::min<size_t>( capFrames, nFrames );
 	// the queue heads count pixel slots x frames of a band in 32 bits
-	cap = std::min<size_t>( cap, std::max<size_t>( 1, 0x7FFFFFFFull / ( pixelSlots + 64 * (size_t) ctx->queueWidth ) ) );
+	cap = std::min<size_t>( cap, std::max<size_t>( 1, 0x7FFFFFFFull / ( pixelSlots + 64 * (size_t) ctx->queueGrid.width ) ) );
 
 	if( ctx->knobs.chunkFrames >= 1 ) {    // tests: force several launch pairs
 		cap = std::min<size_t>( cap, (size_t) ctx->knobs.chunkFrames );
@@ -966,29 +808,22 @@ int growFrameBuf( pbr_ctx* ctx, uint32_t nFrames, size_t* chunkCap ) {
 	return PBR_OK;
 }
 
-// The dealing order of a render call of nFrames frames, by its size (costTileOrder / expensiveLastTileOrder): spatial, cost
-// classes or expensive last; P is pointed at it and lastDeal names it.  Until the schedule tuner has settled, everything is
-// dealt spatially: its chunks are short launches whatever the call's length, the cost orders are made for one length each
-// (expensive-last costs a 2-frame launch 6 %), and a plan's fitted fixed cost must not depend on which of them its chunks
-// happened to run in (seen: the 6-waves plan kept over the two-paths one, -3.6 %).
-void dealOrder( pbr_ctx* ctx, uint32_t nFrames, bool settled, DevParams* P ) {
-	const Knobs& knobs = ctx->knobs;
-	int dealt = 0;   // 0 spatial, 1 cost classes, 2 expensive last
-
-	if( !ctx->orderPinned && ctx->costLearnt && knobs.dealOrder != 0 && ( settled || knobs.dealOrder > 0 ) ) {
-		const size_t tileFrames = (size_t) ctx->numLocalTiles * nFrames;
-		const size_t costLimit = ( ctx->cfg.tile_world > 1u ) ? kCostOrderShardTileFrames : kCostOrderTileFrames;
-		dealt = ( knobs.dealOrder > 0 ) ? std::min( knobs.dealOrder, 2 ) : ( tileFrames <= costLimit ) ? 1 : ( tileFrames <= kSpatialOrderTileFrames ) ? 0 : 2;
-	}
-
-	std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", ctx->orderPinned ? "pinned" : ( dealt == 1 ) ? "cost-classes" : ( dealt == 2 ) ? "expensive-last" : "spatial" );
-	P->tileOrder = ( dealt == 1 ) ? ctx->dCostOrder : ( dealt == 2 ) ? ctx->dLastOrder : ctx->dTileOrder;
-	const unsigned* first = ( dealt != 0 ) ? ctx->costBandFirst : ctx->bandFirst;
+// P deals the table `order` (device memory), whose bands' stretches start at first[]
+void pointAtTable( DevParams* P, const unsigned* order, const unsigned* first ) {
+	P->tileOrder = order;
 
 	for( int band = 0; band < PT_BANDS; band++ ) {
 		P->bandFirst[band] = first[band];
 		P->bandTiles[band] = first[band + 1] - first[band];
 	}
+}
+
+// The table a round of `tiles` tiles x `frames` frames is dealt from (pt_deal.hpp, dealRule); lastDeal names its order.
+// settled: the schedule tuner has settled, or the plan is fixed.
+const DealTable& dealOrder( pbr_ctx* ctx, size_t tiles, uint32_t frames, bool settled ) {
+	const DealOrder dealt = dealRule( ctx->orderPinned, ctx->costLearnt, ctx->knobs.dealOrder, settled, ctx->cfg.tile_world > 1u, tiles, frames );
+	std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", dealName( ctx->orderPinned, dealt ) );
+	return ctx->deal[dealt];
 }
 
 // [1] the path loop (or a record slot of the asynchronous node phase that never filled), [2] a traversal that took more
@@ -1064,6 +899,75 @@ int runFocusChain( pbr_ctx* ctx, DevParams* P, const float4* prev, bool first ) 
 	return PBR_OK;
 }
 
+// What every render call starts with: the guard flags cleared, the call's seeds staged, the queue heads zero, and in P the scene
+// and everything of the call that no launch of it changes.  focusGiven: the camera has a focus point and the caller passed the
+// focus pixel's previous-frame distance (pbr_set_focus_depth) — consuming it is the caller's business.
+int beginRender( pbr_ctx* ctx, const float* seeds, uint32_t nSeeds, const pbr_camera* cam, float pxDim, bool explicitWeight, float weight,
+                 bool focusGiven, DevParams* out, uint32_t* hotAvail ) {
+	// the kernels' error flags are of THIS render (host-mapped memory; no launch of this context is in flight here)
+	for( int k = 0; k < 4; k++ ) {
+		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
+	}
+
+	PBR_TRY( stageSeeds( ctx, seeds, nSeeds ) );
+
+	// the queue heads: foldFrames zeroes them behind every path-tracing launch, so only the first launch of a context
+	// (and any launch after one that did not end in foldFrames) has to
+	if( !ctx->workClean ) {
+		HIP_TRY( ctx, hipMemsetAsync( ctx->dWork, 0, kWorkBytes, ctx->stream ) );
+	}
+
+	ctx->workClean = false;
+
+	DevParams& P = *out;
+	PBR_TRY( sceneParams( ctx, &P, hotAvail ) );   // P.nodes, P.firstRef / walkFirst for the configured traversal
+	P.triPN = ctx->dTriPN;
+	P.phongAlpha = ctx->cfg.phong_tessellation;
+	P.imgIn = ctx->dImgIn;
+	P.imgOut = ctx->dImgOut;
+	P.imgDbg = ctx->dImgDbg;
+	P.counters = ctx->dCounters;
+	P.workCounter = ctx->dWork;
+	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
+	P.aperture = cam->lense[0] / cam->lense[1];
+	P.samplesF = (float) ctx->cfg.samples;
+	P.focusX = cam->focusPoint[0];
+	P.focusY = cam->focusPoint[1];
+	P.focusGiven = focusGiven ? 1 : 0;
+	P.focusDepth = ctx->focusDepth;
+	P.lenseFocal = cam->lense[0];
+	P.lenseAperture = cam->lense[1];
+	P.tilesX = ctx->tilesX;
+	invariantDivisor( (unsigned) ctx->tilesX, P.tilesXDiv );
+	P.numLocalTiles = ctx->numLocalTiles;
+	P.tileWorld = (int) ctx->cfg.tile_world;
+	P.tileRank = (int) ctx->cfg.tile_rank;
+	P.maxDepth = (int) ctx->cfg.max_depth;
+	P.maxAddedDepth = (int) ctx->cfg.max_added_depth;
+	P.samples = (int) ctx->cfg.samples;
+	P.useExplicitWeight = explicitWeight ? 1 : 0;
+	P.explicitWeight = weight;
+	P.antiAliasing = ctx->cfg.anti_aliasing;
+	P.sky[0] = ctx->cfg.sky_light[0];
+	P.sky[1] = ctx->cfg.sky_light[1];
+	P.sky[2] = ctx->cfg.sky_light[2];
+	return PBR_OK;
+}
+
+// ... and ends with, behind its last fold: the call's time on the device, and what the diagnostics report of its launches
+int endRender( pbr_ctx* ctx, double traceMs, uint32_t launches ) {
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	ctx->workClean = true;   // the last fold left the queue heads at zero
+
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	ctx->lastTraceMs = traceMs;
+	ctx->lastTraceLaunches = launches;
+	return PBR_OK;
+}
+
 // chained: pbr_render_dof — many frames with depth of field in one call, the focus chain ahead of every launch
 int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* seeds,
             bool explicitWeight, float weight, float pxDim, const pbr_camera* cam, bool chained = false ) {
@@ -1091,55 +995,10 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
-	// the kernels' error flags are of THIS render (host-mapped memory; no launch of this context is in flight here)
-	for( int k = 0; k < 4; k++ ) {
-		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
-	}
-
-	PBR_TRY( stageSeeds( ctx, seeds, nFrames ) );
-
-	// the queue heads: foldFrames zeroes them behind every path-tracing launch, so only the first launch of a context
-	// (and any launch after one that did not end in foldFrames) has to
-	if( !ctx->workClean ) {
-		HIP_TRY( ctx, hipMemsetAsync( ctx->dWork, 0, kWorkBytes, ctx->stream ) );
-	}
-
-	ctx->workClean = false;
-
 	DevParams P;
 	uint32_t hotAvail = 0;
-	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );   // P.nodes, P.firstRef / walkFirst for the configured traversal
-	P.triPN = ctx->dTriPN;
-	P.phongAlpha = ctx->cfg.phong_tessellation;
-	P.imgIn = ctx->dImgIn;
-	P.imgOut = ctx->dImgOut;
-	P.imgDbg = ctx->dImgDbg;
-	P.counters = ctx->dCounters;
-	P.workCounter = ctx->dWork;
-	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
-	P.aperture = cam->lense[0] / cam->lense[1];
-	P.samplesF = (float) ctx->cfg.samples;
-	P.focusX = cam->focusPoint[0];
-	P.focusY = cam->focusPoint[1];
-	P.focusGiven = ( dof && ctx->focusGiven ) ? 1 : 0;
-	P.focusDepth = ctx->focusDepth;
+	PBR_TRY( beginRender( ctx, seeds, nFrames, cam, pxDim, explicitWeight, weight, dof && ctx->focusGiven, &P, &hotAvail ) );
 	ctx->focusGiven = false;   // one frame's worth: the next frame needs the next distance
-	P.lenseFocal = cam->lense[0];
-	P.lenseAperture = cam->lense[1];
-	P.tilesX = ctx->tilesX;
-	invariantDivisor( (unsigned) ctx->tilesX, P.tilesXDiv );
-	P.numLocalTiles = ctx->numLocalTiles;
-	P.tileWorld = (int) ctx->cfg.tile_world;
-	P.tileRank = (int) ctx->cfg.tile_rank;
-	P.maxDepth = (int) ctx->cfg.max_depth;
-	P.maxAddedDepth = (int) ctx->cfg.max_added_depth;
-	P.samples = (int) ctx->cfg.samples;
-	P.useExplicitWeight = explicitWeight ? 1 : 0;
-	P.explicitWeight = weight;
-	P.antiAliasing = ctx->cfg.anti_aliasing;
-	P.sky[0] = ctx->cfg.sky_light[0];
-	P.sky[1] = ctx->cfg.sky_light[1];
-	P.sky[2] = ctx->cfg.sky_light[2];
 
 	const bool phong = ( ctx->cfg.phong_tessellation > 0.0f );
 
@@ -1158,7 +1017,8 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	// Phong tessellation has one plan; a pinned plan renders without tuning
 	const Plan* plans = chain ? ctx->chainPlans : ctx->plans;   // the tuner's choice holds for both builds of a plan's kernel
 	const Plan* forced = phong ? &ctx->phongPlan : ( ctx->pinnedPlan >= 0 ) ? &plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )] : nullptr;
-	dealOrder( ctx, nFrames, forced != nullptr || ctx->tuner.settled(), &P );
+	const DealTable& table = dealOrder( ctx, (size_t) ctx->numLocalTiles, nFrames, forced != nullptr || ctx->tuner.settled() );
+	pointAtTable( &P, table.dev, table.first );
 	P.frameBuf = ctx->dFrameBuf;
 	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
 	P.frameStride = (unsigned) pixelSlots;
@@ -1214,16 +1074,8 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		done += n;
 	}
 
-	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	ctx->workClean = true;   // the last foldFrames left the queue heads at zero
-
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	ctx->lastTraceMs = traceMs;
+	PBR_TRY( endRender( ctx, traceMs, launches ) );
 	ctx->lastChainMs = chainMs;
-	ctx->lastTraceLaunches = launches;
 	ctx->launchesSinceLearn += launches;
 	PBR_TRY( checkGuard( ctx ) );
 	return learnTileCosts( ctx, cam, pxDim );
@@ -1235,21 +1087,6 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 // table names), and foldFramesAdaptive folds and tests exactly those tiles.  numLocalTiles / frameStride stay the full values:
 // they size the frame buffer.  The call neither feeds the schedule tuner nor the tile-cost learner, and the context's dealing
 // tables stay as they are — the renders before and after it behave as if it had not been.
-
-// Which of the context's tables a round of `tiles` active tiles x `frames` frames is filtered from: dealOrder()'s rule by size
-// (a short round: falling cost classes if they have been learnt), for a plan that is fixed.  0 spatial (or pinned), 1 cost
-// classes, 2 expensive last.
-int adaptiveDealTable( const pbr_ctx* ctx, size_t tiles, uint32_t frames ) {
-	const Knobs& knobs = ctx->knobs;
-
-	if( ctx->orderPinned || !ctx->costLearnt || knobs.dealOrder == 0 ) {
-		return 0;
-	}
-
-	const size_t tileFrames = tiles * frames;
-	const size_t costLimit = ( ctx->cfg.tile_world > 1u ) ? kCostOrderShardTileFrames : kCostOrderTileFrames;
-	return ( knobs.dealOrder > 0 ) ? std::min( knobs.dealOrder, 2 ) : ( tileFrames <= costLimit ) ? 1 : ( tileFrames <= kSpatialOrderTileFrames ) ? 0 : 2;
-}
 
 int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float pxDim, const pbr_camera* cam, const pbr_adaptive_params& A ) {
 	if( !ctx->hasScene || !ctx->configured ) {
@@ -1280,53 +1117,10 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 	ctx->adaptiveStats = false;
 	ctx->lastChainMs = 0.0;
 
-	// the kernels' error flags are of THIS render (host-mapped memory; no launch of this context is in flight here)
-	for( int k = 0; k < 4; k++ ) {
-		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
-	}
-
-	PBR_TRY( stageSeeds( ctx, seeds, A.max_frames ) );
-
-	if( !ctx->workClean ) {
-		HIP_TRY( ctx, hipMemsetAsync( ctx->dWork, 0, kWorkBytes, ctx->stream ) );
-	}
-
-	ctx->workClean = false;
-
-	// the launch's parameters, as launch() sets them for a render without a focus point
+	// the launch's parameters are launch()'s for a render without a focus point; a pending pbr_set_focus_depth stays pending
 	DevParams P;
 	uint32_t hotAvail = 0;
-	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );
-	P.triPN = ctx->dTriPN;
-	P.phongAlpha = ctx->cfg.phong_tessellation;
-	P.imgIn = ctx->dImgIn;
-	P.imgOut = ctx->dImgOut;
-	P.imgDbg = ctx->dImgDbg;
-	P.counters = ctx->dCounters;
-	P.workCounter = ctx->dWork;
-	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
-	P.aperture = cam->lense[0] / cam->lense[1];
-	P.samplesF = (float) ctx->cfg.samples;
-	P.focusX = cam->focusPoint[0];
-	P.focusY = cam->focusPoint[1];
-	P.focusGiven = 0;
-	P.focusDepth = ctx->focusDepth;
-	P.lenseFocal = cam->lense[0];
-	P.lenseAperture = cam->lense[1];
-	P.tilesX = ctx->tilesX;
-	invariantDivisor( (unsigned) ctx->tilesX, P.tilesXDiv );
-	P.numLocalTiles = ctx->numLocalTiles;
-	P.tileWorld = (int) ctx->cfg.tile_world;
-	P.tileRank = (int) ctx->cfg.tile_rank;
-	P.maxDepth = (int) ctx->cfg.max_depth;
-	P.maxAddedDepth = (int) ctx->cfg.max_added_depth;
-	P.samples = (int) ctx->cfg.samples;
-	P.useExplicitWeight = 0;
-	P.explicitWeight = 0.0f;
-	P.antiAliasing = ctx->cfg.anti_aliasing;
-	P.sky[0] = ctx->cfg.sky_light[0];
-	P.sky[1] = ctx->cfg.sky_light[1];
-	P.sky[2] = ctx->cfg.sky_light[2];
+	PBR_TRY( beginRender( ctx, seeds, A.max_frames, cam, pxDim, false, 0.0f, false, &P, &hotAvail ) );
 
 	PBR_TRY( buildPlans( ctx, hotAvail, phong, false ) );
 	size_t chunkCap = 0;
@@ -1370,17 +1164,14 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 				}
 			}
 
-			const int dealt = adaptiveDealTable( ctx, activeTiles, roundFrames );
-			std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", ctx->orderPinned ? "pinned" : ( dealt == 1 ) ? "cost-classes" : ( dealt == 2 ) ? "expensive-last" : "spatial" );
-			const std::vector<unsigned>& table = ( dealt == 1 ) ? ctx->hCostOrder : ( dealt == 2 ) ? ctx->hLastOrder : ctx->hTileOrder;
-			const unsigned* tableFirst = ( dealt != 0 ) ? ctx->costBandFirst : ctx->bandFirst;
+			const DealTable& table = dealOrder( ctx, activeTiles, roundFrames, true );   // the plan is fixed
 
 			if( activeTiles == tiles ) {
-				dTable = ( dealt == 1 ) ? ctx->dCostOrder : ( dealt == 2 ) ? ctx->dLastOrder : ctx->dTileOrder;
-				std::copy( tableFirst, tableFirst + PT_BANDS + 1, first );
+				dTable = table.dev;
+				std::copy( table.first, table.first + PT_BANDS + 1, first );
 			}
 			else {
-				filterOrder( table, tableFirst, active.data(), PT_BANDS, &order, first );
+				filterOrder( table.host, table.first, active.data(), PT_BANDS, &order, first );
 				HIP_TRY( ctx, hipMemcpyAsync( ctx->dAdaptiveOrder, order.data(), sizeof( unsigned ) * order.size(), hipMemcpyHostToDevice, ctx->stream ) );
 				HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // the source is pageable
 				dTable = ctx->dAdaptiveOrder;
@@ -1390,13 +1181,7 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 				return fail( ctx, PBR_ESTATE, "pbr_render_adaptive: the dealing table names %u of %zu active tiles", first[PT_BANDS], activeTiles );
 			}
 
-			P.tileOrder = dTable;
-
-			for( int band = 0; band < PT_BANDS; band++ ) {
-				P.bandFirst[band] = first[band];
-				P.bandTiles[band] = first[band + 1] - first[band];
-			}
-
+			pointAtTable( &P, dTable, first );
 			roundStart = false;
 		}
 
@@ -1443,15 +1228,7 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 		}
 	}
 
-	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	ctx->workClean = true;   // the last fold left the queue heads at zero
-
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	ctx->lastTraceMs = traceMs;
-	ctx->lastTraceLaunches = launches;
+	PBR_TRY( endRender( ctx, traceMs, launches ) );
 	ctx->lastAdaptiveRounds = rounds;
 	ctx->lastAdaptiveUnits = units;
 	ctx->lastAdaptiveFoldMs = foldMs;
@@ -1842,13 +1619,17 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	HIP_TRY( ctx, hipDeviceSynchronize() );   // the memsets ran on the null stream; launches use ctx->stream
 
 	// the local tiles as a grid for the banded queue: its true shape when unsharded, about that when sharded
-	ctx->queueWidth = std::max( 1, ( ctx->tilesX + (int) cfg->tile_world - 1 ) / (int) cfg->tile_world );
-	ctx->queueRows = ( ctx->numLocalTiles + ctx->queueWidth - 1 ) / ctx->queueWidth;
-	spatialTileOrder( ctx, &ctx->hTileOrder, ctx->bandFirst );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileOrder, sizeof( unsigned ) * ctx->hTileOrder.size() ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCostOrder, sizeof( unsigned ) * ctx->hTileOrder.size() ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dLastOrder, sizeof( unsigned ) * std::max<size_t>( 1, ctx->hTileOrder.size() ) ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileCost, sizeof( float ) * std::max<size_t>( 1, ctx->hTileOrder.size() ) ) );
+	ctx->queueGrid = dealGrid( ctx->tilesX, ctx->numLocalTiles, (int) cfg->tile_world );
+	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &ctx->deal[kDealSpatial].host, ctx->deal[kDealSpatial].first );
+	const size_t tiles = ctx->deal[kDealSpatial].host.size();
+
+	for( int order = 0; order < kDealOrders; order++ ) {
+		// a context without local tiles gets no table of the first two orders (a null pointer: learnTileCosts then learns nothing)
+		const size_t entries = ( order == kDealExpensiveLast ) ? std::max<size_t>( 1, tiles ) : tiles;
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->deal[order].dev, sizeof( unsigned ) * entries ) );
+	}
+
+	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileCost, sizeof( float ) * std::max<size_t>( 1, tiles ) ) );
 	ctx->costLearnt = false;
 	ctx->launchesSinceLearn = 0;
 	PBR_TRY( uploadTileOrder( ctx ) );
@@ -2856,8 +2637,8 @@ int pbr_diag_get_tile_order( pbr_ctx* ctx, int which, uint32_t* order, uint32_t 
 		return fail( ctx, PBR_ESTATE, "diag_get_tile_order: no cost order has been learnt yet (it is built after the first render)" );
 	}
 
-	const std::vector<unsigned>& table = ( which == 1 ) ? ctx->hCostOrder : ( which == 2 ) ? ctx->hLastOrder : ctx->hTileOrder;
-	const uint32_t n = (uint32_t) table.size();
+	const DealTable& table = ctx->deal[( which == kDealCostClasses || which == kDealExpensiveLast ) ? which : kDealSpatial];
+	const uint32_t n = (uint32_t) table.host.size();
 
 	if( count != nullptr ) {
 		*count = n;
@@ -2865,7 +2646,7 @@ int pbr_diag_get_tile_order( pbr_ctx* ctx, int which, uint32_t* order, uint32_t 
 
 	if( band_first != nullptr ) {
 		for( int band = 0; band <= PT_BANDS; band++ ) {
-			band_first[band] = ( which != 0 ) ? ctx->costBandFirst[band] : ctx->bandFirst[band];
+			band_first[band] = table.first[band];
 		}
 	}
 
@@ -2874,7 +2655,7 @@ int pbr_diag_get_tile_order( pbr_ctx* ctx, int which, uint32_t* order, uint32_t 
 			return fail( ctx, PBR_EINVAL, "diag_get_tile_order: %u entries do not fit a buffer of %u", n, capacity );
 		}
 
-		std::memcpy( order, table.data(), sizeof( uint32_t ) * n );
+		std::memcpy( order, table.host.data(), sizeof( uint32_t ) * n );
 	}
 
 	return PBR_OK;
@@ -2888,58 +2669,24 @@ int pbr_diag_set_tile_order( pbr_ctx* ctx, const uint32_t* order, uint32_t count
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	std::vector<unsigned> spatial;
 	unsigned spatialFirst[PT_BANDS + 1];
-	spatialTileOrder( ctx, &spatial, spatialFirst );
+	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &spatial, spatialFirst );
+	DealTable& table = ctx->deal[kDealSpatial];
 
 	if( order == nullptr ) {
-		ctx->hTileOrder = spatial;
-		std::memcpy( ctx->bandFirst, spatialFirst, sizeof( spatialFirst ) );
+		table.host = spatial;
+		std::memcpy( table.first, spatialFirst, sizeof( spatialFirst ) );
 		ctx->orderPinned = false;
 		return uploadTileOrder( ctx );
 	}
 
-	if( count != (uint32_t) spatial.size() ) {
-		return fail( ctx, PBR_EINVAL, "diag_set_tile_order: %u entries, the queue has %zu tiles", count, spatial.size() );
+	std::string why;
+
+	if( tileOrderCheck( order, count, band_first, spatial, spatialFirst, PT_BANDS, &why ) != PBR_OK ) {
+		return fail( ctx, PBR_EINVAL, "%s", why.c_str() );
 	}
 
-	const uint32_t* first = ( band_first != nullptr ) ? band_first : spatialFirst;
-
-	if( first[0] != 0u || first[PT_BANDS] != count ) {
-		return fail( ctx, PBR_EINVAL, "diag_set_tile_order: the bands' stretches must cover the table: band_first[0] = 0, band_first[8] = %u", count );
-	}
-
-	for( int band = 0; band < PT_BANDS; band++ ) {
-		if( first[band] > first[band + 1] ) {
-			return fail( ctx, PBR_EINVAL, "diag_set_tile_order: band_first must not decrease (band %d)", band );
-		}
-	}
-
-	// the table must name every local tile exactly once: a unit dealt twice or never is a wrong image.  Without band_first the
-	// bands are the spatial ones and every band's stretch must hold that band's own tiles.
-	std::vector<unsigned char> bandOf( spatial.size(), 1 );
-
-	if( band_first == nullptr ) {
-		for( int band = 0; band < PT_BANDS; band++ ) {
-			for( unsigned k = spatialFirst[band]; k < spatialFirst[band + 1]; k++ ) {
-				bandOf[spatial[k]] = (unsigned char) ( band + 1 );
-			}
-		}
-	}
-
-	for( int band = 0; band < PT_BANDS; band++ ) {
-		for( unsigned k = first[band]; k < first[band + 1]; k++ ) {
-			const uint32_t tile = order[k];
-			const unsigned char want = ( band_first == nullptr ) ? (unsigned char) ( band + 1 ) : (unsigned char) 1;
-
-			if( tile >= (uint32_t) bandOf.size() || bandOf[tile] != want ) {
-				return fail( ctx, PBR_EINVAL, "diag_set_tile_order: entry %u (tile %u) is not a tile of band %d, or is named twice", k, tile, band );
-			}
-
-			bandOf[tile] = 0;
-		}
-	}
-
-	ctx->hTileOrder.assign( order, order + count );
-	std::memcpy( ctx->bandFirst, first, sizeof( spatialFirst ) );
+	table.host.assign( order, order + count );
+	std::memcpy( table.first, ( band_first != nullptr ) ? band_first : spatialFirst, sizeof( spatialFirst ) );
 	ctx->orderPinned = true;
 	return uploadTileOrder( ctx );
 }

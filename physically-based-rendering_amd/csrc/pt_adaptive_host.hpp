@@ -1,6 +1,7 @@
 // pt_adaptive_host.hpp — the host side of pbr_render_adaptive (pbr_hip.hip, launchAdaptive) that needs no device: what the
-// call refuses, how its frames fall into rounds and launch pairs, and the dealing table of a round that renders only the
-// tiles that are still active.  Host code only, no HIP: tests/adaptive_driver.cpp builds it with a plain C++17 compiler.
+// call refuses and how its frames fall into rounds and launch pairs (the dealing table of a round that renders only the tiles
+// that are still active: pt_deal.hpp, filterOrder).  Host code only, no HIP: tests/adaptive_driver.cpp builds it with a plain
+// C++17 compiler.
 //
 // An adaptive render runs in ROUNDS.  Round 0 renders frames [0, min_frames) of every local tile; every later round the next
 // min( round_frames, max_frames - done ) frames of the tiles that have not stopped.  A tile's convergence is tested at round
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "pbr_hip.h"
+#include "pt_deal.hpp"   // filterOrder: a round's dealing table; whoever drives an adaptive render needs both
 
 // Why pbr_render_adaptive refuses these arguments (PBR_EINVAL, the message in *why), or PBR_OK.
 inline int adaptiveCheck( const pbr_adaptive_params* params, const float* seeds, const pbr_camera* cam, std::string* why ) {
@@ -88,24 +90,4 @@ inline uint32_t adaptiveRounds( const std::vector<AdaptivePair>& pairs ) {
 	}
 
 	return rounds;
-}
-
-// A dealing table (pt_kernel.hpp, nextSlot: band b's stretch is order[ bandFirst[b] .. bandFirst[b + 1] )) without the tiles
-// whose active[tile] is 0: every band keeps its surviving tiles in the order they had; a band may come out empty (two equal
-// bandFirst entries — nextSlot takes a band of 0 tiles as exhausted).  bands = PT_BANDS; bandFirst and outFirst hold bands + 1.
-inline void filterOrder( const std::vector<unsigned>& order, const unsigned* bandFirst, const unsigned* active, int bands,
-                         std::vector<unsigned>* out, unsigned* outFirst ) {
-	out->clear();
-
-	for( int band = 0; band < bands; band++ ) {
-		outFirst[band] = (unsigned) out->size();
-
-		for( unsigned k = bandFirst[band]; k < bandFirst[band + 1]; k++ ) {
-			if( active[order[k]] != 0u ) {
-				out->push_back( order[k] );
-			}
-		}
-	}
-
-	outFirst[bands] = (unsigned) out->size();
 }

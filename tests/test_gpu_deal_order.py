@@ -6,6 +6,7 @@ oracle's bit for bit.  Every plan, sharded and unsharded, single-frame and multi
 import numpy as np
 import pytest
 
+import deal_order_tables
 from conftest import same_values, describe_mismatch
 
 pytestmark = pytest.mark.gpu
@@ -187,6 +188,26 @@ def test_a_shard_deals_falling_classes_for_longer(pbr, gpu_device):
                 assert dev.last_deal()[0] == "expensive-last"
         finally:
             dev.close()
+
+
+@pytest.mark.parametrize("grid", ["64x64", "200x120", "200x120 rank 1 of 3"])
+def test_a_configured_context_deals_the_recorded_spatial_table(pbr, gpu_device, grid):
+    """The grid pbr_configure hands to the dealing unit is the one the recorded tables were made for: with another width the
+    table would still be a permutation per band, and only the locality would be lost."""
+    w, h, world, rank = deal_order_tables.GRIDS[grid]
+    want = deal_order_tables.SPATIAL[grid]
+    sc = _scene(pbr, "cornell", 0)
+    cfg = sc.config(w, h)
+    cfg.tile_world, cfg.tile_rank = world, rank
+    dev = pbr.Device(gpu_device)
+    try:
+        dev.upload_scene(sc.desc)
+        dev.configure(cfg)
+        order, first = dev.tile_order()
+        assert first.tolist() == [int(v) for v in want["first"].split()]
+        assert order.tolist() == [int(v) for v in want["spatial"].split()]
+    finally:
+        dev.close()
 
 
 def test_a_table_that_is_not_a_permutation_is_refused(pbr, gpu_device):
