@@ -13,7 +13,9 @@
 // device now.  Images rendered over it agree with images over the reference's tree statistically,
 // not bit for bit (the walk order decides ties and the triangle test starts from the leaf box's
 // tNear, pt_intersect.cl:96-120).  Its result is deterministic: boxes are exact min / max, the keys
-// are unique, ties are ordered.
+// are unique, ties are ordered.  tests/bvh_build_ref.py restates both builders in numpy binary32,
+// operation by operation; that restatement is the definition the tests trust and hold this file to, bit
+// for bit (tests/test_gpu_bvh_build.py) — a change to the arithmetic or to an order here is a change there.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, same_values, describe_mismatch
+from flat_tree import check_flat_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -493,49 +494,6 @@ def test_cl_adaptor_driven_like_the_reference(pbr, oracle, gpu_device, cfg):
     # an upload like the reference's): same frames
     image, debug = sc.render_through_cl_adaptor(5, refeed_every=2)
     assert same_values(image, want), describe_mismatch(image, want)
-
-
-def check_flat_tree(nodes, facesV_out, facesV_in, vertices):
-    """Structural invariants of the reference's flat format for a tree with <= 2 faces per leaf."""
-    n = nodes.shape[0]
-    leaf = nodes[:, 3] >= 0
-    assert not leaf[0] and nodes[0, 3] == -1
-    # every face exactly once, in leaf order
-    first = nodes[leaf, 3].astype(np.int64)
-    second = nodes[leaf, 7].astype(np.int64)
-    assert ((second == -1) | (second == first + 1)).all()
-    covered = np.sort(np.concatenate([first, second[second >= 0]]))
-    assert np.array_equal(covered, np.arange(facesV_in.shape[0]))
-    key = lambda f: np.sort(f.view([("", f.dtype)] * 4).ravel())
-    assert np.array_equal(key(np.ascontiguousarray(facesV_out)), key(np.ascontiguousarray(facesV_in)))      # a permutation of the input
-    # depth-first order: a container's subtree is [i + 1, end) with end = its miss link, or the enclosing end
-    end = np.empty(n, np.int64)
-    stack = [n]
-    for i in range(n):
-        while stack and i >= stack[-1]:
-            stack.pop()
-        enclosing = stack[-1] if stack else n
-        if leaf[i]:
-            end[i] = i + 1
-        else:
-            link = int(nodes[i, 7])
-            assert link == -1 or i + 1 < link <= n
-            end[i] = link if link != -1 else enclosing
-            assert end[i] <= enclosing
-            stack.append(end[i])
-    # boxes: a leaf's box is the exact bound of its faces, a container's the bound of its subtree's leaves
-    tri = vertices[facesV_out[:, :3].astype(np.int64), :3]                    # (m, 3, 3)
-    flo, fhi = tri.min(1), tri.max(1)
-    for i in np.nonzero(leaf)[0][:4000]:
-        f0, f1 = int(nodes[i, 3]), int(nodes[i, 7])
-        lo, hi = flo[f0], fhi[f0]
-        if f1 >= 0:
-            lo, hi = np.minimum(lo, flo[f1]), np.maximum(hi, fhi[f1])
-        assert np.array_equal(nodes[i, 0:3], lo) and np.array_equal(nodes[i, 4:7], hi)
-    for i in np.nonzero(~leaf)[0][1:2000]:
-        sub = np.arange(i + 1, end[i])
-        sub = sub[leaf[sub]]
-        assert np.array_equal(nodes[i, 0:3], nodes[sub, 0:3].min(0)) and np.array_equal(nodes[i, 4:7], nodes[sub, 4:7].max(0))
 
 
 @pytest.mark.parametrize("traversal", [0, 2])
