@@ -32,10 +32,10 @@ extern "C" {
 
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
- * version 9 pbr_update_vertices and pbr_read_bvh).  A caller that loads the library at run time — or
+ * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 9
+#define PBR_ABI_VERSION 10
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -309,6 +309,51 @@ typedef struct pbr_denoise_params {
 	float sigma_albedo;
 } pbr_denoise_params;
 int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_params* params, float* rgba, float* features );
+
+/* The variance pbr_render_adaptive estimates anyway, handed to the filter (csrc/pt_denoise_guided.hpp).
+ * THE VARIANCE OF A PIXEL.  The last pbr_render_adaptive( first_sample_count = n0 ) left, per pixel, Welford's second moment
+ * M2 of the luminance Y = ( 0.2126 r + 0.7152 g ) + 0.0722 b over the c frames its tile rendered (csrc/pt_adaptive.hpp):
+ *     var = M2 / (float) ( c - 1 ) / (float) ( n0 + c )         two binary32 divisions, in that order
+ * — for n0 = 0 the `v` of the tile's error estimate, the variance of the pixel's mean; for n0 > 0 the sample variance of this
+ * call's frames spread over all n0 + c frames of the running mean.  Reproducible to the bit (tests/guided_denoise_ref.py).
+ * pbr_read_variance: `variance` = width x height floats, row 0 = bottom like pbr_read_output.
+ * STATE.  Both calls need the accumulated image to be what the last pbr_render_adaptive left: PBR_ESTATE (the message names
+ * pbr_render_adaptive) before the first adaptive call, and after anything that writes or swaps imageIn / imageOut since —
+ * pbr_render_frame, pbr_accumulate, pbr_render, pbr_render_dof, pbr_write_input, pbr_reset_accum, pbr_import_tiles,
+ * pbr_configure, another adaptive call that failed.  pbr_read_tile_stats is not bound by this.  PBR_ESTATE with
+ * tile_world > 1: the variance of other ranks' tiles is not gathered.  PBR_EINVAL as pbr_denoise: null arguments, passes
+ * outside 1 .. 8, a standard deviation that is negative or not finite.  A refused call changes nothing; neither call modifies
+ * the accumulation, the moments or the tile stats.
+ * THE FILTER is pbr_denoise's a-trous with a luminance term scaled by the LOCAL standard deviation in place of the colour
+ * term, and the variance filtered along with the colour — the spatial part of SVGF (Schied et al. 2017) without the temporal
+ * one.  Pass k = 0 .. passes - 1, step s = 2^k, works on colour C_k and variance V_k; C_0 = the accumulated image, V_0 = var.
+ * For the pixel p, in this order and each operation in binary32:
+ *   1. local variance: g = sum G_i G_j V_k( p + (i, j) ) / sum G_i G_j over |i|, |j| <= 1, G = {0.25, 0.5, 0.25} — taps ONE
+ *      pixel apart whatever s is; taps outside the image or whose V is not finite are left out; g = 0 if none is left;
+ *      sd = sqrt( g )
+ *   2. luminance term of a tap q: e_l = | Y( C_k( q ) ) - Y( C_k( p ) ) | / ( sigma_luminance * sd + 1e-6 );
+ *      sigma_luminance = 0: e_l = 0
+ *   3. e = e_l, plus for a hit centre the normal, world and albedo terms exactly as pbr_denoise has them, added in that order
+ *   4. the 5 x 5 taps, s pixels apart, visited row by row (j outer, i inner); skipped: taps outside the image, across the
+ *      hit / miss divide, with !( e < inf ), or with V_k( q ) not finite;  w = ( spline_i * spline_j ) * expf( -e )
+ *   5. C_k+1( p ) = sum w C_k( q ) / sum w;   V_k+1( p ) = sum ( w * w ) V_k( q ) / ( sum w * sum w );
+ *      if sum w is not in (0, inf), colour and variance stay as they were
+ * With sigma_luminance = 0 the colour is bit for bit pbr_denoise's with sigma_color = 0 and the same other parameters.
+ *   rgba          host, width x height x 4 floats: filtered colour, .w = the accumulated first-hit distance as pbr_denoise
+ *   variance_out  optional (NULL): host, width x height floats, V after the last pass
+ *   features      optional (NULL): as pbr_denoise
+ * pbr_last_kernel_ms reports the device time of the untile, variance, feature and filter kernels (pbr_read_variance: of
+ * the variance kernel). */
+int pbr_read_variance( pbr_ctx* ctx, float* variance );
+typedef struct pbr_denoise_guided_params {
+	uint32_t passes;          /* 1 .. 8 */
+	float sigma_luminance;    /* in standard deviations of the pixel's mean; 0 switches the term off */
+	float sigma_normal;       /* these three as pbr_denoise_params */
+	float sigma_world;
+	float sigma_albedo;
+} pbr_denoise_guided_params;
+int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_guided_params* params,
+                        float* rgba, float* variance_out, float* features );
 
 /* Opt-in fast BVH build on the device: faces in Morton order, clustered bottom-up by
  * surface area, at most 2 faces per leaf, emitted in the reference's flat format — what BVH::getNodes + the packing

@@ -42,6 +42,16 @@ class DenoiseParams(ctypes.Structure):
         super().__init__(passes, sigma_color, sigma_normal, sigma_world, sigma_albedo)
 
 
+class GuidedDenoiseParams(ctypes.Structure):
+    """pbr_denoise_guided_params.  sigma_luminance is in standard deviations of the pixel's mean (the variance
+    pbr_render_adaptive estimates), so one value serves every sample count."""
+    _fields_ = [("passes", ctypes.c_uint32), ("sigma_luminance", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_world", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
+
+    def __init__(self, passes=5, sigma_luminance=4.0, sigma_normal=0.25, sigma_world=3.0, sigma_albedo=0.1):
+        super().__init__(passes, sigma_luminance, sigma_normal, sigma_world, sigma_albedo)
+
+
 class SceneDesc(ctypes.Structure):
     """pbr_scene_desc"""
     _fields_ = [
@@ -102,7 +112,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 9
+ABI_VERSION = 10
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -169,7 +179,9 @@ for _name, _args in (
         ("pbr_diag_last_adaptive", [_vp, _up, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_update_vertices", [_vp, ctypes.c_void_p, ctypes.c_uint32]),                                                # ABI version 9
         ("pbr_read_bvh", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up]),
-        ("pbr_diag_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t])):
+        ("pbr_diag_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
+        ("pbr_read_variance", [_vp, _fp]),                                                                               # ABI version 10
+        ("pbr_denoise_guided", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(GuidedDenoiseParams), _fp, _fp, _fp])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -537,6 +549,26 @@ class Device:
         self._check(hip.pbr_denoise(self._ctx, px_dim, ctypes.byref(cam), ctypes.byref(params), out.ctypes.data_as(_fp),
                                     feat.ctypes.data_as(_fp) if features else None))
         return (out, feat) if features else out
+
+    def read_variance(self):
+        """pbr_read_variance: (H, W) float32, the variance of every pixel's mean luminance as the last render_adaptive
+        estimated it (M2 / (c - 1) / (first_sample_count + c), c the frames of the pixel's tile)."""
+        out = np.empty((self.height, self.width), np.float32)
+        self._check(hip.pbr_read_variance(self._ctx, _as_fp(out)))
+        return out
+
+    def denoise_guided(self, px_dim, cam, params=None, variance=False, features=False):
+        """pbr_denoise_guided: `denoise` right behind render_adaptive, with a luminance term in units of the local standard
+        deviation in place of sigma_color.  (H, W, 4) float32; with variance=True also the filtered variance (H, W), with
+        features=True the feature buffers as `denoise` gives them — in that order."""
+        params = params if params is not None else GuidedDenoiseParams()
+        out = np.empty((self.height, self.width, 4), np.float32)
+        var = np.empty((self.height, self.width), np.float32) if variance else None
+        feat = np.empty((3, self.height, self.width, 4), np.float32) if features else None
+        self._check(hip.pbr_denoise_guided(self._ctx, px_dim, ctypes.byref(cam), ctypes.byref(params), out.ctypes.data_as(_fp),
+                                           var.ctypes.data_as(_fp) if variance else None, feat.ctypes.data_as(_fp) if features else None))
+        extra = ([var] if variance else []) + ([feat] if features else [])
+        return (out, *extra) if extra else out
 
     def counters(self):
         c = Counters()

@@ -22,6 +22,7 @@
 // are no longer part of this source; their kernels are kept for the record under lab/src/.
 #include "bvh_build.hpp"
 #include "pt_denoise.hpp"
+#include "pt_denoise_guided.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 #include "pt_deal.hpp"
@@ -181,6 +182,10 @@ struct pbr_ctx {
 	unsigned* dAdaptiveOrder = nullptr;
 	hipEvent_t evFoldStart = nullptr, evFoldStop = nullptr;
 	bool adaptiveStats = false;          // dTileFrames / dTileError hold the last adaptive call's
+	// pbr_read_variance, pbr_denoise_guided: dMoments / dTileFrames describe the accumulated image as it is now — set by a successful
+	// adaptive call, cleared by whatever writes or swaps imageIn / imageOut — and that call's first_sample_count
+	bool varianceCurrent = false;
+	uint32_t varianceFirstCount = 0;
 	uint32_t lastAdaptiveRounds = 0;     // of the last adaptive call: rounds (= convergence tests per tile that reached the end),
 	uint64_t lastAdaptiveUnits = 0;      // (pixel, frame) units traced,
 	double lastAdaptiveFoldMs = 0.0;     // time inside foldFramesAdaptive
@@ -295,6 +300,7 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->dTileError = nullptr;
 	ctx->dMoments = nullptr;
 	ctx->adaptiveStats = false;
+	ctx->varianceCurrent = false;
 	ctx->dTileCost = nullptr;
 	ctx->costLearnt = false;
 	ctx->orderPinned = false;
@@ -992,6 +998,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 
 	const bool chain = dof && chained;
 	ctx->lastChainMs = 0.0;
+	ctx->varianceCurrent = false;
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
@@ -1115,6 +1122,7 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 	}
 
 	ctx->adaptiveStats = false;
+	ctx->varianceCurrent = false;
 	ctx->lastChainMs = 0.0;
 
 	// the launch's parameters are launch()'s for a render without a focus point; a pending pbr_set_focus_depth stays pending
@@ -1654,6 +1662,7 @@ int pbr_write_input( pbr_ctx* ctx, const float* rgba ) {
 		return fail( ctx, PBR_EINVAL, "write_input: null source" );
 	}
 
+	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	HIP_TRY( ctx, hipMemcpyAsync( ctx->dRows, rgba, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyHostToDevice, ctx->stream ) );
 	const size_t n = (size_t) ctx->numLocalTiles * 64;
@@ -1669,6 +1678,7 @@ int pbr_reset_accum( pbr_ctx* ctx ) {
 		return fail( ctx, PBR_ESTATE, "reset_accum before pbr_configure" );
 	}
 
+	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const size_t fullBytes = sizeof( float4 ) * 64 * (size_t) ctx->numTiles;
 	HIP_TRY( ctx, hipMemsetAsync( ctx->dImgIn, 0, fullBytes, ctx->stream ) );
@@ -1690,6 +1700,7 @@ int pbr_accumulate( pbr_ctx* ctx ) {
 		return fail( ctx, PBR_ESTATE, "accumulate before pbr_configure" );
 	}
 
+	ctx->varianceCurrent = false;
 	float4* tmp = ctx->dImgIn;
 	ctx->dImgIn = ctx->dImgOut;
 	ctx->dImgOut = tmp;
@@ -1744,6 +1755,8 @@ int pbr_render_adaptive( pbr_ctx* ctx, uint32_t first_sample_count, const float*
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
 	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	ctx->varianceFirstCount = first_sample_count;
+	ctx->varianceCurrent = true;   // the moments and the frame counts are those of the image as it stands
 	return PBR_OK;
 }
 
@@ -1904,6 +1917,7 @@ int pbr_import_tiles( pbr_ctx* ctx, const void* d_all ) {
 		return fail( ctx, PBR_EINVAL, "import_tiles: null source" );
 	}
 
+	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( ctx->dFull == nullptr ) {
@@ -2016,6 +2030,146 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
 
+	if( features != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( features, dPosition.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( features + 4 * pixels, dNormal.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( features + 8 * pixels, dAlbedo.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	return PBR_OK;
+}
+
+namespace {
+
+// pbr_read_variance / pbr_denoise_guided: the moments must describe the accumulated image as it is
+int varianceUsable( pbr_ctx* ctx, const char* who ) {
+	if( !ctx->hasScene || !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene / pbr_configure", who );
+	}
+	if( ctx->cfg.tile_world > 1 ) {
+		return fail( ctx, PBR_ESTATE, "%s with tile sharding: the variance pbr_render_adaptive keeps of other ranks' tiles is not gathered", who );
+	}
+	if( !ctx->varianceCurrent || ctx->dMoments == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "%s needs the accumulated image as the last pbr_render_adaptive left it: no adaptive call yet, or the image was written since", who );
+	}
+
+	return PBR_OK;
+}
+
+}  // namespace
+
+// The variance of every pixel's mean luminance after pbr_render_adaptive (csrc/pt_denoise_guided.hpp, pixelVariance).
+int pbr_read_variance( pbr_ctx* ctx, float* variance ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( variance == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "read_variance: null destination" );
+	}
+
+	PBR_TRY( varianceUsable( ctx, "read_variance" ) );
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
+	const size_t pixels = (size_t) w * (size_t) h;
+	const dim3 block( 64, 4 );
+	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	// dRows (W x H float4) is the staging of every read-back: its first quarter holds the floats
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+		ctx->varianceFirstCount, (const float4*) nullptr, (float*) ctx->dRows, (float4*) nullptr, w, h, ctx->tilesX );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( variance, ctx->dRows, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	return PBR_OK;
+}
+
+// pbr_denoise with the adaptive render's variance in place of sigma_color (csrc/pt_denoise_guided.hpp): the luminance term is
+// in units of the local standard deviation, and the variance is filtered along.  Leaves the accumulation, the moments and
+// the tile stats untouched.
+int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_guided_params* params,
+                        float* rgba, float* variance_out, float* features ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( !ctx->hasScene || !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "denoise_guided before pbr_upload_scene / pbr_configure" );
+	}
+	if( cam == nullptr || params == nullptr || rgba == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "denoise_guided: null camera, parameters or destination" );
+	}
+	if( params->passes < 1 || params->passes > 8 ) {
+		return fail( ctx, PBR_EINVAL, "denoise_guided: 1 .. 8 passes (got %u)", params->passes );
+	}
+
+	const float sigmas[4] = { params->sigma_luminance, params->sigma_normal, params->sigma_world, params->sigma_albedo };
+
+	for( int k = 0; k < 4; k++ ) {
+		if( !( sigmas[k] >= 0.0f ) || !std::isfinite( sigmas[k] ) ) {
+			return fail( ctx, PBR_EINVAL, "denoise_guided: standard deviations must be finite and >= 0 (0 switches a term off)" );
+		}
+	}
+
+	PBR_TRY( varianceUsable( ctx, "denoise_guided" ) );
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
+	const size_t pixels = (size_t) w * (size_t) h;
+	DevBuf dPosition, dNormal, dAlbedo, dPing, dPong, dOriginal, dVariance;
+	HIP_TRY( ctx, dPosition.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dNormal.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dAlbedo.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dPing.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dPong.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dOriginal.alloc( sizeof( float4 ) * pixels ) );
+	HIP_TRY( ctx, dVariance.alloc( sizeof( float ) * pixels ) );
+
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
+	setCamera( &P, cam, w, h, pxDim );
+
+	const dim3 block( 64, 4 );
+	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, (float4*) dOriginal.p, w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+		ctx->varianceFirstCount, (const float4*) dOriginal.p, (float*) nullptr, (float4*) dPing.p, w, h, ctx->tilesX );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p );
+	HIP_TRY( ctx, hipGetLastError() );
+
+	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
+	float4* in = (float4*) dPing.p;
+	float4* out = (float4*) dPong.p;
+
+	for( uint32_t pass = 0; pass < params->passes; pass++ ) {
+		const bool last = ( pass + 1 == params->passes );
+		ptd::GuidedArgs A;
+		A.width = w;
+		A.height = h;
+		A.step = 1 << pass;
+		A.sigmaLuminance = params->sigma_luminance;
+		A.invNormal = inverseSquare( params->sigma_normal );
+		A.invAlbedo = inverseSquare( params->sigma_albedo );
+		A.worldScale = params->sigma_world * (float) A.step * pxDim;
+		hipLaunchKernelGGL( ptd::atrousGuidedPass, grid, block, 0, ctx->stream, A, (const float4*) in, out,
+			(const float4*) dPosition.p, (const float4*) dNormal.p, (const float4*) dAlbedo.p,
+			(const float4*) ( last ? dOriginal.p : nullptr ), (float*) ( last ? dVariance.p : nullptr ) );
+		std::swap( in, out );
+	}
+
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+
+	if( variance_out != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( variance_out, dVariance.p, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
 	if( features != nullptr ) {
 		HIP_TRY( ctx, hipMemcpyAsync( features, dPosition.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
 		HIP_TRY( ctx, hipMemcpyAsync( features + 4 * pixels, dNormal.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
