@@ -3,14 +3,16 @@
  *
  * Not part of the drop-in boundary (the reference has nothing comparable): they expose single
  * stages of the device path — the math layer, closest-hit traversal, BRDF evaluation, new-ray
- * sampling — so the parity tests can compare each stage with the oracle's hook of the same
- * shape (oracle/pt_oracle.h: orc_math, orc_trace_rays, orc_brdf_eval, orc_new_ray) instead of
- * only whole images.  Host pointers in, host pointers out; synchronous.
+ * sampling, the cubic solver and the patch intersection of Phong tessellation — so the parity tests
+ * can compare each stage with the oracle's hook of the same shape (oracle/pt_oracle.h: orc_math,
+ * orc_trace_rays, orc_brdf_eval, orc_new_ray, orc_solve_cubic, orc_phong_face) instead of only whole
+ * images, and with float64 references.  Host pointers in, host pointers out; synchronous.
  *
- * pbr_diag_math, pbr_diag_brdf and pbr_diag_new_ray compute in the arithmetic of the context's last successful
- * pbr_configure: the native one (v_sin / v_rcp / v_log / ... , csrc/pt_math.hpp) when it set arith = PBR_ARITH_NATIVE,
- * the exact one — the oracle's definitions, bit for bit — with no configuration or arith = exact.  A library built
- * without the native diagnostics answers PBR_ESTATE in the native case.
+ * pbr_diag_math, pbr_diag_brdf, pbr_diag_new_ray, pbr_diag_solve_cubic and pbr_diag_phong_face compute in the arithmetic
+ * of the context's last successful pbr_configure: the native one (v_sin / v_rcp / v_log / ... , csrc/pt_math.hpp) when it
+ * set arith = PBR_ARITH_NATIVE, the exact one — the oracle's definitions, bit for bit — with no configuration or arith =
+ * exact.  A library built without the native diagnostics answers PBR_ESTATE in the native case.  pbr_diag_trace is always
+ * exact.
  */
 #ifndef PBR_HIP_DIAG_H
 #define PBR_HIP_DIAG_H
@@ -21,11 +23,16 @@
 extern "C" {
 #endif
 
-/* op: 0 sin, 1 cos, 2 tan, 3 acos, 4 atan, 5 pow( x, y ), 6 fract( sin( x ) * 43758.5453123 ) */
+/* op: 0 sin, 1 cos, 2 tan, 3 acos, 4 atan, 5 pow( x, y ), 6 fract( sin( x ) * 43758.5453123 ), 7 cbrt (binary64 in both
+ * arithmetics) */
 int pbr_diag_math( pbr_ctx* ctx, int op, const float* x, const float* y, int n, float* out );
 
-/* Closest-hit traversal (pt_bvh.cl:82-123) of n rays {origin, dir} against the uploaded scene.
- * out_t[n], out_face[n], out_normal[3n] (0 on a miss), out_counts[2n] = {node visits, face tests}. */
+/* Closest-hit traversal (pt_bvh.cl:82-123) of n rays {origin, dir} against the uploaded scene, in the walk of the
+ * configured traversal, always in the exact arithmetic.
+ * out_t[n], out_face[n], out_normal[3n] (0 on a miss), out_counts[2n] = {node visits, face tests}.
+ * Follows the configuration as orc_trace_rays does: with phong_tessellation > 0 configured and a scene whose vertex
+ * normals were usable it runs the Phong-tessellation build of the walk (curved faces as patches) and out_normal is the
+ * hit's own normal — the patch normal of a curved face; otherwise flat triangles and the face's geometric normal. */
 int pbr_diag_trace( pbr_ctx* ctx, const float* rays, int n, float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts );
 
 /* BRDF evaluation with material 0 of the uploaded scene.  in: n x 16 {out_dir[3], in_dir[3],
@@ -35,6 +42,19 @@ int pbr_diag_brdf( pbr_ctx* ctx, const float* in, int n, float* out );
 /* getNewRay (pt_brdf.cl:344-378) with material 0.  in: n x 12 {origin[3], dir[3], normal[3], t,
  * seed, pad}; out: n x 8 {origin[3], dir[3], seed after, addDepth}. */
 int pbr_diag_new_ray( pbr_ctx* ctx, const float* in, int n, float* out );
+
+/* solveCubic (pt_utils.cl:108-199) alone, no scene needed.  in: n x 4 {a0, a1, a2, a3} of a0 x^3 + a1 x^2 + a2 x + a3;
+ * out: n x 4 {count, x0, x1, x2}, the slots beyond count written as 0 (orc_solve_cubic). */
+int pbr_diag_solve_cubic( pbr_ctx* ctx, const float* in, int n, float* out );
+
+/* phongTessTriAndRayIntersect (pt_phongtess.cl:56-212) alone, no scene needed: called directly, not through the face test
+ * that sends a face with three equal normals to the flat intersection, so near-equal and equal normals reach it.
+ * in: n x 32 {P1[3], P2[3], P3[3], N1[3], N2[3], N3[3], origin[3], dir[3], rayT, tNear, tFar, alpha, pad[4]};
+ * out: n x 4 {t (INFINITY: no hit), normal[3] (0 on a miss)} (orc_phong_face).
+ * tNear / tFar are the slab interval of the leaf's box as the walk hands them over.  A hit is accepted only for
+ * |tNear| <= t <= min( rayT, tFar ) (pt_phongtess.cl:202): for an origin INSIDE the box tNear is negative, and hits nearer
+ * than |tNear| are dropped.  That is the reference's behaviour, kept as it is — which is why the interval is an input here. */
+int pbr_diag_phong_face( pbr_ctx* ctx, const float* in, int n, float* out );
 
 /* Traversal-only throughput probe: streams n rays {ox,oy,oz,-, dx,dy,dz,-} through a persistent
  * closest-hit kernel `repeats` times with `lds_slots` hot nodes staged in LDS; best kernel time in

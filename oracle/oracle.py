@@ -132,6 +132,10 @@ def lib():
         _lib.orc_brdf_eval.restype = None
         _lib.orc_new_ray.argtypes = [ctypes.c_int, ctypes.c_void_p, _fp, ctypes.c_int, _fp]
         _lib.orc_new_ray.restype = None
+        _lib.orc_solve_cubic.argtypes = [_fp, ctypes.c_int, _fp]
+        _lib.orc_solve_cubic.restype = None
+        _lib.orc_phong_face.argtypes = [_fp, ctypes.c_int, _fp]
+        _lib.orc_phong_face.restype = None
         _lib.orc_walk_order_count.argtypes = [ctypes.c_int]
         _lib.orc_walk_order_count.restype = ctypes.c_int
         _lib.orc_build_walk_orders.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -145,7 +149,7 @@ def _ptr(a):
     return a.ctypes.data_as(_fp)
 
 
-MATH_OPS = {"sin": 0, "cos": 1, "tan": 2, "acos": 3, "atan": 4, "pow": 5, "randhash": 6}
+MATH_OPS = {"sin": 0, "cos": 1, "tan": 2, "acos": 3, "atan": 4, "pow": 5, "randhash": 6, "cbrt": 7}
 
 
 def math(op, x, y=None):
@@ -153,6 +157,22 @@ def math(op, x, y=None):
     y = np.ascontiguousarray(x if y is None else y, np.float32)
     out = np.empty_like(x)
     lib().orc_math(MATH_OPS[op], _ptr(x), _ptr(y), x.size, _ptr(out))
+    return out
+
+
+def solve_cubic(items):
+    """orc_solve_cubic: n x 4 {a0, a1, a2, a3} -> n x 4 {count, x0, x1, x2}."""
+    items = np.ascontiguousarray(items, np.float32).reshape(-1, 4)
+    out = np.empty((items.shape[0], 4), np.float32)
+    lib().orc_solve_cubic(_ptr(items), items.shape[0], _ptr(out))
+    return out
+
+
+def phong_face(items):
+    """orc_phong_face: n x 32 {P1, P2, P3, N1, N2, N3, origin, dir, rayT, tNear, tFar, alpha, pad[4]} -> n x 4 {t, normal}."""
+    items = np.ascontiguousarray(items, np.float32).reshape(-1, 32)
+    out = np.empty((items.shape[0], 4), np.float32)
+    lib().orc_phong_face(_ptr(items), items.shape[0], _ptr(out))
     return out
 
 

@@ -1979,6 +1979,7 @@ void orc_math( int op, const float* x, const float* y, int n, float* out ) {
 			case 4: out[i] = det_atan( x[i] ); break;
 			case 5: out[i] = det_pow( x[i], y[i] ); break;
 			case 6: out[i] = det_fract( det_sin( x[i] ) * 43758.5453123f ); break;
+			case 7: out[i] = det_cbrt( x[i] ); break;
 			default: out[i] = 0.0f; break;
 		}
 	}
@@ -2049,5 +2050,42 @@ void orc_new_ray( int brdf, const void* mtl, const float* in, int n, float* out 
 		o[3] = nr.dir.x; o[4] = nr.dir.y; o[5] = nr.dir.z;
 		o[6] = seed;
 		o[7] = (float) addDepth;
+	}
+}
+
+/* solveCubic alone: in n x 4 {a0, a1, a2, a3}; out n x 4 {count, x0, x1, x2}, slots beyond count = 0 */
+void orc_solve_cubic( const float* in, int n, float* out ) {
+	for( int i = 0; i < n; i++ ) {
+		const float* p = in + (size_t) i * 4;
+		float x[3] = { 0.0f, 0.0f, 0.0f };
+		const int count = solveCubic( p[0], p[1], p[2], p[3], x );
+		float* o = out + (size_t) i * 4;
+		o[0] = (float) count;
+
+		for( int k = 0; k < 3; k++ ) {
+			o[1 + k] = ( k < count ) ? x[k] : 0.0f;
+		}
+	}
+}
+
+/* phongTessTriAndRayIntersect alone (NOT checkFaceIntersection: equal normals are not diverted to the flat test).
+ * in n x 32 {P1[3], P2[3], P3[3], N1[3], N2[3], N3[3], origin[3], dir[3], rayT, tNear, tFar, alpha, pad[4]};
+ * out n x 4 {t, normal[3]} */
+void orc_phong_face( const float* in, int n, float* out ) {
+	for( int i = 0; i < n; i++ ) {
+		const float* p = in + (size_t) i * 32;
+		ray4 ray;
+		ray.origin = V3( p[18], p[19], p[20] );
+		ray.dir = V3( p[21], p[22], p[23] );
+		ray.normal = V3( 0.0f, 0.0f, 0.0f );
+		ray.t = p[24];
+		ray.hitFace = 0;
+		float t = ORC_INF;
+		const v3 normal = phongTessTriAndRayIntersect(
+			V3( p[0], p[1], p[2] ), V3( p[3], p[4], p[5] ), V3( p[6], p[7], p[8] ),
+			V3( p[9], p[10], p[11] ), V3( p[12], p[13], p[14] ), V3( p[15], p[16], p[17] ),
+			&ray, &t, p[25], p[26], p[27] );
+		float* o = out + (size_t) i * 4;
+		o[0] = t; o[1] = normal.x; o[2] = normal.y; o[3] = normal.z;
 	}
 }

@@ -129,7 +129,7 @@ void orc_debug_set_walk_max( uint32_t* slot );
 void orc_debug_set_walk_log( uint32_t* log, uint32_t cap, uint32_t* count );
 
 /* Deterministic math layer, elementwise over n values (for ULP tests).
- * op: 0 sin, 1 cos, 2 tan, 3 acos, 4 atan, 5 pow(x,y), 6 rand-hash fract(sin(x)*43758.5453123) */
+ * op: 0 sin, 1 cos, 2 tan, 3 acos, 4 atan, 5 pow(x,y), 6 rand-hash fract(sin(x)*43758.5453123), 7 cbrt */
 void orc_math( int op, const float* x, const float* y, int n, float* out );
 
 /* BRDF unit hooks (for parity tests against the HIP diag kernels).
@@ -141,6 +141,18 @@ void orc_brdf_eval(
 /* getNewRay (pt_brdf.cl:344-378): in n x 12 {origin[3], dir[3], normal[3], t, seed, pad};
  * out n x 8 {origin[3], dir[3], seed_after, addDepth}. */
 void orc_new_ray( int brdf, const void* mtl, const float* in, int n, float* out );
+
+/* Phong tessellation, stage by stage (for tests against float64 and against the HIP diag kernels of the same shape).
+ * solveCubic (pt_utils.cl:108-199): in n x 4 {a0, a1, a2, a3} of a0 x^3 + a1 x^2 + a2 x + a3; out n x 4
+ * {count, x0, x1, x2}, the slots beyond count written as 0. */
+void orc_solve_cubic( const float* in, int n, float* out );
+
+/* phongTessTriAndRayIntersect (pt_phongtess.cl:56-212) called directly — not through checkFaceIntersection, so near-equal
+ * and equal vertex normals reach it.  in: n x 32 {P1[3], P2[3], P3[3], N1[3], N2[3], N3[3], origin[3], dir[3], rayT, tNear,
+ * tFar, alpha, pad[4]}; out: n x 4 {t (INFINITY: no hit), normal[3] (0 on a miss)}.
+ * A hit is accepted only for |tNear| <= t <= min( rayT, tFar ) (pt_phongtess.cl:202): with the origin inside the leaf's box
+ * tNear is negative and hits nearer than |tNear| are dropped.  That is the reference's behaviour, restated here. */
+void orc_phong_face( const float* in, int n, float* out );
 
 #ifdef __cplusplus
 }

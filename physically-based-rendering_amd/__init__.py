@@ -181,7 +181,9 @@ for _name, _args in (
         ("pbr_read_bvh", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up]),
         ("pbr_diag_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
         ("pbr_read_variance", [_vp, _fp]),                                                                               # ABI version 10
-        ("pbr_denoise_guided", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(GuidedDenoiseParams), _fp, _fp, _fp])):
+        ("pbr_denoise_guided", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(GuidedDenoiseParams), _fp, _fp, _fp]),
+        ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -583,7 +585,7 @@ class Device:
 
     # ---- diagnostic stages (include/pbr_hip_diag.h) ----
 
-    MATH_OPS = {"sin": 0, "cos": 1, "tan": 2, "acos": 3, "atan": 4, "pow": 5, "randhash": 6}
+    MATH_OPS = {"sin": 0, "cos": 1, "tan": 2, "acos": 3, "atan": 4, "pow": 5, "randhash": 6, "cbrt": 7}
 
     def diag_math(self, op, x, y=None):
         x = np.ascontiguousarray(x, np.float32)
@@ -613,6 +615,20 @@ class Device:
         items = np.ascontiguousarray(items, np.float32).reshape(-1, 12)
         out = np.empty((items.shape[0], 8), np.float32)
         self._check(hip.pbr_diag_new_ray(self._ctx, _as_fp(items), items.shape[0], _as_fp(out)))
+        return out
+
+    def diag_solve_cubic(self, items):
+        """pbr_diag_solve_cubic: n x 4 {a0, a1, a2, a3} -> n x 4 {count, x0, x1, x2}."""
+        items = np.ascontiguousarray(items, np.float32).reshape(-1, 4)
+        out = np.empty((items.shape[0], 4), np.float32)
+        self._check(hip.pbr_diag_solve_cubic(self._ctx, _as_fp(items), items.shape[0], _as_fp(out)))
+        return out
+
+    def diag_phong_face(self, items):
+        """pbr_diag_phong_face: n x 32 {P1, P2, P3, N1, N2, N3, origin, dir, rayT, tNear, tFar, alpha, pad[4]} -> n x 4 {t, normal}."""
+        items = np.ascontiguousarray(items, np.float32).reshape(-1, 32)
+        out = np.empty((items.shape[0], 4), np.float32)
+        self._check(hip.pbr_diag_phong_face(self._ctx, _as_fp(items), items.shape[0], _as_fp(out)))
         return out
 
     def guard_trips(self):

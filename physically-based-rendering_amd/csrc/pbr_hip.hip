@@ -2437,9 +2437,10 @@ namespace {
 
 typedef void ( *DiagMathFn )( int, const float*, const float*, int, float* );
 typedef void ( *DiagItemFn )( const ptk::DevParams, const float*, int, float* );
+typedef void ( *DiagPlainFn )( const float*, int, float* );
 
-// The kernel of a diagnostic stage (0 math, 1 BRDF, 2 new ray) in the arithmetic of the configuration in force: the native
-// flavour's after a successful pbr_configure with arith = PBR_ARITH_NATIVE, else (no configuration, or arith = exact) the
+// The kernel of a diagnostic stage (0 math, 1 BRDF, 2 new ray, 3 solveCubic, 4 Phong-tessellated face) in the arithmetic of
+// the configuration in force: the native flavour's after a successful pbr_configure with arith = PBR_ARITH_NATIVE, else (no configuration, or arith = exact) the
 // exact one of this translation unit.  Null: the native unit is not linked in.
 const void* diagKernel( const pbr_ctx* ctx, int stage, uint32_t brdf ) {
 	if( ctx->configured && ctx->cfg.arith != 0 ) {
@@ -2448,7 +2449,9 @@ const void* diagKernel( const pbr_ctx* ctx, int stage, uint32_t brdf ) {
 	switch( stage ) {
 		case 0: return (const void*) ptk::diagMath;
 		case 1: return ( brdf == 0 ) ? (const void*) ptk::diagBrdf<0> : (const void*) ptk::diagBrdf<1>;
-		default: return ( brdf == 0 ) ? (const void*) ptk::diagNewRay<0> : (const void*) ptk::diagNewRay<1>;
+		case 2: return ( brdf == 0 ) ? (const void*) ptk::diagNewRay<0> : (const void*) ptk::diagNewRay<1>;
+		case 3: return (const void*) ptk::diagSolveCubic;
+		default: return (const void*) ptk::diagPhongFace;
 	}
 }
 
@@ -2500,14 +2503,17 @@ int pbr_diag_trace( pbr_ctx* ctx, const float* rays, int n, float* out_t, int32_
 	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
-	if( ctx->numLights > 0 ) {
-		hipLaunchKernelGGL( ptk::diagTrace<true>, grid, block, 0, ctx->stream, P, (const float*) dRays.p, n,
-			(float*) dT.p, (int*) dFace.p, (float*) dNormal.p, (unsigned*) dCounts.p );
-	}
-	else {
-		hipLaunchKernelGGL( ptk::diagTrace<false>, grid, block, 0, ctx->stream, P, (const float*) dRays.p, n,
-			(float*) dT.p, (int*) dFace.p, (float*) dNormal.p, (unsigned*) dCounts.p );
-	}
+	// Phong tessellation configured and the vertex-normal records uploaded: the PHONG build of the walk, as a render takes it
+	const bool phong = ctx->configured && ctx->cfg.phong_tessellation > 0.0f && ctx->dTriPN != nullptr;
+	P.triPN = ctx->dTriPN;
+	P.phongAlpha = phong ? ctx->cfg.phong_tessellation : 0.0f;
+	const void* kernel = ( ctx->numLights > 0 )
+		? ( phong ? (const void*) ptk::diagTrace<true, true> : (const void*) ptk::diagTrace<true, false> )
+		: ( phong ? (const void*) ptk::diagTrace<false, true> : (const void*) ptk::diagTrace<false, false> );
+	typedef void ( *DiagTraceFn )( const ptk::DevParams, const float*, int, float*, int*, float*, unsigned* );
+
+	hipLaunchKernelGGL( (DiagTraceFn) kernel, grid, block, 0, ctx->stream, P, (const float*) dRays.p, n,
+		(float*) dT.p, (int*) dFace.p, (float*) dNormal.p, (unsigned*) dCounts.p );
 
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
@@ -2550,10 +2556,40 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	return PBR_OK;
 }
 
+// pbr_diag_solve_cubic / pbr_diag_phong_face: items that need nothing of a scene
+int diagPlain( pbr_ctx* ctx, const char* what, int stage, const float* in, int n, float* out, int inWidth, int outWidth ) {
+	if( ctx == nullptr || ctx->stream == nullptr || in == nullptr || out == nullptr || n <= 0 ) {
+		return fail( ctx, PBR_EINVAL, "%s: bad argument", what );
+	}
+	const DiagPlainFn kernel = (DiagPlainFn) diagKernel( ctx, stage, 0u );
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "%s: this library was built without the native-arithmetic diagnostics", what );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	DevBuf dIn, dOut;
+	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * inWidth * (size_t) n ) );
+	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * outWidth * (size_t) n ) );
+	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, (const float*) dIn.p, n, (float*) dOut.p );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * outWidth * (size_t) n, hipMemcpyDeviceToHost ) );
+	return PBR_OK;
+}
+
 }  // namespace
 
 int pbr_diag_brdf( pbr_ctx* ctx, const float* in, int n, float* out ) {
 	return diagPerItem( ctx, in, n, out, 16, 4, false );
+}
+
+int pbr_diag_solve_cubic( pbr_ctx* ctx, const float* in, int n, float* out ) {
+	return diagPlain( ctx, "diag_solve_cubic", 3, in, n, out, 4, 4 );
+}
+
+int pbr_diag_phong_face( pbr_ctx* ctx, const float* in, int n, float* out ) {
+	return diagPlain( ctx, "diag_phong_face", 4, in, n, out, 32, 4 );
 }
 
 int pbr_diag_new_ray( pbr_ctx* ctx, const float* in, int n, float* out ) {

@@ -177,8 +177,9 @@ __global__ void scatterGathered( const float4* all, float4* tiles, int numTiles,
 // (diagMath, diagBrdf and diagNewRay: pt_diag.hpp)
 // ---------------------------------------------------------------------------------------
 
-// rays: n x {origin, dir}; outputs as orc_trace_rays
-template<bool LIGHTS>
+// rays: n x {origin, dir}; outputs as orc_trace_rays.  PHONG: the Phong-tessellation build of the walk (curved faces are
+// intersected as patches, P.triPN / P.phongAlpha) and the hit's own normal, as the reference's ray carries it.
+template<bool LIGHTS, bool PHONG = false>
 __global__ void diagTrace( const DevParams P, const float* rays, int n, float* outT, int* outFace, float* outNormal, unsigned* outCounts ) {
 	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
 
@@ -192,14 +193,20 @@ __global__ void diagTrace( const DevParams P, const float* rays, int n, float* o
 	Hit hit;
 	hit.t = inff();
 	hit.face = 0;
+	hit.normal = mk3( 0.0f, 0.0f, 0.0f );
 	unsigned nodes = 0, tris = 0;
-	traverse<false, LIGHTS, false>( P, nullptr, ray, hit, nodes, tris );
+	traverse<false, LIGHTS, false, PHONG>( P, nullptr, ray, hit, nodes, tris );
 
 	f3 normal = mk3( 0.0f, 0.0f, 0.0f );
 
 	if( hit.t != inff() ) {
-		int material;
-		normal = faceNormal( P, hit.face, &material );
+		if( PHONG ) {
+			normal = hit.normal;
+		}
+		else {
+			int material;
+			normal = faceNormal( P, hit.face, &material );
+		}
 	}
 
 	outT[i] = hit.t;

@@ -1,5 +1,5 @@
-// The stage diagnostics behind pbr_diag_math / pbr_diag_brdf / pbr_diag_new_ray (include/pbr_hip_diag.h): one thread
-// per item.  Included by pt_aux.hpp (pbr_hip.hip: no flavour, the exact arithmetic) and by pt_diag_native.hip, which
+// The stage diagnostics behind pbr_diag_math / pbr_diag_brdf / pbr_diag_new_ray / pbr_diag_solve_cubic /
+// pbr_diag_phong_face (include/pbr_hip_diag.h): one thread per item.  Included by pt_aux.hpp (pbr_hip.hip: no flavour, the exact arithmetic) and by pt_diag_native.hip, which
 // compiles them once more in the native-arithmetic flavour (PT_FLAVOUR=2, pt_flavour.hpp) for a context configured
 // with pbr_config.arith = PBR_ARITH_NATIVE.
 #pragma once
@@ -25,6 +25,7 @@ __global__ void diagMath( int op, const float* x, const float* y, int n, float* 
 		case 4: out[i] = atan1( x[i] ); break;
 		case 5: out[i] = pow1( x[i], y[i] ); break;
 		case 6: out[i] = fract( sin1( x[i] ) * 43758.5453123f ); break;
+		case 7: out[i] = cbrt1( x[i] ); break;
 		default: out[i] = 0.0f; break;
 	}
 }
@@ -80,6 +81,46 @@ __global__ void diagNewRay( const DevParams P, const float* in, int n, float* ou
 	o[3] = newDir.x; o[4] = newDir.y; o[5] = newDir.z;
 	o[6] = seed;
 	o[7] = addDepth ? 1.0f : 0.0f;
+}
+
+// in: n x 4 {a0, a1, a2, a3}; out: n x 4 {count, x0, x1, x2} (as orc_solve_cubic); the slots beyond count are 0
+__global__ void diagSolveCubic( const float* in, int n, float* out ) {
+	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
+
+	if( i >= n ) {
+		return;
+	}
+
+	const float* p = in + (size_t) i * 4;
+	float x[3] = { 0.0f, 0.0f, 0.0f };
+	const int count = solveCubic( p[0], p[1], p[2], p[3], x );
+	float* o = out + (size_t) i * 4;
+	o[0] = (float) count;
+	o[1] = ( count > 0 ) ? x[0] : 0.0f;
+	o[2] = ( count > 1 ) ? x[1] : 0.0f;
+	o[3] = ( count > 2 ) ? x[2] : 0.0f;
+}
+
+// in: n x 32 {P1, P2, P3, N1, N2, N3, origin, dir, rayT, tNear, tFar, alpha, pad[4]}; out: n x 4 {t, normal} (as
+// orc_phong_face).  phongTessTriAndRayIntersect itself, not phongFaceT: equal normals are not diverted to the flat test.
+__global__ void diagPhongFace( const float* in, int n, float* out ) {
+	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
+
+	if( i >= n ) {
+		return;
+	}
+
+	const float* p = in + (size_t) i * 32;
+	Ray ray;
+	ray.origin = mk3( p[18], p[19], p[20] );
+	ray.dir = mk3( p[21], p[22], p[23] );
+	f3 normal;
+	const float t = phongTessTriAndRayIntersect(
+		mk3( p[0], p[1], p[2] ), mk3( p[3], p[4], p[5] ), mk3( p[6], p[7], p[8] ),
+		mk3( p[9], p[10], p[11] ), mk3( p[12], p[13], p[14] ), mk3( p[15], p[16], p[17] ),
+		ray, p[24], p[25], p[26], p[27], &normal );
+	float* o = out + (size_t) i * 4;
+	o[0] = t; o[1] = normal.x; o[2] = normal.y; o[3] = normal.z;
 }
 
 }  // namespace ptk

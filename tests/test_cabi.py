@@ -152,6 +152,23 @@ def test_entry_points_refuse_a_missing_context(pbr):
     assert ctypes.sizeof(pbr.DenoiseParams) == 20
 
 
+def test_phong_stage_hooks_are_declared_bound_and_refuse_a_missing_context(pbr, oracle):
+    """pbr_diag_solve_cubic / pbr_diag_phong_face and the oracle's hooks of the same shape: declared in both headers,
+    bound by both harnesses, an error (no crash) for a NULL context; "cbrt" is op 7 of both math hooks."""
+    buf = (ctypes.c_float * 32)()
+    null = ctypes.c_void_p()
+    assert pbr.hip.pbr_diag_solve_cubic(null, buf, 1, buf) != 0 and pbr.hip.pbr_diag_phong_face(null, buf, 1, buf) != 0
+    with open(os.path.join(ROOT, "include", "pbr_hip_diag.h")) as f:
+        header = f.read()
+    assert "int pbr_diag_solve_cubic(" in header and "int pbr_diag_phong_face(" in header
+    with open(os.path.join(ROOT, "oracle", "pt_oracle.h")) as f:
+        header = f.read()
+    assert "void orc_solve_cubic(" in header and "void orc_phong_face(" in header
+    assert pbr.Device.MATH_OPS["cbrt"] == oracle.MATH_OPS["cbrt"] == 7
+    assert hasattr(pbr.Device, "diag_solve_cubic") and hasattr(pbr.Device, "diag_phong_face")
+    assert oracle.solve_cubic([[0, 0, 2, -1]]).tolist() == [[1.0, 0.5, 0.0, 0.0]]
+
+
 def test_concurrent_builders_never_publish_a_half_written_library(tmp_path):
     """The ranks of a multi-process job all import the package and may all find a library stale: builds are serialised by
     a file lock, written aside and moved into place, so every process loads a complete library."""
