@@ -22,14 +22,20 @@
 
 // ---- the node phase of two walks, software-pipelined -------------------------------------------------------------------
 // Walk A's records live in v[46:53], walk B's in v[64:71], the slab test's temporaries in v54 - v63 (as nodePhaseAsm), the
-// cursors in v72 / v73: a prefetched record overwrites v53 / v71.  s[86:87] / s[88:89] = the lanes whose walk A / B goes on,
-// s[90:91] / s[92:93] = the lanes that parked on a hit leaf, s80 / s81 = "A's / B's last fetch issued loads of both kinds".
+// cursors in v53 / v71, the records' last words (round 11; as nodePhaseAsm since round 3).  s[86:87] / s[88:89] = the lanes whose
+// walk A / B goes on, VCC != 0 = "the last fetch — the OTHER walk's, seen from a wait — issued loads of both kinds".
 // A wait in front of a slab test is COUNTED — s_waitcnt vmcnt(2) lgkmcnt(2): everything but the other walk's two loads of
 // each kind, which were issued later — only when that other fetch did issue both kinds (an instruction with an empty EXEC
 // may or may not count); otherwise everything is waited for.  A walk's next records are requested as soon as its visit has
 // decided which lanes go on — the exit test runs under the requests; when `keep` or fewer walks go on, each walk takes the visit
 // its request is for (a node phase may always run one visit longer) and the phase ends with nothing in flight.
-// Per walk 24 vector instructions per visit (nodePhaseAsm: 22) and ~13 scalar ones.  What the loop's shape is worth, measured
+// Per walk-visit 24 vector instructions (nodePhaseAsm: 22) and 11 scalar ones, the wait among them (nodePhaseAsm: 8), plus the
+// loop's five per pair of visits (two s_bcnt1: a lane may hold two walks, so no combined mask counts them).  Up to round 10: 24
+// and 14 — round 11 took the cursor's copy and the parked lanes' tNear select out of the chain between a record's arrival and
+// the next request (the copy is gone, tNear and the leaf word are kept behind the request, under EXEC = the parked lanes, which
+// replaces the parked masks and their collection when the phase ends), carries the flag in VCC (one s_cselect_b64 and one
+// s_cbranch_vccz instead of two s_cselect_b32, s_cmp and a branch) and lets s_and_saveexec write the walk's mask itself.
+// Registers v72 / v73, s80 - s82 and s[90:93] fell idle by that.  What the loop's shape is worth, measured
 // step by step on the Sponza-class scene (profiles/r04/experiments/two_paths_per_lane.txt, 7.): the uncommon cases (a full
 // wait, a walk without lanes) out of line, ONE taken branch per iteration instead of three: +1.1 %; everything that does not
 // need the records (EXEC, the visit counter) in front of the wait instead of behind it: +0.9 %; the next request issued
@@ -50,40 +56,45 @@
 		"v_max_f32 v63, v58, v59\n" \
 		"v_max_f32 v62, v55, v57\n" \
 		"v_min3_f32 v61, v61, v62, v63\n"
-#define PT_DUAL_FETCH( walk, cur, n0, n1lo, n1hi, flag, skip ) \
+// A walk's request: the cold records first — the global load is what the visit waits for —, then the resident ones (round 11).
+// VCC carries the flag "this fetch issued loads of both kinds" to the other walk's wait: the compare leaves the cold lanes
+// in VCC (a compare writes 0 for the lanes outside EXEC), s_and_saveexec makes them EXEC, s_xor the resident ones with
+// SCC = "there are some", and s_cselect_b64 keeps VCC where SCC is set and clears it otherwise — VCC != 0 exactly when both
+// sets have lanes.  Nothing between here and the other walk's wait writes VCC (a visit's compares write s[94:95] / s[98:99]).
+#define PT_DUAL_FETCH( walk, cur, n0, n1lo, n1hi, skip ) \
 		"s_mov_b64 exec, " walk "\n" \
 		"s_cbranch_execz " skip "9f\n" \
-		"v_cmp_gt_i32 vcc, %[numHotBytes], " cur "\n" \
+		"v_cmp_le_i32 vcc, %[numHotBytes], " cur "\n" \
 		"s_and_saveexec_b64 s[94:95], vcc\n" \
-		"s_cselect_b32 s82, 1, 0\n" \
-		"ds_read_b128 v[" n0 "], " cur "\n" \
-		"ds_read_b128 v[" n1lo ":" n1hi "], " cur " offset:16\n" \
-		"s_xor_b64 exec, exec, s[94:95]\n" \
-		"s_cselect_b32 " flag ", s82, 0\n" \
 		"global_load_dwordx4 v[" n0 "], " cur ", %[nodes]\n" \
 		"global_load_dwordx4 v[" n1lo ":" n1hi "], " cur ", %[nodes] offset:16\n" \
+		"s_xor_b64 exec, exec, s[94:95]\n" \
+		"s_cselect_b64 vcc, vcc, 0\n" \
+		"ds_read_b128 v[" n0 "], " cur "\n" \
+		"ds_read_b128 v[" n1lo ":" n1hi "], " cur " offset:16\n" \
 	skip ":\n"
 // the counted wait; the uncommon case (the other fetch did not issue both kinds) waits for everything, out of line
-#define PT_DUAL_WAIT( otherFlag, full, go ) \
-		"s_cmp_eq_u32 " otherFlag ", 1\n" \
-		"s_cbranch_scc0 " full "f\n" \
+#define PT_DUAL_WAIT( full, go ) \
+		"s_cbranch_vccz " full "f\n" \
 		"s_waitcnt vmcnt(2) lgkmcnt(2)\n" \
 	go ":\n"
 // a walk without lanes requests nothing: its flag says so (out of line)
-#define PT_DUAL_FETCH_NONE( flag, skip ) \
+#define PT_DUAL_FETCH_NONE( skip ) \
 	skip "9:\n" \
-		"s_mov_b32 " flag ", 0\n" \
+		"s_mov_b64 vcc, 0\n" \
 		"s_branch " skip "b\n"
 #define PT_DUAL_WAIT_FULL( full, go ) \
 	full ":\n" \
 		"s_waitcnt vmcnt(0) lgkmcnt(0)\n" \
 		"s_branch " go "b\n"
 // One walk's visit: what does not need the records stands in front of the wait; behind it the slab test, the hit chain, and
-// s[98:99] = the lanes that stand on a hit leaf.  A parked lane's leaf word stays in the record's register (v52 / v70: no
-// later fetch of that walk includes the lane) and is collected when the phase ends; its tNear is a slab temporary, kept at once.
-// W = "A" / "B"; walk, park = the walk's mask pairs; r0..r7 = the eight record registers; cur = its cursor register.
+// s[98:99] = the lanes that stand on a hit leaf.  The cursor lives in the record's last register (v53 / v71), as in nodePhaseAsm:
+// the last word IS the reference to continue at unless the box is a hit container, a load may overwrite its own address
+// register, and a lane that has left the walk — parked, ended, or sitting the phase out — is in no later fetch of that walk,
+// so its last word stays where it is until the phase ends (the same holds for a parked lane's leaf word in v52 / v70).
+// W = "A" / "B"; walk = the walk's mask pair; r0..r7 = the eight record registers.
 #define PT_DUAL_VISIT_CORE( ... ) PT_DUAL_VISIT_CORE_( __VA_ARGS__ )      /* (the register lists are macros: expanded before the call) */
-#define PT_DUAL_VISIT_CORE_( skip, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7, cur ) \
+#define PT_DUAL_VISIT_CORE_( skip, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
 		"s_mov_b64 exec, " walk "\n" \
 		"s_cbranch_execz " skip "f\n" \
 		"v_add_u32 %[visits" W "], 1, %[visits" W "]\n" \
@@ -94,43 +105,51 @@
 		"v_cmpx_le_f32 v60, v61\n" \
 		"v_cmp_gt_i32 s[98:99], 0, v" r6 "\n" \
 		"v_cndmask_b32 v" r7 ", v" r6 ", v" r7 ", s[98:99]\n" \
-		"v_cndmask_b32 %[tNear" W "], %[tNear" W "], v60, s[98:99]\n" \
 		"s_mov_b64 exec, " walk "\n" \
-		"v_mov_b32 " cur ", v" r7 "\n"                        /* the cursor, where the next prefetch cannot reach it */ \
-		"v_cmp_le_i32 s[94:95], 0, " cur "\n"
+		"v_cmp_le_i32 s[94:95], 0, v" r7 "\n"
+// what a visit owes the lanes that parked on a hit leaf: the leaf's word and tNear (a slab temporary the other walk's visit
+// overwrites) — behind the request, which does not need them
+#define PT_DUAL_KEEP_PARKED( W, r6 ) \
+		"s_mov_b64 exec, s[98:99]\n" \
+		"v_mov_b32 %[tNear" W "], v60\n" \
+		"v_mov_b32 %[leafWord" W "], v" r6 "\n"
 // ... and, in the loop, the request for its next records at once: the lanes that go on are EXEC straight from the two masks,
-// the bookkeeping (walk mask, parked mask) follows the loads
+// and become the walk's mask on the way (s_and_saveexec)
 #define PT_DUAL_VISIT_AND_FETCH( ... ) PT_DUAL_VISIT_AND_FETCH_( __VA_ARGS__ )
-#define PT_DUAL_VISIT_AND_FETCH_( skip, wait, none, resume, W, walk, park, flag, r0, r1, r2, r3, r4, r5, r6, r7, cur ) \
-		PT_DUAL_VISIT_CORE( skip, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7, cur ) \
+#define PT_DUAL_VISIT_AND_FETCH_( skip, empty, wait, none, resume, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+		PT_DUAL_VISIT_CORE( empty, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
 		"s_andn2_b64 exec, s[94:95], s[98:99]\n" \
 		"s_cbranch_scc0 " none "f\n" \
-		"v_cmp_gt_i32 vcc, %[numHotBytes], " cur "\n" \
-		"s_and_saveexec_b64 s[94:95], vcc\n" \
-		"s_cselect_b32 s82, 1, 0\n" \
-		"ds_read_b128 v[" r0 ":" r3 "], " cur "\n" \
-		"ds_read_b128 v[" r4 ":" r7 "], " cur " offset:16\n" \
-		"s_xor_b64 exec, exec, s[94:95]\n" \
-		"s_cselect_b32 " flag ", s82, 0\n" \
-		"global_load_dwordx4 v[" r0 ":" r3 "], " cur ", %[nodes]\n" \
-		"global_load_dwordx4 v[" r4 ":" r7 "], " cur ", %[nodes] offset:16\n" \
-		"s_mov_b64 " walk ", s[94:95]\n" \
+		"v_cmp_le_i32 vcc, %[numHotBytes], v" r7 "\n" \
+		"s_and_saveexec_b64 " walk ", vcc\n" \
+		"global_load_dwordx4 v[" r0 ":" r3 "], v" r7 ", %[nodes]\n" \
+		"global_load_dwordx4 v[" r4 ":" r7 "], v" r7 ", %[nodes] offset:16\n" \
+		"s_xor_b64 exec, exec, " walk "\n" \
+		"s_cselect_b64 vcc, vcc, 0\n" \
+		"ds_read_b128 v[" r0 ":" r3 "], v" r7 "\n" \
+		"ds_read_b128 v[" r4 ":" r7 "], v" r7 " offset:16\n" \
 	resume ":\n" \
-		"s_or_b64 " park ", " park ", s[98:99]\n" \
+		PT_DUAL_KEEP_PARKED( W, r6 ) \
 	skip ":\n"
-#define PT_DUAL_VISIT_NONE( none, resume, walk, flag ) \
+// nobody goes on: nothing to request, and the flag says so (out of line)
+#define PT_DUAL_VISIT_NONE( none, resume, walk ) \
 	none ":\n" \
-		"s_mov_b32 " flag ", 0\n" \
+		"s_mov_b64 vcc, 0\n" \
 		"s_mov_b64 " walk ", 0\n" \
 		"s_branch " resume "b\n"
+// a walk that has no lanes left takes no visit and issues nothing — which the other walk's wait must know: VCC would still
+// hold that other walk's own flag (out of line)
+#define PT_DUAL_VISIT_EMPTY( empty, skip ) \
+	empty ":\n" \
+		"s_mov_b64 vcc, 0\n" \
+		"s_branch " skip "b\n"
 #define PT_DUAL_VISIT_LAST( ... ) PT_DUAL_VISIT_LAST_( __VA_ARGS__ )
-#define PT_DUAL_VISIT_LAST_( skip, W, walk, park, r0, r1, r2, r3, r4, r5, r6, r7, cur ) \
-		PT_DUAL_VISIT_CORE( skip, "s_waitcnt vmcnt(0) lgkmcnt(0)\n", W, walk, r0, r1, r2, r3, r4, r5, r6, r7, cur ) \
-		"s_andn2_b64 " walk ", s[94:95], s[98:99]\n" \
-		"s_or_b64 " park ", " park ", s[98:99]\n" \
+#define PT_DUAL_VISIT_LAST_( skip, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+		PT_DUAL_VISIT_CORE( skip, "s_waitcnt vmcnt(0) lgkmcnt(0)\n", W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+		PT_DUAL_KEEP_PARKED( W, r6 ) \
 	skip ":\n"
-#define PT_DUAL_REGS_A "46", "47", "48", "49", "50", "51", "52", "53", "v72"
-#define PT_DUAL_REGS_B "64", "65", "66", "67", "68", "69", "70", "71", "v73"
+#define PT_DUAL_REGS_A "46", "47", "48", "49", "50", "51", "52", "53"
+#define PT_DUAL_REGS_B "64", "65", "66", "67", "68", "69", "70", "71"
 
 // refA / refB: the walks' cursors (< 0: this slot sits the phase out).  A lane whose walk parks on a hit leaf gets the
 // leaf's word and tNear in leafWordA / tNearA (leafWordB / tNearB); the caller passes 0 in and reads != 0 as "parked".
@@ -149,16 +168,14 @@ PT_DEV void nodePhaseDualPipe(
 		"s_mov_b64 s[84:85], exec\n"
 		"v_cmp_le_i32 s[86:87], 0, %[refA]\n"
 		"v_cmp_le_i32 s[88:89], 0, %[refB]\n"
-		"s_mov_b64 s[90:91], 0\n"
-		"s_mov_b64 s[92:93], 0\n"
-		"v_mov_b32 v72, %[refA]\n"
-		"v_mov_b32 v73, %[refB]\n"
-		PT_DUAL_FETCH( "s[86:87]", "v72", "46:49", "50", "53", "s80", "10" )
-		PT_DUAL_FETCH( "s[88:89]", "v73", "64:67", "68", "71", "s81", "11" )
+		"v_mov_b32 v53, %[refA]\n"
+		"v_mov_b32 v71, %[refB]\n"
+		PT_DUAL_FETCH( "s[86:87]", "v53", "46:49", "50", "53", "10" )
+		PT_DUAL_FETCH( "s[88:89]", "v71", "64:67", "68", "71", "11" )
 	"1:\n"
 		// walk A on its records (B's request, issued after them, may stay in flight), and A's next request; then B the same way
-		PT_DUAL_VISIT_AND_FETCH( "4", PT_DUAL_WAIT( "s81", "12", "13" ), "14", "19", "A", "s[86:87]", "s[90:91]", "s80", PT_DUAL_REGS_A )
-		PT_DUAL_VISIT_AND_FETCH( "5", PT_DUAL_WAIT( "s80", "15", "16" ), "17", "20", "B", "s[88:89]", "s[92:93]", "s81", PT_DUAL_REGS_B )
+		PT_DUAL_VISIT_AND_FETCH( "4", "22", PT_DUAL_WAIT( "12", "13" ), "14", "19", "A", "s[86:87]", PT_DUAL_REGS_A )
+		PT_DUAL_VISIT_AND_FETCH( "5", "23", PT_DUAL_WAIT( "15", "16" ), "17", "20", "B", "s[88:89]", PT_DUAL_REGS_B )
 		"s_bcnt1_i32_b64 s96, s[86:87]\n"
 		"s_bcnt1_i32_b64 s97, s[88:89]\n"
 		"s_add_i32 s96, s96, s97\n"
@@ -166,23 +183,21 @@ PT_DEV void nodePhaseDualPipe(
 		"s_cbranch_scc1 1b\n"
 		// enough walks have left.  The records that are on their way are not dropped: each walk takes that visit (a node phase
 		// may always run one visit longer), and the phase ends with nothing in flight
-		PT_DUAL_VISIT_LAST( "6", "A", "s[86:87]", "s[90:91]", PT_DUAL_REGS_A )
-		PT_DUAL_VISIT_LAST( "7", "B", "s[88:89]", "s[92:93]", PT_DUAL_REGS_B )
+		PT_DUAL_VISIT_LAST( "6", "A", "s[86:87]", PT_DUAL_REGS_A )
+		PT_DUAL_VISIT_LAST( "7", "B", "s[88:89]", PT_DUAL_REGS_B )
 		"s_waitcnt vmcnt(0) lgkmcnt(0)\n"
-		"s_mov_b64 exec, s[90:91]\n"                          // the leaf words of the lanes that parked in this phase
-		"v_mov_b32 %[leafWordA], v52\n"
-		"s_mov_b64 exec, s[92:93]\n"
-		"v_mov_b32 %[leafWordB], v70\n"
 		"s_mov_b64 exec, s[84:85]\n"
-		"v_mov_b32 %[refA], v72\n"
-		"v_mov_b32 %[refB], v73\n"
+		"v_mov_b32 %[refA], v53\n"
+		"v_mov_b32 %[refB], v71\n"
 		"s_branch 21f\n"
 		PT_DUAL_WAIT_FULL( "12", "13" )
 		PT_DUAL_WAIT_FULL( "15", "16" )
-		PT_DUAL_FETCH_NONE( "s80", "10" )
-		PT_DUAL_FETCH_NONE( "s81", "11" )
-		PT_DUAL_VISIT_NONE( "14", "19", "s[86:87]", "s80" )
-		PT_DUAL_VISIT_NONE( "17", "20", "s[88:89]", "s81" )
+		PT_DUAL_FETCH_NONE( "10" )
+		PT_DUAL_FETCH_NONE( "11" )
+		PT_DUAL_VISIT_NONE( "14", "19", "s[86:87]" )
+		PT_DUAL_VISIT_NONE( "17", "20", "s[88:89]" )
+		PT_DUAL_VISIT_EMPTY( "22", "4" )
+		PT_DUAL_VISIT_EMPTY( "23", "5" )
 	"21:\n"
 		: [refA] "+v"( refA ), [refB] "+v"( refB ), [visitsA] "+v"( visitsA ), [visitsB] "+v"( visitsB ),
 		  [leafWordA] "+v"( leafWordA ), [tNearA] "+v"( tNearA ), [leafWordB] "+v"( leafWordB ), [tNearB] "+v"( tNearB )
@@ -190,7 +205,11 @@ PT_DEV void nodePhaseDualPipe(
 		  [oxyB] "v"( oxyB ), [ozzB] "v"( ozzB ), [ixyB] "v"( ixyB ), [izzB] "v"( izzB ), [rayTB] "v"( rayTB ),
 		  [keep] "s"( keep ), [numHotBytes] "s"( P.numHotBytes ), [nodes] "s"( P.nodes ), [eps] "s"( eps )
 		: "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63",
-		  "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73",
+		  "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71",
+		  // (v72 / v73 — the cursors until round 11 — and s80 - s82, s[90:93] — the flags and the parked masks — are not used any
+		  // more and stay reserved: with them free hipcc allocates the kernels' registers differently — 123 vector registers
+		  // instead of 125, the same four waves —, and pathTracingDual<0, false, true> then keeps 20 B in scratch, which it did not)
+		  "v72", "v73",
 		  "s80", "s81", "s82", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "vcc", "scc"
 	);
 }
@@ -204,6 +223,8 @@ PT_DEV void nodePhaseDualPipe(
 #undef PT_DUAL_VISIT_AND_FETCH_
 #undef PT_DUAL_VISIT_LAST_
 #undef PT_DUAL_VISIT_NONE
+#undef PT_DUAL_VISIT_EMPTY
+#undef PT_DUAL_KEEP_PARKED
 #undef PT_DUAL_VISIT_LAST
 #undef PT_DUAL_REGS_A
 #undef PT_DUAL_REGS_B

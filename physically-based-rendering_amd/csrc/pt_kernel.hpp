@@ -977,14 +977,20 @@ PT_DEV void nodePhaseAsm(
 	// costs three times what one in front of it costs; pt_dual.hpp gained 2 % from the same reordering), and the exit test was
 	// three scalar instructions and the loop's taken branch of it.  When the phase ends with a request on its way, the lanes it
 	// is for take that visit too (a node phase may always run one visit longer: per lane the sequence of visits is the same).
+	// The request itself asks for the COLD records first (round 11): EXEC = the lanes that go on whose cursor is not below
+	// numHotBytes, the two global loads, then the rest of the lanes — the resident ones — and the two LDS reads.  The global
+	// load is the request the visit waits for (an LDS read is back in 50 - 100 cycles, an L1 miss in ~190), so it leaves
+	// first; the instruction count is the same.  A lane is in one set only, so the cold lanes' return — which overwrites
+	// their v53 last — never touches the address a resident lane's LDS read has yet to use; a negative cursor is in neither
+	// set, because the lanes that go on have none (on entry every lane of EXEC is walking).
 #define PT_NODE_PHASE_FETCH \
-		"v_cmp_gt_i32 vcc, %[numHotBytes], v53\n" \
+		"v_cmp_le_i32 vcc, %[numHotBytes], v53\n" \
 		"s_and_saveexec_b64 %[active], vcc\n" \
-		"ds_read_b128 v[46:49], v53\n" \
-		"ds_read_b128 v[50:53], v53 offset:16\n" \
-		"s_xor_b64 exec, exec, %[active]\n" \
 		"global_load_dwordx4 v[46:49], v53, %[nodes]\n" \
 		"global_load_dwordx4 v[50:53], v53, %[nodes] offset:16\n" \
+		"s_xor_b64 exec, exec, %[active]\n" \
+		"ds_read_b128 v[46:49], v53\n" \
+		"ds_read_b128 v[50:53], v53 offset:16\n" \
 		"s_mov_b64 exec, %[active]\n"
 	// EXEC = the lanes whose box is hit.  A hit container continues at w0, everything else at w1;
 	// the lanes on a hit leaf park; then the lanes that go on: alive and not parked.
@@ -1070,7 +1076,8 @@ PT_DEV void nodePhaseAsm(
 // The same node phase over compact records (above): the cursor lives in v45 — the load of the ray's own next word overwrites
 // it (a load may overwrite a register that earlier loads of the same phase used as their address: they have issued), so a
 // missed box or a leaf finds its successor in place, and a hit container takes one of its two first children instead.
-// 27 vector + 8 scalar instructions and three loads per visit.
+// 27 vector + 8 scalar instructions and three loads per visit; the cold lanes' three loads first, then the resident lanes' three
+// LDS reads (round 11, as nodePhaseAsm: the load of the cursor is the last of its kind, and a lane is in one set only).
 template<bool ANYHIT>
 PT_DEV void nodePhaseAsmCompact(
 	const DevParams& P, const f2v oxy, const f2v ozz, const f2v ixy, const f2v izz, float rayT, int keep, int kOff,
@@ -1083,15 +1090,15 @@ PT_DEV void nodePhaseAsmCompact(
 
 #define PT_NODE_PHASE_FETCH \
 		"v_add_u32 v62, v45, %[kOff]\n" \
-		"v_cmp_gt_i32 vcc, %[numHotBytes], v45\n" \
+		"v_cmp_le_i32 vcc, %[numHotBytes], v45\n" \
 		"s_and_saveexec_b64 %[active], vcc\n" \
-		"ds_read_b128 v[46:49], v45\n" \
-		"ds_read_b128 v[50:53], v45 offset:16\n" \
-		"ds_read_b32 v45, v62\n" \
-		"s_xor_b64 exec, exec, %[active]\n" \
 		"global_load_dwordx4 v[46:49], v45, %[nodes]\n" \
 		"global_load_dwordx4 v[50:53], v45, %[nodes] offset:16\n" \
 		"global_load_dword v45, v62, %[nodes]\n" \
+		"s_xor_b64 exec, exec, %[active]\n" \
+		"ds_read_b128 v[46:49], v45\n" \
+		"ds_read_b128 v[50:53], v45 offset:16\n" \
+		"ds_read_b32 v45, v62\n" \
 		"s_mov_b64 exec, %[active]\n"
 #define PT_NODE_PHASE_VISIT( cull ) \
 		"v_add_u32 %[visits], 1, %[visits]\n" \
@@ -2104,7 +2111,8 @@ PT_DEV bool stepPixel( const DevParams& P, const float4* lds, PixelState& st, La
 // A band has PT_SUB = 4 HEADS: head s deals tiles s, s + 4, s + 8 ... of the band's order, so the four advance through the same
 // neighbourhood side by side.  A wave draws from the head of its wave index in the block (mod 4) and, once it has left its own
 // band, from the same sub-head of the band it helps — the thieves of a band spread over its four heads.  A head is one address
-// that every XCD's atomics must reach in memory: it hands out ≈ 90 draws / µs, and the launch draws 250 – 600 / µs.  With one head
+// that every XCD's atomics must reach in memory: it hands out ≈ 90 draws / µs, and the launch as a whole draws 129 – 168 / µs on average
+// (measured, TCC_ATOMIC: profiles/r06/experiments/queue_draw_rate.txt) — more than one head serves, less than a band's four.  With one head
 // per band the end of a launch, when the XCDs that have run dry converge on the few bands that still hold tiles, was bound by
 // that: 64-frame launches dealt spatially +6.5 % (Cornell), +2.1 % (Sponza-class), +8.6 % (Dragon-class), +0.9 % (hairball)
 // with four heads; eight heads per band are slower again (profiles/r06/experiments/queue_subheads_4_8.txt).
