@@ -29,7 +29,13 @@
 // may or may not count); otherwise everything is waited for.  A walk's next records are requested as soon as its visit has
 // decided which lanes go on — the exit test runs under the requests; when `keep` or fewer walks go on, each walk takes the visit
 // its request is for (a node phase may always run one visit longer) and the phase ends with nothing in flight.
-// Per walk-visit 24 vector instructions (nodePhaseAsm: 22) and 11 scalar ones, the wait among them (nodePhaseAsm: 8), plus the
+// Round 12 (request first): the cold request leaves three scalar-unit steps behind the cursor's v_cndmask — the walk's mask
+// less the lanes that just parked, one signed compare against numHotBytes (false for an ended walk's negative cursor: no alive
+// test), s_and_saveexec —; the resident lanes (one unsigned compare, which is the alive test too), the walk's next mask, the
+// flag and "nobody goes on" (no branch any more: an empty request, then the empty-walk skip) stand behind the global loads, and
+// walk A's last visit takes the counted wait.  The invariants are written out at PT_DUAL_VISIT_AND_FETCH.
+// Per walk-visit 24 vector instructions (nodePhaseAsm: 22; one of the 24 is the v_cmpx that finds the resident lanes, which
+// replaced the alive compare) and 11 scalar ones, the wait among them (nodePhaseAsm: 8), plus the
 // loop's five per pair of visits (two s_bcnt1: a lane may hold two walks, so no combined mask counts them).  Up to round 10: 24
 // and 14 — round 11 took the cursor's copy and the parked lanes' tNear select out of the chain between a record's arrival and
 // the next request (the copy is gone, tNear and the leaf word are kept behind the request, under EXEC = the parked lanes, which
@@ -104,48 +110,70 @@
 		"v_cmpx_gt_f32 %[rayT" W "], v60\n" \
 		"v_cmpx_le_f32 v60, v61\n" \
 		"v_cmp_gt_i32 s[98:99], 0, v" r6 "\n" \
-		"v_cndmask_b32 v" r7 ", v" r6 ", v" r7 ", s[98:99]\n" \
-		"s_mov_b64 exec, " walk "\n" \
-		"v_cmp_le_i32 s[94:95], 0, v" r7 "\n"
+		"v_cndmask_b32 v" r7 ", v" r6 ", v" r7 ", s[98:99]\n"
 // what a visit owes the lanes that parked on a hit leaf: the leaf's word and tNear (a slab temporary the other walk's visit
 // overwrites) — behind the request, which does not need them
 #define PT_DUAL_KEEP_PARKED( W, r6 ) \
 		"s_mov_b64 exec, s[98:99]\n" \
 		"v_mov_b32 %[tNear" W "], v60\n" \
 		"v_mov_b32 %[leafWord" W "], v" r6 "\n"
-// ... and, in the loop, the request for its next records at once: the lanes that go on are EXEC straight from the two masks,
-// and become the walk's mask on the way (s_and_saveexec)
+// ... and, in the loop, the request for its next records at once (round 12: request first).  Behind the v_cndmask that puts
+// the next reference into the cursor there are three scalar-unit steps up to the first global load (up to round 11: six) —
+//     s_andn2 exec, walk, s[98:99]          the walk's lanes that did not just park
+//     v_cmp_le_i32 vcc, numHotBytes, cursor the cold ones among them: numHotBytes >= 0, so the SIGNED compare is false for
+//                                           every lane whose walk has ended (cursor < 0) — no alive test in front of it
+//     s_and_saveexec s[94:95], vcc          EXEC = the cold lanes
+// — and behind the two loads the resident lanes (numHotBytes >u cursor, UNSIGNED: true exactly for 0 <= cursor <
+// numHotBytes, so it is the alive test as well; v_cmpx writes EXEC and s[94:95] alike), their two LDS reads, the walk's next
+// mask = cold | resident, and the flag.  Eight instructions around the four memory ones, as before.  Invariants:
+//  - A cold lane's cursor register is overwritten when its load returns, at any time after issue.  Every instruction behind
+//    the request that reads the cursor therefore runs with the cold lanes out of EXEC: the resident set is derived under
+//    EXEC = ( walk & ~parked ) & ~cold (s_xor: cold is a subset), never under the walk's whole mask.
+//  - A lane is in at most one of { cold, resident, parked, ended }.  A parked or ended lane is in no later fetch of that walk,
+//    so its last word, leaf word and tNear stay where they are until the phase ends (PT_DUAL_KEEP_PARKED reads them behind
+//    the request, under EXEC = s[98:99]).
+//  - numHotBytes = 0 (knob lds_slots = 0): no resident lane ever, the global loads carry every lane that goes on.
+//    numHotBytes at or above the tree's size: no cold lane ever, the global loads issue with an empty EXEC.
+//  - The flag: VCC = the cold lanes, kept by s_cselect_b64 only where s_cmp_lg_u64 found resident lanes too — VCC != 0
+//    exactly when both sets have lanes; a fetch with an empty cold set, an empty resident set, or both leaves VCC = 0, and
+//    the other walk's wait is then for everything (whether an instruction with an empty EXEC counts is not known here).
+//    Nothing between here and the other walk's wait writes VCC.
+//  - "Nobody goes on" does not branch at all any more: that request has neither kind of lane (four memory instructions with
+//    EXEC = 0, which write no register), it leaves VCC = 0 and the walk's mask = 0, and the walk's next visit is the one
+//    PT_DUAL_VISIT_CORE has always skipped for a walk without lanes (s_cbranch_execz, out of line: VCC = 0) — no visit runs
+//    on records nobody asked for.
 #define PT_DUAL_VISIT_AND_FETCH( ... ) PT_DUAL_VISIT_AND_FETCH_( __VA_ARGS__ )
-#define PT_DUAL_VISIT_AND_FETCH_( skip, empty, wait, none, resume, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+#define PT_DUAL_VISIT_AND_FETCH_( skip, empty, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
 		PT_DUAL_VISIT_CORE( empty, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
-		"s_andn2_b64 exec, s[94:95], s[98:99]\n" \
-		"s_cbranch_scc0 " none "f\n" \
+		"s_andn2_b64 exec, " walk ", s[98:99]\n" \
 		"v_cmp_le_i32 vcc, %[numHotBytes], v" r7 "\n" \
-		"s_and_saveexec_b64 " walk ", vcc\n" \
+		"s_and_saveexec_b64 s[94:95], vcc\n" \
 		"global_load_dwordx4 v[" r0 ":" r3 "], v" r7 ", %[nodes]\n" \
 		"global_load_dwordx4 v[" r4 ":" r7 "], v" r7 ", %[nodes] offset:16\n" \
-		"s_xor_b64 exec, exec, " walk "\n" \
-		"s_cselect_b64 vcc, vcc, 0\n" \
+		"s_xor_b64 exec, exec, s[94:95]\n" \
+		"v_cmpx_gt_u32_e64 s[94:95], %[numHotBytes], v" r7 "\n" \
 		"ds_read_b128 v[" r0 ":" r3 "], v" r7 "\n" \
 		"ds_read_b128 v[" r4 ":" r7 "], v" r7 " offset:16\n" \
-	resume ":\n" \
+		"s_or_b64 " walk ", vcc, s[94:95]\n" \
+		"s_cmp_lg_u64 s[94:95], 0\n" \
+		"s_cselect_b64 vcc, vcc, 0\n" \
 		PT_DUAL_KEEP_PARKED( W, r6 ) \
 	skip ":\n"
-// nobody goes on: nothing to request, and the flag says so (out of line)
-#define PT_DUAL_VISIT_NONE( none, resume, walk ) \
-	none ":\n" \
-		"s_mov_b64 vcc, 0\n" \
-		"s_mov_b64 " walk ", 0\n" \
-		"s_branch " resume "b\n"
 // a walk that has no lanes left takes no visit and issues nothing — which the other walk's wait must know: VCC would still
 // hold that other walk's own flag (out of line)
 #define PT_DUAL_VISIT_EMPTY( empty, skip ) \
 	empty ":\n" \
 		"s_mov_b64 vcc, 0\n" \
 		"s_branch " skip "b\n"
+// The visits the phase ends with (no request follows).  Walk A's takes the counted wait like every visit of the loop (round
+// 12): when the loop is left VCC is still the flag of walk B's last fetch — between PT_DUAL_VISIT_AND_FETCH( B ) and here stand
+// s_cselect_b64 (which wrote it), PT_DUAL_KEEP_PARKED (s_mov exec, two v_mov), s_bcnt1 x 2, s_add, s_cmp and the branch
+// that fell through, which write EXEC and SCC only; a walk B without lanes set VCC = 0 (PT_DUAL_VISIT_EMPTY) — and B's loads
+// are the two youngest of each kind, so A's slab test runs while B's records are still on their way.  Walk B's waits for
+// everything: nothing was issued after its request (and A's visit has written VCC by then: its v_cmpx do).
 #define PT_DUAL_VISIT_LAST( ... ) PT_DUAL_VISIT_LAST_( __VA_ARGS__ )
-#define PT_DUAL_VISIT_LAST_( skip, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
-		PT_DUAL_VISIT_CORE( skip, "s_waitcnt vmcnt(0) lgkmcnt(0)\n", W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+#define PT_DUAL_VISIT_LAST_( skip, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
+		PT_DUAL_VISIT_CORE( skip, wait, W, walk, r0, r1, r2, r3, r4, r5, r6, r7 ) \
 		PT_DUAL_KEEP_PARKED( W, r6 ) \
 	skip ":\n"
 #define PT_DUAL_REGS_A "46", "47", "48", "49", "50", "51", "52", "53"
@@ -174,8 +202,8 @@ PT_DEV void nodePhaseDualPipe(
 		PT_DUAL_FETCH( "s[88:89]", "v71", "64:67", "68", "71", "11" )
 	"1:\n"
 		// walk A on its records (B's request, issued after them, may stay in flight), and A's next request; then B the same way
-		PT_DUAL_VISIT_AND_FETCH( "4", "22", PT_DUAL_WAIT( "12", "13" ), "14", "19", "A", "s[86:87]", PT_DUAL_REGS_A )
-		PT_DUAL_VISIT_AND_FETCH( "5", "23", PT_DUAL_WAIT( "15", "16" ), "17", "20", "B", "s[88:89]", PT_DUAL_REGS_B )
+		PT_DUAL_VISIT_AND_FETCH( "4", "22", PT_DUAL_WAIT( "12", "13" ), "A", "s[86:87]", PT_DUAL_REGS_A )
+		PT_DUAL_VISIT_AND_FETCH( "5", "23", PT_DUAL_WAIT( "15", "16" ), "B", "s[88:89]", PT_DUAL_REGS_B )
 		"s_bcnt1_i32_b64 s96, s[86:87]\n"
 		"s_bcnt1_i32_b64 s97, s[88:89]\n"
 		"s_add_i32 s96, s96, s97\n"
@@ -183,8 +211,8 @@ PT_DEV void nodePhaseDualPipe(
 		"s_cbranch_scc1 1b\n"
 		// enough walks have left.  The records that are on their way are not dropped: each walk takes that visit (a node phase
 		// may always run one visit longer), and the phase ends with nothing in flight
-		PT_DUAL_VISIT_LAST( "6", "A", "s[86:87]", PT_DUAL_REGS_A )
-		PT_DUAL_VISIT_LAST( "7", "B", "s[88:89]", PT_DUAL_REGS_B )
+		PT_DUAL_VISIT_LAST( "6", PT_DUAL_WAIT( "24", "25" ), "A", "s[86:87]", PT_DUAL_REGS_A )
+		PT_DUAL_VISIT_LAST( "7", "s_waitcnt vmcnt(0) lgkmcnt(0)\n", "B", "s[88:89]", PT_DUAL_REGS_B )
 		"s_waitcnt vmcnt(0) lgkmcnt(0)\n"
 		"s_mov_b64 exec, s[84:85]\n"
 		"v_mov_b32 %[refA], v53\n"
@@ -192,10 +220,9 @@ PT_DEV void nodePhaseDualPipe(
 		"s_branch 21f\n"
 		PT_DUAL_WAIT_FULL( "12", "13" )
 		PT_DUAL_WAIT_FULL( "15", "16" )
+		PT_DUAL_WAIT_FULL( "24", "25" )
 		PT_DUAL_FETCH_NONE( "10" )
 		PT_DUAL_FETCH_NONE( "11" )
-		PT_DUAL_VISIT_NONE( "14", "19", "s[86:87]" )
-		PT_DUAL_VISIT_NONE( "17", "20", "s[88:89]" )
 		PT_DUAL_VISIT_EMPTY( "22", "4" )
 		PT_DUAL_VISIT_EMPTY( "23", "5" )
 	"21:\n"
@@ -222,7 +249,6 @@ PT_DEV void nodePhaseDualPipe(
 #undef PT_DUAL_VISIT_AND_FETCH
 #undef PT_DUAL_VISIT_AND_FETCH_
 #undef PT_DUAL_VISIT_LAST_
-#undef PT_DUAL_VISIT_NONE
 #undef PT_DUAL_VISIT_EMPTY
 #undef PT_DUAL_KEEP_PARKED
 #undef PT_DUAL_VISIT_LAST

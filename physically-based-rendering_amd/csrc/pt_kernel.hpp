@@ -977,12 +977,31 @@ PT_DEV void nodePhaseAsm(
 	// costs three times what one in front of it costs; pt_dual.hpp gained 2 % from the same reordering), and the exit test was
 	// three scalar instructions and the loop's taken branch of it.  When the phase ends with a request on its way, the lanes it
 	// is for take that visit too (a node phase may always run one visit longer: per lane the sequence of visits is the same).
-	// The request itself asks for the COLD records first (round 11): EXEC = the lanes that go on whose cursor is not below
-	// numHotBytes, the two global loads, then the rest of the lanes — the resident ones — and the two LDS reads.  The global
-	// load is the request the visit waits for (an LDS read is back in 50 - 100 cycles, an L1 miss in ~190), so it leaves
-	// first; the instruction count is the same.  A lane is in one set only, so the cold lanes' return — which overwrites
-	// their v53 last — never touches the address a resident lane's LDS read has yet to use; a negative cursor is in neither
-	// set, because the lanes that go on have none (on entry every lane of EXEC is walking).
+	// The request itself asks for the COLD records first (round 11): the global load is the request the visit waits for (an
+	// LDS read is back in 50 - 100 cycles, an L1 miss in ~190).  Since round 12 nothing the cold request does not need stands in
+	// front of it: behind the v_cndmask that puts the next reference into v53 there are THREE scalar-unit steps up to the first
+	// global_load (up to round 11: seven) —
+	//     s_andn2 exec, active, vcc       the walk's lanes that did not just park (VCC = the lanes on a hit leaf)
+	//     v_cmp_le_i32 mA, numHotBytes, v53    the cold ones among them: numHotBytes >= 0, so the SIGNED compare is false for
+	//                                     every lane whose walk has ended (v53 < 0) — no alive test in front of it
+	//     s_and_saveexec active, mA       EXEC = the cold lanes, active = the walk's lanes that did not park
+	// — and behind the two loads: the park mask, the resident lanes (numHotBytes >u v53, UNSIGNED: true exactly for
+	// 0 <= v53 < numHotBytes, so it is the alive test as well) and their two LDS reads, the walk's next mask = cold | resident,
+	// and "nobody goes on".  The instruction counts per visit are what they were (one compare became a v_cmpx, the branch moved).  Invariants:
+	//  - A cold lane's v53 is overwritten when its load returns, at any time after issue.  Every instruction behind the request
+	//    that reads v53 therefore runs with the cold lanes out of EXEC: the resident set is derived under
+	//    EXEC = ( active & ~parked ) & ~cold (s_xor: cold is a subset), never under the walk's whole mask.
+	//  - A lane is in at most one of { cold, resident, parked, ended }.  A parked or ended lane is in no later fetch of this
+	//    phase, so its v53, its leaf word v52 and tNear / tFar v60 / v61 stay where they are until the phase ends.
+	//  - numHotBytes = 0 (knob lds_slots = 0): no resident lane ever, the global loads carry every lane that goes on and the
+	//    LDS reads issue with an empty EXEC.  numHotBytes at or above the tree's size: no cold lane ever, the global loads
+	//    issue with an empty EXEC.  An instruction with an empty EXEC writes no register; the visit's wait is for everything.
+	//  - "Nobody goes on" no longer branches in front of the request: that request then has neither kind of lane (four memory
+	//    instructions with EXEC = 0), and the branch BEHIND it leaves the loop — no visit runs on records nobody asked for.
+	//    That exit is taken without a wait, so those four may still be counted in vmcnt / lgkmcnt when the phase returns (up to
+	//    round 11 nothing had been issued at that point).  They write no register, every later wait of the kernel is for
+	//    everything it needs, and an empty cold set has always issued its loads with EXEC = 0 in the same way.
+	// The entry fetch is round 11's: on entry every lane of EXEC is walking, so the lanes that go on have no negative cursor.
 #define PT_NODE_PHASE_FETCH \
 		"v_cmp_le_i32 vcc, %[numHotBytes], v53\n" \
 		"s_and_saveexec_b64 %[active], vcc\n" \
@@ -992,14 +1011,28 @@ PT_DEV void nodePhaseAsm(
 		"ds_read_b128 v[46:49], v53\n" \
 		"ds_read_b128 v[50:53], v53 offset:16\n" \
 		"s_mov_b64 exec, %[active]\n"
+	// a visit's request: v_cmpx writes EXEC and VCC alike (gfx9), and s_or leaves SCC = "somebody goes on"
+#define PT_NODE_PHASE_REQUEST \
+		"s_andn2_b64 exec, %[active], vcc\n" \
+		"v_cmp_le_i32 %[mA], %[numHotBytes], v53\n" \
+		"s_and_saveexec_b64 %[active], %[mA]\n" \
+		"global_load_dwordx4 v[46:49], v53, %[nodes]\n" \
+		"global_load_dwordx4 v[50:53], v53, %[nodes] offset:16\n" \
+		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
+		"s_xor_b64 exec, exec, %[active]\n" \
+		"v_cmpx_gt_u32 vcc, %[numHotBytes], v53\n" \
+		"ds_read_b128 v[46:49], v53\n" \
+		"ds_read_b128 v[50:53], v53 offset:16\n" \
+		"s_or_b64 %[active], vcc, %[mA]\n" \
+		"s_mov_b64 exec, %[active]\n"
 	// EXEC = the lanes whose box is hit.  A hit container continues at w0, everything else at w1;
-	// the lanes on a hit leaf park; then the lanes that go on: alive and not parked.
+	// the lanes on a hit leaf park (VCC); who goes on is the request's business (above).
 	// Round 3: the cursor lives in v53 for the whole phase — the record's last word IS the reference to continue at
 	// unless the box is a hit container, so the load that fetches a record also advances the cursor (a load may
 	// overwrite its own address register), and the per-visit copy of w1 is gone; and tFar is min3 of the three slab
 	// exits as they stand: pt_intersect.cl's fmin( ., INFINITY ) on the third only matters when all three are NaN, and
 	// then tNear is NaN too and the box is missed either way (the C++ statement below keeps the reference's form).
-	// 22 vector + 8 scalar instructions per visit.
+	// 22 vector + 8 scalar instructions per visit, the request's among them.
 #define PT_NODE_PHASE_VISIT( cull ) \
 		"v_add_u32 %[visits], 1, %[visits]\n" \
 		"s_waitcnt vmcnt(0) lgkmcnt(0)\n" \
@@ -1020,11 +1053,7 @@ PT_DEV void nodePhaseAsm(
 		"v_cmpx_lt_f32 %[eps], v61\n" \
 		cull \
 		"v_cmp_gt_i32 vcc, 0, v52\n" \
-		"v_cndmask_b32 v53, v52, v53, vcc\n" \
-		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
-		"s_mov_b64 exec, %[active]\n" \
-		"v_cmp_le_i32 %[mA], 0, v53\n" \
-		"s_andn2_b64 exec, %[mA], vcc\n"
+		"v_cndmask_b32 v53, v52, v53, vcc\n"
 #define PT_NODE_PHASE_LOOP( cull ) \
 		"s_mov_b64 %[saved], exec\n" \
 		"s_mov_b64 %[parkMask], 0\n" \
@@ -1032,12 +1061,13 @@ PT_DEV void nodePhaseAsm(
 		PT_NODE_PHASE_FETCH \
 	"1:\n" \
 		PT_NODE_PHASE_VISIT( cull ) \
-		"s_cbranch_scc0 3f\n"                                 /* nobody goes on: nothing to request */ \
-		PT_NODE_PHASE_FETCH \
+		PT_NODE_PHASE_REQUEST \
+		"s_cbranch_scc0 3f\n"                                 /* nobody goes on: the request had no lane, nothing is on its way */ \
 		"s_bcnt1_i32_b64 %[count], exec\n" \
 		"s_cmp_gt_i32 %[count], %[keep]\n" \
 		"s_cbranch_scc1 1b\n" \
 		PT_NODE_PHASE_VISIT( cull )                            /* the phase ends; the records on their way are not dropped */ \
+		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
 	"3:\n" \
 		"s_mov_b64 exec, %[saved]\n" \
 		"v_mov_b32 %[ref], v53\n" \
@@ -1068,6 +1098,7 @@ PT_DEV void nodePhaseAsm(
 	}
 
 #undef PT_NODE_PHASE_FETCH
+#undef PT_NODE_PHASE_REQUEST
 #undef PT_NODE_PHASE_VISIT
 #undef PT_NODE_PHASE_LOOP
 #undef PT_NODE_PHASE_OPERANDS
@@ -1077,7 +1108,11 @@ PT_DEV void nodePhaseAsm(
 // it (a load may overwrite a register that earlier loads of the same phase used as their address: they have issued), so a
 // missed box or a leaf finds its successor in place, and a hit container takes one of its two first children instead.
 // 27 vector + 8 scalar instructions and three loads per visit; the cold lanes' three loads first, then the resident lanes' three
-// LDS reads (round 11, as nodePhaseAsm: the load of the cursor is the last of its kind, and a lane is in one set only).
+// LDS reads (round 11, as nodePhaseAsm: the load of the cursor is the last of its kind, and a lane is in one set only).  Round 12,
+// as nodePhaseAsm and with its invariants: four steps between the cursor's v_cndmask and the first global load (s_andn2, the
+// signed compare, the v_add_u32 of the cursor's own word's address, s_and_saveexec; up to round 11: eight), the rest behind the loads.
+// "Nobody goes on" leaves the loop behind a request of six memory instructions with EXEC = 0, without a wait: they may still be
+// counted when the phase returns and write no register.
 template<bool ANYHIT>
 PT_DEV void nodePhaseAsmCompact(
 	const DevParams& P, const f2v oxy, const f2v ozz, const f2v ixy, const f2v izz, float rayT, int keep, int kOff,
@@ -1099,6 +1134,24 @@ PT_DEV void nodePhaseAsmCompact(
 		"ds_read_b128 v[46:49], v45\n" \
 		"ds_read_b128 v[50:53], v45 offset:16\n" \
 		"ds_read_b32 v45, v62\n" \
+		"s_mov_b64 exec, %[active]\n"
+	// a visit's request, as nodePhaseAsm's (round 12): v62 = the address of the cursor's own word for every lane of the walk
+	// that did not park — the third global load needs it, the third LDS read uses it after the cold lanes' v45 may be gone
+#define PT_NODE_PHASE_REQUEST \
+		"s_andn2_b64 exec, %[active], vcc\n" \
+		"v_cmp_le_i32 %[mA], %[numHotBytes], v45\n" \
+		"v_add_u32 v62, v45, %[kOff]\n" \
+		"s_and_saveexec_b64 %[active], %[mA]\n" \
+		"global_load_dwordx4 v[46:49], v45, %[nodes]\n" \
+		"global_load_dwordx4 v[50:53], v45, %[nodes] offset:16\n" \
+		"global_load_dword v45, v62, %[nodes]\n" \
+		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
+		"s_xor_b64 exec, exec, %[active]\n" \
+		"v_cmpx_gt_u32 vcc, %[numHotBytes], v45\n" \
+		"ds_read_b128 v[46:49], v45\n" \
+		"ds_read_b128 v[50:53], v45 offset:16\n" \
+		"ds_read_b32 v45, v62\n" \
+		"s_or_b64 %[active], vcc, %[mA]\n" \
 		"s_mov_b64 exec, %[active]\n"
 #define PT_NODE_PHASE_VISIT( cull ) \
 		"v_add_u32 %[visits], 1, %[visits]\n" \
@@ -1124,11 +1177,7 @@ PT_DEV void nodePhaseAsmCompact(
 		"v_cmp_ne_u32 %[mB], 0, v62\n" \
 		"v_cndmask_b32 v63, v52, v53, %[mB]\n" \
 		"v_sub_u32 v63, v63, v62\n" \
-		"v_cndmask_b32 v45, v63, v45, vcc\n" \
-		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
-		"s_mov_b64 exec, %[active]\n" \
-		"v_cmp_le_i32 %[mA], 0, v45\n" \
-		"s_andn2_b64 exec, %[mA], vcc\n"
+		"v_cndmask_b32 v45, v63, v45, vcc\n"
 #define PT_NODE_PHASE_LOOP( cull ) \
 		"s_mov_b64 %[saved], exec\n" \
 		"s_mov_b64 %[parkMask], 0\n" \
@@ -1136,12 +1185,13 @@ PT_DEV void nodePhaseAsmCompact(
 		PT_NODE_PHASE_FETCH \
 	"1:\n" \
 		PT_NODE_PHASE_VISIT( cull ) \
+		PT_NODE_PHASE_REQUEST \
 		"s_cbranch_scc0 3f\n" \
-		PT_NODE_PHASE_FETCH \
 		"s_bcnt1_i32_b64 %[count], exec\n" \
 		"s_cmp_gt_i32 %[count], %[keep]\n" \
 		"s_cbranch_scc1 1b\n" \
 		PT_NODE_PHASE_VISIT( cull ) \
+		"s_or_b64 %[parkMask], %[parkMask], vcc\n" \
 	"3:\n" \
 		"s_mov_b64 exec, %[saved]\n" \
 		"v_mov_b32 %[ref], v45\n" \
@@ -1171,6 +1221,7 @@ PT_DEV void nodePhaseAsmCompact(
 	}
 
 #undef PT_NODE_PHASE_FETCH
+#undef PT_NODE_PHASE_REQUEST
 #undef PT_NODE_PHASE_VISIT
 #undef PT_NODE_PHASE_LOOP
 #undef PT_NODE_PHASE_OPERANDS
