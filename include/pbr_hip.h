@@ -32,10 +32,11 @@ extern "C" {
 
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
- * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided).  A caller that loads the library at run time — or
+ * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
+ * version 11 pbr_denoise_temporal and pbr_temporal_reset).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 10
+#define PBR_ABI_VERSION 11
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -354,6 +355,63 @@ typedef struct pbr_denoise_guided_params {
 } pbr_denoise_guided_params;
 int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_guided_params* params,
                         float* rgba, float* variance_out, float* features );
+
+/* The temporal part of the variance-guided denoise (csrc/pt_temporal.hpp): pbr_denoise_guided with a per-pixel HISTORY that
+ * survives camera moves.  The context keeps, of the previous successful call, the integrated colour and variance, the
+ * first-hit features, the history lengths, the camera and pxDim.  A call re-projects that history through the previous
+ * camera, rejects it across disocclusions, blends it with the new render by sample weight and runs the guided filter on the
+ * result.  Static geometry only (moving geometry would need per-vertex motion: the history is dropped instead, see STATE).
+ * THE DEFINITION, operation by operation in binary32 — reproducible to the bit (tests/temporal_ref.py).  C = the accumulated
+ * image, V = pbr_read_variance's variance, P | t, N | hit, A | material = the feature buffers of pbr_denoise under `cam`;
+ * primes are the previous successful call's: its integrated buffer I', its three feature buffers, its lengths L', its camera
+ * (eye', cu', cv', cw' = its u, v, w) and halfPx' = pxDim' * 0.5f.  dot( a, b ) = ( ax*bx + ay*by ) + az*bz.  For the pixel
+ * (px, py) of a w x h image:
+ *   1. candidate.  Hit pixel: d = P.xyz - eye'.  Miss pixel: d = cw + inner * halfPx of the CURRENT camera, exactly as the
+ *      feature pass builds its ray direction before normalizing it — inner = ( ( ( ( cu - cu * (float) w ) + cu * ( 2.0f * (float) px ) )
+ *      + cv ) - cv * (float) h ) + cv * ( 2.0f * (float) py ), per component (the sky is at infinity: translation is ignored).
+ *      a = dot( d, cu' ) / dot( cu', cu' ), b likewise with cv', c with cw'.  !( c > 0 ): no candidate.
+ *      fx = ( a / ( c * halfPx' ) + (float) ( w - 1 ) ) * 0.5f, fy the same with b and h; a value that is not finite: no candidate.
+ *      (This inverts the camera-ray construction for an orthogonal basis, which is what PathTracer::fillCameraBasis and
+ *      pbrh_camera_lookat hand out; for any other basis the formula is still what is computed.)
+ *   2. taps.  x0 = floorf( fx ), tx = fx - x0, likewise y0, ty.  Taps ( x0 + i, y0 + j ), j outer, i inner, i, j in {0, 1};
+ *      bw = ( i ? tx : 1 - tx ) * ( j ? ty : 1 - ty ).  A tap is valid if it is inside the image, bw > 0, N'.w == N.w, I' is finite
+ *      in all four words, and — for a hit centre — A'.w == A.w, dot( N', N ) >= normal_cos and
+ *      squaredDistance3( P', P ) <= r * r with r = ( sigma_world * pxDim ) * P.w (this last term is skipped when sigma_world == 0).
+ *   3. history value.  S = sum of bw over the valid taps in visiting order.  S > 0: Hc = ( sum bw * I'.rgb ) / S,
+ *      Hv = ( sum ( bw * bw ) * I'.w ) / ( S * S ), Hl = L' of the valid tap with the largest bw (on ties the first in visiting
+ *      order).  Otherwise there is no history.
+ *   4. blend.  Without history, with C or V not finite, or with max_history == 1: I = {C, V} copied bit for bit, L = 1.
+ *      Otherwise L = min( Hl + 1, max_history ), alpha = 1.0f / (float) L, I.rgb = Hc + alpha * ( C - Hc ),
+ *      I.w = ( ( 1 - alpha ) * ( 1 - alpha ) ) * Hv + ( alpha * alpha ) * V.  On the first call after the history was dropped no
+ *      pixel has a candidate.  (Steps 1 - 3 do not look at max_history: `history` reports them for max_history == 1 too.)
+ *   5. filter.  filter->passes passes of pbr_denoise_guided's filter, unchanged, on colour I.rgb and variance I.w; the last pass
+ *      restores .w from the accumulated image as pbr_denoise_guided does.
+ *   6. store.  I, the three feature buffers, L, cam and pxDim become the history.  What is fed back is the PRE-FILTER I: the
+ *      filter's blur does not compound from call to call.
+ *   rgba          host, width x height x 4 floats: filtered colour, .w = the accumulated first-hit distance
+ *   variance_out  optional (NULL): host, width x height floats, V after the last pass
+ *   integrated    optional (NULL): host, width x height x 4 floats: I, .w = the integrated variance — the filter's input
+ *   history       optional (NULL): host, width x height x 4 floats {fx, fy, L, valid}: the candidate (NaN, NaN where there is
+ *                 none), the history length after this call, the accepted taps as a bit mask (bit 2 * j + i) — all as floats
+ * STATE.  Preconditions as pbr_denoise_guided: unsharded, right behind a successful pbr_render_adaptive (PBR_ESTATE otherwise).
+ * A second pbr_denoise_temporal without a new successful pbr_render_adaptive in between is PBR_ESTATE: it would integrate the
+ * same render twice.  PBR_EINVAL: null cam, temporal, filter or rgba; max_history outside 1 .. 1024; normal_cos outside
+ * [-1, 1] or NaN; sigma_world negative or not finite; the filter's argument checks.  The history is dropped — the next call
+ * starts at L = 1 everywhere — by pbr_temporal_reset, pbr_configure, pbr_upload_scene and pbr_update_vertices; NOT by renders,
+ * pbr_reset_accum, pbr_denoise or pbr_denoise_guided: a camera move with a fresh accumulation is the use case.  A refused call
+ * changes nothing; a successful one does not modify the accumulation, the moments or the tile stats.
+ * The history (two sets of four width x height float4 planes + lengths, swapped by pointer, and the filter's working planes)
+ * is allocated by the first call after pbr_configure and freed by pbr_configure / pbr_destroy: no allocation per call.
+ * pbr_last_kernel_ms reports the device time of the untile, variance, feature, integrate and filter kernels. */
+typedef struct pbr_temporal_params {
+	uint32_t max_history;   /* 1 .. 1024: cap of the history length L; 1 = no reuse */
+	float normal_cos;       /* a history tap is valid if dot( n_prev, n ) >= normal_cos; -1 .. 1 */
+	float sigma_world;      /* ... and if |x_prev - x|^2 <= ( sigma_world * pxDim * t )^2; finite, >= 0; 0 = term off */
+} pbr_temporal_params;
+int pbr_temporal_reset( pbr_ctx* ctx );
+int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam,
+                          const pbr_temporal_params* temporal, const pbr_denoise_guided_params* filter,
+                          float* rgba, float* variance_out, float* integrated, float* history );
 
 /* Opt-in fast BVH build on the device: faces in Morton order, clustered bottom-up by
  * surface area, at most 2 faces per leaf, emitted in the reference's flat format — what BVH::getNodes + the packing

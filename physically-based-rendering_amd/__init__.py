@@ -52,6 +52,16 @@ class GuidedDenoiseParams(ctypes.Structure):
         super().__init__(passes, sigma_luminance, sigma_normal, sigma_world, sigma_albedo)
 
 
+class TemporalParams(ctypes.Structure):
+    """pbr_temporal_params: the history of pbr_denoise_temporal.  max_history caps the history length (1 = no reuse); a
+    history tap counts if its normal's cosine with the pixel's is >= normal_cos and it lies within sigma_world pixel
+    footprints of the pixel's first hit (0 switches that term off)."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("normal_cos", ctypes.c_float), ("sigma_world", ctypes.c_float)]
+
+    def __init__(self, max_history=32, normal_cos=0.9, sigma_world=3.0):
+        super().__init__(max_history, normal_cos, sigma_world)
+
+
 class SceneDesc(ctypes.Structure):
     """pbr_scene_desc"""
     _fields_ = [
@@ -112,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 10
+ABI_VERSION = 11
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -182,6 +192,9 @@ for _name, _args in (
         ("pbr_diag_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_size_t]),
         ("pbr_read_variance", [_vp, _fp]),                                                                               # ABI version 10
         ("pbr_denoise_guided", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(GuidedDenoiseParams), _fp, _fp, _fp]),
+        ("pbr_temporal_reset", [_vp]),                                                                                   # ABI version 11
+        ("pbr_denoise_temporal", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(TemporalParams), ctypes.POINTER(GuidedDenoiseParams),
+                                  _fp, _fp, _fp, _fp]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp])):
     if hasattr(hip, _name):
@@ -570,6 +583,27 @@ class Device:
         self._check(hip.pbr_denoise_guided(self._ctx, px_dim, ctypes.byref(cam), ctypes.byref(params), out.ctypes.data_as(_fp),
                                            var.ctypes.data_as(_fp) if variance else None, feat.ctypes.data_as(_fp) if features else None))
         extra = ([var] if variance else []) + ([feat] if features else [])
+        return (out, *extra) if extra else out
+
+    def temporal_reset(self):
+        """pbr_temporal_reset: drops denoise_temporal's history; the next call starts at L = 1 everywhere."""
+        self._check(hip.pbr_temporal_reset(self._ctx))
+
+    def denoise_temporal(self, px_dim, cam, temporal=None, filter=None, variance=False, integrated=False, history=False):
+        """pbr_denoise_temporal: `denoise_guided` with a per-pixel history that is re-projected through the previous call's
+        camera — once per render_adaptive, after a camera move too.  (H, W, 4) float32; with variance=True also the filtered
+        variance (H, W), with integrated=True the filter's input (H, W, 4) {colour, variance}, with history=True (H, W, 4)
+        {fx, fy, L, valid} — in that order."""
+        temporal = temporal if temporal is not None else TemporalParams()
+        filter = filter if filter is not None else GuidedDenoiseParams()
+        out = np.empty((self.height, self.width, 4), np.float32)
+        var = np.empty((self.height, self.width), np.float32) if variance else None
+        integ = np.empty((self.height, self.width, 4), np.float32) if integrated else None
+        hist = np.empty((self.height, self.width, 4), np.float32) if history else None
+        self._check(hip.pbr_denoise_temporal(self._ctx, px_dim, ctypes.byref(cam), ctypes.byref(temporal), ctypes.byref(filter),
+                                             out.ctypes.data_as(_fp), var.ctypes.data_as(_fp) if variance else None,
+                                             integ.ctypes.data_as(_fp) if integrated else None, hist.ctypes.data_as(_fp) if history else None))
+        extra = ([var] if variance else []) + ([integ] if integrated else []) + ([hist] if history else [])
         return (out, *extra) if extra else out
 
     def counters(self):

@@ -23,6 +23,7 @@
 #include "bvh_build.hpp"
 #include "pt_denoise.hpp"
 #include "pt_denoise_guided.hpp"
+#include "pt_temporal.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 #include "pt_deal.hpp"
@@ -189,6 +190,24 @@ struct pbr_ctx {
 	uint32_t lastAdaptiveRounds = 0;     // of the last adaptive call: rounds (= convergence tests per tile that reached the end),
 	uint64_t lastAdaptiveUnits = 0;      // (pixel, frame) units traced,
 	double lastAdaptiveFoldMs = 0.0;     // time inside foldFramesAdaptive
+	// pbr_denoise_temporal (pt_temporal.hpp): two sets of row-major W x H planes {integrated colour | variance, position, normal,
+	// albedo} + the history lengths — set temporalSet holds the previous successful call's, the other one is written by the
+	// next call and becomes the history by flipping temporalSet: nothing is copied.  Behind them the filter's working planes.
+	// All allocated by the first temporal call after pbr_configure, freed with the images
+	float4* dTemporalI[2] = { nullptr, nullptr };
+	float4* dTemporalPosition[2] = { nullptr, nullptr };
+	float4* dTemporalNormal[2] = { nullptr, nullptr };
+	float4* dTemporalAlbedo[2] = { nullptr, nullptr };
+	unsigned* dTemporalLength[2] = { nullptr, nullptr };
+	float4* dTemporalPing = nullptr;
+	float4* dTemporalPong = nullptr;
+	float4* dTemporalInfo = nullptr;     // {fx, fy, L, valid} of a call that asks for it
+	float* dTemporalVariance = nullptr;
+	int temporalSet = 0;
+	bool temporalHistory = false;        // set temporalSet holds a history: cleared by pbr_temporal_reset, pbr_configure, pbr_upload_scene, pbr_update_vertices
+	bool temporalFresh = false;          // a pbr_render_adaptive succeeded since the last successful temporal call
+	pbr_camera temporalCam = {};         // the history's camera and pixel size
+	float temporalPxDim = 0.0f;
 };
 
 namespace {
@@ -301,6 +320,25 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->dMoments = nullptr;
 	ctx->adaptiveStats = false;
 	ctx->varianceCurrent = false;
+
+	for( int set = 0; set < 2; set++ ) {
+		(void) hipFree( ctx->dTemporalI[set] );
+		(void) hipFree( ctx->dTemporalPosition[set] );
+		(void) hipFree( ctx->dTemporalNormal[set] );
+		(void) hipFree( ctx->dTemporalAlbedo[set] );
+		(void) hipFree( ctx->dTemporalLength[set] );
+		ctx->dTemporalI[set] = ctx->dTemporalPosition[set] = ctx->dTemporalNormal[set] = ctx->dTemporalAlbedo[set] = nullptr;
+		ctx->dTemporalLength[set] = nullptr;
+	}
+
+	(void) hipFree( ctx->dTemporalPing );
+	(void) hipFree( ctx->dTemporalPong );
+	(void) hipFree( ctx->dTemporalInfo );
+	(void) hipFree( ctx->dTemporalVariance );
+	ctx->dTemporalPing = ctx->dTemporalPong = ctx->dTemporalInfo = nullptr;
+	ctx->dTemporalVariance = nullptr;
+	ctx->temporalHistory = false;
+	ctx->temporalFresh = false;
 	ctx->dTileCost = nullptr;
 	ctx->costLearnt = false;
 	ctx->orderPinned = false;
@@ -1402,6 +1440,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeScene( ctx );
+	ctx->temporalHistory = false;   // pbr_denoise_temporal: the history's features are the old scene's
 
 	auto toDevice = [ctx]( float4** dst, const std::vector<Quad>& src ) {
 		HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( Quad ) * src.size() ) );
@@ -1505,6 +1544,7 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	ctx->temporalHistory = false;   // pbr_denoise_temporal: static geometry only
 	const auto uploadStart = std::chrono::steady_clock::now();
 	HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
 	ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
@@ -1757,6 +1797,7 @@ int pbr_render_adaptive( pbr_ctx* ctx, uint32_t first_sample_count, const float*
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	ctx->varianceFirstCount = first_sample_count;
 	ctx->varianceCurrent = true;   // the moments and the frame counts are those of the image as it stands
+	ctx->temporalFresh = true;     // pbr_denoise_temporal: a render it has not integrated yet
 	return PBR_OK;
 }
 
@@ -2180,6 +2221,194 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 	float ms = 0.0f;
 	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
 	ctx->lastKernelMs = (double) ms;
+	return PBR_OK;
+}
+
+// pbr_denoise_temporal's history is dropped: the next call starts every pixel at L = 1.
+int pbr_temporal_reset( pbr_ctx* ctx ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+
+	ctx->temporalHistory = false;
+	return PBR_OK;
+}
+
+// pbr_denoise_guided with a history in front of the filter (csrc/pt_temporal.hpp): the previous call's integrated colour and
+// variance are fetched through the previous camera, blended with this render by sample weight, filtered, and kept — before
+// the filter — for the next call.  Leaves the accumulation, the moments and the tile stats untouched.
+int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_temporal_params* temporal, const pbr_denoise_guided_params* filter,
+                          float* rgba, float* variance_out, float* integrated, float* history ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( !ctx->hasScene || !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "denoise_temporal before pbr_upload_scene / pbr_configure" );
+	}
+	if( cam == nullptr || temporal == nullptr || filter == nullptr || rgba == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "denoise_temporal: null camera, parameters or destination" );
+	}
+	if( temporal->max_history < 1 || temporal->max_history > 1024 ) {
+		return fail( ctx, PBR_EINVAL, "denoise_temporal: max_history 1 .. 1024 (got %u)", temporal->max_history );
+	}
+	if( !( temporal->normal_cos >= -1.0f && temporal->normal_cos <= 1.0f ) ) {
+		return fail( ctx, PBR_EINVAL, "denoise_temporal: normal_cos must be in [-1, 1]" );
+	}
+	if( !( temporal->sigma_world >= 0.0f ) || !std::isfinite( temporal->sigma_world ) ) {
+		return fail( ctx, PBR_EINVAL, "denoise_temporal: sigma_world must be finite and >= 0 (0 switches the term off)" );
+	}
+	if( filter->passes < 1 || filter->passes > 8 ) {
+		return fail( ctx, PBR_EINVAL, "denoise_temporal: 1 .. 8 passes (got %u)", filter->passes );
+	}
+
+	const float sigmas[4] = { filter->sigma_luminance, filter->sigma_normal, filter->sigma_world, filter->sigma_albedo };
+
+	for( int k = 0; k < 4; k++ ) {
+		if( !( sigmas[k] >= 0.0f ) || !std::isfinite( sigmas[k] ) ) {
+			return fail( ctx, PBR_EINVAL, "denoise_temporal: the filter's standard deviations must be finite and >= 0 (0 switches a term off)" );
+		}
+	}
+
+	PBR_TRY( varianceUsable( ctx, "denoise_temporal" ) );
+
+	if( !ctx->temporalFresh ) {
+		return fail( ctx, PBR_ESTATE, "denoise_temporal has integrated this render already: it needs a new pbr_render_adaptive before every call" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
+	const size_t pixels = (size_t) w * (size_t) h;
+
+	if( ctx->dTemporalVariance == nullptr ) {
+		// first use since pbr_configure: all or nothing is kept, dTemporalVariance last
+		auto plane = [ctx, pixels]( float4** dst ) {
+			HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( float4 ) * pixels ) );
+			return PBR_OK;
+		};
+		int status = PBR_OK;
+
+		for( int set = 0; set < 2 && status == PBR_OK; set++ ) {
+			for( float4** dst : { &ctx->dTemporalI[set], &ctx->dTemporalPosition[set], &ctx->dTemporalNormal[set], &ctx->dTemporalAlbedo[set] } ) {
+				if( status == PBR_OK && *dst == nullptr ) {
+					status = plane( dst );
+				}
+			}
+
+			if( status == PBR_OK && ctx->dTemporalLength[set] == nullptr && hipMalloc( (void**) &ctx->dTemporalLength[set], sizeof( unsigned ) * pixels ) != hipSuccess ) {
+				status = fail( ctx, PBR_EDEVICE, "denoise_temporal: no device memory for the history" );
+			}
+		}
+
+		for( float4** dst : { &ctx->dTemporalPing, &ctx->dTemporalPong, &ctx->dTemporalInfo } ) {
+			if( status == PBR_OK && *dst == nullptr ) {
+				status = plane( dst );
+			}
+		}
+
+		PBR_TRY( status );
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTemporalVariance, sizeof( float ) * pixels ) );
+		ctx->temporalHistory = false;
+	}
+
+	const int prev = ctx->temporalSet, cur = 1 - prev;
+	float4* dI = ctx->dTemporalI[cur];
+	float4* dPosition = ctx->dTemporalPosition[cur];
+	float4* dNormal = ctx->dTemporalNormal[cur];
+	float4* dAlbedo = ctx->dTemporalAlbedo[cur];
+	float4* dOriginal = ctx->dRows;   // the staging of every read-back: free between calls
+
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
+	setCamera( &P, cam, w, h, pxDim );
+
+	ptd::TemporalArgs T;
+	T.width = w;
+	T.height = h;
+	T.hasHistory = ctx->temporalHistory ? 1 : 0;
+	T.maxHistory = temporal->max_history;
+	T.normalCos = temporal->normal_cos;
+	T.worldTerm = ( temporal->sigma_world != 0.0f ) ? 1 : 0;
+	T.worldScale = temporal->sigma_world * pxDim;
+	const pbr_camera& old = ctx->temporalCam;
+	const float* oldBasis[4] = { &old.eye.x, &old.u.x, &old.v.x, &old.w.x };
+	float* oldDst[4] = { T.eye, T.cu, T.cv, T.cw };
+
+	for( int i = 0; i < 4; i++ ) {
+		for( int k = 0; k < 3; k++ ) {
+			oldDst[i][k] = oldBasis[i][k];
+		}
+	}
+
+	T.halfPx = ctx->temporalPxDim * 0.5f;
+
+	for( int k = 0; k < 3; k++ ) {
+		T.curCu[k] = P.cu[k];
+		T.curCv[k] = P.cv[k];
+		T.curCw[k] = P.cw[k];
+		T.curCamA[k] = P.camA[k];
+		T.curCvH[k] = P.cvH[k];
+	}
+
+	T.curHalfPx = P.halfPx;
+
+	const dim3 block( 64, 4 );
+	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+		ctx->varianceFirstCount, (const float4*) dOriginal, (float*) nullptr, dI, w, h, ctx->tilesX );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo );
+	hipLaunchKernelGGL( ptd::temporalIntegrate, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
+		(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
+		(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur],
+		( history != nullptr ) ? ctx->dTemporalInfo : (float4*) nullptr );
+	HIP_TRY( ctx, hipGetLastError() );
+
+	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
+	const float4* in = dI;   // the first pass reads I and leaves it as it is: it is the next call's history
+	float4* out = ctx->dTemporalPing;
+
+	for( uint32_t pass = 0; pass < filter->passes; pass++ ) {
+		const bool last = ( pass + 1 == filter->passes );
+		ptd::GuidedArgs A;
+		A.width = w;
+		A.height = h;
+		A.step = 1 << pass;
+		A.sigmaLuminance = filter->sigma_luminance;
+		A.invNormal = inverseSquare( filter->sigma_normal );
+		A.invAlbedo = inverseSquare( filter->sigma_albedo );
+		A.worldScale = filter->sigma_world * (float) A.step * pxDim;
+		hipLaunchKernelGGL( ptd::atrousGuidedPass, grid, block, 0, ctx->stream, A, in, out,
+			(const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
+			(const float4*) ( last ? dOriginal : nullptr ), (float*) ( last ? ctx->dTemporalVariance : nullptr ) );
+		in = out;
+		out = ( out == ctx->dTemporalPing ) ? ctx->dTemporalPong : ctx->dTemporalPing;
+	}
+
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+
+	if( variance_out != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( variance_out, ctx->dTemporalVariance, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+	if( integrated != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( integrated, dI, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+	if( history != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( history, ctx->dTemporalInfo, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	// the set just written becomes the history, by pointer
+	ctx->temporalSet = cur;
+	ctx->temporalHistory = true;
+	ctx->temporalFresh = false;
+	ctx->temporalCam = *cam;
+	ctx->temporalPxDim = pxDim;
 	return PBR_OK;
 }
 
