@@ -33,10 +33,10 @@ extern "C" {
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
- * version 11 pbr_denoise_temporal and pbr_temporal_reset).  A caller that loads the library at run time — or
+ * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 11
+#define PBR_ABI_VERSION 12
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -397,7 +397,8 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
  * A second pbr_denoise_temporal without a new successful pbr_render_adaptive in between is PBR_ESTATE: it would integrate the
  * same render twice.  PBR_EINVAL: null cam, temporal, filter or rgba; max_history outside 1 .. 1024; normal_cos outside
  * [-1, 1] or NaN; sigma_world negative or not finite; the filter's argument checks.  The history is dropped — the next call
- * starts at L = 1 everywhere — by pbr_temporal_reset, pbr_configure, pbr_upload_scene and pbr_update_vertices; NOT by renders,
+ * starts at L = 1 everywhere — by pbr_temporal_reset, pbr_configure, pbr_upload_scene and pbr_update_vertices (the last one unless
+ * pbr_temporal_track_motion is on, see MOVING GEOMETRY below); NOT by renders,
  * pbr_reset_accum, pbr_denoise or pbr_denoise_guided: a camera move with a fresh accumulation is the use case.  A refused call
  * changes nothing; a successful one does not modify the accumulation, the moments or the tile stats.
  * The history (two sets of four width x height float4 planes + lengths, swapped by pointer, and the filter's working planes)
@@ -412,6 +413,48 @@ int pbr_temporal_reset( pbr_ctx* ctx );
 int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam,
                           const pbr_temporal_params* temporal, const pbr_denoise_guided_params* filter,
                           float* rgba, float* variance_out, float* integrated, float* history );
+
+/* MOVING GEOMETRY: per-vertex motion for pbr_denoise_temporal.  pbr_temporal_track_motion( ctx, 1 ) makes the history survive
+ * pbr_update_vertices: the context then keeps H, the vertex positions the history was made under (those current at the last
+ * successful pbr_denoise_temporal), and a call that finds the geometry moved asks of every hit pixel "where was this point of
+ * the surface when the history was made?" before it looks the history up.  The flag is per context, 0 after pbr_create, needs
+ * no scene and survives pbr_configure and pbr_upload_scene (which still drop the history, as does pbr_temporal_reset).  With
+ * the flag off nothing changes: pbr_update_vertices drops the history.
+ * H: the first successful pbr_update_vertices after a successful pbr_denoise_temporal copies the vertices as they are on the
+ * device into a second buffer (device to device, allocated then: 16 bytes per vertex) before it overwrites them; later updates
+ * before the next temporal call leave that copy alone; a successful temporal call makes the current vertices H again (nothing
+ * is copied).  Turning the flag off frees the buffer, and drops the history if the geometry has moved since it was made.
+ * WHICH PATH.  pbr_denoise_temporal (signature unchanged) runs the definition above — the static path, bit for bit — if
+ * tracking is off, if there is no history, or if no pbr_update_vertices succeeded since the history was made.  Otherwise the
+ * MOTION PATH: step 0 in front, steps 1 and 2 changed as stated, steps 3 - 6 unchanged; `history` keeps its meaning.  All
+ * operations binary32, none fused; dot as above; cross( p, q ) = ( py*qz - pz*qy, pz*qx - px*qz, px*qy - py*qx ), each
+ * component two products and one subtraction; sqrtf and / correctly rounded.  V = the current vertices, H as above; f = the
+ * first-hit face of the pixel, an index into the uploaded facesV (which is in leaf order); a, b, c = the .xyz of
+ * V[facesV[f].x], V[facesV[f].y], V[facesV[f].z] and a', b', c' the same corners from H; P, N, A the current features.
+ *   0. motion, per hit pixel.  The face is UNMOVED if a == a', b == b', c == c' in all nine coordinates (compared as floats):
+ *      Pprev = P.xyz and nref = N.xyz bit for bit, len = 1, code 1.  Otherwise e1 = b - a, e2 = c - a, w = P.xyz - a;
+ *      d11 = dot( e1, e1 ), d12 = dot( e1, e2 ), d22 = dot( e2, e2 ); w1 = dot( w, e1 ), w2 = dot( w, e2 );
+ *      den = d11 * d22 - d12 * d12; u = ( d22 * w1 - d12 * w2 ) / den; v = ( d11 * w2 - d12 * w1 ) / den;
+ *      e1' = b' - a', e2' = c' - a'; Pprev = ( a' + e1' * u ) + e2' * v (a vector times a scalar: per component).
+ *      n = cross( e1, e2 ), n' = cross( e1', e2' ); if dot( N, n ) < 0 then n' = -n'; nref = n', NOT normalised;
+ *      len = sqrtf( dot( n', n' ) ).  code 2 if u, v and the three words of Pprev are finite, else 3.
+ *      A miss pixel has motion {0, 0, 0, 0} and face -1; a hit pixel motion {Pprev, (float) code} and face f.
+ *   1. candidate.  Hit pixel: d = Pprev - eye'; with code 3 there is no candidate.  Miss pixels: unchanged.
+ *   2. taps.  For a hit centre the normal test is dot( N', nref ) >= normal_cos * len and the distance test
+ *      squaredDistance3( P', Pprev ) <= r * r, with r unchanged: ( sigma_world * pxDim ) * P.w.  On an unmoved face these ARE the
+ *      static tests ( normal_cos * 1.0f, Pprev = P ).  The material test, the hit / miss test, the finite-history test, the
+ *      bilinear weights and the choice of Hl are unchanged.
+ * pbr_read_temporal_motion copies the planes of step 0 as the last successful pbr_denoise_temporal left them:
+ *   motion  optional (NULL): host, width x height x 4 floats {Pprev.x, Pprev.y, Pprev.z, code}
+ *   face    optional (NULL): host, width x height int32
+ * PBR_ESTATE before such a call, after pbr_configure, and if that call ran the static path.  Both calls return PBR_ESTATE on
+ * an unusable context and PBR_EINVAL for a null one.  The two float4 planes and the face plane (36 bytes per pixel) are
+ * allocated by the first call that takes the motion path and freed with the history; nothing is allocated per call.
+ * NOT COVERED: tile-sharded contexts (pbr_denoise_temporal refuses them), changes of topology (pbr_update_vertices takes
+ * positions only), Phong tessellation and ray-ordered traversals (pbr_update_vertices refuses both, unchanged), and lights:
+ * a light that moves or changes changes the shading, which no test of step 2 sees — call pbr_temporal_reset. */
+int pbr_temporal_track_motion( pbr_ctx* ctx, int on );
+int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face );
 
 /* Opt-in fast BVH build on the device: faces in Morton order, clustered bottom-up by
  * surface area, at most 2 faces per leaf, emitted in the reference's flat format — what BVH::getNodes + the packing

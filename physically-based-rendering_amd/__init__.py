@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 11
+ABI_VERSION = 12
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -195,6 +195,8 @@ for _name, _args in (
         ("pbr_temporal_reset", [_vp]),                                                                                   # ABI version 11
         ("pbr_denoise_temporal", [_vp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(TemporalParams), ctypes.POINTER(GuidedDenoiseParams),
                                   _fp, _fp, _fp, _fp]),
+        ("pbr_temporal_track_motion", [_vp, ctypes.c_int]),                                                              # ABI version 12
+        ("pbr_read_temporal_motion", [_vp, _fp, ctypes.POINTER(ctypes.c_int32)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp])):
     if hasattr(hip, _name):
@@ -588,6 +590,20 @@ class Device:
     def temporal_reset(self):
         """pbr_temporal_reset: drops denoise_temporal's history; the next call starts at L = 1 everywhere."""
         self._check(hip.pbr_temporal_reset(self._ctx))
+
+    def temporal_track_motion(self, on):
+        """pbr_temporal_track_motion: while on, update_vertices keeps denoise_temporal's history, and a call behind an update
+        follows every hit pixel's face back to where it was (per-vertex motion).  Off by default; survives configure and
+        upload_scene."""
+        self._check(hip.pbr_temporal_track_motion(self._ctx, 1 if on else 0))
+
+    def temporal_motion(self):
+        """pbr_read_temporal_motion: (motion (H, W, 4) float32 {Pprev, code}, face (H, W) int32, -1 = miss) of the last
+        denoise_temporal, if it took the motion path (PbrError otherwise)."""
+        motion = np.empty((self.height, self.width, 4), np.float32)
+        face = np.empty((self.height, self.width), np.int32)
+        self._check(hip.pbr_read_temporal_motion(self._ctx, motion.ctypes.data_as(_fp), face.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return motion, face
 
     def denoise_temporal(self, px_dim, cam, temporal=None, filter=None, variance=False, integrated=False, history=False):
         """pbr_denoise_temporal: `denoise_guided` with a per-pixel history that is re-projected through the previous call's

@@ -24,6 +24,7 @@
 #include "pt_denoise.hpp"
 #include "pt_denoise_guided.hpp"
 #include "pt_temporal.hpp"
+#include "pt_temporal_host.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 #include "pt_deal.hpp"
@@ -204,7 +205,17 @@ struct pbr_ctx {
 	float4* dTemporalInfo = nullptr;     // {fx, fy, L, valid} of a call that asks for it
 	float* dTemporalVariance = nullptr;
 	int temporalSet = 0;
-	bool temporalHistory = false;        // set temporalSet holds a history: cleared by pbr_temporal_reset, pbr_configure, pbr_upload_scene, pbr_update_vertices
+	// is set temporalSet a history, has the geometry moved since it was made, which path does a call take: pt_temporal_host.hpp.
+	// The history is dropped by pbr_temporal_reset, pbr_configure, pbr_upload_scene and — without motion tracking — pbr_update_vertices
+	TemporalPolicy temporal;
+	// pbr_temporal_track_motion: H, the vertex positions the history was made under — a copy of dVertices taken by the first
+	// pbr_update_vertices after a temporal call, allocated then, freed with the scene and when tracking is turned off (not part
+	// of refitBytes) — and the planes of the motion path: first-hit face, {Pprev, code}, {nref, len}; allocated by the first call
+	// that takes that path, freed with the history
+	float4* dHistVertices = nullptr;
+	int* dTemporalFace = nullptr;
+	float4* dTemporalMotion = nullptr;
+	float4* dTemporalReference = nullptr;
 	bool temporalFresh = false;          // a pbr_render_adaptive succeeded since the last successful temporal call
 	pbr_camera temporalCam = {};         // the history's camera and pixel size
 	float temporalPxDim = 0.0f;
@@ -270,8 +281,9 @@ void freeScene( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dRefitRecordOf );
 	(void) hipFree( ctx->dRefitTop );
 	(void) hipFree( ctx->dRefitLevelFirst );
+	(void) hipFree( ctx->dHistVertices );
 	ctx->dFacesV = nullptr;
-	ctx->dVertices = ctx->dRootBox = nullptr;
+	ctx->dVertices = ctx->dRootBox = ctx->dHistVertices = nullptr;
 	ctx->dRefitSlots = ctx->dRefitInfo = ctx->dRefitTop = ctx->dRefitLevelFirst = nullptr;
 	ctx->dRefitHeights = nullptr;
 	ctx->dRefitRecordOf = nullptr;
@@ -336,8 +348,13 @@ void freeImages( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dTemporalInfo );
 	(void) hipFree( ctx->dTemporalVariance );
 	ctx->dTemporalPing = ctx->dTemporalPong = ctx->dTemporalInfo = nullptr;
+	(void) hipFree( ctx->dTemporalFace );
+	(void) hipFree( ctx->dTemporalMotion );
+	(void) hipFree( ctx->dTemporalReference );
 	ctx->dTemporalVariance = nullptr;
-	ctx->temporalHistory = false;
+	ctx->dTemporalFace = nullptr;
+	ctx->dTemporalMotion = ctx->dTemporalReference = nullptr;
+	ctx->temporal.configure();
 	ctx->temporalFresh = false;
 	ctx->dTileCost = nullptr;
 	ctx->costLearnt = false;
@@ -1440,7 +1457,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeScene( ctx );
-	ctx->temporalHistory = false;   // pbr_denoise_temporal: the history's features are the old scene's
+	ctx->temporal.drop();   // pbr_denoise_temporal: the history's features are the old scene's
 
 	auto toDevice = [ctx]( float4** dst, const std::vector<Quad>& src ) {
 		HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( Quad ) * src.size() ) );
@@ -1486,7 +1503,7 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 		};
 		const Quad rootBox[2] = { { s->bvh[0].bbMin.x, s->bvh[0].bbMin.y, s->bvh[0].bbMin.z, -1.0f }, { s->bvh[0].bbMax.x, s->bvh[0].bbMax.y, s->bvh[0].bbMax.z, -1.0f } };
 		PBR_TRY( keep( (void**) &ctx->dFacesV, s->facesV, sizeof( pbr_uint4 ) * s->num_faces ) );
-		PBR_TRY( keep( (void**) &ctx->dVertices, nullptr, sizeof( pbr_float4 ) * s->num_vertices ) );
+		PBR_TRY( keep( (void**) &ctx->dVertices, s->vertices, sizeof( pbr_float4 ) * s->num_vertices ) );   // the positions a first update's motion starts from
 		PBR_TRY( keep( (void**) &ctx->dRootBox, rootBox, sizeof( rootBox ) ) );
 		PBR_TRY( keep( (void**) &ctx->dRefitSlots, refit.slots.data(), sizeof( uint32_t ) * refit.slots.size() ) );
 		PBR_TRY( keep( (void**) &ctx->dRefitInfo, refit.info.data(), sizeof( uint32_t ) * refit.info.size() ) );
@@ -1544,7 +1561,22 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	ctx->temporalHistory = false;   // pbr_denoise_temporal: static geometry only
+
+	// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
+	// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below does
+	// not: it waits for the copy
+	if( ctx->temporal.update() ) {
+		const size_t bytes = std::max<size_t>( sizeof( pbr_float4 ) * ctx->numVertices, 16 );
+		hipError_t kept = ( ctx->dHistVertices != nullptr ) ? hipSuccess : hipMalloc( (void**) &ctx->dHistVertices, bytes );
+		kept = ( kept != hipSuccess ) ? kept : hipMemcpyAsync( ctx->dHistVertices, ctx->dVertices, sizeof( pbr_float4 ) * ctx->numVertices, hipMemcpyDeviceToDevice, ctx->stream );
+		kept = ( kept != hipSuccess ) ? kept : hipStreamSynchronize( ctx->stream );
+
+		if( kept != hipSuccess ) {
+			ctx->temporal.drop();
+			return fail( ctx, PBR_EDEVICE, "pbr_update_vertices: keeping the history's vertex positions: %s", hipGetErrorString( kept ) );
+		}
+	}
+
 	const auto uploadStart = std::chrono::steady_clock::now();
 	HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
 	ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
@@ -2044,7 +2076,7 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ( sharded ? ctx->dFull : ctx->dImgOut ), (float4*) dPing.p,
 		w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
 	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
@@ -2181,7 +2213,7 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, (float4*) dOriginal.p, w, h, ctx->tilesX, 1, 0 );
 	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
 		ctx->varianceFirstCount, (const float4*) dOriginal.p, (float*) nullptr, (float4*) dPing.p, w, h, ctx->tilesX );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
 	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
@@ -2230,7 +2262,54 @@ int pbr_temporal_reset( pbr_ctx* ctx ) {
 		return PBR_EINVAL;
 	}
 
-	ctx->temporalHistory = false;
+	ctx->temporal.drop();
+	return PBR_OK;
+}
+
+// Per-vertex motion for pbr_denoise_temporal: while it is on, pbr_update_vertices keeps the history (and the vertex positions it
+// was made under) instead of dropping it.  A flag of the context: needs no scene, survives pbr_configure and pbr_upload_scene.
+int pbr_temporal_track_motion( pbr_ctx* ctx, int on ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	ctx->temporal.track( on != 0 );
+
+	if( on == 0 && ctx->dHistVertices != nullptr ) {
+		HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+		HIP_TRY( ctx, hipFree( ctx->dHistVertices ) );
+		ctx->dHistVertices = nullptr;
+	}
+
+	return PBR_OK;
+}
+
+// The planes of the last successful pbr_denoise_temporal's motion step: {Pprev, code} and the first-hit face per pixel.
+int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->temporal.lastMotion || ctx->dTemporalFace == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_read_temporal_motion: the last successful pbr_denoise_temporal did not take the motion path (it needs pbr_temporal_track_motion, a history and a pbr_update_vertices since that history)" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const size_t pixels = (size_t) ctx->cfg.width * (size_t) ctx->cfg.height;
+
+	if( motion != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( motion, ctx->dTemporalMotion, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+	if( face != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( face, ctx->dTemporalFace, sizeof( int32_t ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
 
@@ -2307,7 +2386,24 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 
 		PBR_TRY( status );
 		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTemporalVariance, sizeof( float ) * pixels ) );
-		ctx->temporalHistory = false;
+		ctx->temporal.drop();
+	}
+
+	// static geometry, or per-vertex motion in front of the integration (pt_temporal_host.hpp decides)
+	const TemporalPolicy::Path path = ctx->temporal.path();
+
+	if( path == TemporalPolicy::MOTION && ctx->dTemporalFace == nullptr ) {
+		// first use of the motion path since pbr_configure: all or nothing is kept, dTemporalFace last
+		for( float4** dst : { &ctx->dTemporalMotion, &ctx->dTemporalReference } ) {
+			if( *dst == nullptr ) {
+				HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( float4 ) * pixels ) );
+			}
+		}
+
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTemporalFace, sizeof( int ) * pixels ) );
+	}
+	if( path == TemporalPolicy::MOTION && ( ctx->dHistVertices == nullptr || ctx->dFacesV == nullptr ) ) {
+		return fail( ctx, PBR_ESTATE, "denoise_temporal: the history's vertex positions are missing" );   // cannot happen: `moved` implies the copy
 	}
 
 	const int prev = ctx->temporalSet, cur = 1 - prev;
@@ -2324,7 +2420,7 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	ptd::TemporalArgs T;
 	T.width = w;
 	T.height = h;
-	T.hasHistory = ctx->temporalHistory ? 1 : 0;
+	T.hasHistory = ctx->temporal.history ? 1 : 0;
 	T.maxHistory = temporal->max_history;
 	T.normalCos = temporal->normal_cos;
 	T.worldTerm = ( temporal->sigma_world != 0.0f ) ? 1 : 0;
@@ -2357,11 +2453,25 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
 	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
 		ctx->varianceFirstCount, (const float4*) dOriginal, (float*) nullptr, dI, w, h, ctx->tilesX );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo );
-	hipLaunchKernelGGL( ptd::temporalIntegrate, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
-		(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
-		(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur],
-		( history != nullptr ) ? ctx->dTemporalInfo : (float4*) nullptr );
+	float4* const dInfo = ( history != nullptr ) ? ctx->dTemporalInfo : (float4*) nullptr;
+
+	if( path == TemporalPolicy::MOTION ) {
+		hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo, ctx->dTemporalFace );
+		hipLaunchKernelGGL( ptd::temporalMotion, grid, block, 0, ctx->stream, w, h, (const int*) ctx->dTemporalFace, (const float4*) dPosition, (const float4*) dNormal,
+			(const uint4*) ctx->dFacesV, (const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, ctx->dTemporalMotion, ctx->dTemporalReference );
+		hipLaunchKernelGGL( ptd::temporalIntegrate<true>, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
+			(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
+			(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur], dInfo,
+			(const float4*) ctx->dTemporalMotion, (const float4*) ctx->dTemporalReference );
+	}
+	else {
+		hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo, (int*) nullptr );
+		hipLaunchKernelGGL( ptd::temporalIntegrate<false>, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
+			(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
+			(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur], dInfo,
+			(const float4*) nullptr, (const float4*) nullptr );
+	}
+
 	HIP_TRY( ctx, hipGetLastError() );
 
 	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
@@ -2405,7 +2515,7 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	ctx->lastKernelMs = (double) ms;
 	// the set just written becomes the history, by pointer
 	ctx->temporalSet = cur;
-	ctx->temporalHistory = true;
+	ctx->temporal.succeeded( path );   // ... made under the current vertices
 	ctx->temporalFresh = false;
 	ctx->temporalCam = *cam;
 	ctx->temporalPxDim = pxDim;

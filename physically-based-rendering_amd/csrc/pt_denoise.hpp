@@ -49,8 +49,9 @@ PT_DEV Ray centreRay( const DevParams& P, int px, int py ) {
 	return ray;
 }
 
-// position {x, y, z, t}, normal {x, y, z, hit ? 1 : 0} (turned towards the viewer: faces are two-sided), albedo {Kd, material}
-__global__ void firstHitFeatures( const DevParams P, float4* position, float4* normal, float4* albedo ) {
+// position {x, y, z, t}, normal {x, y, z, hit ? 1 : 0} (turned towards the viewer: faces are two-sided), albedo {Kd, material};
+// faceOut (may be null): the face that was hit — its index in `tris`, which is the scene's facesV order — or -1 for a miss
+__global__ void firstHitFeatures( const DevParams P, float4* position, float4* normal, float4* albedo, int* faceOut ) {
 	const int x = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
 	const int y = (int) ( blockIdx.y * blockDim.y + threadIdx.y );
 
@@ -70,6 +71,11 @@ __global__ void firstHitFeatures( const DevParams P, float4* position, float4* n
 		position[at] = make_float4( 0.0f, 0.0f, 0.0f, inff() );
 		normal[at] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
 		albedo[at] = make_float4( 0.0f, 0.0f, 0.0f, -1.0f );
+
+		if( faceOut != nullptr ) {
+			faceOut[at] = -1;
+		}
+
 		return;
 	}
 
@@ -85,6 +91,10 @@ __global__ void firstHitFeatures( const DevParams P, float4* position, float4* n
 	position[at] = make_float4( p.x, p.y, p.z, hit.t );
 	normal[at] = make_float4( n.x, n.y, n.z, 1.0f );
 	albedo[at] = make_float4( kd.x, kd.y, kd.z, (float) material );
+
+	if( faceOut != nullptr ) {
+		faceOut[at] = hit.face;
+	}
 }
 
 __device__ __forceinline__ float squaredDistance3( float4 a, float4 b ) {
