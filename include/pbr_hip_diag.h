@@ -3,12 +3,15 @@
  *
  * Not part of the drop-in boundary (the reference has nothing comparable): they expose single
  * stages of the device path — the math layer, closest-hit traversal, BRDF evaluation, new-ray
- * sampling, the cubic solver and the patch intersection of Phong tessellation — so the parity tests
+ * sampling, the cubic solver and the patch intersection of Phong tessellation, the camera ray, the
+ * intersection primitives of the walk (triangle, box, sphere) and the surface step of a bounce — so the parity tests
  * can compare each stage with the oracle's hook of the same shape (oracle/pt_oracle.h: orc_math,
- * orc_trace_rays, orc_brdf_eval, orc_new_ray, orc_solve_cubic, orc_phong_face) instead of only whole
+ * orc_trace_rays, orc_brdf_eval, orc_new_ray, orc_solve_cubic, orc_phong_face, orc_camera_ray, orc_intersect,
+ * orc_surface_step) instead of only whole
  * images, and with float64 references.  Host pointers in, host pointers out; synchronous.
  *
- * pbr_diag_math, pbr_diag_brdf, pbr_diag_new_ray, pbr_diag_solve_cubic and pbr_diag_phong_face compute in the arithmetic
+ * pbr_diag_math, pbr_diag_brdf, pbr_diag_new_ray, pbr_diag_solve_cubic, pbr_diag_phong_face, pbr_diag_camera_ray,
+ * pbr_diag_intersect and pbr_diag_surface_step compute in the arithmetic
  * of the context's last successful pbr_configure: the native one (v_sin / v_rcp / v_log / ... , csrc/pt_math.hpp) when it
  * set arith = PBR_ARITH_NATIVE, the exact one — the oracle's definitions, bit for bit — with no configuration or arith =
  * exact.  A library built without the native diagnostics answers PBR_ESTATE in the native case.  pbr_diag_trace is always
@@ -55,6 +58,32 @@ int pbr_diag_solve_cubic( pbr_ctx* ctx, const float* in, int n, float* out );
  * |tNear| <= t <= min( rayT, tFar ) (pt_phongtess.cl:202): for an origin INSIDE the box tNear is negative, and hits nearer
  * than |tNear| are dropped.  That is the reference's behaviour, kept as it is — which is why the interval is an input here. */
 int pbr_diag_phong_face( pbr_ctx* ctx, const float* in, int n, float* out );
+
+/* initRay with anti-aliasing and the depth-of-field lens (pathtracing.cl:25-48, pt_utils.cl:327-373) for n pixels of the
+ * camera `cam` at pixel dimension pxDim.  Width, height and anti-aliasing are the configuration's (PBR_ESTATE without one);
+ * the kernel is handed the camera exactly as a render call's kernels are.
+ * in: n x 8 {px, py, seed, tFocus, tObject, pad[3]} (px, py whole numbers; tFocus / tObject as getPreviousFocus gives them:
+ * -1 = depth of field off); out: n x 8 {origin[3], dir[3], seed after, 0} — the seed after tells the draws taken: 2, or 4
+ * with the lens (orc_camera_ray). */
+int pbr_diag_camera_ray( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const float* in, int n, float* out );
+
+/* The primitives of the walk alone, no scene needed.  in: n x 24, out: n x 4 (orc_intersect).
+ * op 0, flatTriAndRayIntersect (pt_intersect.cl:92-129) on the face record the upload forms (B - A, C - A in binary32):
+ *   in {A[3], B[3], C[3], origin[3], dir[3], rayT, tNear, pad[7]}; out {t (INFINITY: no hit), 0, 0, 0}
+ * op 1, intersectBox (pt_intersect.cl:11-25) with the inverse direction of the walk, and the hit conditions of the
+ *   closest-hit walk (pt_bvh.cl:107-110) and of the shadow walk (:151-154, no `rayT > tNear` cull):
+ *   in {min[3], max[3], origin[3], dir[3], rayT, pad[11]}; out {closest-hit verdict, any-hit verdict, tNear, tFar}
+ * op 2, intersectSphere (pt_intersect.cl:37-77; d2 is compared with r, not r * r, as the reference does):
+ *   in {pos[3], r, origin[3], dir[3], pad[14]}; out {hit, tNear (0 on a miss), 0, 0} */
+int pbr_diag_intersect( pbr_ctx* ctx, int op, const float* in, int n, float* out );
+
+/* The surface step of one bounce with material 0 and the scene's BRDF: getNewRay's direction from the unflipped normal, the
+ * normal flip (pathtracing.cl:298-300), then updateColor (pathtracing.cl:89-178) — the shadow-ray contribution when `lit`,
+ * and the throughput factor.
+ * in: n x 24 {origin[3], dir[3], normal[3] (unflipped), t, seed, color[3], lit (0 / 1), lightDir[3], lightRgb[3], pad[3]};
+ * out: n x 12 {newDir[3], seed after, addDepth, color after[3], finalColor after starting from 0 [3], secondaryPaths
+ * increment} (orc_surface_step). */
+int pbr_diag_surface_step( pbr_ctx* ctx, const float* in, int n, float* out );
 
 /* Traversal-only throughput probe: streams n rays {ox,oy,oz,-, dx,dy,dz,-} through a persistent
  * closest-hit kernel `repeats` times with `lds_slots` hot nodes staged in LDS; best kernel time in

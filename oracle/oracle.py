@@ -86,6 +86,12 @@ class OrcScene(ctypes.Structure):
     ]
 
 
+class OrcCamera(ctypes.Structure):
+    """orc_camera: camera_cl (PathTracer.h:25-32), 80 bytes — the layout of pbr_camera."""
+    _fields_ = [("eye", ctypes.c_float * 4), ("w", ctypes.c_float * 4), ("u", ctypes.c_float * 4), ("v", ctypes.c_float * 4),
+                ("focusPoint", ctypes.c_int32 * 2), ("lense", ctypes.c_float * 2)]
+
+
 class OrcCounters(ctypes.Structure):
     _fields_ = [("nodes", ctypes.c_uint64), ("tris", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("paths", ctypes.c_uint64)]
 
@@ -136,6 +142,12 @@ def lib():
         _lib.orc_solve_cubic.restype = None
         _lib.orc_phong_face.argtypes = [_fp, ctypes.c_int, _fp]
         _lib.orc_phong_face.restype = None
+        _lib.orc_camera_ray.argtypes = [ctypes.POINTER(OrcConfig), ctypes.c_void_p, ctypes.c_float, _fp, ctypes.c_int, _fp]
+        _lib.orc_camera_ray.restype = None
+        _lib.orc_intersect.argtypes = [ctypes.c_int, _fp, ctypes.c_int, _fp]
+        _lib.orc_intersect.restype = None
+        _lib.orc_surface_step.argtypes = [ctypes.c_int, ctypes.c_void_p, _fp, ctypes.c_int, _fp]
+        _lib.orc_surface_step.restype = None
         _lib.orc_walk_order_count.argtypes = [ctypes.c_int]
         _lib.orc_walk_order_count.restype = ctypes.c_int
         _lib.orc_build_walk_orders.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -173,6 +185,36 @@ def phong_face(items):
     items = np.ascontiguousarray(items, np.float32).reshape(-1, 32)
     out = np.empty((items.shape[0], 4), np.float32)
     lib().orc_phong_face(_ptr(items), items.shape[0], _ptr(out))
+    return out
+
+
+INTERSECT_OPS = {"triangle": 0, "box": 1, "sphere": 2}
+
+
+def camera_ray(width, height, anti_aliasing, cam, px_dim, items):
+    """orc_camera_ray: n x 8 {px, py, seed, tFocus, tObject, pad[3]} -> n x 8 {origin, dir, seed after, 0}; cam: a pbr_camera."""
+    items = np.ascontiguousarray(items, np.float32).reshape(-1, 8)
+    out = np.empty((items.shape[0], 8), np.float32)
+    c = OrcConfig()
+    c.width, c.height, c.anti_aliasing = int(width), int(height), float(anti_aliasing)
+    lib().orc_camera_ray(ctypes.byref(c), ctypes.addressof(cam), float(px_dim), _ptr(items), items.shape[0], _ptr(out))
+    return out
+
+
+def intersect(op, items):
+    """orc_intersect: n x 24 (layout by op, pt_oracle.h) -> n x 4."""
+    items = np.ascontiguousarray(items, np.float32).reshape(-1, 24)
+    out = np.empty((items.shape[0], 4), np.float32)
+    lib().orc_intersect(INTERSECT_OPS[op], _ptr(items), items.shape[0], _ptr(out))
+    return out
+
+
+def surface_step(brdf, mtl, items):
+    """orc_surface_step: n x 24 -> n x 12; mtl: the material's wire format as a float32 array."""
+    items = np.ascontiguousarray(items, np.float32).reshape(-1, 24)
+    mtl = np.ascontiguousarray(mtl, np.float32)
+    out = np.empty((items.shape[0], 12), np.float32)
+    lib().orc_surface_step(int(brdf), mtl.ctypes.data, _ptr(items), items.shape[0], _ptr(out))
     return out
 
 

@@ -2089,3 +2089,121 @@ void orc_phong_face( const float* in, int n, float* out ) {
 		o[0] = t; o[1] = normal.x; o[2] = normal.y; o[3] = normal.z;
 	}
 }
+
+/* initRay (pathtracing.cl:25-48) with antiAliasing and depthOfField (pt_utils.cl:327-373).
+ * in n x 8 {px, py, seed, tFocus, tObject, pad[3]}; out n x 8 {origin[3], dir[3], seed after, 0} */
+void orc_camera_ray( const orc_config* cfg, const orc_camera* cam, float pxDim, const float* in, int n, float* out ) {
+	ctx_t c;
+	memset( &c, 0, sizeof( c ) );
+	c.cfg = cfg;
+
+	for( int i = 0; i < n; i++ ) {
+		const float* p = in + (size_t) i * 8;
+		float seed = p[2];
+		const ray4 ray = initRay( &c, (int) p[0], (int) p[1], pxDim, cam, &seed, p[3], p[4] );
+		float* o = out + (size_t) i * 8;
+		o[0] = ray.origin.x; o[1] = ray.origin.y; o[2] = ray.origin.z;
+		o[3] = ray.dir.x; o[4] = ray.dir.y; o[5] = ray.dir.z;
+		o[6] = seed;
+		o[7] = 0.0f;
+	}
+}
+
+/* The primitives of the walk alone.  in n x 24, out n x 4.
+ * op 0 {A, B, C, origin, dir, rayT, tNear}: flatTriAndRayIntersect -> {t, 0, 0, 0}
+ * op 1 {min, max, origin, dir, rayT}: intersectBox with the inverse direction of traverse, and the hit conditions of
+ *      traverse (pt_bvh.cl:107-110) and traverseShadows (:151-154) -> {closest-hit verdict, any-hit verdict, tNear, tFar}
+ * op 2 {pos, r, origin, dir}: intersectSphere -> {hit, tNear (0 on a miss), 0, 0} */
+void orc_intersect( int op, const float* in, int n, float* out ) {
+	for( int i = 0; i < n; i++ ) {
+		const float* p = in + (size_t) i * 24;
+		float* o = out + (size_t) i * 4;
+		ray4 ray;
+		memset( &ray, 0, sizeof( ray ) );
+		o[0] = o[1] = o[2] = o[3] = 0.0f;
+
+		if( op == 0 ) {
+			ray.origin = V3( p[9], p[10], p[11] );
+			ray.dir = V3( p[12], p[13], p[14] );
+			ray.t = p[15];
+			float t = ORC_INF;
+			flatTriAndRayIntersect( V3( p[0], p[1], p[2] ), V3( p[3], p[4], p[5] ), V3( p[6], p[7], p[8] ), &ray, &t, p[16] );
+			o[0] = t;
+		}
+		else if( op == 1 ) {
+			orc_float4 bbMin = { p[0], p[1], p[2], 0.0f };
+			orc_float4 bbMax = { p[3], p[4], p[5], 0.0f };
+			ray.origin = V3( p[6], p[7], p[8] );
+			ray.dir = V3( p[9], p[10], p[11] );
+			ray.t = p[12];
+			const v3 invDir = V3( det_rcp( ray.dir.x ), det_rcp( ray.dir.y ), det_rcp( ray.dir.z ) );
+			float tNear = 0.0f;
+			float tFar = ORC_INF;
+			const int slab = intersectBox( &ray, &invDir, bbMin, bbMax, &tNear, &tFar );
+			o[0] = ( slab && tFar > EPSILON5 && ray.t > tNear ) ? 1.0f : 0.0f;
+			o[1] = ( slab && tFar > EPSILON5 ) ? 1.0f : 0.0f;
+			o[2] = tNear;
+			o[3] = tFar;
+		}
+		else if( op == 2 ) {
+			ray.origin = V3( p[4], p[5], p[6] );
+			ray.dir = V3( p[7], p[8], p[9] );
+			float tNear = 0.0f, tFar = ORC_INF;
+			const int hit = intersectSphere( &ray, V3( p[0], p[1], p[2] ), p[3], &tNear, &tFar );
+			o[0] = hit ? 1.0f : 0.0f;
+			o[1] = hit ? tNear : 0.0f;
+		}
+	}
+}
+
+/* The surface step of one bounce (pathtracing.cl:281-303): seed += t, getNewRay from the unflipped normal, the normal flip,
+ * updateColor.  in n x 24 {origin[3], dir[3], normal[3], t, seed, color[3], lit, lightDir[3], lightRgb[3], pad[3]};
+ * out n x 12 {newDir[3], seed after, addDepth, color after[3], finalColor after starting from 0 [3], secondaryPaths increment}.
+ * lit = 0: no light reached the point (lightRaySource stays (-1, -1, -1), pathtracing.cl:284). */
+void orc_surface_step( int brdf, const void* mtl, const float* in, int n, float* out ) {
+	const mtl_t m = mtl_from_wire( brdf, mtl );
+	orc_config cfg;
+	ctx_t c;
+	memset( &cfg, 0, sizeof( cfg ) );
+	memset( &c, 0, sizeof( c ) );
+	cfg.brdf = brdf;
+	cfg.shadow_rays = 1;
+	c.cfg = &cfg;
+
+	for( int i = 0; i < n; i++ ) {
+		const float* p = in + (size_t) i * 24;
+		ray4 ray, lightRay;
+		memset( &lightRay, 0, sizeof( lightRay ) );
+		ray.origin = V3( p[0], p[1], p[2] );
+		ray.dir = V3( p[3], p[4], p[5] );
+		ray.normal = V3( p[6], p[7], p[8] );
+		ray.t = p[9];
+		ray.hitFace = 0;
+		float seed = p[10];
+		v3 color = V3( p[11], p[12], p[13] );
+		v3 finalColor = V3( 0.0f, 0.0f, 0.0f );
+		uint32_t secondaryPaths = 0;
+		int addDepth = 0;
+		lightRay.t = ORC_INF;
+		lightRay.dir = V3( p[15], p[16], p[17] );
+		const v3 lightRaySource = ( p[14] != 0.0f ) ? V3( p[18], p[19], p[20] ) : V3( -1.0f, -1.0f, -1.0f );
+
+		seed += ray.t;
+
+		const ray4 newRay = getNewRay( &c, &ray, &m, &seed, &addDepth );
+
+		if( v3_dot( ray.normal, v3_neg( ray.dir ) ) <= 0.0f ) {
+			ray.normal = v3_neg( ray.normal );
+		}
+
+		updateColor( &c, &ray, &newRay, &m, &lightRay, lightRaySource, &secondaryPaths, &color, &finalColor );
+
+		float* o = out + (size_t) i * 12;
+		o[0] = newRay.dir.x; o[1] = newRay.dir.y; o[2] = newRay.dir.z;
+		o[3] = seed;
+		o[4] = (float) addDepth;
+		o[5] = color.x; o[6] = color.y; o[7] = color.z;
+		o[8] = finalColor.x; o[9] = finalColor.y; o[10] = finalColor.z;
+		o[11] = (float) secondaryPaths;
+	}
+}

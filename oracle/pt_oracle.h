@@ -154,6 +154,24 @@ void orc_solve_cubic( const float* in, int n, float* out );
  * tNear is negative and hits nearer than |tNear| are dropped.  That is the reference's behaviour, restated here. */
 void orc_phong_face( const float* in, int n, float* out );
 
+/* initRay (pathtracing.cl:25-48) with antiAliasing and depthOfField (pt_utils.cl:327-373); cfg gives width, height and
+ * anti_aliasing.  in: n x 8 {px, py, seed, tFocus, tObject, pad[3]}; out: n x 8 {origin[3], dir[3], seed after, 0}. */
+void orc_camera_ray( const orc_config* cfg, const orc_camera* cam, float pxDim, const float* in, int n, float* out );
+
+/* The primitives of the walk alone.  in: n x 24, out: n x 4.
+ * op 0, flatTriAndRayIntersect (pt_intersect.cl:92-129): in {A[3], B[3], C[3], origin[3], dir[3], rayT, tNear, pad[7]};
+ *   out {t (INFINITY: no hit), 0, 0, 0}
+ * op 1, intersectBox (pt_intersect.cl:11-25) and the hit conditions of traverse (pt_bvh.cl:107-110) / traverseShadows
+ *   (:151-154): in {min[3], max[3], origin[3], dir[3], rayT, pad[11]}; out {closest-hit verdict, any-hit verdict, tNear, tFar}
+ * op 2, intersectSphere (pt_intersect.cl:37-77): in {pos[3], r, origin[3], dir[3], pad[14]}; out {hit, tNear, 0, 0} */
+void orc_intersect( int op, const float* in, int n, float* out );
+
+/* The surface step of one bounce (pathtracing.cl:281-303): seed += t, getNewRay (unflipped normal), the flip, updateColor.
+ * in: n x 24 {origin[3], dir[3], normal[3], t, seed, color[3], lit (0 / 1), lightDir[3], lightRgb[3], pad[3]};
+ * out: n x 12 {newDir[3], seed after, addDepth, color after[3], finalColor after starting from 0 [3], secondaryPaths
+ * increment}. */
+void orc_surface_step( int brdf, const void* mtl, const float* in, int n, float* out );
+
 #ifdef __cplusplus
 }
 #endif

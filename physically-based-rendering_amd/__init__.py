@@ -198,7 +198,10 @@ for _name, _args in (
         ("pbr_temporal_track_motion", [_vp, ctypes.c_int]),                                                              # ABI version 12
         ("pbr_read_temporal_motion", [_vp, _fp, ctypes.POINTER(ctypes.c_int32)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
-        ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp])):
+        ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_intersect", [_vp, ctypes.c_int, _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_surface_step", [_vp, _fp, ctypes.c_int, _fp])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -679,6 +682,30 @@ class Device:
         items = np.ascontiguousarray(items, np.float32).reshape(-1, 32)
         out = np.empty((items.shape[0], 4), np.float32)
         self._check(hip.pbr_diag_phong_face(self._ctx, _as_fp(items), items.shape[0], _as_fp(out)))
+        return out
+
+    def diag_camera_ray(self, px_dim, cam, items):
+        """pbr_diag_camera_ray: n x 8 {px, py, seed, tFocus, tObject, pad[3]} -> n x 8 {origin, dir, seed after, 0}."""
+        items = np.ascontiguousarray(items, np.float32).reshape(-1, 8)
+        out = np.empty((items.shape[0], 8), np.float32)
+        self._check(hip.pbr_diag_camera_ray(self._ctx, px_dim, ctypes.byref(cam), _as_fp(items), items.shape[0], _as_fp(out)))
+        return out
+
+    INTERSECT_OPS = {"triangle": 0, "box": 1, "sphere": 2}
+
+    def diag_intersect(self, op, items):
+        """pbr_diag_intersect: n x 24 (layout by op, include/pbr_hip_diag.h) -> n x 4."""
+        items = np.ascontiguousarray(items, np.float32).reshape(-1, 24)
+        out = np.empty((items.shape[0], 4), np.float32)
+        self._check(hip.pbr_diag_intersect(self._ctx, self.INTERSECT_OPS[op], _as_fp(items), items.shape[0], _as_fp(out)))
+        return out
+
+    def diag_surface_step(self, items):
+        """pbr_diag_surface_step: n x 24 {origin, dir, normal, t, seed, color, lit, lightDir, lightRgb, pad[3]} -> n x 12
+        {newDir, seed after, addDepth, color, finalColor, secondaryPaths increment}."""
+        items = np.ascontiguousarray(items, np.float32).reshape(-1, 24)
+        out = np.empty((items.shape[0], 12), np.float32)
+        self._check(hip.pbr_diag_surface_step(self._ctx, _as_fp(items), items.shape[0], _as_fp(out)))
         return out
 
     def guard_trips(self):

@@ -2778,7 +2778,8 @@ typedef void ( *DiagMathFn )( int, const float*, const float*, int, float* );
 typedef void ( *DiagItemFn )( const ptk::DevParams, const float*, int, float* );
 typedef void ( *DiagPlainFn )( const float*, int, float* );
 
-// The kernel of a diagnostic stage (0 math, 1 BRDF, 2 new ray, 3 solveCubic, 4 Phong-tessellated face) in the arithmetic of
+// The kernel of a diagnostic stage (0 math, 1 BRDF, 2 new ray, 3 solveCubic, 4 Phong-tessellated face, 5 camera ray, 6 the
+// intersection primitives, 7 the surface step) in the arithmetic of
 // the configuration in force: the native flavour's after a successful pbr_configure with arith = PBR_ARITH_NATIVE, else (no configuration, or arith = exact) the
 // exact one of this translation unit.  Null: the native unit is not linked in.
 const void* diagKernel( const pbr_ctx* ctx, int stage, uint32_t brdf ) {
@@ -2790,6 +2791,9 @@ const void* diagKernel( const pbr_ctx* ctx, int stage, uint32_t brdf ) {
 		case 1: return ( brdf == 0 ) ? (const void*) ptk::diagBrdf<0> : (const void*) ptk::diagBrdf<1>;
 		case 2: return ( brdf == 0 ) ? (const void*) ptk::diagNewRay<0> : (const void*) ptk::diagNewRay<1>;
 		case 3: return (const void*) ptk::diagSolveCubic;
+		case 5: return (const void*) ptk::diagCameraRay;
+		case 6: return (const void*) ptk::diagIntersect;
+		case 7: return ( brdf == 0 ) ? (const void*) ptk::diagSurfaceStep<0> : (const void*) ptk::diagSurfaceStep<1>;
 		default: return (const void*) ptk::diagPhongFace;
 	}
 }
@@ -2865,14 +2869,14 @@ int pbr_diag_trace( pbr_ctx* ctx, const float* rays, int n, float* out_t, int32_
 
 namespace {
 
-int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, int outWidth, bool newRay ) {
+int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, int outWidth, int stage ) {
 	if( ctx == nullptr || !ctx->hasScene ) {
 		return fail( ctx, PBR_ESTATE, "diag before pbr_upload_scene" );
 	}
 	if( in == nullptr || out == nullptr || n <= 0 ) {
 		return fail( ctx, PBR_EINVAL, "diag: bad argument" );
 	}
-	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, newRay ? 2 : 1, ctx->sceneBrdf );
+	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, stage, ctx->sceneBrdf );
 	if( kernel == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "diag: this library was built without the native-arithmetic diagnostics" );
 	}
@@ -2920,7 +2924,7 @@ int diagPlain( pbr_ctx* ctx, const char* what, int stage, const float* in, int n
 }  // namespace
 
 int pbr_diag_brdf( pbr_ctx* ctx, const float* in, int n, float* out ) {
-	return diagPerItem( ctx, in, n, out, 16, 4, false );
+	return diagPerItem( ctx, in, n, out, 16, 4, 1 );
 }
 
 int pbr_diag_solve_cubic( pbr_ctx* ctx, const float* in, int n, float* out ) {
@@ -2932,7 +2936,65 @@ int pbr_diag_phong_face( pbr_ctx* ctx, const float* in, int n, float* out ) {
 }
 
 int pbr_diag_new_ray( pbr_ctx* ctx, const float* in, int n, float* out ) {
-	return diagPerItem( ctx, in, n, out, 12, 8, true );
+	return diagPerItem( ctx, in, n, out, 12, 8, 2 );
+}
+
+int pbr_diag_surface_step( pbr_ctx* ctx, const float* in, int n, float* out ) {
+	return diagPerItem( ctx, in, n, out, 24, 12, 7 );
+}
+
+int pbr_diag_camera_ray( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const float* in, int n, float* out ) {
+	if( ctx == nullptr || ctx->stream == nullptr || cam == nullptr || in == nullptr || out == nullptr || n <= 0 ) {
+		return fail( ctx, PBR_EINVAL, "diag_camera_ray: bad argument" );
+	}
+	if( !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "diag_camera_ray before pbr_configure" );
+	}
+	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, 5, 0u );
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag_camera_ray: this library was built without the native-arithmetic diagnostics" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	DevBuf dIn, dOut;
+	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * 8 * (size_t) n ) );
+	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * 8 * (size_t) n ) );
+	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
+
+	// the camera as beginRender hands it to a render's kernels; initRay reads nothing else of P
+	DevParams P;
+	std::memset( &P, 0, sizeof( P ) );
+	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
+	P.aperture = cam->lense[0] / cam->lense[1];
+	P.antiAliasing = ctx->cfg.anti_aliasing;
+
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * 8 * (size_t) n, hipMemcpyDeviceToHost ) );
+	return PBR_OK;
+}
+
+int pbr_diag_intersect( pbr_ctx* ctx, int op, const float* in, int n, float* out ) {
+	if( ctx == nullptr || ctx->stream == nullptr || in == nullptr || out == nullptr || n <= 0 || op < 0 || op > 2 ) {
+		return fail( ctx, PBR_EINVAL, "diag_intersect: bad argument" );
+	}
+	typedef void ( *DiagOpFn )( int, const float*, int, float* );
+	const DiagOpFn kernel = (DiagOpFn) diagKernel( ctx, 6, 0u );
+	if( kernel == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag_intersect: this library was built without the native-arithmetic diagnostics" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	DevBuf dIn, dOut;
+	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * 24 * (size_t) n ) );
+	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * 4 * (size_t) n ) );
+	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * 24 * (size_t) n, hipMemcpyHostToDevice ) );
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, op, (const float*) dIn.p, n, (float*) dOut.p );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * 4 * (size_t) n, hipMemcpyDeviceToHost ) );
+	return PBR_OK;
 }
 
 // Experimental: stream n rays {ox,oy,oz,_, dx,dy,dz,_} through the traversal-only probe `repeats`

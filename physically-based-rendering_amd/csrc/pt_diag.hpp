@@ -1,5 +1,5 @@
 // The stage diagnostics behind pbr_diag_math / pbr_diag_brdf / pbr_diag_new_ray / pbr_diag_solve_cubic /
-// pbr_diag_phong_face (include/pbr_hip_diag.h): one thread per item.  Included by pt_aux.hpp (pbr_hip.hip: no flavour, the exact arithmetic) and by pt_diag_native.hip, which
+// pbr_diag_phong_face / pbr_diag_camera_ray / pbr_diag_intersect / pbr_diag_surface_step (include/pbr_hip_diag.h): one thread per item.  Included by pt_aux.hpp (pbr_hip.hip: no flavour, the exact arithmetic) and by pt_diag_native.hip, which
 // compiles them once more in the native-arithmetic flavour (PT_FLAVOUR=2, pt_flavour.hpp) for a context configured
 // with pbr_config.arith = PBR_ARITH_NATIVE.
 #pragma once
@@ -121,6 +121,140 @@ __global__ void diagPhongFace( const float* in, int n, float* out ) {
 		ray, p[24], p[25], p[26], p[27], &normal );
 	float* o = out + (size_t) i * 4;
 	o[0] = t; o[1] = normal.x; o[2] = normal.y; o[3] = normal.z;
+}
+
+// in: n x 8 {px, py, seed, tFocus, tObject, pad[3]}; out: n x 8 {origin, dir, seed after, 0} (as orc_camera_ray).  P carries
+// the camera as a render call sets it (setCamera, pbr_hip.hip), the aperture and the configuration's anti-aliasing.
+__global__ void diagCameraRay( const DevParams P, const float* in, int n, float* out ) {
+	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
+
+	if( i >= n ) {
+		return;
+	}
+
+	const float* p = in + (size_t) i * 8;
+	float seed = p[2];
+	const Ray ray = initRay( P, (int) p[0], (int) p[1], seed, p[3], p[4] );
+	float* o = out + (size_t) i * 8;
+	o[0] = ray.origin.x; o[1] = ray.origin.y; o[2] = ray.origin.z;
+	o[3] = ray.dir.x; o[4] = ray.dir.y; o[5] = ray.dir.z;
+	o[6] = seed;
+	o[7] = 0.0f;
+}
+
+// in: n x 24, out: n x 4 (as orc_intersect).
+// op 0 {A, B, C, origin, dir, rayT, tNear}: the face record as the upload and refitFaces form it, then triangleT -> {t, 0, 0, 0}
+// op 1 {min, max, origin, dir, rayT}: the node record in boxHit's layout, the inverse direction as traverse forms it, then
+//      boxHit<false> and boxHit<true> -> {closest-hit verdict, any-hit verdict, tNear, tFar}
+// op 2 {pos, r, origin, dir}: intersectSphere -> {hit, tNear, 0, 0}
+__global__ void diagIntersect( int op, const float* in, int n, float* out ) {
+	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
+
+	if( i >= n ) {
+		return;
+	}
+
+	const float* p = in + (size_t) i * 24;
+	float* o = out + (size_t) i * 4;
+	Ray ray;
+	o[0] = o[1] = o[2] = o[3] = 0.0f;
+
+	if( op == 0 ) {
+		const f3 a = mk3( p[0], p[1], p[2] );
+		const f3 b = mk3( p[3], p[4], p[5] );
+		const f3 c = mk3( p[6], p[7], p[8] );
+		const float e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z;
+		const float e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;
+		TriRecord rec;
+		rec.r0 = make_float4( a.x, a.y, a.z, e1x );
+		rec.r1 = make_float4( e1y, e1z, e2x, e2y );
+		rec.r2 = make_float4( e2z, 0.0f, 0.0f, 0.0f );
+		ray.origin = mk3( p[9], p[10], p[11] );
+		ray.dir = mk3( p[12], p[13], p[14] );
+		o[0] = triangleT( rec, ray, p[15], p[16] );
+	}
+	else if( op == 1 ) {
+		const float4 n0 = make_float4( p[0], p[1], p[3], p[4] );
+		const float4 n1 = make_float4( p[2], p[5], 0.0f, 0.0f );
+		ray.origin = mk3( p[6], p[7], p[8] );
+		ray.dir = mk3( p[9], p[10], p[11] );
+		const f3 invDir = mk3( div1( 1.0f, ray.dir.x ), div1( 1.0f, ray.dir.y ), div1( 1.0f, ray.dir.z ) );
+		float tNear, tFar, tNearAny;
+		const bool closest = boxHit<false>( n0, n1, ray, invDir, p[12], &tNear, &tFar );
+		const bool any = boxHit<true>( n0, n1, ray, invDir, p[12], &tNearAny );
+		o[0] = closest ? 1.0f : 0.0f;
+		o[1] = any ? 1.0f : 0.0f;
+		o[2] = tNear;
+		o[3] = tFar;
+	}
+	else if( op == 2 ) {
+		ray.origin = mk3( p[4], p[5], p[6] );
+		ray.dir = mk3( p[7], p[8], p[9] );
+		float tNear = 0.0f;
+		const bool hit = intersectSphere( ray, mk3( p[0], p[1], p[2] ), p[3], &tNear );
+		o[0] = hit ? 1.0f : 0.0f;
+		o[1] = hit ? tNear : 0.0f;
+	}
+}
+
+// The surface step of shadeStep (pt_kernel.hpp) from `seed += hit.t` to `color = color * throughput( ... )`, restated here
+// statement by statement around the same device functions, with the template arguments of the lean lock-step kernel
+// (pathTracing<.., 4>: CALLS = false, LATE = false): the new ray from the UNflipped normal, the flip, then the two
+// evaluations with the tangent frame the new-ray stage left behind.  Material 0.
+// in: n x 24 {origin, dir, normal, t, seed, color, lit, lightDir, lightRgb, pad[3]}; out: n x 12 {newDir, seed after, addDepth,
+// color after, finalColor after (from 0), secondaryPaths increment} (as orc_surface_step)
+template<int BRDF>
+__global__ void diagSurfaceStep( const DevParams P, const float* in, int n, float* out ) {
+	const int i = (int) ( blockIdx.x * blockDim.x + threadIdx.x );
+
+	if( i >= n ) {
+		return;
+	}
+
+	const float* p = in + (size_t) i * 24;
+	const Material mtl = loadMaterial<false>( P, 0 );
+	Ray ray;
+	ray.origin = mk3( p[0], p[1], p[2] );
+	ray.dir = mk3( p[3], p[4], p[5] );
+	f3 normal = mk3( p[6], p[7], p[8] );
+	const float t = p[9];
+	float seed = p[10];
+	f3 color = mk3( p[11], p[12], p[13] );
+	const f3 lightDir = mk3( p[15], p[16], p[17] );
+	const f3 lightRgb = mk3( p[18], p[19], p[20] );
+	const bool lit = ( p[14] != 0.0f ) && ( lightRgb.x >= 0.0f );
+	f3 finalColor = mk3( 0.0f, 0.0f, 0.0f );
+	unsigned secondaryPaths = 0;
+	bool addDepth = false;
+
+	seed += t;
+
+	TangentFrame frame;
+	frame.valid = false;
+	const f3 newDir = newRayDir<BRDF, false>( ray.dir, normal, mtl, seed, addDepth, &frame );
+
+	if( dot( normal, -ray.dir ) <= 0.0f ) {
+		normal = -normal;
+	}
+
+	if( lit ) {
+		f3 add;
+
+		if( shadowContribution<BRDF, false, false>( mtl, ray.dir, lightDir, normal, color, lightRgb, &add, &frame ) ) {
+			finalColor = finalColor + add;
+			secondaryPaths += 1;
+		}
+	}
+
+	color = color * throughput<BRDF, false, false>( mtl, ray.dir, newDir, normal, &frame );
+
+	float* o = out + (size_t) i * 12;
+	o[0] = newDir.x; o[1] = newDir.y; o[2] = newDir.z;
+	o[3] = seed;
+	o[4] = addDepth ? 1.0f : 0.0f;
+	o[5] = color.x; o[6] = color.y; o[7] = color.z;
+	o[8] = finalColor.x; o[9] = finalColor.y; o[10] = finalColor.z;
+	o[11] = (float) secondaryPaths;
 }
 
 }  // namespace ptk

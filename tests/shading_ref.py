@@ -1,4 +1,5 @@
-"""A float64 restatement of the shading stages: BRDF evaluation and new-ray sampling.
+"""A float64 restatement of the shading stages: BRDF evaluation, new-ray sampling, and what a bounce does with them
+(updateColor and the composed surface step).
 
 The oracle (oracle/pt_oracle.c) and the HIP kernels are checked against each other bit for bit; this module is the
 independent check of both.  It is derived from the reference's OpenCL sources, not from either implementation:
@@ -8,6 +9,8 @@ independent check of both.  It is derived from the reference's OpenCL sources, n
   source/opencl/pt_utils.cl  bisect (7), rand (39-44), fresnel (53-56), jitter (306-318), reflect (426),
                              refract (436-465)
   source/opencl/pt_header.cl NI_AIR (13), PI_X2 (17)
+  source/opencl/pathtracing.cl updateColor (89-178), and the lines of the kernel around it (281-303): getNewRay from the
+                             unflipped normal, the normal flip, updateColor
 
 Everything is numpy float64, vectorised over samples.  The reference's quirks are kept: the Schlick pdf is
 t / ( 4 pi dot( V_OUT, h ) ) as written, the tangent frame is cross( n.yzx, n ) (undefined for a normal along
@@ -66,6 +69,12 @@ class _Ev:
         self.dec, self.q = {}, {}
 
     def r(self, x):
+        # a rounding point is a binary32 value: below half the smallest subnormal it IS zero and past the largest finite
+        # value it IS infinite, with whatever follows from that (the quotient of two such values is 0 / 0 or inf / inf, not
+        # their ratio)
+        with np.errstate(invalid="ignore"):
+            x = np.where(np.abs(x) < 2.0 ** -150, np.copysign(0.0, x), x)
+            x = np.where(np.abs(x) >= 2.0 ** 128 * (1.0 - 2.0 ** -25), np.copysign(np.inf, x), x)
         if self.rng is None:
             return x
         sign = self.rng.choice((-1.0, 1.0), size=np.shape(x))
@@ -212,12 +221,26 @@ def _D(ev, t, vOut, vIn, w, r, p):
     return ev.r(ev.r(lam + ani) + fres)
 
 
+def _half_vector(ev, v_out, v_in):
+    """h = fast_normalize( V_OUT + V_IN ).  In the surface step's evaluation at the SAMPLED direction (an evaluation that
+    says so: `opposite_undefined`, set by surface_step alone) the two directions can be opposite — a ray transmitted
+    straight through, a mirror hit at exactly grazing incidence —, the sum is zero or its own rounding noise in binary32
+    and h is 0 / 0 or noise: undefined in the reference itself.  Such a sample is NaN there and finite noise under the
+    rounding trials, so that its measured sensitivity is infinite and `judge` accepts whatever the arithmetic under test
+    makes of it.  Everywhere else this is the plain normalisation."""
+    s = ev.r(v_out + v_in)
+    if getattr(ev, "opposite_undefined", False) and ev.rng is None:
+        gone = (s * s).sum(axis=1) <= (16.0 * U) ** 2
+        s = np.where(gone[:, None], np.nan, s)
+    return _normalize(ev, s)
+
+
 def brdf_schlick(ev, mtl, x):
     """pt_brdf.cl:125-149 -> (n, 3) {brdf, u, pdf}."""
     p, r = mtl[2], mtl[3]
     normal, v_in, v_out = x["normal"], x["in"], -x["out"]
     un = _normalize(ev, _cross(ev, _yzx(normal), normal))
-    h = _normalize(ev, ev.r(v_out + v_in))
+    h = _half_vector(ev, v_out, v_in)
     t = _dot(ev, h, normal)
     vIn = _dot(ev, v_in, normal)
     vOut = _dot(ev, v_out, normal)
@@ -268,7 +291,7 @@ def brdf_shirley_ashikhmin(ev, mtl, x):
     un = _normalize(ev, _cross(ev, _yzx(normal), normal))
     vn = _normalize(ev, _cross(ev, normal, un))
     k1, k2 = x["in"], -x["out"]
-    h = _normalize(ev, ev.r(k1 + k2))
+    h = _half_vector(ev, k2, k1)
     dotHU, dotHV, dotHN = _dot(ev, h, un), _dot(ev, h, vn), _dot(ev, h, normal)
     dotNK1, dotNK2 = _dot(ev, normal, k1), _dot(ev, normal, k2)
     dotHK1 = _dot(ev, h, k1)
@@ -370,6 +393,107 @@ def new_ray(brdf):
     return fn
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# updateColor and the surface step
+# ---------------------------------------------------------------------------------------------------------------------
+
+PDF_CUT = float(np.float32(0.00001))          # pathtracing.cl:107 / :141, a float literal
+
+
+class _Sub:
+    """One evaluation seen by a sub-stage that runs more than once in it: the decisions carry a prefix."""
+
+    def __init__(self, ev, prefix, opposite_undefined=False):
+        self.ev, self.prefix, self.n, self.rng = ev, prefix, ev.n, ev.rng
+        self.opposite_undefined = opposite_undefined
+
+    def r(self, x):
+        return self.ev.r(x)
+
+    def decide(self, key, *args, **kwargs):
+        return self.ev.decide(self.prefix + key, *args, **kwargs)
+
+
+def _colours(brdf, mtl):
+    """(rgbDiff, rgbSpec) of the material's wire format."""
+    at = 4 if brdf == 0 else 8
+    return np.asarray(mtl[at:at + 3], np.float64)[None, :], np.asarray(mtl[at + 4:at + 7], np.float64)[None, :]
+
+
+def _clamp01(x):
+    """clamp( x, 0, 1 ) = fmin( fmax( x, 0 ), 1 )."""
+    return np.fmin(np.fmax(x, 0.0), 1.0)
+
+
+def _brdf_colour(ev, brdf, mtl, prefix, out_dir, in_dir, normal, active, cut):
+    """What updateColor makes of one BRDF evaluation (pathtracing.cl:105-112 / :120-124 Schlick, :136-150 / :160-173
+    Shirley-Ashikhmin): (the colour factor (n, 3), passes — |pdf| > 1e-5, decided only when `cut`).  Schlick: the factor
+    fresnel4( u, rgbSpec ) * brdf * d + ( 1 - d ) with brdf = brdf * lambert / pdf; S-A: clamp( brdfColor / maxRGB )."""
+    d = mtl[0]
+    kd, ks = _colours(brdf, mtl)
+    # (a Shirley-Ashikhmin lobe of a large exponent underflows off its peak: spec and pdf are both 0 in binary32 then, and
+    # their quotient NaN — _Ev.r models that range)
+    res = brdf_eval(brdf)(_Sub(ev, prefix, opposite_undefined=not cut), mtl, {"out": out_dir, "in": in_dir, "normal": normal})["val"]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        pdf = res[:, 2] if brdf == 0 else res[:, 3]
+        passes = np.ones(ev.n, bool)
+        if cut:
+            passes = ev.decide(prefix + "pdfcut", np.abs(pdf) > PDF_CUT, q=np.abs(pdf) - PDF_CUT, scale=np.abs(pdf) + PDF_CUT, active=active)
+        one_d = ev.r(1.0 - d)
+        if brdf == 0:
+            lam = np.maximum(_dot(ev, normal, in_dir), 0.0)                 # lambert: max( dot( n, l ), 0 )
+            b = ev.r(ev.r(res[:, 0] * lam) / pdf)                           # native_divide
+            f4 = _fresnel(ev, res[:, 1][:, None], ks)
+            return ev.r(ev.r(ev.r(f4 * b[:, None]) * d) + one_d), passes
+        rs = mtl[4]
+        spec, diff = ev.r(res[:, 0] / pdf), ev.r(res[:, 1] / pdf)
+        fr = _fresnel(ev, res[:, 2], rs)
+        brdf_s = ev.r(ev.r(spec[:, None] * ks) * fr[:, None])
+        brdf_d = ev.r(ev.r(diff[:, None] * kd) * ev.r(1.0 - rs))
+        bc = ev.r(ev.r(ev.r(brdf_s + brdf_d) * d) + one_d)
+        max_rgb = np.maximum(1.0, bc.max(axis=1))
+        return _clamp01(ev.r(bc / max_rgb[:, None])), passes
+
+
+def surface_step(brdf):
+    """One bounce between the hit and the next ray, pathtracing.cl:281-303: getNewRay with the UNflipped normal, the flip
+    of the normal towards the arriving ray (:298-300), updateColor (:89-178) with the flipped one.
+    fn( ev, mtl, x ) with x = {dir, normal, color, lightDir, lightRgb (n, 3), lit (n,), draws (n, DRAWS)} ->
+    {val: (n, 10) {newDir[3], color after[3], finalColor after starting from 0 [3], secondaryPaths increment},
+     used, add}.  The draws start behind `seed += t` (:281), which the caller forms in binary32."""
+    sample = new_ray(brdf)
+
+    def fn(ev, mtl, x):
+        d, n, color, light_dir, light_rgb = x["dir"], x["normal"], x["color"], x["lightDir"], x["lightRgb"]
+        kd, _ = _colours(brdf, mtl)
+        zero = np.zeros((ev.n, 3))
+        nr = sample(ev, mtl, {"origin": zero, "dir": d, "normal": n, "t": np.zeros(ev.n), "draws": x["draws"]})
+        new_dir = nr["val"][:, 3:6]
+        front = _dot(ev, n, -d)
+        flip = ev.decide("U.flip", front <= 0.0, q=front, active=np.ones(ev.n, bool))
+        nf = _sel(flip, -n, n)
+        # `if( lightRaySource.x >= 0 )`: on inputs
+        lit = ev.decide("U.lit", (x["lit"] != 0.0) & (light_rgb[:, 0] >= 0.0))
+        with np.errstate(invalid="ignore", over="ignore"):
+            k, passes = _brdf_colour(ev, brdf, mtl, "L.", d, light_dir, nf, lit, True)
+            got_light = lit & passes
+            if brdf == 0:
+                add = ev.r(ev.r(ev.r(color * light_rgb) * kd) * k)          # color * lightRaySource * rgbDiff * ( ... )
+            else:
+                add = ev.r(ev.r(ev.r(k * light_rgb) * mtl[0]) + ev.r(1.0 - mtl[0]))
+            final = _sel(got_light, add, zero)
+            k, _ = _brdf_colour(ev, brdf, mtl, "N.", d, new_dir, nf, np.ones(ev.n, bool), False)
+            after = ev.r(color * (ev.r(kd * k) if brdf == 0 else k))
+        val = np.concatenate([new_dir, after, final, got_light.astype(np.float64)[:, None]], axis=1)
+        return {"val": val, "used": nr["used"], "add": nr["add"]}
+
+    fn.dir_cols = (0, 1, 2)
+    fn.seed_col, fn.add_col = 10, 11
+    # dot( normal, -dir ) is formed by the sampler and again by the flip, from the same operands in the same order
+    fn.linked = (("U.flip", "SA.front"), ("U.flip", "R.into"))
+    return fn
+
+
 def brdf_eval(brdf):
     """The BRDF evaluation of one model: fn( ev, mtl, x ) with x = {out, in, normal}; no direction outputs."""
     return brdf_schlick if brdf == 0 else brdf_shirley_ashikhmin
@@ -445,8 +569,10 @@ class Analysis:
         return out
 
     def subset(self, idx, flip):
-        """The analysis of samples idx with decision `flip` taken the other way (the decisions after it recomputed)."""
-        force = {flip: (~self.dec[flip][0][idx], np.zeros(idx.size, bool))}
+        """The analysis of samples idx with decision `flip` (or each of a tuple of decisions: branches on one and the same
+        computed quantity) taken the other way (the decisions after it recomputed)."""
+        keys = (flip,) if isinstance(flip, str) else flip
+        force = {k: (~self.dec[k][0][idx], np.zeros(idx.size, bool)) for k in keys}
         return Analysis(self.fn, self.mtl, {k: v[idx] for k, v in self.x.items()}, self.mtl_keys, force, flush=self.flush)
 
     def scale(self):
@@ -464,8 +590,8 @@ class Analysis:
             ok = np.where(np.isfinite(ref), np.abs(val - ref) <= tol, ~np.isfinite(val))
         ok = (ok | np.isinf(self.delta)).all(axis=1)
         if "used" in self.res:
-            ok &= got[:, 6] == seeds[np.arange(self.n), self.res["used"]]
-            ok &= got[:, 7] == self.res["add"].astype(np.float32)
+            ok &= got[:, getattr(self.fn, "seed_col", 6)] == seeds[np.arange(self.n), self.res["used"]]
+            ok &= got[:, getattr(self.fn, "add_col", 7)] == self.res["add"].astype(np.float32)
         return ok
 
 
@@ -483,6 +609,14 @@ def check(fn, mtl, x, got, K, mtl_keys, seeds=None, flush=False):
         if idx.size:
             alt = an.subset(idx, key)
             ok[idx] |= alt.judge(got[idx], K, None if seeds is None else seeds[idx])
+    # branches on one and the same computed quantity (fn.linked: tuples of decisions) go the other way together
+    undecided = an.ambiguous(K)
+    for group in getattr(fn, "linked", ()):
+        if all(k in undecided for k in group):
+            idx = np.flatnonzero(np.logical_and.reduce([undecided[k] for k in group]) & ~ok)
+            if idx.size:
+                alt = an.subset(idx, group)
+                ok[idx] |= alt.judge(got[idx], K, None if seeds is None else seeds[idx])
     return {"ok": ok, "ambiguous": amb, "ratio": _ratio(an, got, amb), "analysis": an}
 
 

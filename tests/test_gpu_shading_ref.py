@@ -1,5 +1,7 @@
-"""The HIP kernels' math layer, BRDF evaluation and new-ray sampling (pbr_diag_math / pbr_diag_brdf / pbr_diag_new_ray)
-against float64, with no oracle in the loop, in both arithmetics.
+"""The HIP kernels' math layer, BRDF evaluation, new-ray sampling and surface step (pbr_diag_math / pbr_diag_brdf /
+pbr_diag_new_ray / pbr_diag_surface_step) against float64, with no oracle in the loop, in both arithmetics; the surface step
+(new ray, normal flip, updateColor with the tangent frame handed on) in the exact arithmetic also bit for bit against the
+oracle's hook.
 
 Exact arithmetic: the random batches, the edge set and the threshold seeds of test_shading_ref_cpu.py against the
 float64 restatement of the reference's formulas (tests/shading_ref.py), at the same error bounds (K_EXACT).
@@ -25,7 +27,9 @@ import numpy as np
 import pytest
 
 from test_gpu_parity import make_scene, single_material_desc
-from test_shading_ref_cpu import (AMBIGUOUS_MAX, K_EXACT, MEDIAN_MAX, Stages, run_edges, run_random,
+from conftest import describe_mismatch, same_values
+from test_shading_ref_cpu import (AMBIGUOUS_MAX, K_EXACT, MEDIAN_MAX, Stages, run_edges, run_edges_surface, run_random,
+                                  run_perpendicular_surface, run_random_surface,
                                   run_threshold_seeds)
 
 NATIVE_SCALE = 32
@@ -52,8 +56,9 @@ def configure(pbr, dev, brdf, arith, mtl=None):
     return sc, desc, keep
 
 
-def device_stages(pbr, dev, arith=0):
-    """The device as the stage under test, in the arithmetic `arith`."""
+def device_stages(pbr, dev, arith=0, oracle=None):
+    """The device as the stage under test, in the arithmetic `arith`; with an oracle, every surface-step batch must equal
+    its hook bit for bit."""
     state = {"key": None}
 
     def use(brdf, mtl):
@@ -69,12 +74,21 @@ def device_stages(pbr, dev, arith=0):
         use(brdf, mtl)
         return dev.diag_new_ray(nr)
 
+    def surface_fn(brdf, mtl, it):
+        use(brdf, mtl)
+        got = dev.diag_surface_step(it)
+        if oracle is not None:
+            want = oracle.surface_step(brdf, mtl, it)
+            assert same_values(got, want), "surface step %d %r: %s" % (brdf, mtl[:6].tolist(), describe_mismatch(got, want))
+        return got
+
     def randhash(x):                      # called after brdf_fn / ray_fn: the context is configured by then
         return dev.diag_math("randhash", x)
 
     if arith == 0:
-        return Stages(brdf_fn, ray_fn, randhash)
-    return Stages(brdf_fn, ray_fn, randhash, NATIVE_SCALE * MEDIAN_MAX, NATIVE_SCALE * AMBIGUOUS_MAX, flush=True)
+        return Stages(brdf_fn, ray_fn, randhash, surface_fn=surface_fn, prepare=use)
+    return Stages(brdf_fn, ray_fn, randhash, NATIVE_SCALE * MEDIAN_MAX, NATIVE_SCALE * AMBIGUOUS_MAX, flush=True, surface_fn=surface_fn,
+                  prepare=use)
 
 
 @pytest.mark.parametrize("brdf", [0, 1])
@@ -210,3 +224,39 @@ def test_native_mode_edge_set_matches_float64(pbr, device, brdf):
 @pytest.mark.parametrize("brdf", [0, 1])
 def test_native_mode_threshold_draws_match_float64(pbr, oracle, device, brdf):
     run_threshold_seeds(device_stages(pbr, device, 1), brdf, K_NATIVE, lambda x: oracle.math("randhash", x))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the surface step: new ray, normal flip, updateColor
+# ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_surface_step_random_batches_equal_the_oracle_and_match_float64(pbr, oracle, device, brdf):
+    run_random_surface(device_stages(pbr, device, 0, oracle), brdf, K_EXACT, seed=1)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_surface_step_edge_set_equals_the_oracle_and_matches_float64(pbr, oracle, device, brdf):
+    run_edges_surface(device_stages(pbr, device, 0, oracle), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_surface_step_random_batches_match_float64(pbr, device, brdf):
+    med, top = run_random_surface(device_stages(pbr, device, 1), brdf, K_NATIVE, seed=2)
+    print("native surface step, brdf %d: largest median %.3g, largest error / bound %.3g of K_NATIVE = %d" % (brdf, med, top, K_NATIVE))
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_surface_step_edge_set_matches_float64(pbr, device, brdf):
+    top = run_edges_surface(device_stages(pbr, device, 1), brdf, K_NATIVE)
+    print("native surface step, brdf %d, edge set: largest error / bound %.3g of K_NATIVE = %d" % (brdf, top, K_NATIVE))
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_exact_mode_surface_step_exactly_perpendicular_equals_the_oracle_and_takes_the_flip(pbr, oracle, device, brdf):
+    run_perpendicular_surface(device_stages(pbr, device, 0, oracle), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_native_mode_surface_step_exactly_perpendicular_matches_float64(pbr, device, brdf):
+    run_perpendicular_surface(device_stages(pbr, device, 1), brdf, K_NATIVE)

@@ -1,4 +1,4 @@
-"""The oracle's BRDF evaluation and new-ray sampling (orc_brdf_eval / orc_new_ray) against the float64 restatement of
+"""The oracle's BRDF evaluation, new-ray sampling and surface step (orc_brdf_eval / orc_new_ray / orc_surface_step) against the float64 restatement of
 the reference's formulas (tests/shading_ref.py): random batches like the GPU soak's, a fixed set of edge cases and
 seeds whose draws land on the samplers' thresholds.  No GPU: this holds the oracle — and with it, through the bit-exact
 parity tests, the HIP kernels' exact mode — to the reference's formulas, and holds the reference module itself to
@@ -198,6 +198,109 @@ def check_brdf(brdf, mtl, ev, got, K, flush=False):
     return sr.check(sr.brdf_eval(brdf), m, brdf_inputs(ev), got, K, BRDF_MTL_KEYS[brdf], flush=flush)
 
 
+SURFACE_MTL_KEYS = {0: (1, 2, 3, 4, 5, 6, 8, 9, 10), 1: (1, 2, 3, 4, 5, 8, 9, 10, 12, 13, 14)}
+SURFACE_JUDGE_COLS = [0, 1, 2, 5, 6, 7, 8, 9, 10, 11, 3, 4]     # the hook's n x 12 as surface_step's val, then seed and addDepth
+
+
+def surface_items(normal, dir_, light_dir, t, seed, color, lit, light_rgb):
+    it = np.zeros((normal.shape[0], 24), np.float32)
+    it[:, 3:6], it[:, 6:9], it[:, 9], it[:, 10], it[:, 11:14], it[:, 14] = dir_, normal, t, seed, color, lit
+    it[:, 15:18], it[:, 18:21] = light_dir, light_rgb
+    it[:, 0:3] = 0.25
+    return it
+
+
+def surface_inputs(it, draws):
+    r = it.astype(np.float64)
+    return {"dir": r[:, 3:6], "normal": r[:, 6:9], "color": r[:, 11:14], "lit": r[:, 14], "lightDir": r[:, 15:18],
+            "lightRgb": r[:, 18:21], "draws": draws.astype(np.float64)}
+
+
+def surface_seeds(it):
+    """`seed += t` (pathtracing.cl:281), in binary32: where the step's draws start."""
+    return (it[:, 10] + it[:, 9]).astype(np.float32)
+
+
+def check_surface(brdf, mtl, it, got, draws, seq, K, flush=False):
+    m = sr.f32(mtl)
+    return sr.check(sr.surface_step(brdf), m, surface_inputs(it, draws), got[:, SURFACE_JUDGE_COLS], K, SURFACE_MTL_KEYS[brdf], seeds=seq, flush=flush)
+
+
+def random_surface(rng, n, randhash):
+    """Random surface steps, lit and unlit, a quarter with back-facing normals.  The draws are inputs, taken from the
+    arithmetic under test: the hash has some 2^-9 of resolution (fract of a product near 4e4) and is exactly 0 once in a
+    few hundred draws, where both samplers return the lobe's peak itself, h = n — the BRDFs' singular point.  The seeds are
+    chosen so that none of a sample's draws is 0; what the samplers do with a draw of 0 is the threshold seeds' business."""
+    m = 2 * n
+    normal, out_dir, light_dir = random_directions(rng, m)
+    normal[: m // 4] *= -1                                   # back-facing normals: the flip runs, the tangent frame is dropped
+    it = surface_items(normal, out_dir, light_dir, rng.uniform(0.01, 5, m), rng.uniform(0, 300, m), rng.uniform(0, 1, (m, 3)),
+                       rng.integers(0, 2, m), rng.uniform(0, 2, (m, 3)))
+    draws, _ = draws_for(randhash, surface_seeds(it))
+    keep = np.flatnonzero((draws > 0).all(axis=1))
+    assert keep.size >= n
+    return it[rng.permutation(keep)[:n]]
+
+
+SOFT_LOBE = 10.0        # Shirley-Ashikhmin exponents up to this: see decided_material
+
+
+def decided_material(rng, brdf):
+    """A random material whose surface step has no singular point a sample can reach with probability above the cap:
+    opaque (d = 1: no refracted or mirrored ray, whose evaluation has h = n or h = 0 / 0), and for Shirley-Ashikhmin both
+    exponents at most SOFT_LOBE.  A lobe of exponent e puts ( e + 1 ) eps of its samples within 1 - dotHN <= eps of its
+    peak, where the exponent of the evaluation is 0 / 0; with eps = K * 8 * 2^-24 — the error bound of a dot product of two
+    normalised vectors — that is 8e-5 ( e + 1 ) in the exact and 2.4e-4 ( e + 1 ) in the native arithmetic, each against its
+    cap of 1e-4 and 3.2e-3: e <= 10 keeps the native share inside, and the exact one inside for the batches of the suite."""
+    while True:
+        mtl = random_material(rng, brdf)
+        mtl[0] = 1.0
+        if brdf == 0 or max(mtl[2], mtl[3]) <= SOFT_LOBE:
+            return mtl
+
+
+def sampled_direction_bound(brdf, mtl, K, n):
+    """An upper bound, from the material alone, of the share of a batch that may be ambiguous in the evaluation at the
+    sampled direction, for the materials decided_material excludes: the refracting samples (a share 1 - d of the batch, three
+    standard deviations added; every mirrored and every straight-through ray is among them) and, for Shirley-Ashikhmin,
+    the samples within the error bound of the lobe's peak, ( max( nu, nv ) + 1 ) K 8 2^-24 (decided_material)."""
+    d = float(mtl[0])
+    bound = (1.0 - d) + 3.0 * np.sqrt(max(d * (1.0 - d), 0.0) / n)
+    if brdf == 1:
+        bound += (max(float(mtl[2]), float(mtl[3])) + 1.0) * K * 8.0 * sr.U
+    return min(1.0, bound)
+
+
+def edge_surface():
+    """The BRDF edge directions (normals on the axes and next to +-(1,1,1), h = n, grazing, back-facing), and on top:
+    the arriving ray along and against the normal and perpendicular to it, the light below the surface (the pdf cut),
+    colours of 0 and above 1, lit and unlit.
+    "Perpendicular" is 2^-12 either side of it, so that the flip runs either way and the tangent frame is reused and
+    dropped: at exactly 0 the flip, the samplers' own tests of the same dot product and the BRDFs' vOut == 0 guards are all
+    undecided at once, and `check` follows one undecided branch at a time."""
+    normal, out_dir, in_dir = edge_directions()
+    off = np.abs((normal.astype(np.float64) * out_dir).sum(1)) > 2.0 ** -20      # the exactly grazing triples: see below
+    # ... and a normal exactly along +-(1,1,1): its tangent frame is normalize( 0 ), undefined in the reference (shading_ref);
+    # the BRDF evaluation's own edge set keeps it, the normals an ulp off the diagonal stay here
+    off &= ~((normal[:, 0] == normal[:, 1]) & (normal[:, 1] == normal[:, 2]))
+    normal, out_dir, in_dir = normal[off], out_dir[off], in_dir[off]
+    extra_n = edge_normals().astype(np.float64)
+    extra_n = extra_n[~((extra_n[:, 0] == extra_n[:, 1]) & (extra_n[:, 1] == extra_n[:, 2]))]
+    extra_n /= np.linalg.norm(extra_n, axis=1, keepdims=True)
+    t1 = unit(np.cross(extra_n, [0.3, -0.5, 0.81]))
+    leave = unit(extra_n + 0.5 * t1)
+    tilt = 2.0 ** -12
+    blocks = [(normal, out_dir, in_dir), (normal, out_dir, -in_dir),
+              (extra_n, -extra_n, leave), (extra_n, extra_n, leave), (extra_n, unit(t1 - tilt * extra_n), leave),
+              (extra_n, unit(t1 + tilt * extra_n), leave), (extra_n, -extra_n, -leave)]
+    normal, out_dir, light = (np.concatenate([b[i] for b in blocks]).astype(np.float32) for i in range(3))
+    n = normal.shape[0]
+    colours = np.array([(0, 0, 0), (1, 1, 1), (2.5, 0.5, 1.5), (0.3, 0.6, 0.9)], np.float32)
+    k = np.arange(n)
+    return surface_items(normal, out_dir, light, np.full(n, 2.0), 17.0 + k * 1.5, colours[k % 4], (k // 4) % 2 == 0,
+                         np.array([(1, 1, 1), (3, 2, 0.5), (0, 0, 0)], np.float32)[k % 3])
+
+
 def check_new_ray(brdf, mtl, nr, got, draws, seq, K, flush=False):
     m = sr.f32(mtl)
     return sr.check(sr.new_ray(brdf), m, ray_inputs(nr, draws), got, K, RAY_MTL_KEYS[brdf], seeds=seq, flush=flush)
@@ -218,9 +321,12 @@ def assert_ok(res, what, x, got, random_batch=False, median_max=MEDIAN_MAX):
 class Stages:
     """The stage implementation under test: the oracle here, the device in test_gpu_shading_ref.py."""
 
-    def __init__(self, brdf_fn, ray_fn, randhash, median_max=MEDIAN_MAX, ambiguous_max=AMBIGUOUS_MAX, flush=False):
-        """flush: the arithmetic under test flushes subnormal results to 0."""
-        self.brdf, self.ray, self.randhash = brdf_fn, ray_fn, randhash
+    def __init__(self, brdf_fn, ray_fn, randhash, median_max=MEDIAN_MAX, ambiguous_max=AMBIGUOUS_MAX, flush=False, surface_fn=None,
+                 prepare=None):
+        """flush: the arithmetic under test flushes subnormal results to 0.  prepare( brdf, mtl ): whatever randhash needs
+        done before it is asked ahead of a stage call (the device: its configuration)."""
+        self.brdf, self.ray, self.randhash, self.surface = brdf_fn, ray_fn, randhash, surface_fn
+        self.prepare = prepare or (lambda brdf, mtl: None)
         self.median_max, self.ambiguous_max, self.flush = median_max, ambiguous_max, flush
 
     def brdf_case(self, brdf, mtl, ev, K, random_batch=False):
@@ -235,6 +341,139 @@ class Stages:
         res = check_new_ray(brdf, mtl, nr, got, draws, seq, K, self.flush)
         assert_ok(res, "new ray %d %r" % (brdf, mtl[:6].tolist()), ray_inputs(nr, draws), got, random_batch, self.median_max)
         return res
+
+    def surface_case(self, brdf, mtl, it, K, random_batch=False):
+        got = self.surface(brdf, mtl, it)
+        draws, seq = draws_for(self.randhash, surface_seeds(it))
+        res = check_surface(brdf, mtl, it, got, draws, seq, K, self.flush)
+        res["got"] = got
+        assert_ok(res, "surface step %d %r" % (brdf, mtl[:6].tolist()), surface_inputs(it, draws), got[:, SURFACE_JUDGE_COLS], random_batch, self.median_max)
+        return res
+
+
+def input_ambiguous(res, K):
+    """The samples with an ambiguous decision other than those inside the BRDF evaluation at the SAMPLED direction (the
+    "N." decisions of shading_ref.surface_step)."""
+    amb = np.zeros(res["analysis"].n, bool)
+    for key, a in res["analysis"].ambiguous(K).items():
+        if not key.startswith("N."):
+            amb |= a
+    return amb
+
+
+def run_random_surface(stages, brdf, K, materials=6, n=2048, seed=0):
+    """Surface steps over random materials and directions, lit and unlit.  Returns (median, largest) error / bound.
+
+    Half the batches use decided_material: there EVERY decision of the step is held to the ambiguity cap, and the median is
+    over whole batches.  The other half use random_material as it is — glass, sharp lobes —, where the evaluation at the
+    SAMPLED direction reaches the BRDFs' singular set whatever the inputs: a mirrored ray (total reflection, reflectance >=
+    draw) has h = n exactly, where the Schlick model's cross( cross( h, n ), n ) is the zero vector and its anisotropy term
+    noise in the reference itself, and a sharp Shirley-Ashikhmin lobe samples its own peak, where the exponent is 0 / 0.
+    There the decisions the inputs control (the samplers', the flip, the light's evaluation and its pdf cut) are held to the
+    cap, the ambiguous share at the sampled direction to sampled_direction_bound — fixed by the material before the run —,
+    and for the Schlick model every such sample must be one that refracted."""
+    rng = np.random.default_rng(57 + brdf + 100 * seed)
+    meds, top, ambiguous, total = [], 0.0, 0, 0
+    for k in range(materials):
+        decided = k < (materials + 1) // 2
+        mtl = decided_material(rng, brdf) if decided else random_material(rng, brdf)
+        stages.prepare(brdf, mtl)
+        res = stages.surface_case(brdf, mtl, random_surface(rng, n, stages.randhash), K, random_batch=True)
+        meds.append(float(np.median(res["ratio"])))
+        top = max(top, float(res["ratio"].max()))
+        by_input = input_ambiguous(res, K)
+        sampled = res["ambiguous"] & ~by_input
+        ambiguous, total = ambiguous + int((res["ambiguous"] if decided else by_input).sum()), total + n
+        if not decided:
+            bound = sampled_direction_bound(brdf, mtl, K, n)
+            print("surface step, brdf %d %r: ambiguous share at the sampled direction %.3g, bound %.3g" % (brdf, mtl[:4].tolist(), sampled.mean(), bound))
+            assert sampled.mean() <= bound + stages.ambiguous_max
+            if brdf == 0:
+                assert (sampled & ~res["analysis"].res["add"]).mean() <= stages.ambiguous_max
+    share = ambiguous / float(total)
+    print("surface step, brdf %d: median error / bound per material %s, largest %.3g, ambiguous share %.3g" % (
+        brdf, [round(m, 3) for m in meds], top, share))
+    assert share <= stages.ambiguous_max, "surface step %d: %d samples of %d ambiguous" % (brdf, ambiguous, total)
+    return max(meds), top
+
+
+def surface_edge_materials(brdf):
+    """Every lobe shape of edge_materials at one of d = 1, 0, 0.5 in turn, and all three d for the first and the last."""
+    m = edge_materials(brdf)
+    return m[::3] + m[1::6] + m[2::6] + m[:3] + m[-3:]
+
+
+def run_edges_surface(stages, brdf, K):
+    it = edge_surface()
+    top, meds, ambiguous, total = 0.0, [], 0, 0
+    materials = surface_edge_materials(brdf)
+    assert {float(m[0]) for m in materials} == {0.0, 0.5, 1.0}
+    for mtl in materials:
+        res = stages.surface_case(brdf, mtl, it, K)
+        top = max(top, float(res["ratio"].max()) if res["ratio"].size else 0.0)
+        meds.append(float(np.median(res["ratio"])) if res["ratio"].size else 0.0)
+        ambiguous, total = ambiguous + int(res["ambiguous"].sum()), total + it.shape[0]
+    print("surface step, brdf %d, edge set of %d per material: median error / bound %.3g (largest of %d materials), largest %.3g, ambiguous share %.3g" % (
+        brdf, it.shape[0], max(meds), len(materials), top, ambiguous / float(total)))
+    return top
+
+
+def perpendicular_surface():
+    """Arriving rays EXACTLY perpendicular to the normal, where binary32 is exact: normals on the axes, directions in the
+    plane across (a product with an exact 0 is exact, so dot( normal, -dir ) is +-0 in any arithmetic), the light above and
+    below, lit.  `dot( normal, -dir ) <= 0` flips the normal here and `< 0` would not: the one place that tells them apart,
+    and the one place where the flip drops a tangent frame at equality."""
+    rows = []
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            n = np.zeros(3)
+            n[axis] = sign
+            for a, b in ((1.0, 0.0), (0.0, -1.0), (0.6, 0.8), (-0.8, 0.6), (0.28, -0.96)):
+                d = np.zeros(3)
+                d[(axis + 1) % 3], d[(axis + 2) % 3] = a, b
+                for up in (0.8, -0.8, 0.28):
+                    light = 0.6 * np.roll(d, 1) * 0 + np.sqrt(1 - up * up) * np.cross(n, d) + up * n
+                    rows.append((n, d, light))
+    normal, dir_, light = (np.array([r[i] for r in rows], np.float32) for i in range(3))
+    n = normal.shape[0]
+    k = np.arange(n)
+    colours = np.array([(1, 1, 1), (0.3, 0.6, 0.9), (2.5, 0.5, 1.5)], np.float32)
+    return surface_items(normal, dir_, light, np.full(n, 2.0), 23.0 + k * 2.5, colours[k % 3], np.ones(n), np.array([(1, 1, 1), (3, 2, 0.5)], np.float32)[k % 2])
+
+
+def perpendicular_materials(brdf):
+    """Opaque ones: a translucent material hit at exactly grazing incidence reflects totally, the ray into itself, and the
+    evaluation of that is 0 / 0 (shading_ref._half_vector)."""
+    if brdf == 1:
+        return [material(1, 1.0, 1.5, nu, nv) for nu, nv in ((0, 0), (3, 7), (100, 10))]
+    return [material(0, 1.0, 1.5, p, r) for p, r in ((1.0, 0.2), (0.3, 0.04), (0.5, 1.0))]
+
+
+def run_perpendicular_surface(stages, brdf, K):
+    """Exactly perpendicular incidence.  In the exact arithmetic the verdict itself is asserted: the result must pass
+    against the reference's own branch — flipped, the samplers' tests of the same +-0 taken as the reference takes them —
+    with no alternative accepted; test_perpendicular_items_tell_the_flip_apart shows that the other branch would fail.
+    In the native arithmetic either branch counts."""
+    it = perpendicular_surface()
+    for mtl in perpendicular_materials(brdf):
+        res = stages.surface_case(brdf, mtl, it, K)
+        an = res["analysis"]
+        assert an.dec["U.flip"][0].all()
+        if not stages.flush:
+            _, seq = draws_for(stages.randhash, surface_seeds(it))
+            # an item with some OTHER quantity within its bound of a threshold (a sampled ray on the horizon) keeps its
+            # alternative; a quantity that is exactly 0 — the dot product in question, vOut — is no such case: binary32 has
+            # the same 0; nor is a quantity that is NaN (the pdf of a light under the flipped normal: pow of a negative base)
+            other = np.zeros(an.n, bool)
+            for key, a in an.ambiguous(K).items():
+                other |= a & ~(an.q[key][0] == 0.0) & ~np.isnan(an.q[key][0])
+            assert other.mean() <= 0.1
+            own = an.judge(res["got"][:, SURFACE_JUDGE_COLS], K, seq) | other
+            assert own.all(), "surface step %d %r: exactly perpendicular items %s miss the reference's own branch" % (
+                brdf, mtl[:6].tolist(), np.flatnonzero(~own).tolist())
+        med = float(np.median(res["ratio"])) if res["ratio"].size else 0.0
+        print("surface step, brdf %d %r, %d exactly perpendicular items: median error / bound %.3g, ambiguous share %.3g" % (
+            brdf, mtl[:4].tolist(), it.shape[0], med, float(res["ambiguous"].mean())))
 
 
 def run_random(stages, brdf, K, materials=12, n=2048, seed=0):
@@ -289,7 +528,7 @@ def oracle_stages(oracle):
         oracle.lib().orc_new_ray(brdf, mtl.ctypes.data, nr.ctypes.data_as(_fp), nr.shape[0], out.ctypes.data_as(_fp))
         return out
 
-    return Stages(brdf_fn, ray_fn, lambda x: oracle.math("randhash", x))
+    return Stages(brdf_fn, ray_fn, lambda x: oracle.math("randhash", x), surface_fn=oracle.surface_step)
 
 
 @pytest.mark.parametrize("brdf", [0, 1])
@@ -306,6 +545,38 @@ def test_oracle_edge_set_matches_float64(oracle, brdf):
 @pytest.mark.parametrize("brdf", [0, 1])
 def test_oracle_threshold_draws_match_float64(oracle, brdf):
     run_threshold_seeds(oracle_stages(oracle), brdf, K_EXACT, lambda x: oracle.math("randhash", x))
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_oracle_surface_step_random_batches_match_float64(oracle, brdf):
+    run_random_surface(oracle_stages(oracle), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_oracle_surface_step_edge_set_matches_float64(oracle, brdf):
+    run_edges_surface(oracle_stages(oracle), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_oracle_surface_step_exactly_perpendicular_matches_float64(oracle, brdf):
+    run_perpendicular_surface(oracle_stages(oracle), brdf, K_EXACT)
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_perpendicular_items_tell_the_flip_apart(oracle, brdf):
+    """Not vacuous: on the exactly perpendicular items the reference with the normal NOT flipped (`< 0` for `<= 0`) gives
+    results that the reference's own branch rejects, for most items of every material."""
+    it = perpendicular_surface()
+    draws, seq = draws_for(lambda x: oracle.math("randhash", x), surface_seeds(it))
+    idx = np.arange(it.shape[0])
+    for mtl in perpendicular_materials(brdf):
+        an = sr.Analysis(sr.surface_step(brdf), sr.f32(mtl), surface_inputs(it, draws), SURFACE_MTL_KEYS[brdf])
+        other = an.subset(idx, "U.flip")
+        wrong = np.zeros((it.shape[0], 12), np.float32)
+        wrong[:, :10] = other.res["val"]
+        wrong[:, 10] = seq[idx, other.res["used"]]
+        wrong[:, 11] = other.res["add"]
+        assert an.judge(wrong, K_EXACT, seq).mean() < 0.5, mtl[:6].tolist()
 
 
 def test_threshold_seeds_reach_their_targets(oracle):
@@ -329,3 +600,24 @@ def test_reference_sees_a_transcription_slip():
     exact = an.res["val"].astype(np.float32)
     assert an.judge(exact, K_EXACT).mean() > 0.999
     assert an.judge(exact * np.float32(1 + 1e-5), K_EXACT).mean() < 0.5
+
+
+@pytest.mark.parametrize("brdf", [0, 1])
+def test_surface_reference_sees_a_transcription_slip(oracle, brdf):
+    """Not vacuous for the surface step either: the float64 result rounded to binary32 passes; the colours one relative
+    1e-5 off fail on most samples that have any."""
+    rng = np.random.default_rng(6)
+    mtl = material(brdf, 1.0, 1.5, *((0.4, 0.3) if brdf == 0 else (200.0, 20.0)))
+    it = random_surface(rng, 512, lambda x: oracle.math("randhash", x))
+    draws, seq = draws_for(lambda x: oracle.math("randhash", x), surface_seeds(it))
+    an = sr.Analysis(sr.surface_step(brdf), sr.f32(mtl), surface_inputs(it, draws), SURFACE_MTL_KEYS[brdf])
+    exact = np.zeros((512, 12), np.float32)
+    exact[:, :10] = an.res["val"]
+    exact[:, 10] = seq[np.arange(512), an.res["used"]]
+    exact[:, 11] = an.res["add"]
+    robust = np.isfinite(an.delta).all(axis=1) & (np.abs(exact[:, 3:6]).max(axis=1) > 0)
+    assert robust.mean() > 0.5
+    assert an.judge(exact, K_EXACT, seq).mean() > 0.999
+    slipped = exact.copy()
+    slipped[:, 3:9] *= np.float32(1 + 1e-5)
+    assert an.judge(slipped, K_EXACT, seq)[robust].mean() < 0.5
