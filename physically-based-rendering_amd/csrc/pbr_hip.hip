@@ -25,6 +25,7 @@
 #include "pt_denoise_guided.hpp"
 #include "pt_temporal.hpp"
 #include "pt_temporal_host.hpp"
+#include "pt_denoise_host.hpp"
 #include "pt_scene_pack.hpp"
 #include "pt_tuner.hpp"
 #include "pt_deal.hpp"
@@ -70,6 +71,63 @@ struct DealTable {
 	std::vector<unsigned> host;
 	unsigned first[PT_BANDS + 1] = {};
 	unsigned* dev = nullptr;
+};
+
+// pbr_denoise_temporal's device planes (pt_temporal.hpp), row-major W x H.  Two sets {integrated colour | variance, position,
+// normal, albedo} + the history lengths: set `set` holds the previous successful call's, the other one is written by the next
+// call and becomes the history by flipping `set` — nothing is copied.  Behind them the filter's working planes, and the
+// planes of the motion path (pbr_temporal_track_motion): first-hit face, {Pprev, code}, {nref, len}.
+struct TemporalPlanes {
+	float4* integrated[2] = {}, * position[2] = {}, * normal[2] = {}, * albedo[2] = {};
+	unsigned* length[2] = {};
+	float4* ping = nullptr, * pong = nullptr;
+	float4* info = nullptr;       // {fx, fy, L, valid} of a call that asks for it
+	float* variance = nullptr;
+	float4* motion = nullptr, * reference = nullptr;
+	int* face = nullptr;
+	int set = 0;
+
+	// visit( slot, bytes per pixel, is it a plane of the motion path )
+	template <class Visit>
+	void each( Visit visit ) {
+		for( float4** plane : { &integrated[0], &integrated[1], &position[0], &position[1], &normal[0], &normal[1], &albedo[0], &albedo[1], &ping, &pong, &info } ) {
+			visit( (void**) plane, sizeof( float4 ), false );
+		}
+
+		visit( (void**) &length[0], sizeof( unsigned ), false );
+		visit( (void**) &length[1], sizeof( unsigned ), false );
+		visit( (void**) &variance, sizeof( float ), false );
+		visit( (void**) &motion, sizeof( float4 ), true );
+		visit( (void**) &reference, sizeof( float4 ), true );
+		visit( (void**) &face, sizeof( int ), true );
+	}
+
+	// The planes that are not there yet — the motion path's only if needMotion.  All or nothing: a call that fails gives back
+	// what it got, and leaves the planes of earlier calls (a history) alone.
+	hipError_t alloc( size_t pixels, bool needMotion ) {
+		const bool hadHistory = ( variance != nullptr );   // all or nothing: one stands for all
+		hipError_t err = hipSuccess;
+		each( [&]( void** slot, size_t bytes, bool ofMotion ) {
+			if( err == hipSuccess && *slot == nullptr && ( needMotion || !ofMotion ) ) {
+				err = hipMalloc( slot, bytes * pixels );
+			}
+		} );
+
+		if( err != hipSuccess ) {
+			free( hadHistory );
+		}
+
+		return err;
+	}
+
+	void free( bool motionOnly = false ) {
+		each( [motionOnly]( void** slot, size_t, bool ofMotion ) {
+			if( ofMotion || !motionOnly ) {
+				(void) hipFree( *slot );
+				*slot = nullptr;
+			}
+		} );
+	}
 };
 
 struct pbr_ctx {
@@ -191,31 +249,16 @@ struct pbr_ctx {
 	uint32_t lastAdaptiveRounds = 0;     // of the last adaptive call: rounds (= convergence tests per tile that reached the end),
 	uint64_t lastAdaptiveUnits = 0;      // (pixel, frame) units traced,
 	double lastAdaptiveFoldMs = 0.0;     // time inside foldFramesAdaptive
-	// pbr_denoise_temporal (pt_temporal.hpp): two sets of row-major W x H planes {integrated colour | variance, position, normal,
-	// albedo} + the history lengths — set temporalSet holds the previous successful call's, the other one is written by the
-	// next call and becomes the history by flipping temporalSet: nothing is copied.  Behind them the filter's working planes.
-	// All allocated by the first temporal call after pbr_configure, freed with the images
-	float4* dTemporalI[2] = { nullptr, nullptr };
-	float4* dTemporalPosition[2] = { nullptr, nullptr };
-	float4* dTemporalNormal[2] = { nullptr, nullptr };
-	float4* dTemporalAlbedo[2] = { nullptr, nullptr };
-	unsigned* dTemporalLength[2] = { nullptr, nullptr };
-	float4* dTemporalPing = nullptr;
-	float4* dTemporalPong = nullptr;
-	float4* dTemporalInfo = nullptr;     // {fx, fy, L, valid} of a call that asks for it
-	float* dTemporalVariance = nullptr;
-	int temporalSet = 0;
-	// is set temporalSet a history, has the geometry moved since it was made, which path does a call take: pt_temporal_host.hpp.
+	// pbr_denoise_temporal (pt_temporal.hpp): the history's planes, allocated by the first temporal call after pbr_configure,
+	// freed with the images
+	TemporalPlanes planes;
+	// is set planes.set a history, has the geometry moved since it was made, which path does a call take: pt_temporal_host.hpp.
 	// The history is dropped by pbr_temporal_reset, pbr_configure, pbr_upload_scene and — without motion tracking — pbr_update_vertices
 	TemporalPolicy temporal;
 	// pbr_temporal_track_motion: H, the vertex positions the history was made under — a copy of dVertices taken by the first
 	// pbr_update_vertices after a temporal call, allocated then, freed with the scene and when tracking is turned off (not part
-	// of refitBytes) — and the planes of the motion path: first-hit face, {Pprev, code}, {nref, len}; allocated by the first call
-	// that takes that path, freed with the history
+	// of refitBytes)
 	float4* dHistVertices = nullptr;
-	int* dTemporalFace = nullptr;
-	float4* dTemporalMotion = nullptr;
-	float4* dTemporalReference = nullptr;
 	bool temporalFresh = false;          // a pbr_render_adaptive succeeded since the last successful temporal call
 	pbr_camera temporalCam = {};         // the history's camera and pixel size
 	float temporalPxDim = 0.0f;
@@ -333,27 +376,7 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->adaptiveStats = false;
 	ctx->varianceCurrent = false;
 
-	for( int set = 0; set < 2; set++ ) {
-		(void) hipFree( ctx->dTemporalI[set] );
-		(void) hipFree( ctx->dTemporalPosition[set] );
-		(void) hipFree( ctx->dTemporalNormal[set] );
-		(void) hipFree( ctx->dTemporalAlbedo[set] );
-		(void) hipFree( ctx->dTemporalLength[set] );
-		ctx->dTemporalI[set] = ctx->dTemporalPosition[set] = ctx->dTemporalNormal[set] = ctx->dTemporalAlbedo[set] = nullptr;
-		ctx->dTemporalLength[set] = nullptr;
-	}
-
-	(void) hipFree( ctx->dTemporalPing );
-	(void) hipFree( ctx->dTemporalPong );
-	(void) hipFree( ctx->dTemporalInfo );
-	(void) hipFree( ctx->dTemporalVariance );
-	ctx->dTemporalPing = ctx->dTemporalPong = ctx->dTemporalInfo = nullptr;
-	(void) hipFree( ctx->dTemporalFace );
-	(void) hipFree( ctx->dTemporalMotion );
-	(void) hipFree( ctx->dTemporalReference );
-	ctx->dTemporalVariance = nullptr;
-	ctx->dTemporalFace = nullptr;
-	ctx->dTemporalMotion = ctx->dTemporalReference = nullptr;
+	ctx->planes.free();
 	ctx->temporal.configure();
 	ctx->temporalFresh = false;
 	ctx->dTileCost = nullptr;
@@ -616,28 +639,37 @@ int sceneParams( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail = nullptr ) {
 	return walk;
 }
 
-// The camera of a w x h image: its vectors, and the launch-invariant sub-expressions of initRay (pt_kernel.hpp) in the same
-// IEEE single operations as the kernel would do (this file is built with -ffp-contract=off like the kernels).
-void setCamera( DevParams* P, const pbr_camera* cam, int w, int h, float pxDim ) {
-	const float* src[4] = { &cam->eye.x, &cam->w.x, &cam->u.x, &cam->v.x };
-	float* dst[4] = { P->eye, P->cw, P->cu, P->cv };
-
-	for( int i = 0; i < 4; i++ ) {
-		for( int k = 0; k < 3; k++ ) {
-			dst[i][k] = src[i][k];
-		}
-	}
-
-	for( int k = 0; k < 3; k++ ) {
-		const float cuW = P->cu[k] * (float) w;
-		P->camA[k] = P->cu[k] - cuW;
-		P->cvH[k] = P->cv[k] * (float) h;
-	}
-
-	P->halfPx = pxDim * 0.5f;
-	P->pxDim = pxDim;
+// The camera of a w x h image: its vectors, and the launch-invariant sub-expressions of initRay (pt_kernel.hpp), as
+// ptd::cameraTerms computes them (pt_denoise_host.hpp: host arithmetic, built with -ffp-contract=off like the kernels).
+ptd::CameraTerms setCamera( DevParams* P, const pbr_camera* cam, int w, int h, float pxDim ) {
+	const ptd::CameraTerms C = ptd::cameraTerms( *cam, w, h, pxDim );
+	ptd::copy3( P->eye, C.eye );
+	ptd::copy3( P->cu, C.cu );
+	ptd::copy3( P->cv, C.cv );
+	ptd::copy3( P->cw, C.cw );
+	ptd::copy3( P->camA, C.camA );
+	ptd::copy3( P->cvH, C.cvH );
+	P->halfPx = C.halfPx;
+	P->pxDim = C.pxDim;
 	P->width = w;
 	P->height = h;
+	return C;
+}
+
+// The image kernels (untile, display, features, variance, the filters): one thread per pixel, 64 x 4 blocks.
+const dim3 kImageBlock( 64, 4 );
+
+dim3 imageGrid( int w, int h ) {
+	return dim3( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+}
+
+// The end of a call that recorded evStart and evStop around its kernels: wait for the stream, keep the time between the two.
+int timedTail( pbr_ctx* ctx ) {
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float ms = 0.0f;
+	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
+	ctx->lastKernelMs = (double) ms;
+	return PBR_OK;
 }
 
 // A plan's recipe: kernel group, name, the state machine's thresholds, block size, and the per-lane path state that two
@@ -1018,12 +1050,8 @@ int beginRender( pbr_ctx* ctx, const float* seeds, uint32_t nSeeds, const pbr_ca
 // ... and ends with, behind its last fold: the call's time on the device, and what the diagnostics report of its launches
 int endRender( pbr_ctx* ctx, double traceMs, uint32_t launches ) {
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	PBR_TRY( timedTail( ctx ) );
 	ctx->workClean = true;   // the last fold left the queue heads at zero
-
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
 	ctx->lastTraceMs = traceMs;
 	ctx->lastTraceLaunches = launches;
 	return PBR_OK;
@@ -1308,9 +1336,7 @@ int readTiled( pbr_ctx* ctx, const float4* tiles, float* rgba, int tileWorld, in
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( ctx->cfg.width + 63 ) / 64, ( ctx->cfg.height + 3 ) / 4 );
-	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, tiles, ctx->dRows,
+	hipLaunchKernelGGL( ptk::untile, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, tiles, ctx->dRows,
 		(int) ctx->cfg.width, (int) ctx->cfg.height, ctx->tilesX, tileWorld, tileRank );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipMemcpyAsync( rgba, ctx->dRows, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
@@ -1605,10 +1631,7 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	}
 
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = ms;
+	PBR_TRY( timedTail( ctx ) );
 	ctx->treeStale = true;
 	ctx->refitUpdates++;
 	freeWalkStreams( ctx );   // none while traversal 0 is configured; an unconfigured context may hold a previous mode's
@@ -1920,10 +1943,8 @@ int pbr_read_display( pbr_ctx* ctx, uint8_t* rgba8, int top_row_first ) {
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( ctx->cfg.width + 63 ) / 64, ( ctx->cfg.height + 3 ) / 4 );
 	// dRows (16 B per pixel) doubles as the 4-B-per-pixel staging buffer
-	hipLaunchKernelGGL( ptk::displayRGBA8, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, (uchar4*) ctx->dRows,
+	hipLaunchKernelGGL( ptk::displayRGBA8, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, (uchar4*) ctx->dRows,
 		(int) ctx->cfg.width, (int) ctx->cfg.height, ctx->tilesX, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank, top_row_first ? 1 : 0 );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipMemcpyAsync( rgba8, ctx->dRows, (size_t) 4 * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
@@ -2014,7 +2035,8 @@ int pbr_read_full( pbr_ctx* ctx, float* rgba ) {
 }
 
 
-// ---- diagnostic entry points (include/pbr_hip_diag.h) -----------------------------------
+// ---- the denoise family: pbr_denoise, pbr_read_variance, pbr_denoise_guided, pbr_denoise_temporal ----------------------
+// What the calls refuse, the pass schedule and the camera terms are host arithmetic: pt_denoise_host.hpp.
 
 namespace {
 
@@ -2024,105 +2046,33 @@ struct DevBuf {
 	hipError_t alloc( size_t bytes ) { return hipMalloc( &p, bytes ? bytes : 4 ); }
 };
 
+// The planes pbr_denoise and pbr_denoise_guided allocate per call: the first-hit features and the filter's two working planes.
+struct FilterPlanes {
+	DevBuf position, normal, albedo, ping, pong;
 
-}  // namespace
+	hipError_t alloc( size_t pixels ) {
+		hipError_t err = hipSuccess;
 
-// The denoise half of the display step (csrc/pt_denoise.hpp): first-hit features from one primary ray per pixel, then
-// edge-avoiding a-trous passes over the accumulated image.  Leaves the accumulation untouched.
-int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_params* params, float* rgba, float* features ) {
-	if( ctx == nullptr || ctx->stream == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( !ctx->hasScene || !ctx->configured ) {
-		return fail( ctx, PBR_ESTATE, "denoise before pbr_upload_scene / pbr_configure" );
-	}
-	if( cam == nullptr || params == nullptr || rgba == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "denoise: null camera, parameters or destination" );
-	}
-	if( params->passes < 1 || params->passes > 8 ) {
-		return fail( ctx, PBR_EINVAL, "denoise: 1 .. 8 passes (got %u)", params->passes );
-	}
-
-	const float sigmas[4] = { params->sigma_color, params->sigma_normal, params->sigma_world, params->sigma_albedo };
-
-	for( int k = 0; k < 4; k++ ) {
-		if( !( sigmas[k] >= 0.0f ) || !std::isfinite( sigmas[k] ) ) {
-			return fail( ctx, PBR_EINVAL, "denoise: standard deviations must be finite and >= 0 (0 switches a feature off)" );
+		for( DevBuf* plane : { &position, &normal, &albedo, &ping, &pong } ) {
+			err = ( err == hipSuccess ) ? plane->alloc( sizeof( float4 ) * pixels ) : err;
 		}
+
+		return err;
 	}
+};
 
-	const bool sharded = ctx->cfg.tile_world > 1;
-
-	if( sharded && ctx->dFull == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "denoise with tile sharding filters the gathered frame: call pbr_import_tiles first" );
-	}
-
-	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
-	const size_t pixels = (size_t) w * (size_t) h;
-	DevBuf dPosition, dNormal, dAlbedo, dPing, dPong;
-	HIP_TRY( ctx, dPosition.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dNormal.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dAlbedo.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dPing.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dPong.alloc( sizeof( float4 ) * pixels ) );
-
-	DevParams P;
-	PBR_TRY( sceneParams( ctx, &P ) );
-	setCamera( &P, cam, w, h, pxDim );
-
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
-	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ( sharded ? ctx->dFull : ctx->dImgOut ), (float4*) dPing.p,
-		w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p, (int*) nullptr );
-	HIP_TRY( ctx, hipGetLastError() );
-
-	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
-	float4* in = (float4*) dPing.p;
-	float4* out = (float4*) dPong.p;
-
-	for( uint32_t pass = 0; pass < params->passes; pass++ ) {
-		ptd::DenoiseArgs A;
-		A.width = w;
-		A.height = h;
-		A.step = 1 << pass;
-		// the colour's standard deviation halves from pass to pass (Dammertz et al. 2010, section 3.3): what the early
-		// passes smoothed, the late, wide ones must not blur again
-		A.invColor = inverseSquare( params->sigma_color / (float) ( 1u << pass ) );
-		A.invNormal = inverseSquare( params->sigma_normal );
-		A.invAlbedo = inverseSquare( params->sigma_albedo );
-		A.worldScale = params->sigma_world * (float) A.step * pxDim;
-		hipLaunchKernelGGL( ptd::atrousPass, grid, block, 0, ctx->stream, A, (const float4*) in, out,
-			(const float4*) dPosition.p, (const float4*) dNormal.p, (const float4*) dAlbedo.p );
-		std::swap( in, out );
-	}
-
-	HIP_TRY( ctx, hipGetLastError() );
-	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-
-	if( features != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( features, dPosition.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( features + 4 * pixels, dNormal.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( features + 8 * pixels, dAlbedo.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	return PBR_OK;
-}
-
-namespace {
-
-// pbr_read_variance / pbr_denoise_guided: the moments must describe the accumulated image as it is
-int varianceUsable( pbr_ctx* ctx, const char* who ) {
+// The front of every call of the family: a scene and a configuration first, then what pt_denoise_host.hpp's check of the
+// arguments said (status, why) — its message becomes the context's error.
+int admit( pbr_ctx* ctx, const char* who, int status = PBR_OK, const std::string& why = std::string() ) {
 	if( !ctx->hasScene || !ctx->configured ) {
 		return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene / pbr_configure", who );
 	}
+
+	return ( status == PBR_OK ) ? PBR_OK : fail( ctx, status, "%s", why.c_str() );
+}
+
+// pbr_read_variance / pbr_denoise_guided / pbr_denoise_temporal: the moments must describe the accumulated image as it is
+int varianceUsable( pbr_ctx* ctx, const char* who ) {
 	if( ctx->cfg.tile_world > 1 ) {
 		return fail( ctx, PBR_ESTATE, "%s with tile sharding: the variance pbr_render_adaptive keeps of other ranks' tiles is not gathered", who );
 	}
@@ -2133,7 +2083,91 @@ int varianceUsable( pbr_ctx* ctx, const char* who ) {
 	return PBR_OK;
 }
 
+// an output the caller may leave out (null): copied behind whatever the stream holds
+int readBack( pbr_ctx* ctx, void* dst, const void* src, size_t bytes ) {
+	if( dst != nullptr ) {
+		HIP_TRY( ctx, hipMemcpyAsync( dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
+	return PBR_OK;
+}
+
+// {position, normal, albedo} into the caller's `features` (may be null)
+int readFeatures( pbr_ctx* ctx, float* features, const FilterPlanes& D, size_t pixels ) {
+	if( features != nullptr ) {
+		PBR_TRY( readBack( ctx, features, D.position.p, sizeof( float4 ) * pixels ) );
+		PBR_TRY( readBack( ctx, features + 4 * pixels, D.normal.p, sizeof( float4 ) * pixels ) );
+		PBR_TRY( readBack( ctx, features + 8 * pixels, D.albedo.p, sizeof( float4 ) * pixels ) );
+	}
+
+	return PBR_OK;
+}
+
+// `passes` launches of ptd::atrousGuidedPass: the first reads `in` (and leaves it as it is), every pass writes the plane of
+// `outs` the one before it did not; the last one restores .w from `original` and writes `varianceOut`.  -> the plane that
+// holds the result.  The caller checks hipGetLastError.
+const float4* guidedPasses( pbr_ctx* ctx, const pbr_denoise_guided_params& params, int w, int h, float pxDim, const float4* in, float4* const outs[2],
+                            const float4* position, const float4* normal, const float4* albedo, const float4* original, float* varianceOut ) {
+	for( uint32_t pass = 0; pass < params.passes; pass++ ) {
+		const bool last = ( pass + 1 == params.passes );
+		float4* const out = outs[pass & 1u];
+		hipLaunchKernelGGL( ptd::atrousGuidedPass, imageGrid( w, h ), kImageBlock, 0, ctx->stream, ptd::guidedPass( params, pass, w, h, pxDim ), in, out,
+			position, normal, albedo, last ? original : (const float4*) nullptr, last ? varianceOut : (float*) nullptr );
+		in = out;
+	}
+
+	return in;
+}
+
 }  // namespace
+
+// The denoise half of the display step (csrc/pt_denoise.hpp): first-hit features from one primary ray per pixel, then
+// edge-avoiding a-trous passes over the accumulated image.  Leaves the accumulation untouched.
+int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_denoise_params* params, float* rgba, float* features ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+
+	std::string why;
+	PBR_TRY( admit( ctx, "pbr_denoise", ptd::denoiseCheck( "pbr_denoise", cam, params, rgba, &why ), why ) );
+	const bool sharded = ctx->cfg.tile_world > 1;
+
+	if( sharded && ctx->dFull == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_denoise with tile sharding filters the gathered frame: call pbr_import_tiles first" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
+	const size_t pixels = (size_t) w * (size_t) h;
+	FilterPlanes D;
+	HIP_TRY( ctx, D.alloc( pixels ) );
+
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P ) );
+	setCamera( &P, cam, w, h, pxDim );
+
+	const dim3 grid = imageGrid( w, h );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ( sharded ? ctx->dFull : ctx->dImgOut ), (float4*) D.ping.p,
+		w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position.p, (float4*) D.normal.p, (float4*) D.albedo.p, (int*) nullptr );
+	HIP_TRY( ctx, hipGetLastError() );
+
+	float4* in = (float4*) D.ping.p;
+	float4* out = (float4*) D.pong.p;
+
+	for( uint32_t pass = 0; pass < params->passes; pass++ ) {
+		hipLaunchKernelGGL( ptd::atrousPass, grid, kImageBlock, 0, ctx->stream, ptd::plainPass( *params, pass, w, h, pxDim ), (const float4*) in, out,
+			(const float4*) D.position.p, (const float4*) D.normal.p, (const float4*) D.albedo.p );
+		std::swap( in, out );
+	}
+
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	PBR_TRY( readBack( ctx, rgba, in, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readFeatures( ctx, features, D, pixels ) );
+	return timedTail( ctx );
+}
 
 // The variance of every pixel's mean luminance after pbr_render_adaptive (csrc/pt_denoise_guided.hpp, pixelVariance).
 int pbr_read_variance( pbr_ctx* ctx, float* variance ) {
@@ -2141,27 +2175,21 @@ int pbr_read_variance( pbr_ctx* ctx, float* variance ) {
 		return PBR_EINVAL;
 	}
 	if( variance == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "read_variance: null destination" );
+		return fail( ctx, PBR_EINVAL, "pbr_read_variance: null destination" );
 	}
 
-	PBR_TRY( varianceUsable( ctx, "read_variance" ) );
+	PBR_TRY( admit( ctx, "pbr_read_variance" ) );
+	PBR_TRY( varianceUsable( ctx, "pbr_read_variance" ) );
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
-	const size_t pixels = (size_t) w * (size_t) h;
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 	// dRows (W x H float4) is the staging of every read-back: its first quarter holds the floats
-	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+	hipLaunchKernelGGL( ptd::pixelVariance, imageGrid( w, h ), kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
 		ctx->varianceFirstCount, (const float4*) nullptr, (float*) ctx->dRows, (float4*) nullptr, w, h, ctx->tilesX );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( variance, ctx->dRows, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	return PBR_OK;
+	HIP_TRY( ctx, hipMemcpyAsync( variance, ctx->dRows, sizeof( float ) * (size_t) w * (size_t) h, hipMemcpyDeviceToHost, ctx->stream ) );
+	return timedTail( ctx );
 }
 
 // pbr_denoise with the adaptive render's variance in place of sigma_color (csrc/pt_denoise_guided.hpp): the luminance term is
@@ -2172,34 +2200,16 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 	if( ctx == nullptr || ctx->stream == nullptr ) {
 		return PBR_EINVAL;
 	}
-	if( !ctx->hasScene || !ctx->configured ) {
-		return fail( ctx, PBR_ESTATE, "denoise_guided before pbr_upload_scene / pbr_configure" );
-	}
-	if( cam == nullptr || params == nullptr || rgba == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "denoise_guided: null camera, parameters or destination" );
-	}
-	if( params->passes < 1 || params->passes > 8 ) {
-		return fail( ctx, PBR_EINVAL, "denoise_guided: 1 .. 8 passes (got %u)", params->passes );
-	}
 
-	const float sigmas[4] = { params->sigma_luminance, params->sigma_normal, params->sigma_world, params->sigma_albedo };
-
-	for( int k = 0; k < 4; k++ ) {
-		if( !( sigmas[k] >= 0.0f ) || !std::isfinite( sigmas[k] ) ) {
-			return fail( ctx, PBR_EINVAL, "denoise_guided: standard deviations must be finite and >= 0 (0 switches a term off)" );
-		}
-	}
-
-	PBR_TRY( varianceUsable( ctx, "denoise_guided" ) );
+	std::string why;
+	PBR_TRY( admit( ctx, "pbr_denoise_guided", ptd::denoiseCheck( "pbr_denoise_guided", cam, params, rgba, &why ), why ) );
+	PBR_TRY( varianceUsable( ctx, "pbr_denoise_guided" ) );
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
 	const size_t pixels = (size_t) w * (size_t) h;
-	DevBuf dPosition, dNormal, dAlbedo, dPing, dPong, dOriginal, dVariance;
-	HIP_TRY( ctx, dPosition.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dNormal.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dAlbedo.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dPing.alloc( sizeof( float4 ) * pixels ) );
-	HIP_TRY( ctx, dPong.alloc( sizeof( float4 ) * pixels ) );
+	FilterPlanes D;
+	DevBuf dOriginal, dVariance;
+	HIP_TRY( ctx, D.alloc( pixels ) );
 	HIP_TRY( ctx, dOriginal.alloc( sizeof( float4 ) * pixels ) );
 	HIP_TRY( ctx, dVariance.alloc( sizeof( float ) * pixels ) );
 
@@ -2207,53 +2217,23 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 	PBR_TRY( sceneParams( ctx, &P ) );
 	setCamera( &P, cam, w, h, pxDim );
 
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+	const dim3 grid = imageGrid( w, h );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, (float4*) dOriginal.p, w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
-		ctx->varianceFirstCount, (const float4*) dOriginal.p, (float*) nullptr, (float4*) dPing.p, w, h, ctx->tilesX );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, (float4*) dPosition.p, (float4*) dNormal.p, (float4*) dAlbedo.p, (int*) nullptr );
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, (float4*) dOriginal.p, w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+		ctx->varianceFirstCount, (const float4*) dOriginal.p, (float*) nullptr, (float4*) D.ping.p, w, h, ctx->tilesX );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position.p, (float4*) D.normal.p, (float4*) D.albedo.p, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
-	float4* in = (float4*) dPing.p;
-	float4* out = (float4*) dPong.p;
-
-	for( uint32_t pass = 0; pass < params->passes; pass++ ) {
-		const bool last = ( pass + 1 == params->passes );
-		ptd::GuidedArgs A;
-		A.width = w;
-		A.height = h;
-		A.step = 1 << pass;
-		A.sigmaLuminance = params->sigma_luminance;
-		A.invNormal = inverseSquare( params->sigma_normal );
-		A.invAlbedo = inverseSquare( params->sigma_albedo );
-		A.worldScale = params->sigma_world * (float) A.step * pxDim;
-		hipLaunchKernelGGL( ptd::atrousGuidedPass, grid, block, 0, ctx->stream, A, (const float4*) in, out,
-			(const float4*) dPosition.p, (const float4*) dNormal.p, (const float4*) dAlbedo.p,
-			(const float4*) ( last ? dOriginal.p : nullptr ), (float*) ( last ? dVariance.p : nullptr ) );
-		std::swap( in, out );
-	}
-
+	float4* const outs[2] = { (float4*) D.pong.p, (float4*) D.ping.p };
+	const float4* result = guidedPasses( ctx, *params, w, h, pxDim, (const float4*) D.ping.p, outs, (const float4*) D.position.p, (const float4*) D.normal.p,
+		(const float4*) D.albedo.p, (const float4*) dOriginal.p, (float*) dVariance.p );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-
-	if( variance_out != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( variance_out, dVariance.p, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-	if( features != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( features, dPosition.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( features + 4 * pixels, dNormal.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( features + 8 * pixels, dAlbedo.p, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	return PBR_OK;
+	PBR_TRY( readBack( ctx, rgba, result, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, variance_out, dVariance.p, sizeof( float ) * pixels ) );
+	PBR_TRY( readFeatures( ctx, features, D, pixels ) );
+	return timedTail( ctx );
 }
 
 // pbr_denoise_temporal's history is dropped: the next call starts every pixel at L = 1.
@@ -2295,20 +2275,14 @@ int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face ) {
 	if( ctx->stream == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "context is not usable" );
 	}
-	if( !ctx->temporal.lastMotion || ctx->dTemporalFace == nullptr ) {
+	if( !ctx->temporal.lastMotion || ctx->planes.face == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_read_temporal_motion: the last successful pbr_denoise_temporal did not take the motion path (it needs pbr_temporal_track_motion, a history and a pbr_update_vertices since that history)" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const size_t pixels = (size_t) ctx->cfg.width * (size_t) ctx->cfg.height;
-
-	if( motion != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( motion, ctx->dTemporalMotion, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-	if( face != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( face, ctx->dTemporalFace, sizeof( int32_t ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-
+	PBR_TRY( readBack( ctx, motion, ctx->planes.motion, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, face, ctx->planes.face, sizeof( int32_t ) * pixels ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -2321,200 +2295,77 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	if( ctx == nullptr || ctx->stream == nullptr ) {
 		return PBR_EINVAL;
 	}
-	if( !ctx->hasScene || !ctx->configured ) {
-		return fail( ctx, PBR_ESTATE, "denoise_temporal before pbr_upload_scene / pbr_configure" );
-	}
-	if( cam == nullptr || temporal == nullptr || filter == nullptr || rgba == nullptr ) {
-		return fail( ctx, PBR_EINVAL, "denoise_temporal: null camera, parameters or destination" );
-	}
-	if( temporal->max_history < 1 || temporal->max_history > 1024 ) {
-		return fail( ctx, PBR_EINVAL, "denoise_temporal: max_history 1 .. 1024 (got %u)", temporal->max_history );
-	}
-	if( !( temporal->normal_cos >= -1.0f && temporal->normal_cos <= 1.0f ) ) {
-		return fail( ctx, PBR_EINVAL, "denoise_temporal: normal_cos must be in [-1, 1]" );
-	}
-	if( !( temporal->sigma_world >= 0.0f ) || !std::isfinite( temporal->sigma_world ) ) {
-		return fail( ctx, PBR_EINVAL, "denoise_temporal: sigma_world must be finite and >= 0 (0 switches the term off)" );
-	}
-	if( filter->passes < 1 || filter->passes > 8 ) {
-		return fail( ctx, PBR_EINVAL, "denoise_temporal: 1 .. 8 passes (got %u)", filter->passes );
-	}
 
-	const float sigmas[4] = { filter->sigma_luminance, filter->sigma_normal, filter->sigma_world, filter->sigma_albedo };
-
-	for( int k = 0; k < 4; k++ ) {
-		if( !( sigmas[k] >= 0.0f ) || !std::isfinite( sigmas[k] ) ) {
-			return fail( ctx, PBR_EINVAL, "denoise_temporal: the filter's standard deviations must be finite and >= 0 (0 switches a term off)" );
-		}
-	}
-
-	PBR_TRY( varianceUsable( ctx, "denoise_temporal" ) );
+	std::string why;
+	PBR_TRY( admit( ctx, "pbr_denoise_temporal", ptd::denoiseTemporalCheck( "pbr_denoise_temporal", cam, temporal, filter, rgba, &why ), why ) );
+	PBR_TRY( varianceUsable( ctx, "pbr_denoise_temporal" ) );
 
 	if( !ctx->temporalFresh ) {
-		return fail( ctx, PBR_ESTATE, "denoise_temporal has integrated this render already: it needs a new pbr_render_adaptive before every call" );
+		return fail( ctx, PBR_ESTATE, "pbr_denoise_temporal has integrated this render already: it needs a new pbr_render_adaptive before every call" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
 	const size_t pixels = (size_t) w * (size_t) h;
+	TemporalPlanes& T = ctx->planes;
+	// static geometry, or per-vertex motion in front of the integration (pt_temporal_host.hpp decides).  The planes come with
+	// the first call since pbr_configure, the motion path's with the first call that takes it; new planes are no history
+	const TemporalPolicy::Path path = ctx->temporal.path();
+	const bool motion = ( path == TemporalPolicy::MOTION ), first = ( T.variance == nullptr );
 
-	if( ctx->dTemporalVariance == nullptr ) {
-		// first use since pbr_configure: all or nothing is kept, dTemporalVariance last
-		auto plane = [ctx, pixels]( float4** dst ) {
-			HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( float4 ) * pixels ) );
-			return PBR_OK;
-		};
-		int status = PBR_OK;
-
-		for( int set = 0; set < 2 && status == PBR_OK; set++ ) {
-			for( float4** dst : { &ctx->dTemporalI[set], &ctx->dTemporalPosition[set], &ctx->dTemporalNormal[set], &ctx->dTemporalAlbedo[set] } ) {
-				if( status == PBR_OK && *dst == nullptr ) {
-					status = plane( dst );
-				}
-			}
-
-			if( status == PBR_OK && ctx->dTemporalLength[set] == nullptr && hipMalloc( (void**) &ctx->dTemporalLength[set], sizeof( unsigned ) * pixels ) != hipSuccess ) {
-				status = fail( ctx, PBR_EDEVICE, "denoise_temporal: no device memory for the history" );
-			}
-		}
-
-		for( float4** dst : { &ctx->dTemporalPing, &ctx->dTemporalPong, &ctx->dTemporalInfo } ) {
-			if( status == PBR_OK && *dst == nullptr ) {
-				status = plane( dst );
-			}
-		}
-
-		PBR_TRY( status );
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTemporalVariance, sizeof( float ) * pixels ) );
+	if( T.alloc( pixels, motion ) != hipSuccess ) {
+		return fail( ctx, PBR_EDEVICE, "pbr_denoise_temporal: no device memory for the history" );
+	}
+	if( first ) {
 		ctx->temporal.drop();
 	}
-
-	// static geometry, or per-vertex motion in front of the integration (pt_temporal_host.hpp decides)
-	const TemporalPolicy::Path path = ctx->temporal.path();
-
-	if( path == TemporalPolicy::MOTION && ctx->dTemporalFace == nullptr ) {
-		// first use of the motion path since pbr_configure: all or nothing is kept, dTemporalFace last
-		for( float4** dst : { &ctx->dTemporalMotion, &ctx->dTemporalReference } ) {
-			if( *dst == nullptr ) {
-				HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( float4 ) * pixels ) );
-			}
-		}
-
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTemporalFace, sizeof( int ) * pixels ) );
-	}
-	if( path == TemporalPolicy::MOTION && ( ctx->dHistVertices == nullptr || ctx->dFacesV == nullptr ) ) {
-		return fail( ctx, PBR_ESTATE, "denoise_temporal: the history's vertex positions are missing" );   // cannot happen: `moved` implies the copy
+	if( motion && ( ctx->dHistVertices == nullptr || ctx->dFacesV == nullptr ) ) {
+		return fail( ctx, PBR_ESTATE, "pbr_denoise_temporal: the history's vertex positions are missing" );   // cannot happen: `moved` implies the copy
 	}
 
-	const int prev = ctx->temporalSet, cur = 1 - prev;
-	float4* dI = ctx->dTemporalI[cur];
-	float4* dPosition = ctx->dTemporalPosition[cur];
-	float4* dNormal = ctx->dTemporalNormal[cur];
-	float4* dAlbedo = ctx->dTemporalAlbedo[cur];
+	const int prev = T.set, cur = 1 - prev;
+	float4* dI = T.integrated[cur];
+	const float4* dPosition = T.position[cur];
+	const float4* dNormal = T.normal[cur];
+	const float4* dAlbedo = T.albedo[cur];
 	float4* dOriginal = ctx->dRows;   // the staging of every read-back: free between calls
 
 	DevParams P;
 	PBR_TRY( sceneParams( ctx, &P ) );
-	setCamera( &P, cam, w, h, pxDim );
+	const ptd::TemporalArgs A = ptd::temporalArgs( *temporal, w, h, pxDim, ctx->temporal.history, ctx->temporalCam, ctx->temporalPxDim,
+		setCamera( &P, cam, w, h, pxDim ) );
 
-	ptd::TemporalArgs T;
-	T.width = w;
-	T.height = h;
-	T.hasHistory = ctx->temporal.history ? 1 : 0;
-	T.maxHistory = temporal->max_history;
-	T.normalCos = temporal->normal_cos;
-	T.worldTerm = ( temporal->sigma_world != 0.0f ) ? 1 : 0;
-	T.worldScale = temporal->sigma_world * pxDim;
-	const pbr_camera& old = ctx->temporalCam;
-	const float* oldBasis[4] = { &old.eye.x, &old.u.x, &old.v.x, &old.w.x };
-	float* oldDst[4] = { T.eye, T.cu, T.cv, T.cw };
-
-	for( int i = 0; i < 4; i++ ) {
-		for( int k = 0; k < 3; k++ ) {
-			oldDst[i][k] = oldBasis[i][k];
-		}
-	}
-
-	T.halfPx = ctx->temporalPxDim * 0.5f;
-
-	for( int k = 0; k < 3; k++ ) {
-		T.curCu[k] = P.cu[k];
-		T.curCv[k] = P.cv[k];
-		T.curCw[k] = P.cw[k];
-		T.curCamA[k] = P.camA[k];
-		T.curCvH[k] = P.cvH[k];
-	}
-
-	T.curHalfPx = P.halfPx;
-
-	const dim3 block( 64, 4 );
-	const dim3 grid( ( w + 63 ) / 64, ( h + 3 ) / 4 );
+	const dim3 grid = imageGrid( w, h );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, block, 0, ctx->stream, (const float4*) ctx->dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::pixelVariance, grid, block, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
 		ctx->varianceFirstCount, (const float4*) dOriginal, (float*) nullptr, dI, w, h, ctx->tilesX );
-	float4* const dInfo = ( history != nullptr ) ? ctx->dTemporalInfo : (float4*) nullptr;
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, T.position[cur], T.normal[cur], T.albedo[cur], motion ? T.face : (int*) nullptr );
 
-	if( path == TemporalPolicy::MOTION ) {
-		hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo, ctx->dTemporalFace );
-		hipLaunchKernelGGL( ptd::temporalMotion, grid, block, 0, ctx->stream, w, h, (const int*) ctx->dTemporalFace, (const float4*) dPosition, (const float4*) dNormal,
-			(const uint4*) ctx->dFacesV, (const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, ctx->dTemporalMotion, ctx->dTemporalReference );
-		hipLaunchKernelGGL( ptd::temporalIntegrate<true>, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
-			(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
-			(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur], dInfo,
-			(const float4*) ctx->dTemporalMotion, (const float4*) ctx->dTemporalReference );
-	}
-	else {
-		hipLaunchKernelGGL( ptd::firstHitFeatures, grid, block, 0, ctx->stream, P, dPosition, dNormal, dAlbedo, (int*) nullptr );
-		hipLaunchKernelGGL( ptd::temporalIntegrate<false>, grid, block, 0, ctx->stream, T, dI, (const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
-			(const float4*) ctx->dTemporalI[prev], (const float4*) ctx->dTemporalPosition[prev], (const float4*) ctx->dTemporalNormal[prev],
-			(const float4*) ctx->dTemporalAlbedo[prev], (const unsigned*) ctx->dTemporalLength[prev], ctx->dTemporalLength[cur], dInfo,
-			(const float4*) nullptr, (const float4*) nullptr );
+	if( motion ) {
+		hipLaunchKernelGGL( ptd::temporalMotion, grid, kImageBlock, 0, ctx->stream, w, h, (const int*) T.face, dPosition, dNormal,
+			(const uint4*) ctx->dFacesV, (const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, T.motion, T.reference );
 	}
 
+	const auto integrate = motion ? ptd::temporalIntegrate<true> : ptd::temporalIntegrate<false>;
+	hipLaunchKernelGGL( integrate, grid, kImageBlock, 0, ctx->stream, A, dI, dPosition, dNormal, dAlbedo,
+		(const float4*) T.integrated[prev], (const float4*) T.position[prev], (const float4*) T.normal[prev],
+		(const float4*) T.albedo[prev], (const unsigned*) T.length[prev], T.length[cur], ( history != nullptr ) ? T.info : (float4*) nullptr,
+		(const float4*) ( motion ? T.motion : nullptr ), (const float4*) ( motion ? T.reference : nullptr ) );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	auto inverseSquare = []( float sigma ) { return ( sigma > 0.0f ) ? 1.0f / ( sigma * sigma ) : 0.0f; };
-	const float4* in = dI;   // the first pass reads I and leaves it as it is: it is the next call's history
-	float4* out = ctx->dTemporalPing;
-
-	for( uint32_t pass = 0; pass < filter->passes; pass++ ) {
-		const bool last = ( pass + 1 == filter->passes );
-		ptd::GuidedArgs A;
-		A.width = w;
-		A.height = h;
-		A.step = 1 << pass;
-		A.sigmaLuminance = filter->sigma_luminance;
-		A.invNormal = inverseSquare( filter->sigma_normal );
-		A.invAlbedo = inverseSquare( filter->sigma_albedo );
-		A.worldScale = filter->sigma_world * (float) A.step * pxDim;
-		hipLaunchKernelGGL( ptd::atrousGuidedPass, grid, block, 0, ctx->stream, A, in, out,
-			(const float4*) dPosition, (const float4*) dNormal, (const float4*) dAlbedo,
-			(const float4*) ( last ? dOriginal : nullptr ), (float*) ( last ? ctx->dTemporalVariance : nullptr ) );
-		in = out;
-		out = ( out == ctx->dTemporalPing ) ? ctx->dTemporalPong : ctx->dTemporalPing;
-	}
-
+	// the first pass reads I and leaves it as it is: it is the next call's history
+	float4* const outs[2] = { T.ping, T.pong };
+	const float4* result = guidedPasses( ctx, *filter, w, h, pxDim, dI, outs, dPosition, dNormal, dAlbedo, dOriginal, T.variance );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( rgba, in, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-
-	if( variance_out != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( variance_out, ctx->dTemporalVariance, sizeof( float ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-	if( integrated != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( integrated, dI, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-	if( history != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( history, ctx->dTemporalInfo, sizeof( float4 ) * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
-	}
-
-	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
+	PBR_TRY( readBack( ctx, rgba, result, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, variance_out, T.variance, sizeof( float ) * pixels ) );
+	PBR_TRY( readBack( ctx, integrated, dI, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, history, T.info, sizeof( float4 ) * pixels ) );
+	PBR_TRY( timedTail( ctx ) );
 	// the set just written becomes the history, by pointer
-	ctx->temporalSet = cur;
+	T.set = cur;
 	ctx->temporal.succeeded( path );   // ... made under the current vertices
 	ctx->temporalFresh = false;
 	ctx->temporalCam = *cam;
@@ -2762,11 +2613,11 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 		*num_nodes_out = treeNodes;
 	}
 
-	float ms = 0.0f;
-	HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evStart, ctx->evStop ) );
-	ctx->lastKernelMs = (double) ms;
-	return PBR_OK;
+	return timedTail( ctx );   // the stream is idle by now
 }
+
+
+// ---- diagnostic entry points (include/pbr_hip_diag.h) -----------------------------------
 
 // The stage diagnostics in the native arithmetic (pt_diag_native.hip); null where that unit was not linked in (lab builds
 // without flavour 2).

@@ -21,18 +21,11 @@
 #pragma once
 
 #include "pt_kernel.hpp"
+#include "pt_denoise_host.hpp"   // DenoiseArgs, GuidedArgs, TemporalArgs: what the host fills, pass by pass
 
 namespace ptd {
 
 using namespace ptk;
-
-struct DenoiseArgs {
-	int width, height, step;
-	float invColor;     // 1 / sigma_color_k^2 of this pass, 0 = off
-	float invNormal;    // 1 / sigma_normal^2, 0 = off
-	float invAlbedo;    // 1 / sigma_albedo^2, 0 = off
-	float worldScale;   // sigma_world * step * pxDim: times the centre's distance = the standard deviation in world units; 0 = off
-};
 
 // the ray through the centre of pixel (px, py): initRay (pathtracing.cl:25-48) without the jitter and the lens
 PT_DEV Ray centreRay( const DevParams& P, int px, int py ) {

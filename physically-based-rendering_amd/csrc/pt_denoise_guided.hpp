@@ -32,14 +32,6 @@
 
 namespace ptd {
 
-struct GuidedArgs {
-	int width, height, step;
-	float sigmaLuminance;   // in standard deviations of the pixel's mean, 0 = off
-	float invNormal;        // as DenoiseArgs
-	float invAlbedo;
-	float worldScale;
-};
-
 __device__ __forceinline__ float luminance( float4 c ) {
 	return ( 0.2126f * c.x + 0.7152f * c.y ) + 0.0722f * c.z;
 }

@@ -52,23 +52,9 @@
 #pragma once
 
 #include "pt_denoise_guided.hpp"
+#include "pt_denoise_host.hpp"   // TemporalArgs
 
 namespace ptd {
-
-struct TemporalArgs {
-	int width, height;
-	int hasHistory;          // 0: the first call after a reset — no pixel has a candidate
-	unsigned maxHistory;
-	float normalCos;
-	int worldTerm;           // sigma_world != 0: the distance term is on
-	float worldScale;        // sigma_world * pxDim of this call
-	// the previous call's camera
-	float eye[3], cu[3], cv[3], cw[3];
-	float halfPx;
-	// this call's camera as setCamera lays it out (centreRay's terms), for the miss pixels
-	float curCu[3], curCv[3], curCw[3], curCamA[3], curCvH[3];
-	float curHalfPx;
-};
 
 __device__ __forceinline__ float dotPlain( f3 a, f3 b ) {
 	return ( a.x * b.x + a.y * b.y ) + a.z * b.z;

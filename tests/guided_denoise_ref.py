@@ -58,6 +58,17 @@ def local_variance(var):
         return np.where(den > 0, num / den, F(0.0)).astype(F)
 
 
+def inverse_square(sigma):
+    """1 / sigma^2 of a pass's arguments, 0 = the term is off."""
+    sigma = F(sigma)
+    return F(1.0) / (sigma * sigma) if sigma > 0 else F(0.0)
+
+
+def world_scale(sigma_world, step, px_dim):
+    """Times the centre's first-hit distance = the world term's standard deviation."""
+    return F(sigma_world) * F(step) * F(px_dim)
+
+
 def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigma_world, sigma_albedo, px_dim, exp64=False):
     """One pass: colour (H, W, 3+), var (H, W) -> (colour' (H, W, 3), var' (H, W))."""
     position, normal, albedo = features
@@ -65,18 +76,13 @@ def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigm
     h, w = var.shape
     hit = normal[..., 3] != 0
 
-    def inverse_square(sigma):
-        sigma = F(sigma)
-        return F(1.0) / (sigma * sigma) if sigma > 0 else F(0.0)
-
     def sqdist(a, b):
         d = a[..., :3] - b[..., :3]
         return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
 
     inv_normal, inv_albedo = inverse_square(sigma_normal), inverse_square(sigma_albedo)
-    world_scale = F(sigma_world) * F(step) * F(px_dim)
     with np.errstate(all="ignore"):
-        s_world = world_scale * position[..., 3]
+        s_world = world_scale(sigma_world, step, px_dim) * position[..., 3]
         inv_world = np.where(hit & (s_world > 0), F(1.0) / (s_world * s_world), F(0.0)).astype(F)
         scale = F(sigma_luminance) * np.sqrt(local_variance(var)) + F(1e-6)
         y0 = adaptive_ref.luminance(colour)

@@ -1,10 +1,12 @@
 // What csrc/pt_temporal.hpp needs from HIP and from the headers it includes, for a HOST build of its two kernels
 // (tests/test_temporal_kernel_host_cpu.py puts this file, the header's namespace ptd and temporal_kernel_shim_tail.inc into one
 // translation unit): one "thread" at a time, blockDim = (1, 1), blockIdx = the pixel.  The arithmetic helpers are the ones of
-// pt_math.hpp / pt_denoise.hpp / pt_denoise_guided.hpp, operation by operation.
+// pt_math.hpp / pt_denoise.hpp / pt_denoise_guided.hpp, operation by operation.  ptd::TemporalArgs is the product's own
+// (csrc/pt_denoise_host.hpp builds without HIP).
 #include <cmath>
 #include <cstddef>
 #include <limits>
+#include "pt_denoise_host.hpp"
 #define __global__
 #define __device__
 #define __forceinline__ inline

@@ -167,6 +167,28 @@ def test_filter_stage_matches_the_numpy_restatement(pbr, device, passes):
     assert s.var_out[finite].mean() < s.integrated[..., 3][finite].mean()
 
 
+def test_without_a_history_the_filter_stage_is_the_guided_filter_s_bit_for_bit(pbr, device):
+    """Without a history `integrated` is the guided filter's working plane — {image rgb, variance} (temporal_ref.integrate, prev is
+    None) — and both filters run the same passes on the same inputs: same colour, same filtered variance.  One, two and three
+    passes end in each of the two output planes."""
+    sc, cfg, px = cornell(pbr, device, 1, 72, 40)
+    cam = view(pbr, sc)
+    image = var = None
+    for passes in (1, 2, 3):
+        render(pbr, device, px, cam, 0, 4)                                    # a temporal call consumes its render: the same one again
+        if image is None:
+            image, var = device.read_output(), device.read_variance()
+        assert same_values(device.read_output(), image) and same_values(device.read_variance(), var)
+        filt = pbr.GuidedDenoiseParams(passes=passes)
+        guided, guided_var = device.denoise_guided(px, cam, filt, variance=True)
+        device.temporal_reset()
+        rgba, var_out, integrated = device.denoise_temporal(px, cam, None, filt, variance=True, integrated=True)
+        assert same_values(rgba, guided), "%d passes, rgba: " % passes + describe_mismatch(rgba, guided)
+        assert same_values(var_out, guided_var), "%d passes, variance: " % passes + describe_mismatch(var_out, guided_var)
+        assert same_values(integrated[..., :3], image[..., :3]) and same_values(integrated[..., 3], var)
+        assert np.nanmax(np.abs(rgba[..., :3] - image[..., :3])) > 1e-3      # ... and the passes did something
+
+
 # ---- 3: disocclusion -------------------------------------------------------------------------------------------------
 
 DISOCCLUDE = dict(right=0.6)

@@ -42,7 +42,8 @@ def kernels(tmp_path_factory):
     source, path = str(where / "kernels.cpp"), str(where / "libtemporalkernels.so")
     with open(source, "w") as f:
         f.write("\n".join(parts))
-    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", source, "-o", path], check=True)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.dirname(HEADER), source, "-o", path], check=True)
     return ctypes.CDLL(path)
 
 
