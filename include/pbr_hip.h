@@ -33,10 +33,11 @@ extern "C" {
 /* The layout of this header's structs and the meaning of its calls, as a number: bumped whenever a struct grows or an
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
- * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion).  A caller that loads the library at run time — or
+ * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
+ * version 13 pbr_refit_ordered_walk).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 12
+#define PBR_ABI_VERSION 13
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -192,11 +193,38 @@ int pbr_validate_scene( const pbr_scene_desc* scene, char* message, size_t capac
  *               the upload, the reason is in the message); a ray-ordered traversal (traversal != 0) is configured (its streams
  *               carry child orders built from the old box centres: configure traversal 0, update, configure the ordered walk
  *               again — it is then built from the refitted boxes, bit-identical to a fresh upload of S' + the same
- *               pbr_configure); phong_tessellation > 0 is configured.
+ *               pbr_configure) unless pbr_refit_ordered_walk is on, see below; phong_tessellation > 0 is configured.
  *   PBR_EINVAL  a null pointer, num_vertices other than the upload's, a coordinate that is not finite (checked on the host).
  * After an update pbr_configure refuses phong_tessellation > 0 (PBR_ESTATE) until the next pbr_upload_scene: tight boxes
  * would clip the patches, and the patches' corners are not updated. */
 int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices );
+/* A REFIT UNDER A RAY-ORDERED WALK (ABI version 13).  pbr_refit_ordered_walk( ctx, 1 ) makes pbr_update_vertices succeed while
+ * traversal 1, 2 or 3 is configured: behind the refit above it rebuilds, on the device and in place, the records of the
+ * configured layout — every record's box, every container's hit word(s) and the axis bit of the compact record, every `next`
+ * word of every order, the place of every cold record in its order's depth-first sequence, and the 32-byte header of eight
+ * first references.  The flag is per context, 0 after pbr_create, needs no scene and survives pbr_configure and
+ * pbr_upload_scene; PBR_EINVAL for a null context, PBR_ESTATE for an unusable one.  With the flag off nothing changes (the
+ * refusal above, bit for bit); with it on and traversal 0 configured the call is the one above.  Every other refusal stays, in
+ * the same order, and leaves the context and the streams as they were.
+ * THE CONTRACT.  After pbr_upload_scene( S ), pbr_configure( t ) and pbr_update_vertices( V' ) with the flag on, the
+ * configured layout's device buffer is BYTE FOR BYTE the one the three-call sequence leaves — pbr_configure( traversal 0 ),
+ * pbr_update_vertices( V' ), pbr_configure( t ) — on a context that uploaded the same S: the records of the tree with the
+ * refitted boxes pbr_read_bvh returns under the hot-node ranking OF THE UPLOAD (the ranking stays stale, as it does for the
+ * reference-order stream: it is only speed), the number of staged records and the header with them.  Hence every call
+ * (pbr_render*, pbr_render_frame, pbr_diag_trace, the counters, the debug image, pbr_denoise*) gives bit for bit what it gives
+ * after a fresh upload of S' and the same pbr_configure.  pbr_diag_read_walk (pbr_hip_diag.h) reads the buffer back.
+ * The orders, operation by operation: a child's key on an axis is bbMin + bbMax of that axis, one binary32 addition of the
+ * refitted box words; schemes 2 and 3 sort a container's children on its own axis, the first of x, y, z whose hi - lo of the
+ * children's keys (lo = ( k < lo ) ? k : lo, hi = ( k > hi ) ? k : hi, from +inf / -inf) is strictly greater than the widest
+ * so far, starting from -1; scheme 1's order k sorts on axis k / 2.  The sort is an insertion sort of the depth-first child list
+ * with strict compares: equal keys keep depth-first order ascending AND descending.
+ * No node, box or record travels to the host (the 32 bytes of the header do: the context keeps the first references), and
+ * nothing is allocated or freed per call: the working tables — some 90 bytes per node for layouts 1 and 2, 60 for layout 3
+ * (pbr_diag_relink_info) — are allocated by the FIRST such update after the layout's records were built, and freed with them (another
+ * layout configured, pbr_configure( traversal 0 ) followed by an update, a new upload).  pbr_last_kernel_ms includes the
+ * re-link's kernels; pbr_diag_relink_info reports their share.  Configuring another ordered layout afterwards builds its
+ * records on the host from the refitted tree, as before. */
+int pbr_refit_ordered_walk( pbr_ctx* ctx, int on );
 /* The current tree in the wire format: the uploaded nodes, after pbr_update_vertices with the refitted boxes (copied back
  * from the device by this call, not by the update).  *num_nodes = the node count; nodes_out = NULL returns the count only,
  * else capacity >= *num_nodes entries.  A caller's rebuild heuristic (e.g. the growth of the boxes' surface area) reads this. */
@@ -451,7 +479,8 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam,
  * an unusable context and PBR_EINVAL for a null one.  The two float4 planes and the face plane (36 bytes per pixel) are
  * allocated by the first call that takes the motion path and freed with the history; nothing is allocated per call.
  * NOT COVERED: tile-sharded contexts (pbr_denoise_temporal refuses them), changes of topology (pbr_update_vertices takes
- * positions only), Phong tessellation and ray-ordered traversals (pbr_update_vertices refuses both, unchanged), and lights:
+ * positions only), Phong tessellation (pbr_update_vertices refuses it, unchanged; ray-ordered traversals are covered once
+ * pbr_refit_ordered_walk is on — the motion path reads faces and vertices, never a node record), and lights:
  * a light that moves or changes changes the shading, which no test of step 2 sees — call pbr_temporal_reset. */
 int pbr_temporal_track_motion( pbr_ctx* ctx, int on );
 int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face );

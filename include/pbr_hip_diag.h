@@ -121,6 +121,18 @@ int pbr_diag_scene_bytes( pbr_ctx* ctx, uint64_t out[3] );
  * the device (pbr_last_kernel_ms excludes it).  upload_ms and why may be NULL. */
 int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char* why, size_t capacity );
 
+/* The configured ray-ordered layout's device buffer as it is now, header included (pbr_refit_ordered_walk's contract is stated
+ * on these bytes): *bytes = its size, first[8] = the context's eight first references, *hot_slots = the 32-byte slots at the head
+ * of the records that are ranked for LDS staging (first and hot_slots may be NULL).  out = NULL returns these only, else
+ * capacity >= *bytes.  PBR_ESTATE when no ordered stream is built, PBR_EINVAL for a null context, null bytes or too little room. */
+int pbr_diag_read_walk( pbr_ctx* ctx, void* out, uint64_t capacity, uint64_t* bytes, int first[8], uint32_t* hot_slots );
+
+/* The re-link of pbr_update_vertices (pbr_refit_ordered_walk; csrc/pt_relink_host.hpp): out[0] the device bytes of its tables as
+ * they are held now (0: none), [1] the top-down levels of the tree they were built for, [2] the kernel launches of the last
+ * update's re-link, [3] 1 if the last pbr_update_vertices re-linked, else 0.  *ms (may be NULL): the device time of those
+ * launches alone; pbr_last_kernel_ms includes it. */
+int pbr_diag_relink_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
+
 /* The kernel behind pbr_diag_last_plan's schedule, as a profiler prints its symbol (without "void " and the argument
  * list): "ptk_f0::pathTracingDual<1, false, false>" — namespace ptk_f<flavour> (bit 0: ray-ordered walk, bit 1: native
  * arithmetic; csrc/pt_flavour.hpp), template arguments BRDF, SHADOW_RAYS, LIGHTS[, waves per SIMD[, PHONGTESS]]. */

@@ -45,6 +45,9 @@ int pbr_multi_upload_scene( pbr_multi* m, const pbr_scene_desc* scene );
 /* pbr_update_vertices on every context, concurrently: every context refits its own copy of the scene, no collective.  A
  * refusal (pbr_hip.h) is the same on every rank and leaves all of them unchanged. */
 int pbr_multi_update_vertices( pbr_multi* m, const pbr_float4* vertices, uint32_t num_vertices );
+/* pbr_refit_ordered_walk on every context: while on, pbr_multi_update_vertices works under a ray-ordered traversal, every
+ * context re-linking its own copy of the configured layout's records (pbr_hip.h). */
+int pbr_multi_refit_ordered_walk( pbr_multi* m, int on );
 /* pbr_configure on every context with tile_world = count, tile_rank = its rank (the caller's values are ignored);
  * allocates the exchange buffers. */
 int pbr_multi_configure( pbr_multi* m, const pbr_config* cfg );

@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 12
+ABI_VERSION = 13
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -197,6 +197,9 @@ for _name, _args in (
                                   _fp, _fp, _fp, _fp]),
         ("pbr_temporal_track_motion", [_vp, ctypes.c_int]),                                                              # ABI version 12
         ("pbr_read_temporal_motion", [_vp, _fp, ctypes.POINTER(ctypes.c_int32)]),
+        ("pbr_refit_ordered_walk", [_vp, ctypes.c_int]),                                                                 # ABI version 13
+        ("pbr_diag_read_walk", [_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int), _up]),
+        ("pbr_diag_relink_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -234,6 +237,8 @@ if hasattr(host, "pbrh_pt_generate_images_adaptive"):
     host.pbrh_pt_generate_images_adaptive.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, _fp]
 if hasattr(host, "pbrh_pt_update_vertices"):
     host.pbrh_pt_update_vertices.argtypes = [_vp, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_refit_ordered_walk"):
+    host.pbrh_pt_refit_ordered_walk.argtypes = [_vp, ctypes.c_int]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -437,6 +442,25 @@ class Device:
         bit for bit what it gives after a fresh upload of the scene with these vertices and the nodes read_bvh() returns."""
         vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
         self._check(hip.pbr_update_vertices(self._ctx, vertices.ctypes.data, vertices.shape[0]))
+
+    def refit_ordered_walk(self, on):
+        """pbr_refit_ordered_walk: while on, update_vertices works under a ray-ordered traversal — the configured layout's records
+        are rebuilt on the device, byte for byte what configure( traversal 0 ), update, configure( ordered ) leaves."""
+        self._check(hip.pbr_refit_ordered_walk(self._ctx, 1 if on else 0))
+
+    def read_walk(self):
+        """pbr_diag_read_walk: (the configured ordered layout's device buffer as uint8, header included; first[8]; hot slots)."""
+        size, first, hot = ctypes.c_uint64(), (ctypes.c_int * 8)(), ctypes.c_uint32()
+        self._check(hip.pbr_diag_read_walk(self._ctx, None, 0, ctypes.byref(size), first, ctypes.byref(hot)))
+        data = np.empty(size.value, np.uint8)
+        self._check(hip.pbr_diag_read_walk(self._ctx, data.ctypes.data, size.value, ctypes.byref(size), first, ctypes.byref(hot)))
+        return data, [int(v) for v in first], int(hot.value)
+
+    def relink_info(self):
+        """pbr_diag_relink_info: the re-link's table bytes, levels, the last update's launches and whether it re-linked, its ms."""
+        out, ms = (ctypes.c_uint64 * 4)(), ctypes.c_double()
+        self._check(hip.pbr_diag_relink_info(self._ctx, out, ctypes.byref(ms)))
+        return {"table_bytes": int(out[0]), "levels": int(out[1]), "launches": int(out[2]), "relinked": bool(out[3]), "ms": float(ms.value)}
 
     def read_bvh(self):
         """pbr_read_bvh: the current tree, (nodes, 8) float32 in the wire format — the uploaded nodes, after update_vertices
@@ -885,6 +909,11 @@ class PathTracer:
         """PathTracer::updateVertices: Device.update_vertices on the tracer's context; starts a new accumulation."""
         vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
         if host.pbrh_pt_update_vertices(self._h, _as_fp(vertices), vertices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def refitOrderedWalk(self, on):
+        """PathTracer::refitOrderedWalk: Device.refit_ordered_walk on the tracer's context."""
+        if host.pbrh_pt_refit_ordered_walk(self._h, 1 if on else 0) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def setFocus(self, x, y):

@@ -32,6 +32,7 @@
 #include "pt_adaptive_host.hpp"
 #include "pt_refit_host.hpp"
 #include "pt_refit.hpp"
+#include "pt_relink.hpp"
 
 using ptk::DevParams;
 
@@ -176,6 +177,21 @@ struct pbr_ctx {
 	uint32_t refitUpdates = 0;     // pbr_update_vertices calls since the upload: > 0 = the boxes are refitted ones, dTriPN is stale
 	bool treeStale = false;        // tree.bvh's boxes are older than the device's (refreshTree)
 	double lastRefitUploadMs = 0.0;
+	// pbr_refit_ordered_walk (pt_relink_host.hpp, pt_relink.hpp): while it is on, pbr_update_vertices under a ray-ordered traversal
+	// rebuilds dNodesWalk's records on the device.  dRelink: one allocation with the static and the working tables of the layout
+	// dNodesWalk holds, made by the first such update and freed with the streams (freeWalkStreams); relinkView points into it
+	bool refitOrdered = false;     // the flag: survives pbr_configure and pbr_upload_scene
+	void* dRelink = nullptr;
+	uint64_t relinkBytes = 0;
+	RelinkView relinkView = {};
+	unsigned* dRelinkLevelNodes = nullptr;   // inside dRelink
+	unsigned* dRelinkLevelFirst = nullptr;
+	std::vector<RelinkRun> relinkRuns;
+	uint32_t relinkLevels = 0, relinkContainers = 0;
+	hipEvent_t evRelinkStart = nullptr, evRelinkStop = nullptr;
+	double lastRelinkMs = 0.0;     // of the last pbr_update_vertices: device time of the re-link kernels alone,
+	uint32_t lastRelinkLaunches = 0;   // their number,
+	bool lastRelinked = false;     // and whether it re-linked at all
 
 	// configuration + images
 	bool configured = false;
@@ -302,6 +318,10 @@ void freeWalkStreams( pbr_ctx* ctx ) {
 	ctx->dNodesWalk = nullptr;
 	ctx->walkBuilt = 0;
 	ctx->walkBytes = 0;
+	(void) hipFree( ctx->dRelink );   // the re-link's tables are a layout's: they go with its records
+	ctx->dRelink = nullptr;
+	ctx->relinkBytes = 0;
+	ctx->relinkRuns.clear();
 }
 
 void freeScene( pbr_ctx* ctx ) {
@@ -1407,6 +1427,8 @@ int pbr_create( int device, pbr_ctx** out ) {
 	HIP_TRY( ctx, hipEventCreate( &ctx->evChainStart ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStart ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStop ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStart ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStop ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChainCarry, sizeof( float ) ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCounters, sizeof( unsigned long long ) * kCounterSlots ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dWork, kWorkBytes ) );
@@ -1440,6 +1462,8 @@ void pbr_destroy( pbr_ctx* ctx ) {
 		(void) hipEventDestroy( ctx->evChainStart );
 		(void) hipEventDestroy( ctx->evFoldStart );
 		(void) hipEventDestroy( ctx->evFoldStop );
+		(void) hipEventDestroy( ctx->evRelinkStart );
+		(void) hipEventDestroy( ctx->evRelinkStop );
 		(void) hipFree( ctx->dChainCarry );
 		(void) hipStreamDestroy( ctx->stream );
 	}
@@ -1566,6 +1590,125 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	return walk.storage.empty() ? PBR_OK : uploadWalkStreams( ctx, walk, ctx->cfg.traversal );
 }
 
+namespace {
+
+// The re-link's tables for the layout dNodesWalk holds (pt_relink_host.hpp, relinkTables): built from the host copy of the tree —
+// its shape and the ranking of the upload; the boxes are not read — on the first re-linked update after the streams were built,
+// kept until the streams go.  Nothing of the context changes when this fails.
+int ensureRelinkTables( pbr_ctx* ctx ) {
+	if( ctx->dRelink != nullptr ) {
+		return PBR_OK;
+	}
+
+	RefitPlan shape;
+	RelinkTables t;
+	refitNesting( ctx->tree, &shape );
+	PBR_TRY( relinkTables( ctx->tree, shape, ctx->walkBuilt, &t, &ctx->error ) );
+
+	if( sizeof( Quad ) * t.storageQuads != ctx->walkBytes ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the re-link expects %zu bytes of records, the streams hold %llu", sizeof( Quad ) * t.storageQuads, (unsigned long long) ctx->walkBytes );
+	}
+
+	// one allocation, every table on a 256-byte boundary
+	size_t bytes = 0;
+	auto place = [&bytes]( size_t size ) {
+		const size_t at = bytes;
+		bytes += ( size + 255 ) & ~(size_t) 255;
+		return at;
+	};
+	const size_t N = t.N;
+	const size_t atRank = place( sizeof( uint32_t ) * N ), atCold = place( sizeof( uint32_t ) * ( N + 1 ) ), atBase = place( sizeof( uint32_t ) * N );
+	const size_t atNodes = place( sizeof( uint32_t ) * t.levelNodes.size() ), atFirst = place( sizeof( uint32_t ) * t.levelFirst.size() );
+	const size_t atAxis = place( N ), atPerm = place( sizeof( uint32_t ) * t.permEntries() );
+	const size_t atNext = place( sizeof( int ) * t.nextEntries() ), atPos = place( sizeof( uint32_t ) * t.posEntries() );
+
+	char* slab = nullptr;
+	HIP_TRY( ctx, hipMalloc( (void**) &slab, bytes ) );
+	hipError_t err = hipMemset( slab, 0, bytes );
+	auto put = [&]( size_t at, const std::vector<uint32_t>& src ) {
+		err = ( err != hipSuccess ) ? err : hipMemcpy( slab + at, src.data(), sizeof( uint32_t ) * src.size(), hipMemcpyHostToDevice );
+	};
+	put( atRank, t.rankOf );
+	put( atCold, t.coldBefore );
+	put( atBase, t.childBase );
+	put( atNodes, t.levelNodes );
+	put( atFirst, t.levelFirst );
+	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();   // the memset ran on the null stream; launches use ctx->stream
+
+	if( err != hipSuccess ) {
+		(void) hipFree( slab );
+		return fail( ctx, PBR_EDEVICE, "pbr_update_vertices: the re-link's tables: %s", hipGetErrorString( err ) );
+	}
+
+	RelinkView& v = ctx->relinkView;
+	v.N = t.N;
+	v.scheme = t.scheme;
+	v.compact = t.compact;
+	v.K = t.K;
+	v.V = t.V;
+	v.streams = t.streams;
+	v.hotPerStream = t.hotPerStream;
+	v.rankOf = (const uint32_t*) ( slab + atRank );
+	v.coldBefore = (const uint32_t*) ( slab + atCold );
+	v.childBase = (const uint32_t*) ( slab + atBase );
+	v.axis = (unsigned char*) ( slab + atAxis );
+	v.perm = (uint32_t*) ( slab + atPerm );
+	v.next = (int*) ( slab + atNext );
+	v.pos = (uint32_t*) ( slab + atPos );
+	ctx->dRelinkLevelNodes = (unsigned*) ( slab + atNodes );
+	ctx->dRelinkLevelFirst = (unsigned*) ( slab + atFirst );
+	ctx->relinkRuns = t.runs;
+	ctx->relinkLevels = t.numLevels();
+	ctx->relinkContainers = (uint32_t) t.levelNodes.size();
+	ctx->relinkBytes = bytes;
+	ctx->dRelink = slab;
+	return PBR_OK;
+}
+
+// The re-link's launches on the context's stream, behind the refit's: sort, the levels top-down, the records.
+int launchRelink( pbr_ctx* ctx ) {
+	RelinkView v = ctx->relinkView;
+	v.refNodes = (const RelinkQuad*) ctx->dNodes;
+	v.refRecordOf = ctx->dRefitRecordOf;
+	v.info = ctx->dRefitInfo;
+	v.header = (int*) ctx->dNodesWalk;
+	v.records = (RelinkQuad*) ( ctx->dNodesWalk + 2 );
+	uint32_t launches = 0;
+	HIP_TRY( ctx, hipEventRecord( ctx->evRelinkStart, ctx->stream ) );
+	hipLaunchKernelGGL( ptl::relinkSortKernel, dim3( ( ctx->relinkContainers + RELINK_THREADS - 1 ) / RELINK_THREADS ), dim3( RELINK_THREADS ), 0, ctx->stream,
+	                    v, ctx->dRelinkLevelNodes, ctx->relinkContainers );
+	HIP_TRY( ctx, hipGetLastError() );
+	launches++;
+
+	for( const RelinkRun& run : ctx->relinkRuns ) {
+		hipLaunchKernelGGL( ptl::relinkLevelsKernel, dim3( run.blocks ), dim3( run.threads ), 0, ctx->stream,
+		                    v, ctx->dRelinkLevelNodes, ctx->dRelinkLevelFirst, run.firstLevel, run.numLevels );
+		HIP_TRY( ctx, hipGetLastError() );
+		launches++;
+	}
+
+	hipLaunchKernelGGL( ptl::relinkRecordsKernel, dim3( ( v.N - 1 + RELINK_THREADS - 1 ) / RELINK_THREADS, v.streams ), dim3( RELINK_THREADS ), 0, ctx->stream, v );
+	HIP_TRY( ctx, hipGetLastError() );
+	launches++;
+	HIP_TRY( ctx, hipEventRecord( ctx->evRelinkStop, ctx->stream ) );
+	ctx->lastRelinkLaunches = launches;
+	return PBR_OK;
+}
+
+}  // namespace
+
+int pbr_refit_ordered_walk( pbr_ctx* ctx, int on ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	ctx->refitOrdered = ( on != 0 );
+	return PBR_OK;
+}
+
 int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices ) {
 	if( ctx == nullptr || ctx->stream == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "context is not usable" );
@@ -1579,7 +1722,9 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	if( !ctx->refit.nested ) {
 		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", ctx->refit.why.c_str() );
 	}
-	if( ctx->configured && ctx->cfg.traversal != 0 ) {
+	const bool ordered = ( ctx->configured && ctx->cfg.traversal != 0 );
+
+	if( ordered && !ctx->refitOrdered ) {
 		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while a ray-ordered traversal (%u) is configured: its streams carry child orders built from the old boxes — configure traversal 0, update, then configure the ordered walk again", ctx->cfg.traversal );
 	}
 	if( ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) {
@@ -1587,6 +1732,14 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	// pbr_refit_ordered_walk: the configured layout's records are re-linked in place behind the refit.  Its tables first: a call
+	// that cannot have them changes nothing
+	const bool relinks = ( ordered && ctx->dNodesWalk != nullptr && ctx->walkBuilt == ctx->cfg.traversal );
+
+	if( relinks ) {
+		PBR_TRY( ensureRelinkTables( ctx ) );
+	}
 
 	// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
 	// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below does
@@ -1630,12 +1783,32 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
+	ctx->lastRelinked = false;
+	ctx->lastRelinkMs = 0.0;
+	ctx->lastRelinkLaunches = 0;
+
+	if( relinks ) {
+		PBR_TRY( launchRelink( ctx ) );
+	}
+
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	PBR_TRY( timedTail( ctx ) );
 	ctx->treeStale = true;
 	ctx->refitUpdates++;
+
+	if( relinks ) {
+		// the eight first references are the context's too (applyWalk): 32 bytes of header, no node, box or record
+		float ms = 0.0f;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evRelinkStart, ctx->evRelinkStop ) );
+		HIP_TRY( ctx, hipMemcpy( ctx->walkFirst, ctx->dNodesWalk, sizeof( ctx->walkFirst ), hipMemcpyDeviceToHost ) );
+		ctx->lastRelinkMs = (double) ms;
+		ctx->lastRelinked = true;
+		return PBR_OK;
+	}
+
 	freeWalkStreams( ctx );   // none while traversal 0 is configured; an unconfigured context may hold a previous mode's
-	return PBR_OK;
+	// the flag is on but the configured layout's records are not there to re-link: they are built on the host, as pbr_configure does
+	return ordered ? buildWalkStreams( ctx, ctx->cfg.traversal ) : PBR_OK;
 }
 
 int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint32_t* num_nodes ) {
@@ -3024,6 +3197,55 @@ int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char*
 	}
 	if( why != nullptr && capacity > 0 ) {
 		std::snprintf( why, capacity, "%s", ctx->refit.why.c_str() );
+	}
+
+	return PBR_OK;
+}
+
+int pbr_diag_read_walk( pbr_ctx* ctx, void* out, uint64_t capacity, uint64_t* bytes, int first[8], uint32_t* hot_slots ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( !ctx->hasScene || ctx->dNodesWalk == nullptr || ctx->walkBuilt == 0 ) {
+		return fail( ctx, PBR_ESTATE, "diag_read_walk: no ray-ordered stream is built" );
+	}
+	if( bytes == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_read_walk: null bytes" );
+	}
+
+	*bytes = ctx->walkBytes;
+
+	if( first != nullptr ) {
+		std::memcpy( first, ctx->walkFirst, sizeof( ctx->walkFirst ) );
+	}
+	if( hot_slots != nullptr ) {
+		*hot_slots = ctx->walkHotAvail;
+	}
+	if( out == nullptr ) {
+		return PBR_OK;
+	}
+	if( capacity < ctx->walkBytes ) {
+		return fail( ctx, PBR_EINVAL, "diag_read_walk: room for %llu bytes, the streams hold %llu", (unsigned long long) capacity, (unsigned long long) ctx->walkBytes );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpy( out, ctx->dNodesWalk, ctx->walkBytes, hipMemcpyDeviceToHost ) );
+	return PBR_OK;
+}
+
+int pbr_diag_relink_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
+	if( ctx == nullptr || out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_relink_info: null argument" );
+	}
+
+	out[0] = ctx->relinkBytes;
+	out[1] = ( ctx->dRelink != nullptr ) ? ctx->relinkLevels : 0;
+	out[2] = ctx->lastRelinkLaunches;
+	out[3] = ctx->lastRelinked ? 1 : 0;
+
+	if( ms != nullptr ) {
+		*ms = ctx->lastRelinkMs;
 	}
 
 	return PBR_OK;

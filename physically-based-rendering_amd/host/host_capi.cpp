@@ -283,6 +283,19 @@ int pbrh_pt_update_vertices( void* tracer, const float* vertices, uint32_t num_v
 	}
 }
 
+int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.refitOrderedWalk( on != 0 );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 void pbrh_pt_set_focus( void* tracer, int x, int y ) {
 	static_cast<HostTracer*>( tracer )->pt.setFocus( x, y );
 }

@@ -250,6 +250,11 @@ int MultiPathTracer::updateVertices( const pbr_float4* vertices, uint32_t numVer
 	return onEveryRank( [&]( int r ) { return pbr_update_vertices( mRanks[(size_t) r].ctx, vertices, numVertices ); } );
 }
 
+// a flag of every context: the next updateVertices re-links the ordered walk's records on every rank
+int MultiPathTracer::refitOrderedWalk( int on ) {
+	return onEveryRank( [&]( int r ) { return pbr_refit_ordered_walk( mRanks[(size_t) r].ctx, on ); } );
+}
+
 int MultiPathTracer::configure( const pbr_config* cfg ) {
 	if( cfg == nullptr ) {
 		mError = "pbr_multi_configure: null config";
@@ -665,6 +670,10 @@ int pbr_multi_upload_scene( pbr_multi* m, const pbr_scene_desc* scene ) {
 
 int pbr_multi_update_vertices( pbr_multi* m, const pbr_float4* vertices, uint32_t num_vertices ) {
 	return ( m == nullptr ) ? PBR_EINVAL : done( m, m->impl->updateVertices( vertices, num_vertices ) );
+}
+
+int pbr_multi_refit_ordered_walk( pbr_multi* m, int on ) {
+	return ( m == nullptr ) ? PBR_EINVAL : done( m, m->impl->refitOrderedWalk( on ) );
 }
 
 int pbr_multi_configure( pbr_multi* m, const pbr_config* cfg ) {

@@ -70,6 +70,7 @@ class MultiPathTracer {
 
 		int uploadScene( const pbr_scene_desc* scene );
 		int updateVertices( const pbr_float4* vertices, uint32_t numVertices );
+		int refitOrderedWalk( int on );
 		int configure( const pbr_config* cfg );
 		int resetAccum();
 		int tune( uint32_t framesPerCall, float pxDim, const pbr_camera* cam, int* plan, int* votes );

@@ -442,6 +442,14 @@ void PathTracer::updateVertices( const pbr_float4* vertices, uint32_t numVertice
 	this->resetSampleCount();
 }
 
+void PathTracer::refitOrderedWalk( bool on ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_refit_ordered_walk( mCtx, on ? 1 : 0 ), "pbr_refit_ordered_walk" );
+}
+
 std::vector<float> PathTracer::generateImagesAdaptive( uint32_t minFrames, uint32_t roundFrames, uint32_t maxFrames, float threshold ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] generateImagesAdaptive before initOpenCLBuffers" );

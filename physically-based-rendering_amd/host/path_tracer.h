@@ -83,6 +83,8 @@ class PathTracer {
 		// pbr_update_vertices: new positions for the scene's vertices (count as uploaded), the BVH refitted on the device; starts
 		// a new accumulation.  The host copy of the scene (buffers()) keeps the uploaded vertices and boxes.
 		void updateVertices( const pbr_float4* vertices, uint32_t numVertices );
+		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
+		void refitOrderedWalk( bool on );
 
 		void resetSampleCount();
 		void setCamera( Camera* camera ) { mCamera = camera; }

@@ -30,6 +30,7 @@ def lib():
         l.pbr_multi_upload_scene.argtypes = [vp, ctypes.POINTER(SceneDesc)]
         l.pbr_multi_configure.argtypes = [vp, ctypes.POINTER(Config)]
         l.pbr_multi_update_vertices.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint32]
+        l.pbr_multi_refit_ordered_walk.argtypes = [vp, ctypes.c_int]
         l.pbr_multi_reset_accum.argtypes = [vp]
         l.pbr_multi_tune.argtypes = [vp, ctypes.c_uint32, ctypes.c_float, ctypes.POINTER(Camera), ip, ip]
         l.pbr_multi_render.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, fp, ctypes.c_float, ctypes.POINTER(Camera), ctypes.c_int]
@@ -84,6 +85,10 @@ class MultiDevice:
         """pbr_multi_update_vertices: Device.update_vertices on every context, concurrently."""
         vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
         self._check(lib().pbr_multi_update_vertices(self._m, vertices.ctypes.data, vertices.shape[0]))
+
+    def refit_ordered_walk(self, on):
+        """pbr_multi_refit_ordered_walk: Device.refit_ordered_walk on every context."""
+        self._check(lib().pbr_multi_refit_ordered_walk(self._m, 1 if on else 0))
 
     def configure(self, cfg):
         self._check(lib().pbr_multi_configure(self._m, ctypes.byref(cfg)))
