@@ -34,10 +34,10 @@ extern "C" {
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
  * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
- * version 13 pbr_refit_ordered_walk).  A caller that loads the library at run time — or
+ * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 13
+#define PBR_ABI_VERSION 14
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -196,7 +196,8 @@ int pbr_validate_scene( const pbr_scene_desc* scene, char* message, size_t capac
  *               pbr_configure) unless pbr_refit_ordered_walk is on, see below; phong_tessellation > 0 is configured.
  *   PBR_EINVAL  a null pointer, num_vertices other than the upload's, a coordinate that is not finite (checked on the host).
  * After an update pbr_configure refuses phong_tessellation > 0 (PBR_ESTATE) until the next pbr_upload_scene: tight boxes
- * would clip the patches, and the patches' corners are not updated. */
+ * would clip the patches, and the patches' corners are not updated.  pbr_update_geometry (below, ABI version 14) is the update
+ * that moves the patches too and works while Phong tessellation is configured. */
 int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices );
 /* A REFIT UNDER A RAY-ORDERED WALK (ABI version 13).  pbr_refit_ordered_walk( ctx, 1 ) makes pbr_update_vertices succeed while
  * traversal 1, 2 or 3 is configured: behind the refit above it rebuilds, on the device and in place, the records of the
@@ -225,6 +226,66 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
  * re-link's kernels; pbr_diag_relink_info reports their share.  Configuring another ordered layout afterwards builds its
  * records on the host from the refitted tree, as before. */
 int pbr_refit_ordered_walk( pbr_ctx* ctx, int on );
+/* A REFIT UNDER PHONG TESSELLATION (ABI version 14).  pbr_update_geometry takes new vertex positions AND new vertex normals for
+ * the uploaded scene and rebuilds on the device what pbr_update_vertices rebuilds — the face records, the per-face normals,
+ * every node's box, the re-link of the configured ordered layout when pbr_refit_ordered_walk is on — and with them the Phong
+ * patch records the patch intersection reads: per face six quads, the three corners, then the three vertex normals, gathered
+ * through facesV / facesN, each with .w = 0.  `vertices` and `normals` are host memory, borrowed for the call.
+ *   normals == NULL with num_normals == 0   positions only: the normals stay the ones the context holds (the upload's, or
+ *                                           those of the last pbr_update_geometry that brought some);
+ *   otherwise                               num_normals must be the upload's count.
+ * The boxes are built with alpha = the configured phong_tessellation (0 for a context that is not configured), so the call
+ * succeeds WHILE Phong tessellation is configured, where pbr_update_vertices refuses.
+ * THE FACE BOX, operation by operation in binary32, none fused (it is the reference builder's thickened box, MathHelp.cpp:250-310
+ * and :325-378, with the refit's fold); p1, p2, p3 are the face's corners a, b, c and n1, n2, n3 its vertex normals:
+ *   lo = hi = p1; fold p2, then p3, with lo = ( v < lo ) ? v : lo and hi = ( v > hi ) ? v : hi per component;
+ *   if alpha > 0 and the three normals are NOT EQUAL — t = ( n1 - n2 ) + ( n2 - n3 ), any fabsf( t.k ) > 0.000001f — fold, in
+ *   this order, the three raised corners p_k + thickness * ng, k = 1, 2, 3, and the nine edge points phongPoint( u, v ) for
+ *   ( u, v ) = ( 0, .5 ) ( .5, 0 ) ( .5, .5 ) ( .25, .75 ) ( .75, .25 ) ( .25, 0 ) ( .75, 0 ) ( 0, .25 ) ( 0, .75 ), where
+ *     dot( a, b ) = ( a.x*b.x + a.y*b.y ) + a.z*b.z      normalize( a ) = a * ( 1.0f / sqrtf( dot( a, a ) ) )
+ *     cross( a, b ) = { a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y }
+ *     e12 = p2 - p1, e13 = p3 - p1, e23 = p3 - p2, e31 = p1 - p3
+ *     c12 = alpha * ( dot( n2, e12 ) * n2 - dot( n1, e12 ) * n1 )
+ *     c23 = alpha * ( dot( n3, e23 ) * n3 - dot( n2, e23 ) * n2 )
+ *     c31 = alpha * ( dot( n1, e31 ) * n1 - dot( n3, e31 ) * n3 )
+ *     ng = normalize( cross( e12, e13 ) )
+ *     m = dot( ng, ( c12 - c23 ) - c31 )
+ *     k = 1.0f / ( ( 4.0f * dot( ng, c23 ) ) * dot( ng, c31 ) - m * m )
+ *     u = k * ( ( 2.0f * dot( ng, c23 ) ) * dot( ng, c31 + e31 ) + dot( ng, c23 - e23 ) * m )
+ *     v = k * ( ( 2.0f * dot( ng, c31 ) ) * dot( ng, c23 - e23 ) + dot( ng, c31 + e31 ) * m )
+ *     u = ( u < 0 || u > 1 ) ? 0 : u, likewise v
+ *     thickness = dot( ng, phongPoint( u, v ) - p1 )
+ *     phongPoint( u, v ):  w = ( 1.0f - u ) - v;  bary = ( p1 * u + p2 * v ) + p3 * w;
+ *                          onPlane( q, p, n ) = q - dot( q - p, n ) * n;
+ *                          tess = ( u * onPlane( bary, p1, n1 ) + v * onPlane( bary, p2, n2 ) ) + w * onPlane( bary, p3, n3 );
+ *                          the point is ( 1.0f - alpha ) * bary + alpha * tess
+ *   a vector times a scalar is three multiplications; `/` and sqrtf are correctly rounded.
+ * A NaN point never enters the fold, because both compares are false (a face without area has ng = NaN: its box is the tight
+ * one; an infinite k gives NaN or 0 for u and v); corners are finite by the host's check, so no box word is ever NaN.
+ *   leaf       ONE running fold: its first face's twelve-or-three points, then its second face's if there is one;
+ *   container  exactly as pbr_update_vertices; the .w words are unchanged.
+ * With alpha = 0 every box is, bit for bit, pbr_update_vertices's.
+ * THE CONTRACT is the refit's: after pbr_upload_scene( S ), pbr_configure( c ) and pbr_update_geometry( V', N' ) every call
+ * (pbr_render*, pbr_render_frame, pbr_diag_trace, the counters, the debug image, pbr_denoise*) gives bit for bit what it gives
+ * after pbr_upload_scene( S' ) and pbr_configure( c ), S' = S with V', N' and the nodes pbr_read_bvh returns — Phong
+ * tessellation included, in all four traversals.  What stays stale stays stale: the hot-node ranking, the tuner's plan, the tile
+ * costs and the dealing orders.  The temporal history is treated as by pbr_update_vertices: dropped, or H kept under
+ * pbr_temporal_track_motion (the motion path stays NOT COVERED under Phong tessellation).
+ * Refusals, each leaving the context unchanged:
+ *   PBR_ESTATE  no scene; a tree that is not properly nested; a ray-ordered traversal without pbr_refit_ordered_walk (the
+ *               refit's own, in its order); `normals` given for a scene that was uploaded without usable vertex normals.
+ *   PBR_EINVAL  a null context; null `vertices`; a count other than the upload's; `normals` and num_normals disagreeing about
+ *               NULL / 0; a position or normal coordinate that is not finite.
+ * THE STATE RULE of pbr_configure: after any update it refuses phong_tessellation > 0 (PBR_ESTATE) unless the most recent
+ * successful update was a pbr_update_geometry AND the alpha of that update equals cfg->phong_tessellation, compared as floats.
+ * A later pbr_update_vertices brings the refusal back (it leaves the patches stale and the boxes tight); a new upload clears it.
+ * Configuring phong_tessellation = 0 over thick boxes is always allowed: thick boxes are conservative, and the contract covers
+ * them through pbr_read_bvh.  pbr_update_vertices itself is unchanged, its refusal under Phong tessellation included.
+ * Nothing is allocated per call: the device tables — 16 bytes per face (its normal indices), 16 per normal, 24 per face (its
+ * thick box, written by the patch kernel and read by the leaf step one launch later) — are made by the FIRST pbr_update_geometry
+ * after an upload from a host copy the upload keeps, and freed with the scene (pbr_diag_patch_refit_info, pbr_hip_diag.h). */
+int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices,
+                         const pbr_float4* normals, uint32_t num_normals );
 /* The current tree in the wire format: the uploaded nodes, after pbr_update_vertices with the refitted boxes (copied back
  * from the device by this call, not by the update).  *num_nodes = the node count; nodes_out = NULL returns the count only,
  * else capacity >= *num_nodes entries.  A caller's rebuild heuristic (e.g. the growth of the boxes' surface area) reads this. */

@@ -121,6 +121,20 @@ int pbr_diag_scene_bytes( pbr_ctx* ctx, uint64_t out[3] );
  * the device (pbr_last_kernel_ms excludes it).  upload_ms and why may be NULL. */
 int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char* why, size_t capacity );
 
+/* pbr_update_geometry (pbr_hip.h): out[0] 1 if the scene has Phong patch records (usable vertex normals at the upload), [1] the
+ * device bytes of the patch refit's tables as they are held now — 16 per face, 16 per normal, 24 per face; 0 until the first
+ * pbr_update_geometry after an upload —, [2] the successful pbr_update_geometry calls since the upload, [3] 1 if the most recent
+ * successful update was one of them (pbr_configure's state rule).  *alpha (may be NULL): the phong_tessellation that update
+ * built its boxes with.  pbr_diag_refit_info's figures do not include any of this; its upload_ms covers the copy of the normals
+ * too when the last update was a pbr_update_geometry that brought some.  PBR_EINVAL for a null context or null out,
+ * PBR_ESTATE without a scene. */
+int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha );
+
+/* The Phong patch records as they are on the device now: six quads per face, the corners, then the vertex normals, .w = 0.
+ * *count = the quads; out = NULL returns the count only, else capacity >= *count quads.  PBR_ESTATE without a scene or for a
+ * scene without usable vertex normals, PBR_EINVAL for a null context, null count or too little room. */
+int pbr_diag_read_patches( pbr_ctx* ctx, pbr_float4* out, uint32_t capacity, uint32_t* count );
+
 /* The configured ray-ordered layout's device buffer as it is now, header included (pbr_refit_ordered_walk's contract is stated
  * on these bytes): *bytes = its size, first[8] = the context's eight first references, *hot_slots = the 32-byte slots at the head
  * of the records that are ranked for LDS staging (first and hot_slots may be NULL).  out = NULL returns these only, else

@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 13
+ABI_VERSION = 14
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -200,6 +200,9 @@ for _name, _args in (
         ("pbr_refit_ordered_walk", [_vp, ctypes.c_int]),                                                                 # ABI version 13
         ("pbr_diag_read_walk", [_vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int), _up]),
         ("pbr_diag_relink_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_update_geometry", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),             # ABI version 14
+        ("pbr_diag_patch_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float)]),
+        ("pbr_diag_read_patches", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -239,6 +242,8 @@ if hasattr(host, "pbrh_pt_update_vertices"):
     host.pbrh_pt_update_vertices.argtypes = [_vp, _fp, ctypes.c_uint32]
 if hasattr(host, "pbrh_pt_refit_ordered_walk"):
     host.pbrh_pt_refit_ordered_walk.argtypes = [_vp, ctypes.c_int]
+if hasattr(host, "pbrh_pt_update_geometry"):
+    host.pbrh_pt_update_geometry.argtypes = [_vp, _fp, ctypes.c_uint32, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -442,6 +447,32 @@ class Device:
         bit for bit what it gives after a fresh upload of the scene with these vertices and the nodes read_bvh() returns."""
         vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
         self._check(hip.pbr_update_vertices(self._ctx, vertices.ctypes.data, vertices.shape[0]))
+
+    def update_geometry(self, vertices, normals=None):
+        """pbr_update_geometry: new positions (n, 4) and, unless None, new vertex normals (m, 4), float32 with n and m as uploaded.
+        What update_vertices rebuilds plus the Phong patch records; the boxes are thick ones for the configured
+        phong_tessellation, so it works while Phong tessellation is configured.  normals=None keeps the context's normals."""
+        vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        if normals is None:
+            self._check(hip.pbr_update_geometry(self._ctx, vertices.ctypes.data, vertices.shape[0], None, 0))
+            return
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+        self._check(hip.pbr_update_geometry(self._ctx, vertices.ctypes.data, vertices.shape[0], normals.ctypes.data, normals.shape[0]))
+
+    def read_patches(self):
+        """pbr_diag_read_patches: the Phong patch records on the device, (faces, 6, 4) float32 — three corners, three normals."""
+        n = ctypes.c_uint32()
+        self._check(hip.pbr_diag_read_patches(self._ctx, None, 0, ctypes.byref(n)))
+        quads = np.empty((n.value // 6, 6, 4), np.float32)
+        self._check(hip.pbr_diag_read_patches(self._ctx, quads.ctypes.data, n.value, ctypes.byref(n)))
+        return quads
+
+    def patch_refit_info(self):
+        """pbr_diag_patch_refit_info: whether the scene has patches, the device bytes update_geometry holds, its calls since the
+        upload, whether the last update was one of them and the phong_tessellation it built its boxes with."""
+        out, alpha = (ctypes.c_uint64 * 4)(), ctypes.c_float()
+        self._check(hip.pbr_diag_patch_refit_info(self._ctx, out, ctypes.byref(alpha)))
+        return {"patches": bool(out[0]), "device_bytes": int(out[1]), "updates": int(out[2]), "last_update": bool(out[3]), "alpha": float(alpha.value)}
 
     def refit_ordered_walk(self, on):
         """pbr_refit_ordered_walk: while on, update_vertices works under a ray-ordered traversal — the configured layout's records
@@ -909,6 +940,14 @@ class PathTracer:
         """PathTracer::updateVertices: Device.update_vertices on the tracer's context; starts a new accumulation."""
         vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
         if host.pbrh_pt_update_vertices(self._h, _as_fp(vertices), vertices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updateGeometry(self, vertices, normals=None):
+        """PathTracer::updateGeometry: Device.update_geometry on the tracer's context; starts a new accumulation."""
+        vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+        if host.pbrh_pt_update_geometry(self._h, _as_fp(vertices), vertices.shape[0], None if normals is None else _as_fp(normals),
+                                        0 if normals is None else normals.shape[0]) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def refitOrderedWalk(self, on):

@@ -32,6 +32,7 @@
 #include "pt_adaptive_host.hpp"
 #include "pt_refit_host.hpp"
 #include "pt_refit.hpp"
+#include "pt_patch_refit.hpp"
 #include "pt_relink.hpp"
 
 using ptk::DevParams;
@@ -174,8 +175,21 @@ struct pbr_ctx {
 	unsigned* dRefitLevelFirst = nullptr;
 	uint32_t numVertices = 0, refitGroups = 0, refitLevels = 0, refitTopNodes = 0, refitSubtrees = 0;
 	uint64_t refitBytes = 0;       // device bytes of all of the above
-	uint32_t refitUpdates = 0;     // pbr_update_vertices calls since the upload: > 0 = the boxes are refitted ones, dTriPN is stale
+	uint32_t refitUpdates = 0;     // pbr_update_vertices / pbr_update_geometry calls since the upload: > 0 = the boxes are refitted ones
 	bool treeStale = false;        // tree.bvh's boxes are older than the device's (refreshTree)
+	// pbr_update_geometry (pt_patch_refit_host.hpp, pt_patch_refit.hpp): the faces' normal indices and the vertex normals, kept
+	// on the host by the upload (only when dTriPN is there) and moved to the device by the first such update together with the
+	// per-face scratch table of thick boxes — no allocation per call; freed with the scene
+	std::vector<pbr_uint4> patchFacesN;
+	std::vector<pbr_float4> patchNormals;
+	uint4* dPatchFacesN = nullptr;
+	float4* dPatchNormals = nullptr;
+	float2* dFaceBoxes = nullptr;  // 24 bytes per face: lo.xyz, hi.xyz
+	uint32_t numNormals = 0;       // the upload's count, usable or not
+	uint64_t patchBytes = 0;       // device bytes of the three tables (0 until the first pbr_update_geometry)
+	uint32_t geometryUpdates = 0;  // successful pbr_update_geometry calls since the upload
+	bool lastUpdateGeometry = false;   // the most recent successful update was a pbr_update_geometry: dTriPN is current, the boxes
+	float patchAlpha = 0.0f;           // ... are thick ones for this phong_tessellation (pbr_configure's state rule)
 	double lastRefitUploadMs = 0.0;
 	// pbr_refit_ordered_walk (pt_relink_host.hpp, pt_relink.hpp): while it is on, pbr_update_vertices under a ray-ordered traversal
 	// rebuilds dNodesWalk's records on the device.  dRelink: one allocation with the static and the working tables of the layout
@@ -345,6 +359,18 @@ void freeScene( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dRefitTop );
 	(void) hipFree( ctx->dRefitLevelFirst );
 	(void) hipFree( ctx->dHistVertices );
+	(void) hipFree( ctx->dPatchFacesN );
+	(void) hipFree( ctx->dPatchNormals );
+	(void) hipFree( ctx->dFaceBoxes );
+	ctx->dPatchFacesN = nullptr;
+	ctx->dPatchNormals = nullptr;
+	ctx->dFaceBoxes = nullptr;
+	std::vector<pbr_uint4>().swap( ctx->patchFacesN );
+	std::vector<pbr_float4>().swap( ctx->patchNormals );
+	ctx->patchBytes = 0;
+	ctx->geometryUpdates = 0;
+	ctx->lastUpdateGeometry = false;
+	ctx->patchAlpha = 0.0f;
 	ctx->dFacesV = nullptr;
 	ctx->dVertices = ctx->dRootBox = ctx->dHistVertices = nullptr;
 	ctx->dRefitSlots = ctx->dRefitInfo = ctx->dRefitTop = ctx->dRefitLevelFirst = nullptr;
@@ -1520,7 +1546,12 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 
 	if( !packed.triPN.empty() ) {
 		PBR_TRY( toDevice( &ctx->dTriPN, packed.triPN ) );
+		// pbr_update_geometry gathers the patches again: the indices and the normals wait on the host for its first call
+		ctx->patchFacesN.assign( s->facesN, s->facesN + s->num_faces );
+		ctx->patchNormals.assign( s->normals, s->normals + s->num_normals );
 	}
+
+	ctx->numNormals = s->num_normals;
 
 	PBR_TRY( toDevice( &ctx->dMats, packed.mats ) );
 	PBR_TRY( toDevice( &ctx->dLights, packed.lights ) );
@@ -1709,29 +1740,85 @@ int pbr_refit_ordered_walk( pbr_ctx* ctx, int on ) {
 	return PBR_OK;
 }
 
-int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices ) {
-	if( ctx == nullptr || ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
+namespace {
+
+// The device tables of pbr_update_geometry, made by the first such call after an upload from the host copies the upload kept:
+// the faces' normal indices, the vertex normals, and the scratch table of the faces' thick boxes.  Nothing of the context
+// changes when this fails.
+int ensurePatchTables( pbr_ctx* ctx ) {
+	if( ctx->dFaceBoxes != nullptr ) {
+		return PBR_OK;
 	}
+
+	const size_t indexBytes = sizeof( pbr_uint4 ) * ctx->patchFacesN.size(), normalBytes = sizeof( pbr_float4 ) * ctx->patchNormals.size();
+	const size_t boxBytes = sizeof( float ) * 6 * (size_t) ctx->numFaces;
+	uint4* indices = nullptr;
+	float4* normals = nullptr;
+	float2* boxes = nullptr;
+	hipError_t err = hipMalloc( (void**) &indices, std::max<size_t>( indexBytes, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &normals, std::max<size_t>( normalBytes, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &boxes, std::max<size_t>( boxBytes, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( indices, ctx->patchFacesN.data(), indexBytes, hipMemcpyHostToDevice );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( normals, ctx->patchNormals.data(), normalBytes, hipMemcpyHostToDevice );
+
+	if( err != hipSuccess ) {
+		(void) hipFree( indices );
+		(void) hipFree( normals );
+		(void) hipFree( boxes );
+		return fail( ctx, PBR_EDEVICE, "pbr_update_geometry: the patch refit's tables: %s", hipGetErrorString( err ) );
+	}
+
+	ctx->dPatchFacesN = indices;
+	ctx->dPatchNormals = normals;
+	ctx->dFaceBoxes = boxes;
+	ctx->patchBytes = indexBytes + normalBytes + boxBytes;
+	std::vector<pbr_uint4>().swap( ctx->patchFacesN );   // the device holds them now
+	std::vector<pbr_float4>().swap( ctx->patchNormals );
+	return PBR_OK;
+}
+
+// What pbr_update_geometry brings beyond the positions; pbr_update_vertices passes none.
+struct PatchUpdate {
+	const pbr_float4* normals;
+	uint32_t num_normals;
+};
+
+// pbr_update_vertices (patches == nullptr) and pbr_update_geometry: the checks, the copy, the launches, the state.
+int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches ) {
 	if( !ctx->hasScene ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_vertices before pbr_upload_scene" );
+		return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene", call );
 	}
 
-	PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error ) );
+	PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error, call ) );
 
+	if( patches != nullptr ) {
+		PBR_TRY( checkRefitNormals( patches->normals, patches->num_normals, ctx->numNormals, &ctx->error ) );
+	}
 	if( !ctx->refit.nested ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", ctx->refit.why.c_str() );
+		return fail( ctx, PBR_ESTATE, "%s: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", call, ctx->refit.why.c_str() );
 	}
 	const bool ordered = ( ctx->configured && ctx->cfg.traversal != 0 );
 
 	if( ordered && !ctx->refitOrdered ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while a ray-ordered traversal (%u) is configured: its streams carry child orders built from the old boxes — configure traversal 0, update, then configure the ordered walk again", ctx->cfg.traversal );
+		return fail( ctx, PBR_ESTATE, "%s while a ray-ordered traversal (%u) is configured: its streams carry child orders built from the old boxes — configure traversal 0, update, then configure the ordered walk again", call, ctx->cfg.traversal );
 	}
-	if( ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) {
+	if( patches == nullptr && ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) {
 		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while Phong tessellation is configured: tight boxes of the flat triangles would clip the patches" );
 	}
+	if( patches != nullptr && patches->normals != nullptr && ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_geometry: new normals for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
+	}
+
+	// the patches are gathered again whenever the scene has any; the boxes are thick ones under a configured phong_tessellation
+	// only (it cannot be configured without patches), and with alpha = 0 they are pbr_update_vertices's, kernel for kernel
+	const bool gathers = ( patches != nullptr && ctx->dTriPN != nullptr );
+	const float alpha = ( gathers && ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) ? ctx->cfg.phong_tessellation : 0.0f;
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( gathers ) {
+		PBR_TRY( ensurePatchTables( ctx ) );
+	}
 
 	// pbr_refit_ordered_walk: the configured layout's records are re-linked in place behind the refit.  Its tables first: a call
 	// that cannot have them changes nothing
@@ -1752,12 +1839,17 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 
 		if( kept != hipSuccess ) {
 			ctx->temporal.drop();
-			return fail( ctx, PBR_EDEVICE, "pbr_update_vertices: keeping the history's vertex positions: %s", hipGetErrorString( kept ) );
+			return fail( ctx, PBR_EDEVICE, "%s: keeping the history's vertex positions: %s", call, hipGetErrorString( kept ) );
 		}
 	}
 
 	const auto uploadStart = std::chrono::steady_clock::now();
 	HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
+
+	if( gathers && patches->normals != nullptr ) {
+		HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, patches->normals, sizeof( pbr_float4 ) * patches->num_normals, hipMemcpyHostToDevice ) );
+	}
+
 	ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
 
 	const uint32_t F = ctx->numFaces;
@@ -1773,8 +1865,17 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
-	hipLaunchKernelGGL( ptr::refitSubtrees, dim3( ctx->refitGroups ), dim3( REFIT_SUBTREE ), 0, ctx->stream, ctx->dRefitSlots, ctx->dRefitInfo,
-	                    ctx->dRefitHeights, ctx->dRefitRecordOf, ctx->dFacesV, ctx->dVertices, ctx->dNodes, ctx->dRootBox );
+	// the patches, and under Phong tessellation the faces' thick boxes for the leaf step one launch later
+	if( gathers ) {
+		const auto kernel = ( alpha > 0.0f ) ? ptr::refitPatches<true> : ptr::refitPatches<false>;
+		hipLaunchKernelGGL( kernel, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dPatchFacesN, ctx->dVertices,
+		                    ctx->dPatchNormals, ctx->dTriPN, ctx->dFaceBoxes, alpha, (int) F );
+		HIP_TRY( ctx, hipGetLastError() );
+	}
+
+	const auto subtrees = ( alpha > 0.0f ) ? ptr::refitSubtrees<true> : ptr::refitSubtrees<false>;
+	hipLaunchKernelGGL( subtrees, dim3( ctx->refitGroups ), dim3( REFIT_SUBTREE ), 0, ctx->stream, ctx->dRefitSlots, ctx->dRefitInfo,
+	                    ctx->dRefitHeights, ctx->dRefitRecordOf, ctx->dFacesV, ctx->dVertices, ctx->dFaceBoxes, ctx->dNodes, ctx->dRootBox );
 	HIP_TRY( ctx, hipGetLastError() );
 
 	if( ctx->refitLevels > 0 ) {
@@ -1795,6 +1896,9 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	PBR_TRY( timedTail( ctx ) );
 	ctx->treeStale = true;
 	ctx->refitUpdates++;
+	ctx->lastUpdateGeometry = ( patches != nullptr );
+	ctx->patchAlpha = alpha;
+	ctx->geometryUpdates += ( patches != nullptr ) ? 1u : 0u;
 
 	if( relinks ) {
 		// the eight first references are the context's too (applyWalk): 32 bytes of header, no node, box or record
@@ -1809,6 +1913,28 @@ int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 	freeWalkStreams( ctx );   // none while traversal 0 is configured; an unconfigured context may hold a previous mode's
 	// the flag is on but the configured layout's records are not there to re-link: they are built on the host, as pbr_configure does
 	return ordered ? buildWalkStreams( ctx, ctx->cfg.traversal ) : PBR_OK;
+}
+
+}  // namespace
+
+int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	return updateScene( ctx, "pbr_update_vertices", vertices, num_vertices, nullptr );
+}
+
+int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices, const pbr_float4* normals, uint32_t num_normals ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	const PatchUpdate patches = { normals, num_normals };
+	return updateScene( ctx, "pbr_update_geometry", vertices, num_vertices, &patches );
 }
 
 int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint32_t* num_nodes ) {
@@ -1852,8 +1978,11 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs vertex normals: the uploaded scene's facesN / normals are missing or out of range" );
 	}
-	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 ) {
-		return fail( ctx, PBR_ESTATE, "Phong tessellation after pbr_update_vertices: the refitted boxes are tight boxes of the flat triangles and would clip the patches, and the patches' corners were not updated — upload the scene again" );
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !ctx->lastUpdateGeometry ) {
+		return fail( ctx, PBR_ESTATE, "Phong tessellation after pbr_update_vertices: the refitted boxes are tight boxes of the flat triangles and would clip the patches, and the patches' corners were not updated — upload the scene again, or call pbr_update_geometry under this phong_tessellation" );
+	}
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !( ctx->patchAlpha == cfg->phong_tessellation ) ) {
+		return fail( ctx, PBR_ESTATE, "Phong tessellation %g after a pbr_update_geometry under %g: the boxes were thickened for that value and could clip these patches — configure %g, or upload the scene again", (double) cfg->phong_tessellation, (double) ctx->patchAlpha, (double) ctx->patchAlpha );
 	}
 	if( cfg->traversal > 3 || cfg->arith > 1 ) {
 		return fail( ctx, PBR_EINVAL, "traversal must be 0 (the reference's walk), 1 (six orders), 2 (eight orders) or 3 (eight orders, compact records); arith 0 (exact) or 1 (native)" );
@@ -3199,6 +3328,55 @@ int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char*
 		std::snprintf( why, capacity, "%s", ctx->refit.why.c_str() );
 	}
 
+	return PBR_OK;
+}
+
+int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_patch_refit_info: null out" );
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "diag_patch_refit_info: no scene" );
+	}
+
+	out[0] = ( ctx->dTriPN != nullptr ) ? 1 : 0;
+	out[1] = ctx->patchBytes;
+	out[2] = ctx->geometryUpdates;
+	out[3] = ctx->lastUpdateGeometry ? 1 : 0;
+
+	if( alpha != nullptr ) {
+		*alpha = ctx->patchAlpha;
+	}
+
+	return PBR_OK;
+}
+
+int pbr_diag_read_patches( pbr_ctx* ctx, pbr_float4* out, uint32_t capacity, uint32_t* count ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( !ctx->hasScene || ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag_read_patches: no scene, or one without usable vertex normals (no Phong patches)" );
+	}
+	if( count == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_read_patches: null count" );
+	}
+
+	*count = ctx->numFaces * 6u;
+
+	if( out == nullptr ) {
+		return PBR_OK;
+	}
+	if( capacity < *count ) {
+		return fail( ctx, PBR_EINVAL, "diag_read_patches: room for %u quads, the patches hold %u", capacity, *count );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpy( out, ctx->dTriPN, sizeof( pbr_float4 ) * (size_t) *count, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 

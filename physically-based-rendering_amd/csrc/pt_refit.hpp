@@ -4,7 +4,9 @@
 //                  a subtraction alone cannot contract, and the library is built with -ffp-contract=off anyway)
 //   refitSubtrees  one workgroup per group of maximal subtrees of at most REFIT_SUBTREE nodes, one thread slot per node: leaf
 //                  boxes from the corners, then the containers height by height over LDS behind a workgroup barrier; every
-//                  box is stored once, box words only, into the node's record of the reference-order stream
+//                  box is stored once, box words only, into the node's record of the reference-order stream.  Its PHONG build
+//                  (pbr_update_geometry under Phong tessellation) makes a leaf's box from the thick boxes of its faces, which
+//                  refitPatches (pt_patch_refit.hpp) stored one launch earlier; everything behind the leaf step is the same
 //   refitTop       the nodes above the cut, one workgroup: level by level (lowest first) from the children's records, a
 //                  workgroup barrier between two levels — launched behind refitSubtrees, so the kernel boundary makes the
 //                  subtree roots' records visible
@@ -62,6 +64,24 @@ __device__ inline Box leafBox( unsigned word, const uint4* facesV, const float4*
 	return b;
 }
 
+// ... and under Phong tessellation: the first face's stored thick box, then the second face's folded in — bit for bit the
+// running fold over the first face's points and then the second's (pt_patch_refit_host.hpp, faceBox)
+__device__ inline Box loadFaceBox( const float2* faceBoxes, unsigned face ) {
+	const float2 q0 = faceBoxes[(size_t) face * 3 + 0], q1 = faceBoxes[(size_t) face * 3 + 1], q2 = faceBoxes[(size_t) face * 3 + 2];
+	return Box { { q0.x, q0.y, q1.x }, { q1.y, q2.x, q2.y } };
+}
+
+__device__ inline Box leafBoxThick( unsigned word, const float2* faceBoxes ) {
+	const unsigned face = word & 0x3FFFFFFFu;
+	Box b = loadFaceBox( faceBoxes, face );
+
+	if( word & 0x40000000u ) {
+		foldBox( b, loadFaceBox( faceBoxes, face + 1 ) );
+	}
+
+	return b;
+}
+
 // The record of the reference-order stream (pt_scene_pack.hpp, encodeRecords32): {lo.x, lo.y, hi.x, hi.y} {lo.z, hi.z, word,
 // word}.  Node 0 has no record (record < 0): its box goes to rootBox, in the wire format's order.
 __device__ inline void storeBox( float4* nodes, float4* rootBox, int record, const Box& b ) {
@@ -99,10 +119,11 @@ __global__ __launch_bounds__( 256 ) void refitFaces( const uint4* __restrict__ f
 	tris[(size_t) f * 3 + 2] = make_float4( e2z, __int_as_float( (int) fv.w ), 0.0f, 0.0f );
 }
 
+template<bool PHONG>
 __global__ __launch_bounds__( REFIT_SUBTREE ) void refitSubtrees( const unsigned* __restrict__ slots, const unsigned* __restrict__ info,
                                                                   const unsigned short* __restrict__ heights, const int* __restrict__ recordOf,
                                                                   const uint4* __restrict__ facesV, const float4* __restrict__ vertices,
-                                                                  float4* nodes, float4* rootBox ) {
+                                                                  const float2* __restrict__ faceBoxes, float4* nodes, float4* rootBox ) {
 	__shared__ float sBox[6][REFIT_SUBTREE];
 	__shared__ unsigned sInfo[REFIT_SUBTREE];
 
@@ -115,7 +136,7 @@ __global__ __launch_bounds__( REFIT_SUBTREE ) void refitSubtrees( const unsigned
 	Box b = {};
 
 	if( valid && height == 0u ) {
-		b = leafBox( word, facesV, vertices );
+		b = PHONG ? leafBoxThick( word, faceBoxes ) : leafBox( word, facesV, vertices );
 
 		for( int k = 0; k < 3; k++ ) {
 			sBox[k][slot] = b.lo[k];

@@ -192,6 +192,31 @@ inline void refitFold( float lo[3], float hi[3], const float vLo[3], const float
 	}
 }
 
+// A container's box: the fold over its children's boxes in `nodes`, depth-first child order, from the first child's.
+inline void refitContainerBox( const RefitPlan& plan, const pbr_bvh_node* nodes, uint32_t i, float lo[3], float hi[3] ) {
+	for( uint32_t c = i + 1; c < plan.end[i]; c = plan.end[c] ) {
+		const float cLo[3] = { nodes[c].bbMin.x, nodes[c].bbMin.y, nodes[c].bbMin.z };
+		const float cHi[3] = { nodes[c].bbMax.x, nodes[c].bbMax.y, nodes[c].bbMax.z };
+
+		if( c == i + 1 ) {
+			std::copy( cLo, cLo + 3, lo );
+			std::copy( cHi, cHi + 3, hi );
+		}
+		else {
+			refitFold( lo, hi, cLo, cHi );
+		}
+	}
+}
+
+inline void refitStoreBox( pbr_bvh_node* nodes, uint32_t i, const float lo[3], const float hi[3] ) {
+	nodes[i].bbMin.x = lo[0];
+	nodes[i].bbMin.y = lo[1];
+	nodes[i].bbMin.z = lo[2];
+	nodes[i].bbMax.x = hi[0];
+	nodes[i].bbMax.y = hi[1];
+	nodes[i].bbMax.z = hi[2];
+}
+
 // The refit in plain C++: the boxes of `nodes` (the tree's, N entries) from the vertices; the .w words stay.
 inline void refitBoxes( const SceneTree& tree, const RefitPlan& plan, const pbr_uint4* facesV, const pbr_float4* vertices, pbr_bvh_node* nodes ) {
 	const uint32_t N = tree.size();
@@ -221,43 +246,52 @@ inline void refitBoxes( const SceneTree& tree, const RefitPlan& plan, const pbr_
 			}
 		}
 		else {
-			for( uint32_t c = i + 1; c < plan.end[i]; c = plan.end[c] ) {
-				const float cLo[3] = { nodes[c].bbMin.x, nodes[c].bbMin.y, nodes[c].bbMin.z };
-				const float cHi[3] = { nodes[c].bbMax.x, nodes[c].bbMax.y, nodes[c].bbMax.z };
-
-				if( c == i + 1 ) {
-					std::copy( cLo, cLo + 3, lo );
-					std::copy( cHi, cHi + 3, hi );
-				}
-				else {
-					refitFold( lo, hi, cLo, cHi );
-				}
-			}
+			refitContainerBox( plan, nodes, i, lo, hi );
 		}
 
-		nodes[i].bbMin.x = lo[0];
-		nodes[i].bbMin.y = lo[1];
-		nodes[i].bbMin.z = lo[2];
-		nodes[i].bbMax.x = hi[0];
-		nodes[i].bbMax.y = hi[1];
-		nodes[i].bbMax.z = hi[2];
+		refitStoreBox( nodes, i, lo, hi );
 	}
 }
 
-// Why pbr_update_vertices refuses these vertices (PBR_EINVAL, the message in *why), or PBR_OK.
-inline int checkRefitVertices( const pbr_float4* vertices, uint32_t num_vertices, uint32_t uploaded, std::string* why ) {
+// Why pbr_update_vertices (or `call`: pbr_update_geometry takes its positions through here) refuses these vertices
+// (PBR_EINVAL, the message in *why), or PBR_OK.
+inline int checkRefitVertices( const pbr_float4* vertices, uint32_t num_vertices, uint32_t uploaded, std::string* why, const char* call = "pbr_update_vertices" ) {
 	if( vertices == nullptr ) {
-		return packFail( why, PBR_EINVAL, "pbr_update_vertices: null vertices" );
+		return packFail( why, PBR_EINVAL, "%s: null vertices", call );
 	}
 	if( num_vertices != uploaded ) {
-		return packFail( why, PBR_EINVAL, "pbr_update_vertices: %u vertices, the uploaded scene has %u (the topology is kept)", num_vertices, uploaded );
+		return packFail( why, PBR_EINVAL, "%s: %u vertices, the uploaded scene has %u (the topology is kept)", call, num_vertices, uploaded );
 	}
 
 	for( uint32_t i = 0; i < num_vertices; i++ ) {
 		const pbr_float4& v = vertices[i];
 
 		if( !std::isfinite( v.x ) || !std::isfinite( v.y ) || !std::isfinite( v.z ) ) {
-			return packFail( why, PBR_EINVAL, "pbr_update_vertices: vertex %u is not finite", i );
+			return packFail( why, PBR_EINVAL, "%s: vertex %u is not finite", call, i );
+		}
+	}
+
+	return PBR_OK;
+}
+
+// ... and why pbr_update_geometry refuses these normals.  NULL with num_normals == 0 keeps the context's normals; otherwise the
+// count is the upload's and every x, y, z is finite (the fourth component is padding, as for a vertex).
+inline int checkRefitNormals( const pbr_float4* normals, uint32_t num_normals, uint32_t uploaded, std::string* why ) {
+	if( ( normals == nullptr ) != ( num_normals == 0 ) ) {
+		return packFail( why, PBR_EINVAL, "pbr_update_geometry: %s normals with num_normals = %u (NULL and 0 keep the normals)", ( normals == nullptr ) ? "null" : "non-null", num_normals );
+	}
+	if( normals == nullptr ) {
+		return PBR_OK;
+	}
+	if( num_normals != uploaded ) {
+		return packFail( why, PBR_EINVAL, "pbr_update_geometry: %u normals, the uploaded scene has %u (the topology is kept)", num_normals, uploaded );
+	}
+
+	for( uint32_t i = 0; i < num_normals; i++ ) {
+		const pbr_float4& n = normals[i];
+
+		if( !std::isfinite( n.x ) || !std::isfinite( n.y ) || !std::isfinite( n.z ) ) {
+			return packFail( why, PBR_EINVAL, "pbr_update_geometry: normal %u is not finite", i );
 		}
 	}
 

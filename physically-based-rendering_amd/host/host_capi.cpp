@@ -283,6 +283,19 @@ int pbrh_pt_update_vertices( void* tracer, const float* vertices, uint32_t num_v
 	}
 }
 
+int pbrh_pt_update_geometry( void* tracer, const float* vertices, uint32_t num_vertices, const float* normals, uint32_t num_normals ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateGeometry( reinterpret_cast<const pbr_float4*>( vertices ), num_vertices, reinterpret_cast<const pbr_float4*>( normals ), num_normals );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
 	HostTracer* t = static_cast<HostTracer*>( tracer );
 

@@ -442,6 +442,15 @@ void PathTracer::updateVertices( const pbr_float4* vertices, uint32_t numVertice
 	this->resetSampleCount();
 }
 
+void PathTracer::updateGeometry( const pbr_float4* vertices, uint32_t numVertices, const pbr_float4* normals, uint32_t numNormals ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateGeometry before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_geometry( mCtx, vertices, numVertices, normals, numNormals ), "pbr_update_geometry" );
+	this->resetSampleCount();
+}
+
 void PathTracer::refitOrderedWalk( bool on ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );

@@ -83,6 +83,10 @@ class PathTracer {
 		// pbr_update_vertices: new positions for the scene's vertices (count as uploaded), the BVH refitted on the device; starts
 		// a new accumulation.  The host copy of the scene (buffers()) keeps the uploaded vertices and boxes.
 		void updateVertices( const pbr_float4* vertices, uint32_t numVertices );
+		// pbr_update_geometry: new positions and, unless null, new vertex normals (counts as uploaded): what updateVertices
+		// rebuilds plus the Phong patches, with boxes thick enough for the configured render.phong_tessellation — the update
+		// that works while Phong tessellation is on; starts a new accumulation
+		void updateGeometry( const pbr_float4* vertices, uint32_t numVertices, const pbr_float4* normals, uint32_t numNormals );
 		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
 		void refitOrderedWalk( bool on );
 

@@ -15,7 +15,19 @@ spread (min .. max), wall times around the synchronous calls:
   (d) the cost of a stale tree: Msamples/s of pbr_render( --frames ) on the refitted tree against the tree pbr_build_bvh
       builds for the moved vertices, at both amplitudes, the same pinned plan.  (The tree host/bvh_builder.cpp builds for moved
       vertices needs a loader path for arrays that the host library does not have; that leg is not in this script.)
-Append the output of the three scenes to profiles/r09/experiments/refit.txt."""
+Append the output of the three scenes to profiles/r09/experiments/refit.txt.
+
+  python scripts/refit_measure.py --scene ... --phong ALPHA [--reps 7] [--out FILE]
+
+pbr_update_geometry under Phong tessellation instead (profiles/r14/experiments/patch_refit.txt).  The scene's own vertex normals
+are used when most faces have unequal ones; otherwise smooth normals are made (the area-weighted mean of the faces around a
+vertex, facesN = facesV).  Positions move as above, normals with tests/patch_refit_ref.py's seeded perturbation.  Reported:
+  (a) pbr_update_geometry( V', N' ) with phong_tessellation = ALPHA configured: device time, the copy of vertices + normals, wall
+  (b) the same scene's pbr_update_vertices( V' ) with Phong tessellation off: the flat refit — the difference is the price of the
+      patches and the thick boxes
+  (c) pbr_upload_scene( S' ) + pbr_configure, wall: the only way to move Phong geometry without pbr_update_geometry
+  (d) the traffic floor next to (a): the flat refit's, plus 96 B per face of patch records written, 16 B per normal and 16 B per
+      face of normal indices read; the 24 B per face of thick boxes written and read again are listed beside it"""
 import os
 import sys
 import time
@@ -45,10 +57,107 @@ def wall(call):
     return (time.perf_counter() - start) * 1e3
 
 
+def smooth_normals(facesV, vertices):
+    """(facesN, normals): one normal per vertex, the normalised sum of the cross products of the faces around it."""
+    f = facesV[:, :3].astype(np.int64)
+    v = vertices[:, :3].astype(np.float64)
+    cross = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    total = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(total, f[:, k], cross)
+    length = np.linalg.norm(total, axis=1, keepdims=True)
+    normals = np.zeros((vertices.shape[0], 4), np.float32)
+    normals[:, :3] = np.where(length > 0, total / np.where(length > 0, length, 1.0), [0.0, 1.0, 0.0])
+    facesN = np.ascontiguousarray(facesV.copy())
+    facesN[:, 3] = 0
+    return facesN, normals
+
+
+def measure_phong(pbr, name, alpha, reps):
+    import patch_refit_ref
+    import refit_ref
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = {k: np.ascontiguousarray(v) for k, v in sc.arrays().items()}
+    flat_cfg, cam, px = sc.config(W, H), sc.camera(), pbr.pixel_dimension(W, H)
+    cfg = pbr.Config.from_buffer_copy(flat_cfg)
+    cfg.phong_tessellation = alpha
+    faces, vertices, nodes = a["facesV"].shape[0], a["vertices"].shape[0], a["bvh"].shape[0]
+
+    def curved(facesN, normals):
+        n = normals[facesN[:, :3].astype(np.int64), :3]
+        t = (n[:, 0] - n[:, 1]) + (n[:, 1] - n[:, 2])
+        return int((np.abs(t) > np.float32(0.000001)).any(axis=1).sum())
+
+    facesN, normals, source = a["facesN"], a["normals"], "the scene's own normals"
+    usable = normals.shape[0] > 0 and facesN.shape[0] == faces and int(facesN[:, :3].max()) < normals.shape[0]
+    if not usable or 2 * curved(facesN, normals) < faces:
+        facesN, normals = smooth_normals(a["facesV"], a["vertices"])
+        source = "smooth normals made here (facesN = facesV)"
+    lines = ["== %s under Phong tessellation %g: %d faces (%d with unequal normals), %d vertices, %d normals, %d nodes; %s"
+             % (name, alpha, faces, curved(facesN, normals), vertices, normals.shape[0], nodes, source)]
+
+    def desc_with(v, n, bvh):
+        d = pbr.SceneDesc.from_buffer_copy(sc.desc)
+        d.vertices, d.bvh, d.num_nodes = v.ctypes.data, bvh.ctypes.data, bvh.shape[0]
+        d.facesN, d.normals, d.num_normals = facesN.ctypes.data, n.ctypes.data, n.shape[0]
+        return d
+
+    dev, flat = pbr.Device(0), pbr.Device(0)
+    dev.upload_scene(desc_with(a["vertices"], normals, a["bvh"]))
+    dev.configure(cfg)
+    flat.upload_scene(desc_with(a["vertices"], normals, a["bvh"]))
+    flat.configure(flat_cfg)
+    dev.update_geometry(a["vertices"], normals)                      # the first call makes the tables
+    lines.append("tables: %d bytes for the patch refit beside the refit's %d" % (dev.patch_refit_info()["device_bytes"], dev.refit_info()["device_bytes"]))
+    for amp in refit_ref.AMPLITUDES:
+        v = refit_ref.deform(a["facesV"], a["vertices"], amp, seed=3)
+        n = patch_refit_ref.perturb_normals(normals, seed=3)
+        device_ms, copy_ms, wall_ms, flat_device_ms, flat_wall_ms = [], [], [], [], []
+        for _ in range(reps):
+            dev.update_geometry(a["vertices"], normals)
+            wall_ms.append(wall(lambda: dev.update_geometry(v, n)))
+            device_ms.append(dev.last_kernel_ms())
+            copy_ms.append(dev.refit_info()["upload_ms"])
+            flat.update_vertices(a["vertices"])
+            flat_wall_ms.append(wall(lambda: flat.update_vertices(v)))
+            flat_device_ms.append(flat.last_kernel_ms())
+        lines.append("(a) %-5s update_geometry, phong %g: device %s ms | copy %s ms | wall %s ms" % (amp, alpha, spread(device_ms), spread(copy_ms), spread(wall_ms)))
+        lines.append("(b) %-5s update_vertices, phong off: device %s ms | wall %s ms" % (amp, spread(flat_device_ms), spread(flat_wall_ms)))
+        refitted = dev.read_bvh()                                        # kept alive: the descriptor only points at it
+        moved = desc_with(v, n, refitted)
+        other = pbr.Device(0)
+
+        def fresh():
+            other.upload_scene(moved)
+            other.configure(cfg)
+        upload = [wall(fresh) for _ in range(reps)]
+        other.close()
+        lines.append("(c) %-5s upload_scene( S' ) + configure: wall %s ms" % (amp, spread(upload)))
+        face_normals = 1 if dev.scene_bytes()["faces"] else 0
+        refit_floor = 16 * vertices + 16 * faces + 48 * faces + 24 * nodes + face_normals * (48 + 16) * faces
+        floor = refit_floor + 96 * faces + 16 * normals.shape[0] + 16 * faces
+        rate = floor / (float(np.median(device_ms)) * 1e-3)
+        lines.append("(d) %-5s traffic floor %d bytes (the flat refit's %d) -> %.1f GB/s = %.1f %% of 8 TB/s; thick boxes, written and read again: %d bytes more"
+                     % (amp, floor, refit_floor, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S, 48 * faces))
+    dev.close()
+    flat.close()
+    return lines
+
+
 def main():
     import refit_ref
     pbr = pbr_loader.load()
     name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
+    if "--phong" in sys.argv:
+        text = "\n".join(measure_phong(pbr, name, float(arg("--phong", "0.6")), reps)) + "\n"
+        sys.stdout.write(text)
+        if "--out" in sys.argv:
+            with open(arg("--out", ""), "a") as f:
+                f.write(text)
+        return
     kind, seed, triangles = SCENES[name]
     pbr.cfg_reset()
     pbr.cfg_set(**{"render.max_depth": 3})
