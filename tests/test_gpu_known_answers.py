@@ -56,7 +56,7 @@ def look(pbr, eye, center):
     return cam
 
 
-@pytest.mark.parametrize("traversal", [0, 1, 2])
+@pytest.mark.parametrize("traversal", [0, 1, 2, 3])
 def test_single_triangle_distances_by_hand(pbr, device, traversal):
     """flatTriAndRayIntersect (pt_intersect.cl:92-129) through the stackless walk: rays straight down on the triangle
     hit at their height, rays beside it or from below its plane's far side in the wrong direction miss; one node visit
@@ -137,7 +137,7 @@ def test_depth_exhausted_paths_contribute_nothing(pbr, device, brdf, traversal, 
     assert c["paths"] == w * h * 3 and c["nodes"] == c["paths"] and c["hits"] == int(hit.sum()) * 3
 
 
-@pytest.mark.parametrize("traversal", [0, 1, 2])
+@pytest.mark.parametrize("traversal", [0, 1, 2, 3])
 def test_closest_hits_against_brute_force_in_float64(pbr, device, traversal):
     """The walk over the host-built BVH (20 k triangles) returns the geometric closest hit: Moeller-Trumbore over ALL
     triangles in float64 numpy, no tree, no oracle."""
