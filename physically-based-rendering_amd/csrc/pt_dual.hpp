@@ -15,7 +15,7 @@
 // In registers per slot: ray, 1 / direction, cursor, closest hit, the parked leaf, mode, the walk's counters (17).  Everything
 // else a path carries between bounces (PixelState's cold half: 16 dwords) lives in LDS, in four lane-linear 16-byte planes
 // per slot behind the staged tree top (P.slotBase; 2 x 64 B x 1024 lanes = 128 KiB, which leaves 1016 staged records), and is
-// in registers only while its slot is shaded.  125 VGPRs, no scratch (BRDF 1 without lights).
+// in registers only while its slot is shaded.  121 VGPRs (125 up to round 14), no scratch (BRDF 1 without lights).
 // Per path the sequence of visits, face tests and random draws is the reference's (pathtracing.cl:207-334, pt_bvh.cl:75-125):
 // same image, same debug image, same counters.
 #ifdef PT_NODE_PHASE_ASM
@@ -47,13 +47,13 @@
 // need the records (EXEC, the visit counter) in front of the wait instead of behind it: +0.9 %; the next request issued
 // straight from the two masks, its bookkeeping behind the loads, and the parked lanes' leaf words collected once, when the
 // phase ends: +0.3 %.  The loop is bound by the length of its dependent chain, not by instruction issue.
-#define PT_DUAL_SLAB( n0a, n0b, n0c, n0d, n1a, n1b, oxy, ozz, ixy, izz ) \
+#define PT_DUAL_SLAB( n0a, n0b, n0c, n0d, n1a, n1b, oxy, ozi, ixy ) \
 		"v_pk_add_f32 v[54:55], v[" n0a ":" n0b "], " oxy " neg_lo:[0,1] neg_hi:[0,1]\n" \
 		"v_pk_add_f32 v[56:57], v[" n0c ":" n0d "], " oxy " neg_lo:[0,1] neg_hi:[0,1]\n" \
-		"v_pk_add_f32 v[58:59], v[" n1a ":" n1b "], " ozz " neg_lo:[0,1] neg_hi:[0,1]\n" \
+		"v_pk_add_f32 v[58:59], v[" n1a ":" n1b "], " ozi " op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n" \
 		"v_pk_mul_f32 v[54:55], " ixy ", v[54:55]\n" \
 		"v_pk_mul_f32 v[56:57], " ixy ", v[56:57]\n" \
-		"v_pk_mul_f32 v[58:59], " izz ", v[58:59]\n" \
+		"v_pk_mul_f32 v[58:59], " ozi ", v[58:59] op_sel:[1,0]\n" \
 		"v_min_f32 v60, v54, v56\n" \
 		"v_min_f32 v61, v55, v57\n" \
 		"v_min_f32 v62, v58, v59\n" \
@@ -105,7 +105,7 @@
 		"s_cbranch_execz " skip "f\n" \
 		"v_add_u32 %[visits" W "], 1, %[visits" W "]\n" \
 		wait \
-		PT_DUAL_SLAB( r0, r1, r2, r3, r4, r5, "%[oxy" W "]", "%[ozz" W "]", "%[ixy" W "]", "%[izz" W "]" ) \
+		PT_DUAL_SLAB( r0, r1, r2, r3, r4, r5, "%[oxy" W "]", "%[ozi" W "]", "%[ixy" W "]" ) \
 		"v_cmpx_lt_f32 %[eps], v61\n" \
 		"v_cmpx_gt_f32 %[rayT" W "], v60\n" \
 		"v_cmpx_le_f32 v60, v61\n" \
@@ -179,13 +179,20 @@
 #define PT_DUAL_REGS_A "46", "47", "48", "49", "50", "51", "52", "53"
 #define PT_DUAL_REGS_B "64", "65", "66", "67", "68", "69", "70", "71"
 
-// refA / refB: the walks' cursors (< 0: this slot sits the phase out).  A lane whose walk parks on a hit leaf gets the
-// leaf's word and tNear in leafWordA / tNearA (leafWordB / tNearB); the caller passes 0 in and reads != 0 as "parked".
+// walkA / walkB: the lanes whose slot A / B walks (wave masks: the caller's ballots of mode == MODE_NODE, which implies a cursor
+// >= 0); refA / refB: the slots' cursors, handed over as they are — a lane outside its walk's mask is in no fetch and no visit of
+// that walk, so its cursor, leaf word and tNear come back untouched.  A lane whose walk parks on a hit leaf gets the leaf's word
+// and tNear in leafWordA / tNearA (leafWordB / tNearB): the caller hands the slots' own fields over (0 for every walking lane:
+// the leaf phase and startWalkDual clear the word) and reads != 0 as "parked"; tNear is defined only where the word is != 0.
+// nodes: P.nodes as the caller holds it — an opaque scalar, see pathTracingDual.
+// The z operands are ONE pair per walk, { origin.z, 1 / dir.z } (round 15): the slab test picks the half it needs by op_sel
+// (v_pk_add: the low half for both results; v_pk_mul: the high half for both), where it used to read { z, z } pairs that the
+// caller rebuilt with a v_mov each, four per round.
 PT_DEV void nodePhaseDualPipe(
-	const DevParams& P,
-	const f2v oxyA, const f2v ozzA, const f2v ixyA, const f2v izzA, float rayTA,
-	const f2v oxyB, const f2v ozzB, const f2v ixyB, const f2v izzB, float rayTB,
-	int keep, int& refA, int& refB, unsigned& visitsA, unsigned& visitsB,
+	const DevParams& P, const float4* nodes,
+	const f2v oxyA, const f2v oziA, const f2v ixyA, float rayTA,
+	const f2v oxyB, const f2v oziB, const f2v ixyB, float rayTB,
+	int keep, unsigned long long walkA, unsigned long long walkB, int& refA, int& refB, unsigned& visitsA, unsigned& visitsB,
 	int& leafWordA, float& tNearA, int& leafWordB, float& tNearB
 ) {
 	const float eps = EPSILON5;
@@ -194,8 +201,8 @@ PT_DEV void nodePhaseDualPipe(
 	asm volatile(
 		"s_waitcnt lgkmcnt(0)\n"
 		"s_mov_b64 s[84:85], exec\n"
-		"v_cmp_le_i32 s[86:87], 0, %[refA]\n"
-		"v_cmp_le_i32 s[88:89], 0, %[refB]\n"
+		"s_mov_b64 s[86:87], %[walkA]\n"
+		"s_mov_b64 s[88:89], %[walkB]\n"
 		"v_mov_b32 v53, %[refA]\n"
 		"v_mov_b32 v71, %[refB]\n"
 		PT_DUAL_FETCH( "s[86:87]", "v53", "46:49", "50", "53", "10" )
@@ -228,9 +235,9 @@ PT_DEV void nodePhaseDualPipe(
 	"21:\n"
 		: [refA] "+v"( refA ), [refB] "+v"( refB ), [visitsA] "+v"( visitsA ), [visitsB] "+v"( visitsB ),
 		  [leafWordA] "+v"( leafWordA ), [tNearA] "+v"( tNearA ), [leafWordB] "+v"( leafWordB ), [tNearB] "+v"( tNearB )
-		: [oxyA] "v"( oxyA ), [ozzA] "v"( ozzA ), [ixyA] "v"( ixyA ), [izzA] "v"( izzA ), [rayTA] "v"( rayTA ),
-		  [oxyB] "v"( oxyB ), [ozzB] "v"( ozzB ), [ixyB] "v"( ixyB ), [izzB] "v"( izzB ), [rayTB] "v"( rayTB ),
-		  [keep] "s"( keep ), [numHotBytes] "s"( P.numHotBytes ), [nodes] "s"( P.nodes ), [eps] "s"( eps )
+		: [oxyA] "v"( oxyA ), [oziA] "v"( oziA ), [ixyA] "v"( ixyA ), [rayTA] "v"( rayTA ),
+		  [oxyB] "v"( oxyB ), [oziB] "v"( oziB ), [ixyB] "v"( ixyB ), [rayTB] "v"( rayTB ),
+		  [keep] "s"( keep ), [walkA] "s"( walkA ), [walkB] "s"( walkB ), [numHotBytes] "s"( P.numHotBytes ), [nodes] "s"( nodes ), [eps] "s"( eps )
 		: "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63",
 		  "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71",
 		  // (v72 / v73 — the cursors until round 11 — and s80 - s82, s[90:93] — the flags and the parked masks — are not used any
@@ -344,31 +351,33 @@ __global__ __launch_bounds__( PBR_BLOCK, 4 ) void pathTracingDual( const DevPara
 
 	while( __ballot( A.mode != MODE_DONE || B.mode != MODE_DONE ) != 0ull ) {
 		// ---- node phase: both slots of every lane ----------------------------------------------------
-		if( A.mode == MODE_NODE || B.mode == MODE_NODE ) {
-			const int walking = __popcll( __ballot( A.mode == MODE_NODE ) ) + __popcll( __ballot( B.mode == MODE_NODE ) );
-			const int keep = walking - P.phPark;
-			const f2v oxyA = { A.ray.origin.x, A.ray.origin.y }, ozzA = { A.ray.origin.z, A.ray.origin.z }, ixyA = { A.invDir.x, A.invDir.y }, izzA = { A.invDir.z, A.invDir.z };
-			const f2v oxyB = { B.ray.origin.x, B.ray.origin.y }, ozzB = { B.ray.origin.z, B.ray.origin.z }, ixyB = { B.invDir.x, B.invDir.y }, izzB = { B.invDir.z, B.invDir.z };
-			int refA = ( A.mode == MODE_NODE ) ? A.cur : -1;      // a slot that is not walking sits the phase out
-			int refB = ( B.mode == MODE_NODE ) ? B.cur : -1;
-			int leafWordA = 0, leafWordB = 0;
-			float tNearA = 0.0f, tNearB = 0.0f;
+		// Round 15: what a round costs around nodePhaseDualPipe (profiles/r15/experiments/dual_round_cost.txt).  The test is
+		// wave-uniform — the two ballots are the walks' masks, which the phase takes as they are (no cursor select in, none out) —
+		// so EXEC is the loop's and nothing is saved or restored around the phase; the slots' cursor, leaf word and tNear are the
+		// phase's operands themselves (no zeroed temporaries, no copies back).  With the phase under a scalar branch hipcc keeps
+		// the node and face pointers in SGPRs across rounds: the s_load_dwordx4 from kernel-argument memory that stood in front
+		// of every node phase's first request, fully exposed, and in front of every leaf phase's, stands in front of the loop.
+		// P.nodes is handed over as an opaque scalar, which forces the same where the compiler would not do it by itself; alone
+		// that was worth nothing measurable (57.93 against 58.00 ms, the runs overlap), and here it only steers the allocator:
+		// without it the chained pathTracingDual<0, true, true> keeps 12 B in scratch instead of 8.
+		const unsigned long long walkA = __builtin_amdgcn_ballot_w64( A.mode == MODE_NODE ), walkB = __builtin_amdgcn_ballot_w64( B.mode == MODE_NODE );
+
+		if( ( walkA | walkB ) != 0ull ) {
+			const int keep = __popcll( walkA ) + __popcll( walkB ) - P.phPark;
+			const f2v oxyA = { A.ray.origin.x, A.ray.origin.y }, oziA = { A.ray.origin.z, A.invDir.z }, ixyA = { A.invDir.x, A.invDir.y };
+			const f2v oxyB = { B.ray.origin.x, B.ray.origin.y }, oziB = { B.ray.origin.z, B.invDir.z }, ixyB = { B.invDir.x, B.invDir.y };
+			const float4* nodes = P.nodes;
+			asm volatile( "" : "+s"( nodes ) );      // opaque: not rematerialised from kernel-argument memory
 			__builtin_amdgcn_s_setprio( PT_WALK_PRIO );
-			nodePhaseDualPipe( P, oxyA, ozzA, ixyA, izzA, A.t, oxyB, ozzB, ixyB, izzB, B.t, ( keep < 0 ) ? 0 : keep, refA, refB, A.nodes, B.nodes,
-			                   leafWordA, tNearA, leafWordB, tNearB );
+			nodePhaseDualPipe( P, nodes, oxyA, oziA, ixyA, A.t, oxyB, oziB, ixyB, B.t, ( keep < 0 ) ? 0 : keep, walkA, walkB, A.cur, B.cur, A.nodes, B.nodes,
+			                   A.leafWord, A.leafTNear, B.leafWord, B.leafTNear );
 			__builtin_amdgcn_s_setprio( 0 );
 
 			if( A.mode == MODE_NODE ) {
-				A.cur = refA;
-				A.leafWord = leafWordA;
-				A.leafTNear = tNearA;
-				A.mode = ( leafWordA != 0 ) ? MODE_LEAF : ( ( refA < 0 ) ? MODE_SHADE : MODE_NODE );
+				A.mode = ( A.leafWord != 0 ) ? MODE_LEAF : ( ( A.cur < 0 ) ? MODE_SHADE : MODE_NODE );
 			}
 			if( B.mode == MODE_NODE ) {
-				B.cur = refB;
-				B.leafWord = leafWordB;
-				B.leafTNear = tNearB;
-				B.mode = ( leafWordB != 0 ) ? MODE_LEAF : ( ( refB < 0 ) ? MODE_SHADE : MODE_NODE );
+				B.mode = ( B.leafWord != 0 ) ? MODE_LEAF : ( ( B.cur < 0 ) ? MODE_SHADE : MODE_NODE );
 			}
 		}
 
