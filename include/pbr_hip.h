@@ -34,10 +34,11 @@ extern "C" {
  * entry point changes (round 5 grew pbr_config from 60 to 68 bytes; version 7 added pbr_render_dof, version 8 pbr_render_adaptive,
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
  * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
- * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry).  A caller that loads the library at run time — or
+ * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry, version 15 pbr_set_parts, pbr_update_transforms and
+ * pbr_read_geometry).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 14
+#define PBR_ABI_VERSION 15
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -286,6 +287,80 @@ int pbr_refit_ordered_walk( pbr_ctx* ctx, int on );
  * after an upload from a host copy the upload keeps, and freed with the scene (pbr_diag_patch_refit_info, pbr_hip_diag.h). */
 int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices,
                          const pbr_float4* normals, uint32_t num_normals );
+/* RIGID OR AFFINE MOTION PER PART, COMPUTED ON THE DEVICE (ABI version 15).  The motion callers mostly have is a few matrices —
+ * doors, wheels, props, a turntable —, not new vertices: pbr_set_parts says once which part every vertex (and every vertex
+ * normal) belongs to and captures the REST POSE, pbr_update_transforms then takes num_parts matrices, computes V' and N' on
+ * the device from the rest pose and does exactly what pbr_update_geometry( V', N' ) does.  Only the matrices travel.
+ *
+ * pbr_set_parts: vertex_part[num_vertices], each < num_parts, num_vertices the upload's count; normal_part likewise for the
+ * vertex normals —
+ *   normal_part == NULL with num_normals == 0   the normals are never transformed (an update then is a
+ *                                               pbr_update_geometry( V', NULL, 0 ));
+ *   otherwise                                   num_normals must be the upload's count, and the scene must have usable vertex
+ *                                               normals (pbr_update_geometry's condition for new normals).
+ * The call captures the rest pose: the vertex positions as they are on the device NOW, copied device to device, and with normal
+ * parts the normals the context holds now (the upload's, or those of the last pbr_update_geometry that brought some).
+ * num_parts == 0 with both pointers NULL drops the parts and frees their buffers; a second call replaces parts and rest pose;
+ * pbr_upload_scene drops them; pbr_configure, pbr_update_vertices and pbr_update_geometry leave them alone — a later transform
+ * starts again from the rest pose, not from what those calls wrote.
+ * Refusals, each leaving the context and the parts that were set unchanged:
+ *   PBR_ESTATE  no scene; normal parts for a scene without usable vertex normals.
+ *   PBR_EINVAL  a null context; null vertex_part; a count other than the upload's; normal_part and num_normals disagreeing about
+ *               NULL / 0; num_parts == 0 with a pointer; an index >= num_parts (the message names the first one).
+ * ALL allocation happens in this call: 16 + 4 bytes per vertex (rest position, part index), the same per normal if normal parts
+ * are given, one 16-byte-per-vertex staging buffer, 96 bytes per part (its record) and a 4-byte flag word
+ * (pbr_diag_transform_info, pbr_hip_diag.h) — and pbr_update_geometry's tables if the scene has patches and no update made them
+ * yet.  pbr_update_transforms allocates nothing.
+ *
+ * pbr_update_transforms: `matrices` is host memory, borrowed for the call, num_parts x 12 floats.  Part k's matrix is row-major
+ * 3 x 4: rows r = 0, 1, 2 are m[4r .. 4r+3], a_r is the first three words of row r, m[4r+3] the translation.  V' and N' are
+ * computed from the REST POSE, never from the current positions: it is not cumulative, there is no drift.
+ * THE DEFINITION, operation by operation in binary32, none fused; dot and cross are pbr_update_geometry's above, `/` and sqrtf
+ * are correctly rounded.
+ *   per part, once, on the host:
+ *     c0 = cross( a1, a2 ), c1 = cross( a2, a0 ), c2 = cross( a0, a1 ), det = dot( a0, c0 );
+ *     if det < 0 every word of c0, c1, c2 is negated.  The nine words travel with the twelve.
+ *   position p of part k:
+ *     p'.x = ( ( m0*p.x + m1*p.y ) + m2*p.z ) + m3, rows 1 and 2 likewise; p'.w = p.w bit for bit
+ *   normal n of part k:
+ *     q.r = dot( c_r, n ), d = dot( q, q );
+ *     if d > 0 and d < inf   n'.xyz = q * ( 1.0f / sqrtf( d ) ) (three multiplications)
+ *     else                   n'.xyz = n.xyz bit for bit;
+ *     n'.w = n.w.  So no normal word is ever NaN.
+ *   AN IDENTITY PART — its twelve words compare equal, as floats, to the identity — copies its rest positions and normals bit
+ *   for bit: -0 stays -0 and a unit normal does not move by an ulp, so unmoved parts ARE unmoved for pbr_denoise_temporal's
+ *   UNMOVED test and for a caller's diff.
+ * THE CONTRACT.  After pbr_set_parts and pbr_update_transforms( M ) every call gives bit for bit what it gives after
+ * pbr_update_geometry( V', N' ) on a context in the same state — pbr_render*, pbr_render_frame, pbr_diag_trace, the counters,
+ * the debug image, pbr_denoise*, pbr_read_bvh, pbr_diag_read_patches, pbr_diag_read_walk — and hence what a fresh upload of S'
+ * gives; in all four traversals (with pbr_refit_ordered_walk for the ordered ones) and under Phong tessellation.  All state
+ * follows pbr_update_geometry's rules unchanged: pbr_configure's state rule (the call counts as a pbr_update_geometry with the
+ * alpha it ran under), pbr_diag_patch_refit_info, pbr_diag_refit_info (its upload_ms now times the asynchronous copy of the part
+ * records from pinned memory) and pbr_diag_relink_info, the temporal history (H is taken before the vertices change;
+ * pbr_temporal_track_motion works through it), and what stays stale.  pbr_last_kernel_ms covers the whole update, the transform
+ * kernels and the read-back of the flag word between them included.
+ * Refusals, each leaving the context, the vertices, the normals and the tree exactly as they were:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  no parts set (the message names pbr_set_parts; a new upload drops them);
+ *   PBR_EINVAL  null `matrices`, or num_parts other than the set one; a matrix word that is not finite; a det that is 0 or not
+ *               finite, or a c word that is not finite (the message names the part);
+ *   then pbr_update_geometry's own refusals, in its order;
+ *   PBR_EINVAL  a coordinate of V' that is not finite — finite matrices can overflow.  This is found ON THE DEVICE, because the
+ *               host never sees V': the transform kernel writes V' to the staging buffer and raises a flag word, the host reads
+ *               its 4 bytes and only then makes the staging buffer the context's vertices (the two pointers are swapped).  The
+ *               normals cannot fail and are written after that check.
+ * OUT OF SCOPE: pbr_multi.h (every rank would take the same matrices: call this on each rank's context), per-vertex skinning
+ * and blend weights, topology changes. */
+int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals,
+                   uint32_t num_parts );
+int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_parts );
+/* The vertex positions and the vertex normals the context holds now — as uploaded, or after any update of any of the three
+ * kinds —, bit for bit, .w included.  pbr_read_bvh's count-only convention: *num_vertices and *num_normals are always set, an
+ * output pointer may be NULL, else its capacity (in quads) must reach the count.  *num_normals is 0 for a scene without usable
+ * vertex normals (they were not kept).  Before the first geometry update the normals are returned from the host copy the upload
+ * keeps.  PBR_EINVAL for a null context, a null count or too little room, PBR_ESTATE without a scene. */
+int pbr_read_geometry( pbr_ctx* ctx, pbr_float4* vertices_out, uint32_t vcap, uint32_t* num_vertices,
+                       pbr_float4* normals_out, uint32_t ncap, uint32_t* num_normals );
 /* The current tree in the wire format: the uploaded nodes, after pbr_update_vertices with the refitted boxes (copied back
  * from the device by this call, not by the update).  *num_nodes = the node count; nodes_out = NULL returns the count only,
  * else capacity >= *num_nodes entries.  A caller's rebuild heuristic (e.g. the growth of the boxes' surface area) reads this. */

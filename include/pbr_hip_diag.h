@@ -130,6 +130,14 @@ int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char*
  * PBR_ESTATE without a scene. */
 int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha );
 
+/* pbr_set_parts / pbr_update_transforms (pbr_hip.h): out[0] the parts (0 if none are set), [1] the device bytes held for them —
+ * 36 per vertex (rest position, staging position, part index), 20 per normal if normal parts are set, 96 per part, 4 of a flag
+ * word —, [2] the successful pbr_update_transforms calls since pbr_set_parts, [3] 1 if the most recent successful update of any
+ * kind was one of them.  *ms (may be NULL): the device time of the transform kernels alone in that update; pbr_last_kernel_ms
+ * covers the whole update.  pbr_set_parts also makes pbr_update_geometry's tables when the scene has patches:
+ * pbr_diag_patch_refit_info's bytes are then no longer 0 before the first update.  PBR_EINVAL for a null context or null out. */
+int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
+
 /* The Phong patch records as they are on the device now: six quads per face, the corners, then the vertex normals, .w = 0.
  * *count = the quads; out = NULL returns the count only, else capacity >= *count quads.  PBR_ESTATE without a scene or for a
  * scene without usable vertex normals, PBR_EINVAL for a null context, null count or too little room. */

@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 14
+ABI_VERSION = 15
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -203,6 +203,10 @@ for _name, _args in (
         ("pbr_update_geometry", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),             # ABI version 14
         ("pbr_diag_patch_refit_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float)]),
         ("pbr_diag_read_patches", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up]),
+        ("pbr_set_parts", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),      # ABI version 15
+        ("pbr_update_transforms", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
+        ("pbr_read_geometry", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up, ctypes.c_void_p, ctypes.c_uint32, _up]),
+        ("pbr_diag_transform_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -244,6 +248,10 @@ if hasattr(host, "pbrh_pt_refit_ordered_walk"):
     host.pbrh_pt_refit_ordered_walk.argtypes = [_vp, ctypes.c_int]
 if hasattr(host, "pbrh_pt_update_geometry"):
     host.pbrh_pt_update_geometry.argtypes = [_vp, _fp, ctypes.c_uint32, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_set_parts"):
+    host.pbrh_pt_set_parts.argtypes = [_vp, _up, ctypes.c_uint32, _up, ctypes.c_uint32, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_transforms"):
+    host.pbrh_pt_update_transforms.argtypes = [_vp, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -458,6 +466,43 @@ class Device:
             return
         normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
         self._check(hip.pbr_update_geometry(self._ctx, vertices.ctypes.data, vertices.shape[0], normals.ctypes.data, normals.shape[0]))
+
+    def set_parts(self, vertex_part, normal_part=None, num_parts=None):
+        """pbr_set_parts: the part of every vertex and, unless None, of every vertex normal (uint32, counts as uploaded), and the
+        number of parts (default: the largest index + 1).  Captures the rest pose — the positions and normals the context holds
+        now.  set_parts(None) drops the parts."""
+        if vertex_part is None:
+            self._check(hip.pbr_set_parts(self._ctx, None, 0, None, 0, 0))
+            return
+        vertex_part = np.ascontiguousarray(vertex_part, np.uint32).reshape(-1)
+        if normal_part is not None:
+            normal_part = np.ascontiguousarray(normal_part, np.uint32).reshape(-1)
+        if num_parts is None:
+            num_parts = int(max(vertex_part.max(initial=0), 0 if normal_part is None else normal_part.max(initial=0))) + 1
+        self._check(hip.pbr_set_parts(self._ctx, vertex_part.ctypes.data, vertex_part.shape[0], None if normal_part is None else normal_part.ctypes.data,
+                                      0 if normal_part is None else normal_part.shape[0], num_parts))
+
+    def update_transforms(self, matrices):
+        """pbr_update_transforms: one row-major 3 x 4 matrix per part, (parts, 12) or (parts, 3, 4) float32.  Positions and
+        normals are computed on the device from the rest pose of set_parts; everything behind is update_geometry's."""
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        self._check(hip.pbr_update_transforms(self._ctx, matrices.ctypes.data, matrices.shape[0]))
+
+    def read_geometry(self):
+        """pbr_read_geometry: (positions (n, 4), normals (m, 4)) as the context holds them now, float32; m = 0 for a scene
+        without usable vertex normals."""
+        nv, nn = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(hip.pbr_read_geometry(self._ctx, None, 0, ctypes.byref(nv), None, 0, ctypes.byref(nn)))
+        vertices, normals = np.empty((nv.value, 4), np.float32), np.empty((nn.value, 4), np.float32)
+        self._check(hip.pbr_read_geometry(self._ctx, vertices.ctypes.data, nv.value, ctypes.byref(nv), normals.ctypes.data, nn.value, ctypes.byref(nn)))
+        return vertices, normals
+
+    def transform_info(self):
+        """pbr_diag_transform_info: the parts, the device bytes held for them, the update_transforms calls since set_parts, whether
+        the last update was one, and the device time of its transform kernels alone."""
+        out, ms = (ctypes.c_uint64 * 4)(), ctypes.c_double()
+        self._check(hip.pbr_diag_transform_info(self._ctx, out, ctypes.byref(ms)))
+        return {"parts": int(out[0]), "device_bytes": int(out[1]), "updates": int(out[2]), "last_update": bool(out[3]), "ms": float(ms.value)}
 
     def read_patches(self):
         """pbr_diag_read_patches: the Phong patch records on the device, (faces, 6, 4) float32 — three corners, three normals."""
@@ -948,6 +993,24 @@ class PathTracer:
         normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
         if host.pbrh_pt_update_geometry(self._h, _as_fp(vertices), vertices.shape[0], None if normals is None else _as_fp(normals),
                                         0 if normals is None else normals.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def setParts(self, vertex_part, normal_part=None, num_parts=None):
+        """PathTracer::setParts: Device.set_parts on the tracer's context."""
+        vertex_part = np.ascontiguousarray(vertex_part, np.uint32).reshape(-1)
+        if normal_part is not None:
+            normal_part = np.ascontiguousarray(normal_part, np.uint32).reshape(-1)
+        if num_parts is None:
+            num_parts = int(max(vertex_part.max(initial=0), 0 if normal_part is None else normal_part.max(initial=0))) + 1
+        if host.pbrh_pt_set_parts(self._h, vertex_part.ctypes.data_as(_up), vertex_part.shape[0],
+                                  None if normal_part is None else normal_part.ctypes.data_as(_up),
+                                  0 if normal_part is None else normal_part.shape[0], num_parts) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updateTransforms(self, matrices):
+        """PathTracer::updateTransforms: Device.update_transforms on the tracer's context; starts a new accumulation."""
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        if host.pbrh_pt_update_transforms(self._h, _as_fp(matrices), matrices.shape[0]) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def refitOrderedWalk(self, on):

@@ -34,6 +34,7 @@
 #include "pt_refit.hpp"
 #include "pt_patch_refit.hpp"
 #include "pt_relink.hpp"
+#include "pt_transform.hpp"
 
 using ptk::DevParams;
 
@@ -206,6 +207,23 @@ struct pbr_ctx {
 	double lastRelinkMs = 0.0;     // of the last pbr_update_vertices: device time of the re-link kernels alone,
 	uint32_t lastRelinkLaunches = 0;   // their number,
 	bool lastRelinked = false;     // and whether it re-linked at all
+	// pbr_set_parts / pbr_update_transforms (pt_transform_host.hpp, pt_transform.hpp): the REST POSE — a copy of the positions
+	// and, with normal parts, of the normals as they were when the parts were set —, the part index of every vertex and normal,
+	// the staging buffer V' is written to before it becomes dVertices (the two pointers are swapped: nothing caches dVertices,
+	// every launch takes it from the context), the part records and the flag word of a position that is not finite.  All of it
+	// is allocated by pbr_set_parts and freed by the next one, by freeParts and with the scene; the records and the flag have a
+	// pinned host twin, so neither copy waits for a staging copy of pageable memory
+	uint32_t numParts = 0;
+	bool partNormals = false;      // normal parts were given: the normals are transformed too
+	float4* dPartRest = nullptr, * dPartRestNormals = nullptr, * dPartStaged = nullptr, * dPartRecords = nullptr;
+	unsigned* dPartOfVertex = nullptr, * dPartOfNormal = nullptr, * dPartFlag = nullptr;
+	ptx::PartRecord* hPartRecords = nullptr;
+	unsigned* hPartFlag = nullptr;
+	uint64_t partBytes = 0;        // device bytes of all of the above
+	uint32_t transformUpdates = 0; // successful pbr_update_transforms calls since pbr_set_parts
+	bool lastUpdateTransforms = false;   // the most recent successful update was a pbr_update_transforms
+	hipEvent_t evXfStart = nullptr, evXfStop = nullptr, evXfNormalsStart = nullptr, evXfNormalsStop = nullptr;
+	double lastTransformMs = 0.0;  // of the last pbr_update_transforms: device time of the transform kernels alone
 
 	// configuration + images
 	bool configured = false;
@@ -338,7 +356,29 @@ void freeWalkStreams( pbr_ctx* ctx ) {
 	ctx->relinkRuns.clear();
 }
 
+// pbr_set_parts( 0 parts ), a second pbr_set_parts, pbr_upload_scene: the parts, the rest pose and their buffers go.
+void freeParts( pbr_ctx* ctx ) {
+	for( void* p : { (void*) ctx->dPartRest, (void*) ctx->dPartRestNormals, (void*) ctx->dPartStaged, (void*) ctx->dPartRecords, (void*) ctx->dPartOfVertex,
+	                 (void*) ctx->dPartOfNormal, (void*) ctx->dPartFlag } ) {
+		(void) hipFree( p );
+	}
+
+	(void) hipHostFree( ctx->hPartRecords );
+	(void) hipHostFree( ctx->hPartFlag );
+	ctx->dPartRest = ctx->dPartRestNormals = ctx->dPartStaged = ctx->dPartRecords = nullptr;
+	ctx->dPartOfVertex = ctx->dPartOfNormal = ctx->dPartFlag = nullptr;
+	ctx->hPartRecords = nullptr;
+	ctx->hPartFlag = nullptr;
+	ctx->numParts = 0;
+	ctx->partNormals = false;
+	ctx->partBytes = 0;
+	ctx->transformUpdates = 0;
+	ctx->lastTransformMs = 0.0;
+}
+
 void freeScene( pbr_ctx* ctx ) {
+	freeParts( ctx );
+	ctx->lastUpdateTransforms = false;
 	(void) hipFree( ctx->dNodes );
 	freeWalkStreams( ctx );
 	(void) hipFree( ctx->dTris );
@@ -1455,6 +1495,10 @@ int pbr_create( int device, pbr_ctx** out ) {
 	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStop ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStart ) );
 	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStop ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evXfStart ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evXfStop ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evXfNormalsStart ) );
+	HIP_TRY( ctx, hipEventCreate( &ctx->evXfNormalsStop ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChainCarry, sizeof( float ) ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCounters, sizeof( unsigned long long ) * kCounterSlots ) );
 	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dWork, kWorkBytes ) );
@@ -1490,6 +1534,10 @@ void pbr_destroy( pbr_ctx* ctx ) {
 		(void) hipEventDestroy( ctx->evFoldStop );
 		(void) hipEventDestroy( ctx->evRelinkStart );
 		(void) hipEventDestroy( ctx->evRelinkStop );
+		(void) hipEventDestroy( ctx->evXfStart );
+		(void) hipEventDestroy( ctx->evXfStop );
+		(void) hipEventDestroy( ctx->evXfNormalsStart );
+		(void) hipEventDestroy( ctx->evXfNormalsStop );
 		(void) hipFree( ctx->dChainCarry );
 		(void) hipStreamDestroy( ctx->stream );
 	}
@@ -1592,6 +1640,11 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 		PBR_TRY( keep( (void**) &ctx->dRefitRecordOf, refit.recordOf.data(), sizeof( int ) * refit.recordOf.size() ) );
 		PBR_TRY( keep( (void**) &ctx->dRefitTop, refit.topNodes.data(), sizeof( uint32_t ) * refit.topNodes.size() ) );
 		PBR_TRY( keep( (void**) &ctx->dRefitLevelFirst, refit.topLevelFirst.data(), sizeof( uint32_t ) * refit.topLevelFirst.size() ) );
+	}
+	else {
+		// no refit, but pbr_read_geometry still answers: the positions alone, outside refitBytes
+		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dVertices, std::max<size_t>( sizeof( pbr_float4 ) * s->num_vertices, 16 ) ) );
+		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, s->vertices, sizeof( pbr_float4 ) * s->num_vertices, hipMemcpyHostToDevice ) );
 	}
 
 	ctx->refitGroups = refit.numGroups();
@@ -1783,16 +1836,49 @@ struct PatchUpdate {
 	uint32_t num_normals;
 };
 
-// pbr_update_vertices (patches == nullptr) and pbr_update_geometry: the checks, the copy, the launches, the state.
-int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches ) {
-	if( !ctx->hasScene ) {
-		return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene", call );
+// What pbr_update_transforms brings INSTEAD of positions and normals: the matrices V' and N' are computed from on the device.
+struct TransformUpdate {
+	const float* matrices;
+	uint32_t num_parts;
+};
+
+// pbr_denoise_temporal under motion tracking: H, the positions the history was made under, is a copy of dVertices taken before
+// an update replaces them.  The copy runs on the stream and is waited for.
+int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
+	const size_t bytes = std::max<size_t>( sizeof( pbr_float4 ) * ctx->numVertices, 16 );
+	hipError_t kept = ( ctx->dHistVertices != nullptr ) ? hipSuccess : hipMalloc( (void**) &ctx->dHistVertices, bytes );
+	kept = ( kept != hipSuccess ) ? kept : hipMemcpyAsync( ctx->dHistVertices, ctx->dVertices, sizeof( pbr_float4 ) * ctx->numVertices, hipMemcpyDeviceToDevice, ctx->stream );
+	kept = ( kept != hipSuccess ) ? kept : hipStreamSynchronize( ctx->stream );
+
+	if( kept != hipSuccess ) {
+		ctx->temporal.drop();
+		return fail( ctx, PBR_EDEVICE, "%s: keeping the history's vertex positions: %s", call, hipGetErrorString( kept ) );
 	}
 
-	PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error, call ) );
+	return PBR_OK;
+}
 
-	if( patches != nullptr ) {
-		PBR_TRY( checkRefitNormals( patches->normals, patches->num_normals, ctx->numNormals, &ctx->error ) );
+// pbr_update_vertices (patches == nullptr), pbr_update_geometry and pbr_update_transforms (moves != nullptr: vertices is null,
+// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set): the checks, the step
+// that brings V' and N' to the device — two copies from the host, or the transform launches —, the shared launches, the state.
+int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches, const TransformUpdate* moves = nullptr ) {
+	if( moves != nullptr ) {
+		if( ctx->numParts == 0 ) {
+			return fail( ctx, PBR_ESTATE, "pbr_update_transforms without parts: pbr_set_parts declares them and captures the rest pose (a new upload drops them)" );
+		}
+
+		PBR_TRY( checkTransforms( moves->matrices, moves->num_parts, ctx->numParts, ctx->hPartRecords, &ctx->error ) );
+	}
+	else {
+		if( !ctx->hasScene ) {
+			return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene", call );
+		}
+
+		PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error, call ) );
+
+		if( patches != nullptr ) {
+			PBR_TRY( checkRefitNormals( patches->normals, patches->num_normals, ctx->numNormals, &ctx->error ) );
+		}
 	}
 	if( !ctx->refit.nested ) {
 		return fail( ctx, PBR_ESTATE, "%s: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", call, ctx->refit.why.c_str() );
@@ -1828,32 +1914,70 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 		PBR_TRY( ensureRelinkTables( ctx ) );
 	}
 
-	// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
-	// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below does
-	// not: it waits for the copy
-	if( ctx->temporal.update() ) {
-		const size_t bytes = std::max<size_t>( sizeof( pbr_float4 ) * ctx->numVertices, 16 );
-		hipError_t kept = ( ctx->dHistVertices != nullptr ) ? hipSuccess : hipMalloc( (void**) &ctx->dHistVertices, bytes );
-		kept = ( kept != hipSuccess ) ? kept : hipMemcpyAsync( ctx->dHistVertices, ctx->dVertices, sizeof( pbr_float4 ) * ctx->numVertices, hipMemcpyDeviceToDevice, ctx->stream );
-		kept = ( kept != hipSuccess ) ? kept : hipStreamSynchronize( ctx->stream );
+	const uint32_t F = ctx->numFaces;
 
-		if( kept != hipSuccess ) {
-			ctx->temporal.drop();
-			return fail( ctx, PBR_EDEVICE, "%s: keeping the history's vertex positions: %s", call, hipGetErrorString( kept ) );
+	// the step that brings V' and N' to the device: two copies from the host, or the transform launches
+	if( moves == nullptr ) {
+		// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
+		// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below
+		// does not: it waits for the copy
+		if( ctx->temporal.update() ) {
+			PBR_TRY( keepHistoryVertices( ctx, call ) );
+		}
+
+		const auto uploadStart = std::chrono::steady_clock::now();
+		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
+
+		if( gathers && patches->normals != nullptr ) {
+			HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, patches->normals, sizeof( pbr_float4 ) * patches->num_normals, hipMemcpyHostToDevice ) );
+		}
+
+		ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	}
+	else {
+		// V' goes to the staging buffer first: finite matrices can overflow, the host never sees V', and a refused call leaves the
+		// context as it was.  So H is copied before the temporal policy hears of an update (a copy nobody reads if the call is
+		// refused), the kernel raises a flag word, the host reads its 4 bytes, and only then the staging buffer becomes dVertices
+		const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
+
+		if( keepsHistory ) {
+			PBR_TRY( keepHistoryVertices( ctx, call ) );
+		}
+
+		const uint32_t V = ctx->numVertices;
+		const auto uploadStart = std::chrono::steady_clock::now();
+		*ctx->hPartFlag = 0u;
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->dPartRecords, ctx->hPartRecords, sizeof( ptx::PartRecord ) * ctx->numParts, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->dPartFlag, ctx->hPartFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
+		const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+		HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
+		hipLaunchKernelGGL( ptr::transformVertices, dim3( ( V + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dPartRest, ctx->dPartOfVertex,
+		                    ctx->dPartRecords, ctx->dPartStaged, ctx->dPartFlag, (int) V );
+		HIP_TRY( ctx, hipGetLastError() );
+		HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->hPartFlag, ctx->dPartFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+
+		if( *ctx->hPartFlag != 0u ) {
+			return fail( ctx, PBR_EINVAL, "pbr_update_transforms: a transformed position is not finite (the matrices are finite, their product with the rest pose overflows; found on the device)" );
+		}
+
+		ctx->temporal.update();   // the H it asks for is kept already
+		std::swap( ctx->dVertices, ctx->dPartStaged );
+		ctx->lastRefitUploadMs = uploadMs;
+
+		if( ctx->partNormals ) {
+			const uint32_t N = ctx->numNormals;
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
+			hipLaunchKernelGGL( ptr::transformNormals, dim3( ( N + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dPartRestNormals, ctx->dPartOfNormal,
+			                    ctx->dPartRecords, ctx->dPatchNormals, (int) N );
+			HIP_TRY( ctx, hipGetLastError() );
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
 		}
 	}
 
-	const auto uploadStart = std::chrono::steady_clock::now();
-	HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
-
-	if( gathers && patches->normals != nullptr ) {
-		HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, patches->normals, sizeof( pbr_float4 ) * patches->num_normals, hipMemcpyHostToDevice ) );
-	}
-
-	ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
-
-	const uint32_t F = ctx->numFaces;
-	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dVertices, ctx->dTris, (int) F );
 	HIP_TRY( ctx, hipGetLastError() );
 
@@ -1899,6 +2023,19 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 	ctx->lastUpdateGeometry = ( patches != nullptr );
 	ctx->patchAlpha = alpha;
 	ctx->geometryUpdates += ( patches != nullptr ) ? 1u : 0u;
+	ctx->lastUpdateTransforms = ( moves != nullptr );
+
+	if( moves != nullptr ) {
+		float ms = 0.0f, normalsMs = 0.0f;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
+
+		if( ctx->partNormals ) {
+			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
+		}
+
+		ctx->lastTransformMs = (double) ms + (double) normalsMs;
+		ctx->transformUpdates++;
+	}
 
 	if( relinks ) {
 		// the eight first references are the context's too (applyWalk): 32 bytes of header, no node, box or record
@@ -1935,6 +2072,150 @@ int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
 
 	const PatchUpdate patches = { normals, num_normals };
 	return updateScene( ctx, "pbr_update_geometry", vertices, num_vertices, &patches );
+}
+
+int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals, uint32_t num_parts ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_parts before pbr_upload_scene" );
+	}
+
+	PBR_TRY( checkParts( vertex_part, num_vertices, ctx->numVertices, normal_part, num_normals, ctx->numNormals, num_parts, &ctx->error ) );
+
+	if( normal_part != nullptr && ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_parts: normal parts for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( num_parts == 0 ) {
+		freeParts( ctx );
+		return PBR_OK;
+	}
+	if( ctx->dTriPN != nullptr ) {
+		PBR_TRY( ensurePatchTables( ctx ) );   // a transform gathers the patches again: its tables are made here, not by an update
+	}
+
+	// everything new first: a call that cannot have its buffers leaves the parts that were set
+	const size_t V = num_vertices, N = num_normals, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
+	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * records = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * flag = nullptr;
+	void* hostRecords = nullptr, * hostFlag = nullptr;
+	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, std::max<size_t>( word * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &records, sizeof( ptx::PartRecord ) * num_parts );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostRecords, sizeof( ptx::PartRecord ) * num_parts, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, vertex_part, word * V, hipMemcpyHostToDevice );
+
+	if( normal_part != nullptr ) {
+		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, std::max<size_t>( word * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, normal_part, word * N, hipMemcpyHostToDevice );
+	}
+
+	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
+
+	if( err != hipSuccess ) {
+		for( void* p : { rest, restNormals, staged, records, ofVertex, ofNormal, flag } ) {
+			(void) hipFree( p );
+		}
+
+		(void) hipHostFree( hostRecords );
+		(void) hipHostFree( hostFlag );
+		return fail( ctx, PBR_EDEVICE, "pbr_set_parts: the rest pose and the part tables: %s", hipGetErrorString( err ) );
+	}
+
+	freeParts( ctx );
+	ctx->dPartRest = (float4*) rest;
+	ctx->dPartRestNormals = (float4*) restNormals;
+	ctx->dPartStaged = (float4*) staged;
+	ctx->dPartRecords = (float4*) records;
+	ctx->dPartOfVertex = (unsigned*) ofVertex;
+	ctx->dPartOfNormal = (unsigned*) ofNormal;
+	ctx->dPartFlag = (unsigned*) flag;
+	ctx->hPartRecords = (ptx::PartRecord*) hostRecords;
+	ctx->hPartFlag = (unsigned*) hostFlag;
+	ctx->numParts = num_parts;
+	ctx->partNormals = ( normal_part != nullptr );
+	ctx->partBytes = ( quad + quad + word ) * V + ( ctx->partNormals ? ( quad + word ) * N : 0 ) + sizeof( ptx::PartRecord ) * num_parts + sizeof( unsigned );
+	return PBR_OK;
+}
+
+int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_parts ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	const PatchUpdate patches = { nullptr, 0 };
+	const TransformUpdate moves = { matrices, num_parts };
+	return updateScene( ctx, "pbr_update_transforms", nullptr, 0, &patches, &moves );
+}
+
+int pbr_read_geometry( pbr_ctx* ctx, pbr_float4* vertices_out, uint32_t vcap, uint32_t* num_vertices, pbr_float4* normals_out, uint32_t ncap, uint32_t* num_normals ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_read_geometry before pbr_upload_scene" );
+	}
+	if( num_vertices == nullptr || num_normals == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_geometry: null num_vertices or num_normals" );
+	}
+
+	*num_vertices = ctx->numVertices;
+	*num_normals = ( ctx->dTriPN != nullptr ) ? ctx->numNormals : 0;   // normals nobody can use were not kept
+
+	if( vertices_out != nullptr && vcap < *num_vertices ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_geometry: room for %u vertices, the scene has %u", vcap, *num_vertices );
+	}
+	if( normals_out != nullptr && ncap < *num_normals ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_geometry: room for %u normals, the scene has %u", ncap, *num_normals );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( vertices_out != nullptr && *num_vertices > 0 ) {
+		HIP_TRY( ctx, hipMemcpy( vertices_out, ctx->dVertices, sizeof( pbr_float4 ) * *num_vertices, hipMemcpyDeviceToHost ) );
+	}
+	if( normals_out != nullptr && *num_normals > 0 ) {
+		if( ctx->dPatchNormals != nullptr ) {
+			HIP_TRY( ctx, hipMemcpy( normals_out, ctx->dPatchNormals, sizeof( pbr_float4 ) * *num_normals, hipMemcpyDeviceToHost ) );
+		}
+		else {
+			std::memcpy( normals_out, ctx->patchNormals.data(), sizeof( pbr_float4 ) * *num_normals );   // still the upload's host copy
+		}
+	}
+
+	return PBR_OK;
+}
+
+int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
+	if( ctx == nullptr || out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_transform_info: null argument" );
+	}
+
+	out[0] = ctx->numParts;
+	out[1] = ctx->partBytes;
+	out[2] = ctx->transformUpdates;
+	out[3] = ctx->lastUpdateTransforms ? 1 : 0;
+
+	if( ms != nullptr ) {
+		*ms = ctx->lastTransformMs;
+	}
+
+	return PBR_OK;
 }
 
 int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint32_t* num_nodes ) {

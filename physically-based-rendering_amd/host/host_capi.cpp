@@ -296,6 +296,32 @@ int pbrh_pt_update_geometry( void* tracer, const float* vertices, uint32_t num_v
 	}
 }
 
+int pbrh_pt_set_parts( void* tracer, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals, uint32_t num_parts ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.setParts( vertex_part, num_vertices, normal_part, num_normals, num_parts );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
+int pbrh_pt_update_transforms( void* tracer, const float* matrices, uint32_t num_parts ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateTransforms( matrices, num_parts );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
 	HostTracer* t = static_cast<HostTracer*>( tracer );
 

@@ -451,6 +451,23 @@ void PathTracer::updateGeometry( const pbr_float4* vertices, uint32_t numVertice
 	this->resetSampleCount();
 }
 
+void PathTracer::setParts( const uint32_t* vertexPart, uint32_t numVertices, const uint32_t* normalPart, uint32_t numNormals, uint32_t numParts ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] setParts before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_set_parts( mCtx, vertexPart, numVertices, normalPart, numNormals, numParts ), "pbr_set_parts" );
+}
+
+void PathTracer::updateTransforms( const float* matrices, uint32_t numParts ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateTransforms before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_transforms( mCtx, matrices, numParts ), "pbr_update_transforms" );
+	this->resetSampleCount();
+}
+
 void PathTracer::refitOrderedWalk( bool on ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );

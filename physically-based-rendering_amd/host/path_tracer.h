@@ -87,6 +87,12 @@ class PathTracer {
 		// rebuilds plus the Phong patches, with boxes thick enough for the configured render.phong_tessellation — the update
 		// that works while Phong tessellation is on; starts a new accumulation
 		void updateGeometry( const pbr_float4* vertices, uint32_t numVertices, const pbr_float4* normals, uint32_t numNormals );
+		// pbr_set_parts: the part of every vertex and (unless null) of every vertex normal; captures the rest pose the
+		// transforms start from
+		void setParts( const uint32_t* vertexPart, uint32_t numVertices, const uint32_t* normalPart, uint32_t numNormals, uint32_t numParts );
+		// pbr_update_transforms: one row-major 3 x 4 matrix per part; positions and normals are computed on the device from
+		// the rest pose, then everything updateGeometry rebuilds; starts a new accumulation
+		void updateTransforms( const float* matrices, uint32_t numParts );
 		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
 		void refitOrderedWalk( bool on );
 

@@ -27,7 +27,19 @@ vertex, facesN = facesV).  Positions move as above, normals with tests/patch_ref
       patches and the thick boxes
   (c) pbr_upload_scene( S' ) + pbr_configure, wall: the only way to move Phong geometry without pbr_update_geometry
   (d) the traffic floor next to (a): the flat refit's, plus 96 B per face of patch records written, 16 B per normal and 16 B per
-      face of normal indices read; the 24 B per face of thick boxes written and read again are listed beside it"""
+      face of normal indices read; the 24 B per face of thick boxes written and read again are listed beside it
+
+  python scripts/refit_measure.py --scene ... --transforms [--phong 0.6] [--reps 7] [--out FILE]
+
+pbr_update_transforms (profiles/r15/experiments/transforms.txt), under the --phong leg's conditions: smooth normals made here,
+phong_tessellation configured.  The scene is cut into parts by connected component (tests/transform_ref.py); part 0 stays where it is, every other part gets a rotation about the y axis and a translation of its
+own, so V' and N' are different arrays for the two calls that are compared on the same context, library and run:
+  (a) pbr_update_transforms( M ): device time of the whole update, of the transform kernels alone, the enqueue of the record
+      copy, wall
+  (b) pbr_update_geometry( V', N' ) with the same V', N' precomputed on the host (not timed): device, copy, wall — the baseline
+  (c) wall - device of both: what a caller pays beyond the kernels.  The statement to support or refute: (a)'s wall time comes
+      down to its device time plus the flag read-back and the launch cost
+  (d) the transform kernels against their traffic floor, 36 B per vertex and per normal"""
 import os
 import sys
 import time
@@ -147,10 +159,89 @@ def measure_phong(pbr, name, alpha, reps):
     return lines
 
 
+def measure_transforms(pbr, name, alpha, reps):
+    import transform_ref
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = {k: np.ascontiguousarray(v) for k, v in sc.arrays().items()}
+    cfg = sc.config(W, H)
+    cfg.phong_tessellation = alpha
+    faces, vertices = a["facesV"].shape[0], a["vertices"].shape[0]
+    # normals as in the --phong leg: the BASELINE scenes carry no smooth normals, so one per vertex is made (facesN = facesV)
+    facesN, normals = smooth_normals(a["facesV"], a["vertices"])
+    count = normals.shape[0]
+    desc = pbr.SceneDesc.from_buffer_copy(sc.desc)
+    desc.facesN, desc.normals, desc.num_normals = facesN.ctypes.data, normals.ctypes.data, count
+    dev = pbr.Device(0)
+    dev.upload_scene(desc)
+    dev.configure(cfg)
+    assert dev.patch_refit_info()["patches"]
+    vertex_part, normal_part, parts = transform_ref.parts_of(name, a["facesV"], facesN, vertices, count)
+    lines = ["== %s by transforms, phong_tessellation %g: %d faces, %d vertices, %d smooth normals made here (facesN = facesV), %d parts by connected component"
+             % (name, alpha, faces, vertices, count, parts)]
+    dev.set_parts(vertex_part, normal_part, parts)
+    lines.append("tables: %d bytes for the parts beside the refit's %d and the patch refit's %d"
+                 % (dev.transform_info()["device_bytes"], dev.refit_info()["device_bytes"], dev.patch_refit_info()["device_bytes"]))
+    rest_n = normals
+
+    def matrices(step):
+        """Part 0 the identity; part k turned about y by an angle of its own and shifted a little, another pose per step."""
+        k = np.arange(parts, dtype=np.float64)
+        angle = 0.05 * step + 0.001 * (k % 97)
+        m = np.zeros((parts, 3, 4))
+        m[:, 0, 0], m[:, 0, 2], m[:, 2, 0], m[:, 2, 2], m[:, 1, 1] = np.cos(angle), np.sin(angle), -np.sin(angle), np.cos(angle), 1.0
+        m[:, :, 3] = 0.01 * step * np.stack([np.cos(k), np.sin(k), np.cos(2.0 * k)], axis=1)
+        m[0] = np.eye(3, 4)
+        return np.ascontiguousarray(m.reshape(parts, 12), np.float32)
+
+    poses = []
+    for step in (1, 2):
+        M = matrices(step)
+        v, n = transform_ref.transform(a["vertices"], vertex_part, rest_n, normal_part, M)
+        poses.append((M, v, n))
+    dev.update_transforms(poses[0][0])                               # both paths warm
+    dev.update_geometry(poses[0][1], poses[0][2])
+    got_v, got_n = None, None
+    xf = {key: [] for key in ("device", "kernels", "copy", "wall")}
+    geo = {key: [] for key in ("device", "copy", "wall")}
+    for rep in range(reps):
+        M, v, n = poses[rep % 2]
+        xf["wall"].append(wall(lambda: dev.update_transforms(M)))
+        xf["device"].append(dev.last_kernel_ms())
+        xf["kernels"].append(dev.transform_info()["ms"])
+        xf["copy"].append(dev.refit_info()["upload_ms"])
+        if rep == 0:
+            got_v, got_n = dev.read_geometry()
+            same = np.array_equal(got_v.view(np.uint32), v.view(np.uint32)) and (n is None or np.array_equal(got_n.view(np.uint32), n.view(np.uint32)))
+            lines.append("read_geometry after the first timed update equals the numpy restatement bit for bit: %s" % same)
+        geo["wall"].append(wall(lambda: dev.update_geometry(v, n)))
+        geo["device"].append(dev.last_kernel_ms())
+        geo["copy"].append(dev.refit_info()["upload_ms"])
+    lines.append("(a) update_transforms: device %s ms | transform kernels %s ms | record copy enqueue %s ms | wall %s ms"
+                 % (spread(xf["device"]), spread(xf["kernels"]), spread(xf["copy"]), spread(xf["wall"])))
+    lines.append("(b) update_geometry( V', N' ): device %s ms | copy %s ms | wall %s ms" % (spread(geo["device"]), spread(geo["copy"]), spread(geo["wall"])))
+    lines.append("(c) wall - device, per repetition: update_transforms %s ms | update_geometry %s ms"
+                 % (spread([w - d for w, d in zip(xf["wall"], xf["device"])]), spread([w - d for w, d in zip(geo["wall"], geo["device"])])))
+    floor = 36 * vertices + 36 * count
+    rate = floor / (float(np.median(xf["kernels"])) * 1e-3)
+    lines.append("(d) transform kernels: traffic floor %d bytes -> %.1f GB/s = %.1f %% of 8 TB/s" % (floor, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S))
+    dev.close()
+    return lines
+
+
 def main():
     import refit_ref
     pbr = pbr_loader.load()
     name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
+    if "--transforms" in sys.argv:
+        text = "\n".join(measure_transforms(pbr, name, float(arg("--phong", "0.6")), reps)) + "\n"
+        sys.stdout.write(text)
+        if "--out" in sys.argv:
+            with open(arg("--out", ""), "a") as f:
+                f.write(text)
+        return
     if "--phong" in sys.argv:
         text = "\n".join(measure_phong(pbr, name, float(arg("--phong", "0.6")), reps)) + "\n"
         sys.stdout.write(text)
