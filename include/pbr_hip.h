@@ -35,10 +35,10 @@ extern "C" {
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
  * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
  * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry, version 15 pbr_set_parts, pbr_update_transforms and
- * pbr_read_geometry).  A caller that loads the library at run time — or
+ * pbr_read_geometry, version 16 pbr_set_skin and pbr_update_skin).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 15
+#define PBR_ABI_VERSION 16
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -350,10 +350,85 @@ int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_
  *               its 4 bytes and only then makes the staging buffer the context's vertices (the two pointers are swapped).  The
  *               normals cannot fail and are written after that check.
  * OUT OF SCOPE: pbr_multi.h (every rank would take the same matrices: call this on each rank's context), per-vertex skinning
- * and blend weights, topology changes. */
+ * and blend weights (not in these two calls: pbr_set_skin and pbr_update_skin below, ABI version 16, do that), topology changes. */
 int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals,
                    uint32_t num_parts );
 int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_parts );
+/* BLEND-WEIGHT SKINNING, COMPUTED ON THE DEVICE (ABI version 16).  Characters, cloth rigs, bending pipes: every vertex (and every
+ * vertex normal) follows up to PBR_SKIN_INFLUENCES bones, each with a weight.  pbr_set_skin says once which bones and weights and
+ * captures the REST POSE, pbr_update_skin then takes num_bones matrices, blends them per element on the device, computes V' and
+ * N' from the rest pose and does exactly what pbr_update_geometry( V', N' ) does.  Only the matrices travel.
+ *
+ * pbr_set_skin: vertex_bones[4*i + j] and vertex_weights[4*i + j] are slot j of vertex i, num_vertices the upload's count;
+ * normal_bones / normal_weights likewise for the vertex normals, which have their own indices (facesN) —
+ *   normal_bones == NULL, normal_weights == NULL, num_normals == 0   the normals are never transformed (an update then is a
+ *                                                                     pbr_update_geometry( V', NULL, 0 ));
+ *   otherwise                                                         num_normals must be the upload's count, and the scene
+ *                                                                     must have usable vertex normals.
+ * It mirrors pbr_set_parts in every rule that is not about weights.  The call captures the rest pose: the vertex positions as
+ * they are on the device NOW, copied device to device, and with normal influences the normals the context holds now.
+ * num_bones == 0 with all four pointers NULL drops the skin and frees its buffers; a second call replaces the skin and the rest
+ * pose; pbr_upload_scene drops the skin; pbr_configure and the other update calls leave it alone — a later skin update starts
+ * again from the rest pose.  A skin and parts are independent: either, both or neither may be set, each has its own rest pose,
+ * neither call touches the other's state.
+ * THE WEIGHTS ARE USED AS GIVEN: they are not normalised and their sum is not checked.
+ * Refusals, each leaving the context and any skin that was set exactly as it was:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  no scene;
+ *   PBR_EINVAL  in this order: null vertex_bones or null vertex_weights; a count other than the upload's (num_vertices, or a
+ *               num_normals that is neither 0 nor the upload's); the three normal arguments disagreeing about NULL / 0;
+ *               num_bones == 0 with a pointer; a bone index >= num_bones in any slot, zero-weight slots included (the message
+ *               names element and slot); a weight that is not finite or is < 0; an element whose four weights are all 0 (the
+ *               message names it);
+ *   PBR_ESTATE  normal influences for a scene without usable vertex normals.
+ * ALL allocation happens in this call: the library repacks the caller's arrays into one 32-byte influence record per element
+ * (four bones, then four weights); 16 + 16 + 32 bytes per vertex (rest position, staging position, influence record), 16 + 32
+ * per normal if normal influences are given, 48 bytes per bone and a 4-byte flag word (pbr_diag_skin_info, pbr_hip_diag.h) —
+ * and pbr_update_geometry's tables if the scene has patches and no update made them yet.  pbr_update_skin allocates nothing.
+ *
+ * pbr_update_skin: `matrices` is host memory, borrowed for the call, num_bones x 12 floats, row-major 3 x 4 in
+ * pbr_update_transforms' layout.  V' and N' are computed from the REST POSE: it never accumulates.
+ * THE DEFINITION, operation by operation in binary32, none fused; dot, cross, `/` and sqrtf are pbr_update_geometry's.
+ *   slots     S = the slots j = 0..3 of the element whose weight compares unequal to 0, in slot order.  A slot with weight 0
+ *             contributes nothing, not even a +0, so an unused slot may name any valid bone.
+ *   blended matrix B, twelve words k:
+ *             for the first slot s of S   B[k] = w_s * m_s[k];
+ *             for each later slot s       B[k] = B[k] + w_s * m_s[k] — a product and then an addition.
+ *   position  p' = transformPosition( B, p ): p'.x = ( ( B0*p.x + B1*p.y ) + B2*p.z ) + B3, rows 1 and 2 likewise; p'.w = p.w
+ *             bit for bit.  It includes the identity rule: a B whose twelve words compare equal, as floats, to the identity
+ *             copies the rest words bit for bit.
+ *   normal    B comes from the normal's own influences; ( c, det ) = cofactors( B ): c0 = cross( a1, a2 ), c1 = cross( a2, a0 ),
+ *             c2 = cross( a0, a1 ), det = dot( a0, c0 ), every word negated if det < 0; n' = transformNormal( c, isIdentity( B ), n )
+ *             as pbr_update_transforms defines it.  So a d that is 0, infinite or NaN copies the rest normal: a singular blend is
+ *             legal and no normal word is ever NaN.
+ * TWO PROPERTIES that follow, and that tests rest on:
+ *   1. ONE-HOT SKIN EQUALS THE RIGID CALL.  An element with exactly one non-zero weight, equal to 1.0f, has B equal to that
+ *      bone's matrix bit for bit (1.0f * x is x, -0 stays -0); its position and normal are bit for bit pbr_update_transforms'
+ *      for a part with that matrix.
+ *   2. UNMOVED ELEMENTS STAY UNMOVED.  Weights 1/2 + 1/2, 1/4 + 3/4 and the like of identity bones give an identity B; such an
+ *      element is UNMOVED for pbr_denoise_temporal.  Weights that are not dyadic may or may not sum to 1.0f: that is NOT
+ *      PROMISED.
+ * THE CONTRACT.  After pbr_set_skin and pbr_update_skin( M ) every call gives bit for bit what it gives after
+ * pbr_update_geometry( V', N' ) on a context in the same state, and hence what a fresh upload of the moved scene gives; in all
+ * four traversals (with pbr_refit_ordered_walk for the ordered ones) and under Phong tessellation.  All state follows
+ * pbr_update_geometry's rules: pbr_configure's state rule, pbr_diag_refit_info, pbr_diag_patch_refit_info and
+ * pbr_diag_relink_info, the temporal history (H is taken before the vertices change; pbr_temporal_track_motion works through
+ * it).  After a skin update pbr_diag_transform_info's last_update is 0; after a transform update the skin's last_update is 0.
+ * Refusals, each leaving the context, the vertices, the normals and the tree exactly as they were:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  no skin set (the message names pbr_set_skin; a new upload drops it);
+ *   PBR_EINVAL  null `matrices`; num_bones other than the set one; a matrix word that is not finite (the message names bone and
+ *               word).  Bones are NOT checked for a zero determinant: the definition handles a singular B;
+ *   then pbr_update_geometry's own refusals, in its order;
+ *   PBR_EINVAL  a coordinate of V' that is not finite.  This is found ON THE DEVICE with pbr_update_transforms' mechanism: the
+ *               kernel writes V' to the staging buffer and raises a flag word, the host reads 4 bytes, only then the pointers
+ *               are swapped, and the normals are written after that check.
+ * OUT OF SCOPE: more than four influences, dual-quaternion skinning, morph targets, pbr_multi.h, topology changes, and any
+ * rebuild of a tree that large deformations have degraded — the refit's boxes remain what pbr_read_bvh shows. */
+#define PBR_SKIN_INFLUENCES 4
+int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* vertex_weights, uint32_t num_vertices,
+                  const uint32_t* normal_bones, const float* normal_weights, uint32_t num_normals, uint32_t num_bones );
+int pbr_update_skin( pbr_ctx* ctx, const float* matrices, uint32_t num_bones );
 /* The vertex positions and the vertex normals the context holds now — as uploaded, or after any update of any of the three
  * kinds —, bit for bit, .w included.  pbr_read_bvh's count-only convention: *num_vertices and *num_normals are always set, an
  * output pointer may be NULL, else its capacity (in quads) must reach the count.  *num_normals is 0 for a scene without usable

@@ -138,6 +138,13 @@ int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha );
  * pbr_diag_patch_refit_info's bytes are then no longer 0 before the first update.  PBR_EINVAL for a null context or null out. */
 int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
 
+/* pbr_set_skin / pbr_update_skin (pbr_hip.h): out[0] the bones (0 if no skin is set), [1] the device bytes held for the skin —
+ * 64 per vertex (rest position, staging position, 32-byte influence record), 48 per normal if normal influences are set, 48
+ * per bone, 4 of a flag word: 64 V + 48 N + 48 bones + 4 —, [2] the successful pbr_update_skin calls since pbr_set_skin,
+ * [3] 1 if the most recent successful update of any kind was one of them.  *ms (may be NULL): the device time of the skin
+ * kernels alone in that update; pbr_last_kernel_ms covers the whole update.  PBR_EINVAL for a null context or null out. */
+int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
+
 /* The Phong patch records as they are on the device now: six quads per face, the corners, then the vertex normals, .w = 0.
  * *count = the quads; out = NULL returns the count only, else capacity >= *count quads.  PBR_ESTATE without a scene or for a
  * scene without usable vertex normals, PBR_EINVAL for a null context, null count or too little room. */

@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 15
+ABI_VERSION = 16
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -207,6 +207,9 @@ for _name, _args in (
         ("pbr_update_transforms", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
         ("pbr_read_geometry", [_vp, ctypes.c_void_p, ctypes.c_uint32, _up, ctypes.c_void_p, ctypes.c_uint32, _up]),
         ("pbr_diag_transform_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_set_skin", [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),  # ABI version 16
+        ("pbr_update_skin", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
+        ("pbr_diag_skin_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -252,6 +255,10 @@ if hasattr(host, "pbrh_pt_set_parts"):
     host.pbrh_pt_set_parts.argtypes = [_vp, _up, ctypes.c_uint32, _up, ctypes.c_uint32, ctypes.c_uint32]
 if hasattr(host, "pbrh_pt_update_transforms"):
     host.pbrh_pt_update_transforms.argtypes = [_vp, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_set_skin"):
+    host.pbrh_pt_set_skin.argtypes = [_vp, _up, _fp, ctypes.c_uint32, _up, _fp, ctypes.c_uint32, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_skin"):
+    host.pbrh_pt_update_skin.argtypes = [_vp, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -273,6 +280,13 @@ class PbrError(RuntimeError):
 
 def _as_fp(a):
     return a.ctypes.data_as(_fp)
+
+
+def _skin_arrays(bones, weights):
+    """A skin's (n, 4) bones as uint32 and weights as float32, contiguous; None stays None."""
+    bones = None if bones is None else np.ascontiguousarray(bones, np.uint32).reshape(-1, 4)
+    weights = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+    return bones, weights
 
 
 # ----------------------------------------------------------------------------------------------
@@ -503,6 +517,35 @@ class Device:
         out, ms = (ctypes.c_uint64 * 4)(), ctypes.c_double()
         self._check(hip.pbr_diag_transform_info(self._ctx, out, ctypes.byref(ms)))
         return {"parts": int(out[0]), "device_bytes": int(out[1]), "updates": int(out[2]), "last_update": bool(out[3]), "ms": float(ms.value)}
+
+    def set_skin(self, vertex_bones, vertex_weights=None, normal_bones=None, normal_weights=None, num_bones=None):
+        """pbr_set_skin: four bones (uint32) and four weights (float32) for every vertex and, unless None, for every vertex
+        normal — (n, 4) arrays, counts as uploaded —, and the number of bones (default: the largest index + 1).  Captures the
+        rest pose — the positions and normals the context holds now.  The weights are used as given.  set_skin(None) drops the
+        skin."""
+        if vertex_bones is None:
+            self._check(hip.pbr_set_skin(self._ctx, None, None, 0, None, None, 0, 0))
+            return
+        vertex_bones, vertex_weights = _skin_arrays(vertex_bones, vertex_weights)
+        normal_bones, normal_weights = _skin_arrays(normal_bones, normal_weights)
+        if num_bones is None:
+            num_bones = int(max(vertex_bones.max(initial=0), 0 if normal_bones is None else normal_bones.max(initial=0))) + 1
+        self._check(hip.pbr_set_skin(self._ctx, vertex_bones.ctypes.data, None if vertex_weights is None else vertex_weights.ctypes.data, vertex_bones.shape[0],
+                                     None if normal_bones is None else normal_bones.ctypes.data, None if normal_weights is None else normal_weights.ctypes.data,
+                                     0 if normal_bones is None else normal_bones.shape[0], num_bones))
+
+    def update_skin(self, matrices):
+        """pbr_update_skin: one row-major 3 x 4 matrix per bone, (bones, 12) or (bones, 3, 4) float32.  Positions and normals
+        are blended on the device from the rest pose of set_skin; everything behind is update_geometry's."""
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        self._check(hip.pbr_update_skin(self._ctx, matrices.ctypes.data, matrices.shape[0]))
+
+    def skin_info(self):
+        """pbr_diag_skin_info: the bones, the device bytes held for the skin, the update_skin calls since set_skin, whether the
+        last update was one, and the device time of its skin kernels alone."""
+        out, ms = (ctypes.c_uint64 * 4)(), ctypes.c_double()
+        self._check(hip.pbr_diag_skin_info(self._ctx, out, ctypes.byref(ms)))
+        return {"bones": int(out[0]), "device_bytes": int(out[1]), "updates": int(out[2]), "last_update": bool(out[3]), "ms": float(ms.value)}
 
     def read_patches(self):
         """pbr_diag_read_patches: the Phong patch records on the device, (faces, 6, 4) float32 — three corners, three normals."""
@@ -1011,6 +1054,23 @@ class PathTracer:
         """PathTracer::updateTransforms: Device.update_transforms on the tracer's context; starts a new accumulation."""
         matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
         if host.pbrh_pt_update_transforms(self._h, _as_fp(matrices), matrices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def setSkin(self, vertex_bones, vertex_weights, normal_bones=None, normal_weights=None, num_bones=None):
+        """PathTracer::setSkin: Device.set_skin on the tracer's context."""
+        vertex_bones, vertex_weights = _skin_arrays(vertex_bones, vertex_weights)
+        normal_bones, normal_weights = _skin_arrays(normal_bones, normal_weights)
+        if num_bones is None:
+            num_bones = int(max(vertex_bones.max(initial=0), 0 if normal_bones is None else normal_bones.max(initial=0))) + 1
+        if host.pbrh_pt_set_skin(self._h, vertex_bones.ctypes.data_as(_up), _as_fp(vertex_weights), vertex_bones.shape[0],
+                                 None if normal_bones is None else normal_bones.ctypes.data_as(_up), None if normal_weights is None else _as_fp(normal_weights),
+                                 0 if normal_bones is None else normal_bones.shape[0], num_bones) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updateSkin(self, matrices):
+        """PathTracer::updateSkin: Device.update_skin on the tracer's context; starts a new accumulation."""
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        if host.pbrh_pt_update_skin(self._h, _as_fp(matrices), matrices.shape[0]) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def refitOrderedWalk(self, on):

@@ -35,6 +35,7 @@
 #include "pt_patch_refit.hpp"
 #include "pt_relink.hpp"
 #include "pt_transform.hpp"
+#include "pt_skin.hpp"
 
 using ptk::DevParams;
 
@@ -224,6 +225,22 @@ struct pbr_ctx {
 	bool lastUpdateTransforms = false;   // the most recent successful update was a pbr_update_transforms
 	hipEvent_t evXfStart = nullptr, evXfStop = nullptr, evXfNormalsStart = nullptr, evXfNormalsStop = nullptr;
 	double lastTransformMs = 0.0;  // of the last pbr_update_transforms: device time of the transform kernels alone
+	// pbr_set_skin / pbr_update_skin (pt_skin_host.hpp, pt_skin.hpp): the skin's own REST POSE, one 32-byte influence record per
+	// vertex and — with normal influences — per normal, the bone records (48 bytes each) in pinned and in device memory.  The
+	// staging buffer and the flag word are of the parts' kind; a skin and parts are independent, so the skin owns a pair of its
+	// own here and neither call touches the other's state.  All of it is allocated by pbr_set_skin and freed by the next one,
+	// by freeSkin and with the scene.  The events evXf* are shared: one update is one kind of move
+	uint32_t numBones = 0;
+	bool skinNormals = false;      // normal influences were given: the normals are skinned too
+	float4* dSkinRest = nullptr, * dSkinRestNormals = nullptr, * dSkinStaged = nullptr, * dSkinBones = nullptr;
+	uint4* dSkinOfVertex = nullptr, * dSkinOfNormal = nullptr;
+	unsigned* dSkinFlag = nullptr;
+	pbr_float4* hSkinBones = nullptr;
+	unsigned* hSkinFlag = nullptr;
+	uint64_t skinBytes = 0;        // device bytes of all of the above
+	uint32_t skinUpdates = 0;      // successful pbr_update_skin calls since pbr_set_skin
+	bool lastUpdateSkin = false;   // the most recent successful update was a pbr_update_skin
+	double lastSkinMs = 0.0;       // of the last pbr_update_skin: device time of the skin kernels alone
 
 	// configuration + images
 	bool configured = false;
@@ -376,9 +393,32 @@ void freeParts( pbr_ctx* ctx ) {
 	ctx->lastTransformMs = 0.0;
 }
 
+// pbr_set_skin( 0 bones ), a second pbr_set_skin, pbr_upload_scene: the skin, its rest pose and their buffers go.
+void freeSkin( pbr_ctx* ctx ) {
+	for( void* p : { (void*) ctx->dSkinRest, (void*) ctx->dSkinRestNormals, (void*) ctx->dSkinStaged, (void*) ctx->dSkinBones, (void*) ctx->dSkinOfVertex,
+	                 (void*) ctx->dSkinOfNormal, (void*) ctx->dSkinFlag } ) {
+		(void) hipFree( p );
+	}
+
+	(void) hipHostFree( ctx->hSkinBones );
+	(void) hipHostFree( ctx->hSkinFlag );
+	ctx->dSkinRest = ctx->dSkinRestNormals = ctx->dSkinStaged = ctx->dSkinBones = nullptr;
+	ctx->dSkinOfVertex = ctx->dSkinOfNormal = nullptr;
+	ctx->dSkinFlag = nullptr;
+	ctx->hSkinBones = nullptr;
+	ctx->hSkinFlag = nullptr;
+	ctx->numBones = 0;
+	ctx->skinNormals = false;
+	ctx->skinBytes = 0;
+	ctx->skinUpdates = 0;
+	ctx->lastSkinMs = 0.0;
+}
+
 void freeScene( pbr_ctx* ctx ) {
 	freeParts( ctx );
 	ctx->lastUpdateTransforms = false;
+	freeSkin( ctx );
+	ctx->lastUpdateSkin = false;
 	(void) hipFree( ctx->dNodes );
 	freeWalkStreams( ctx );
 	(void) hipFree( ctx->dTris );
@@ -1842,6 +1882,12 @@ struct TransformUpdate {
 	uint32_t num_parts;
 };
 
+// What pbr_update_skin brings: one matrix per bone; V' and N' are blended from them on the device.
+struct SkinUpdate {
+	const float* matrices;
+	uint32_t num_bones;
+};
+
 // pbr_denoise_temporal under motion tracking: H, the positions the history was made under, is a copy of dVertices taken before
 // an update replaces them.  The copy runs on the stream and is waited for.
 int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
@@ -1858,11 +1904,20 @@ int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
 	return PBR_OK;
 }
 
-// pbr_update_vertices (patches == nullptr), pbr_update_geometry and pbr_update_transforms (moves != nullptr: vertices is null,
-// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set): the checks, the step
-// that brings V' and N' to the device — two copies from the host, or the transform launches —, the shared launches, the state.
-int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches, const TransformUpdate* moves = nullptr ) {
-	if( moves != nullptr ) {
+// pbr_update_vertices (patches == nullptr), pbr_update_geometry, pbr_update_transforms (moves != nullptr: vertices is null,
+// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set) and pbr_update_skin
+// (skin != nullptr, likewise, never together with moves): the checks, the step that brings V' and N' to the device — two copies
+// from the host, the transform launches or the skin launches —, the shared launches, the state.
+int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches, const TransformUpdate* moves = nullptr,
+                 const SkinUpdate* skin = nullptr ) {
+	if( skin != nullptr ) {
+		if( ctx->numBones == 0 ) {
+			return fail( ctx, PBR_ESTATE, "pbr_update_skin without a skin: pbr_set_skin declares the influences and captures the rest pose (a new upload drops it)" );
+		}
+
+		PBR_TRY( checkSkinMatrices( skin->matrices, skin->num_bones, ctx->numBones, ctx->hSkinBones, &ctx->error ) );
+	}
+	else if( moves != nullptr ) {
 		if( ctx->numParts == 0 ) {
 			return fail( ctx, PBR_ESTATE, "pbr_update_transforms without parts: pbr_set_parts declares them and captures the rest pose (a new upload drops them)" );
 		}
@@ -1916,8 +1971,49 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 
 	const uint32_t F = ctx->numFaces;
 
-	// the step that brings V' and N' to the device: two copies from the host, or the transform launches
-	if( moves == nullptr ) {
+	// the step that brings V' and N' to the device: two copies from the host, the transform launches or the skin launches
+	if( skin != nullptr ) {
+		// pbr_update_transforms' mechanism below, word for word: H first, V' into the skin's staging buffer, the flag word read
+		// back, and only then the pointers are swapped; the normals are written after that check
+		const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
+
+		if( keepsHistory ) {
+			PBR_TRY( keepHistoryVertices( ctx, call ) );
+		}
+
+		const uint32_t V = ctx->numVertices;
+		const auto uploadStart = std::chrono::steady_clock::now();
+		*ctx->hSkinFlag = 0u;
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->dSkinBones, ctx->hSkinBones, sizeof( pbr_float4 ) * 3 * ctx->numBones, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->dSkinFlag, ctx->hSkinFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
+		const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+		HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
+		hipLaunchKernelGGL( ptr::skinVertices, dim3( ( V + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dSkinRest, ctx->dSkinOfVertex,
+		                    ctx->dSkinBones, ctx->dSkinStaged, ctx->dSkinFlag, (int) V );
+		HIP_TRY( ctx, hipGetLastError() );
+		HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( ctx->hSkinFlag, ctx->dSkinFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+
+		if( *ctx->hSkinFlag != 0u ) {
+			return fail( ctx, PBR_EINVAL, "pbr_update_skin: a skinned position is not finite (the matrices are finite, their blend's product with the rest pose overflows; found on the device)" );
+		}
+
+		ctx->temporal.update();   // the H it asks for is kept already
+		std::swap( ctx->dVertices, ctx->dSkinStaged );
+		ctx->lastRefitUploadMs = uploadMs;
+
+		if( ctx->skinNormals ) {
+			const uint32_t N = ctx->numNormals;
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
+			hipLaunchKernelGGL( ptr::skinNormals, dim3( ( N + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dSkinRestNormals, ctx->dSkinOfNormal,
+			                    ctx->dSkinBones, ctx->dPatchNormals, (int) N );
+			HIP_TRY( ctx, hipGetLastError() );
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
+		}
+	}
+	else if( moves == nullptr ) {
 		// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
 		// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below
 		// does not: it waits for the copy
@@ -2035,6 +2131,20 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 
 		ctx->lastTransformMs = (double) ms + (double) normalsMs;
 		ctx->transformUpdates++;
+	}
+
+	ctx->lastUpdateSkin = ( skin != nullptr );
+
+	if( skin != nullptr ) {
+		float ms = 0.0f, normalsMs = 0.0f;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
+
+		if( ctx->skinNormals ) {
+			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
+		}
+
+		ctx->lastSkinMs = (double) ms + (double) normalsMs;
+		ctx->skinUpdates++;
 	}
 
 	if( relinks ) {
@@ -2161,6 +2271,118 @@ int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_par
 	const PatchUpdate patches = { nullptr, 0 };
 	const TransformUpdate moves = { matrices, num_parts };
 	return updateScene( ctx, "pbr_update_transforms", nullptr, 0, &patches, &moves );
+}
+
+int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* vertex_weights, uint32_t num_vertices, const uint32_t* normal_bones,
+                  const float* normal_weights, uint32_t num_normals, uint32_t num_bones ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_skin before pbr_upload_scene" );
+	}
+
+	PBR_TRY( checkSkin( vertex_bones, vertex_weights, num_vertices, ctx->numVertices, normal_bones, normal_weights, num_normals, ctx->numNormals, num_bones, &ctx->error ) );
+
+	if( normal_bones != nullptr && ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_skin: normal influences for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( num_bones == 0 ) {
+		freeSkin( ctx );
+		return PBR_OK;
+	}
+	if( ctx->dTriPN != nullptr ) {
+		PBR_TRY( ensurePatchTables( ctx ) );   // a skin update gathers the patches again: its tables are made here, not by an update
+	}
+
+	// the caller's arrays as one 32-byte record per element
+	const size_t V = num_vertices, N = num_normals, quad = sizeof( pbr_float4 ), record = sizeof( pts::Influence ), bone = 3 * quad;
+	std::vector<pts::Influence> packed( std::max<size_t>( V, N ) );
+
+	// everything new first: a call that cannot have its buffers leaves the skin that was set
+	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * bones = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * flag = nullptr;
+	void* hostBones = nullptr, * hostFlag = nullptr;
+	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, std::max<size_t>( record * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &bones, bone * num_bones );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostBones, bone * num_bones, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
+	packInfluences( vertex_bones, vertex_weights, num_vertices, packed.data() );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, packed.data(), record * V, hipMemcpyHostToDevice );
+
+	if( normal_bones != nullptr ) {
+		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, std::max<size_t>( record * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
+		packInfluences( normal_bones, normal_weights, num_normals, packed.data() );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, packed.data(), record * N, hipMemcpyHostToDevice );
+	}
+
+	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
+
+	if( err != hipSuccess ) {
+		for( void* p : { rest, restNormals, staged, bones, ofVertex, ofNormal, flag } ) {
+			(void) hipFree( p );
+		}
+
+		(void) hipHostFree( hostBones );
+		(void) hipHostFree( hostFlag );
+		return fail( ctx, PBR_EDEVICE, "pbr_set_skin: the rest pose and the influence tables: %s", hipGetErrorString( err ) );
+	}
+
+	freeSkin( ctx );
+	ctx->dSkinRest = (float4*) rest;
+	ctx->dSkinRestNormals = (float4*) restNormals;
+	ctx->dSkinStaged = (float4*) staged;
+	ctx->dSkinBones = (float4*) bones;
+	ctx->dSkinOfVertex = (uint4*) ofVertex;
+	ctx->dSkinOfNormal = (uint4*) ofNormal;
+	ctx->dSkinFlag = (unsigned*) flag;
+	ctx->hSkinBones = (pbr_float4*) hostBones;
+	ctx->hSkinFlag = (unsigned*) hostFlag;
+	ctx->numBones = num_bones;
+	ctx->skinNormals = ( normal_bones != nullptr );
+	ctx->skinBytes = ( quad + quad + record ) * V + ( ctx->skinNormals ? ( quad + record ) * N : 0 ) + bone * num_bones + sizeof( unsigned );
+	return PBR_OK;
+}
+
+int pbr_update_skin( pbr_ctx* ctx, const float* matrices, uint32_t num_bones ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	const PatchUpdate patches = { nullptr, 0 };
+	const SkinUpdate skin = { matrices, num_bones };
+	return updateScene( ctx, "pbr_update_skin", nullptr, 0, &patches, nullptr, &skin );
+}
+
+int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
+	if( ctx == nullptr || out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_skin_info: null argument" );
+	}
+
+	out[0] = ctx->numBones;
+	out[1] = ctx->skinBytes;
+	out[2] = ctx->skinUpdates;
+	out[3] = ctx->lastUpdateSkin ? 1 : 0;
+
+	if( ms != nullptr ) {
+		*ms = ctx->lastSkinMs;
+	}
+
+	return PBR_OK;
 }
 
 int pbr_read_geometry( pbr_ctx* ctx, pbr_float4* vertices_out, uint32_t vcap, uint32_t* num_vertices, pbr_float4* normals_out, uint32_t ncap, uint32_t* num_normals ) {

@@ -322,6 +322,33 @@ int pbrh_pt_update_transforms( void* tracer, const float* matrices, uint32_t num
 	}
 }
 
+int pbrh_pt_set_skin( void* tracer, const uint32_t* vertex_bones, const float* vertex_weights, uint32_t num_vertices, const uint32_t* normal_bones,
+                      const float* normal_weights, uint32_t num_normals, uint32_t num_bones ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.setSkin( vertex_bones, vertex_weights, num_vertices, normal_bones, normal_weights, num_normals, num_bones );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
+int pbrh_pt_update_skin( void* tracer, const float* matrices, uint32_t num_bones ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateSkin( matrices, num_bones );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
 	HostTracer* t = static_cast<HostTracer*>( tracer );
 

@@ -468,6 +468,24 @@ void PathTracer::updateTransforms( const float* matrices, uint32_t numParts ) {
 	this->resetSampleCount();
 }
 
+void PathTracer::setSkin( const uint32_t* vertexBones, const float* vertexWeights, uint32_t numVertices, const uint32_t* normalBones, const float* normalWeights,
+                          uint32_t numNormals, uint32_t numBones ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] setSkin before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_set_skin( mCtx, vertexBones, vertexWeights, numVertices, normalBones, normalWeights, numNormals, numBones ), "pbr_set_skin" );
+}
+
+void PathTracer::updateSkin( const float* matrices, uint32_t numBones ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateSkin before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_skin( mCtx, matrices, numBones ), "pbr_update_skin" );
+	this->resetSampleCount();
+}
+
 void PathTracer::refitOrderedWalk( bool on ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );

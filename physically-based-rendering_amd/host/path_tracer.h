@@ -93,6 +93,13 @@ class PathTracer {
 		// pbr_update_transforms: one row-major 3 x 4 matrix per part; positions and normals are computed on the device from
 		// the rest pose, then everything updateGeometry rebuilds; starts a new accumulation
 		void updateTransforms( const float* matrices, uint32_t numParts );
+		// pbr_set_skin: four bones and four weights for every vertex and (unless null) for every vertex normal; captures the
+		// rest pose the skin updates start from
+		void setSkin( const uint32_t* vertexBones, const float* vertexWeights, uint32_t numVertices, const uint32_t* normalBones, const float* normalWeights,
+		              uint32_t numNormals, uint32_t numBones );
+		// pbr_update_skin: one row-major 3 x 4 matrix per bone; positions and normals are blended on the device from the rest
+		// pose, then everything updateGeometry rebuilds; starts a new accumulation
+		void updateSkin( const float* matrices, uint32_t numBones );
 		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
 		void refitOrderedWalk( bool on );
 

@@ -39,7 +39,19 @@ own, so V' and N' are different arrays for the two calls that are compared on th
   (b) pbr_update_geometry( V', N' ) with the same V', N' precomputed on the host (not timed): device, copy, wall — the baseline
   (c) wall - device of both: what a caller pays beyond the kernels.  The statement to support or refute: (a)'s wall time comes
       down to its device time plus the flag read-back and the launch cost
-  (d) the transform kernels against their traffic floor, 36 B per vertex and per normal"""
+  (d) the transform kernels against their traffic floor, 36 B per vertex and per normal
+
+  python scripts/refit_measure.py --scene ... --skin [--phong 0.6] [--reps 9] [--out FILE]
+
+pbr_update_skin (profiles/r16/experiments/skin.txt), under the --transforms leg's conditions and with its matrices.  The bones are
+the scene's connected components plus one bone nobody uses; the influences are tests/skin_ref.py's influences_for — one-hot
+elements, blends of two, three and four bones, weights that do not sum to 1.  Parts are set on the same context beside the skin.
+One warm-up round of all three calls, then the three alternate on the same context in the same run:
+  (a) pbr_update_skin( M ): device time of the whole update, of the skin kernels alone, wall
+  (b) pbr_update_geometry( V', N' ) with the same V', N' precomputed on the host (not timed): device, copy, wall
+  (c) pbr_update_transforms with the one-hot equivalent — every element follows its own part only —: device, its transform
+      kernels, wall
+  (d) the skin kernels against their traffic floor, 64 B per vertex and per normal (the bone records are not in it)"""
 import os
 import sys
 import time
@@ -231,10 +243,96 @@ def measure_transforms(pbr, name, alpha, reps):
     return lines
 
 
+def measure_skin(pbr, name, alpha, reps):
+    import skin_ref
+    import transform_ref
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = {k: np.ascontiguousarray(v) for k, v in sc.arrays().items()}
+    cfg = sc.config(W, H)
+    cfg.phong_tessellation = alpha
+    faces, vertices = a["facesV"].shape[0], a["vertices"].shape[0]
+    # normals as in the --phong leg: the BASELINE scenes carry no smooth normals, so one per vertex is made (facesN = facesV)
+    facesN, normals = smooth_normals(a["facesV"], a["vertices"])
+    count = normals.shape[0]
+    desc = pbr.SceneDesc.from_buffer_copy(sc.desc)
+    desc.facesN, desc.normals, desc.num_normals = facesN.ctypes.data, normals.ctypes.data, count
+    dev = pbr.Device(0)
+    dev.upload_scene(desc)
+    dev.configure(cfg)
+    assert dev.patch_refit_info()["patches"]
+    vertex_part, normal_part, parts = transform_ref.parts_of(name, a["facesV"], facesN, vertices, count)
+    vb, vw, nb, nw, bones = skin_ref.influences_for(name, a["facesV"], facesN, vertices, count)
+    assert bones == parts + 1
+    slots = np.bincount((vw != 0).sum(axis=1), minlength=5)[1:]
+    lines = ["== %s by a skin, phong_tessellation %g: %d faces, %d vertices, %d smooth normals made here (facesN = facesV), %d bones (the connected components and one nobody uses)"
+             % (name, alpha, faces, vertices, count, bones),
+             "influences: %d / %d / %d / %d vertices with 1 / 2 / 3 / 4 weights that are not 0 (tests/skin_ref.py, influences_for)" % tuple(slots)]
+    dev.set_skin(vb, vw, nb, nw, bones)
+    dev.set_parts(vertex_part, normal_part, parts)
+    assert dev.skin_info()["device_bytes"] == 64 * vertices + 48 * count + 48 * bones + 4
+    lines.append("tables: %d bytes for the skin, %d for the parts, beside the refit's %d and the patch refit's %d"
+                 % (dev.skin_info()["device_bytes"], dev.transform_info()["device_bytes"], dev.refit_info()["device_bytes"], dev.patch_refit_info()["device_bytes"]))
+
+    def matrices(step):
+        """Bone 0 the identity; bone k turned about y by an angle of its own and shifted a little, another pose per step."""
+        k = np.arange(bones, dtype=np.float64)
+        angle = 0.05 * step + 0.001 * (k % 97)
+        m = np.zeros((bones, 3, 4))
+        m[:, 0, 0], m[:, 0, 2], m[:, 2, 0], m[:, 2, 2], m[:, 1, 1] = np.cos(angle), np.sin(angle), -np.sin(angle), np.cos(angle), 1.0
+        m[:, :, 3] = 0.01 * step * np.stack([np.cos(k), np.sin(k), np.cos(2.0 * k)], axis=1)
+        m[0] = np.eye(3, 4)
+        return np.ascontiguousarray(m.reshape(bones, 12), np.float32)
+
+    poses = []
+    for step in (1, 2):
+        M = matrices(step)
+        v, n = skin_ref.skin(a["vertices"], vb, vw, normals, nb, nw, M)
+        poses.append((M, v, n))
+    dev.update_skin(poses[0][0])                                     # all three paths warm
+    dev.update_geometry(poses[0][1], poses[0][2])
+    dev.update_transforms(poses[0][0][:parts])
+    skin = {key: [] for key in ("device", "kernels", "wall")}
+    geo = {key: [] for key in ("device", "copy", "wall")}
+    xf = {key: [] for key in ("device", "kernels", "wall")}
+    for rep in range(reps):
+        M, v, n = poses[rep % 2]
+        skin["wall"].append(wall(lambda: dev.update_skin(M)))
+        skin["device"].append(dev.last_kernel_ms())
+        skin["kernels"].append(dev.skin_info()["ms"])
+        if rep == 0:
+            got_v, got_n = dev.read_geometry()
+            same = np.array_equal(got_v.view(np.uint32), v.view(np.uint32)) and np.array_equal(got_n.view(np.uint32), n.view(np.uint32))
+            lines.append("read_geometry after the first timed update equals the numpy restatement bit for bit: %s" % same)
+        geo["wall"].append(wall(lambda: dev.update_geometry(v, n)))
+        geo["device"].append(dev.last_kernel_ms())
+        geo["copy"].append(dev.refit_info()["upload_ms"])
+        xf["wall"].append(wall(lambda: dev.update_transforms(M[:parts])))
+        xf["device"].append(dev.last_kernel_ms())
+        xf["kernels"].append(dev.transform_info()["ms"])
+    lines.append("(a) update_skin: device %s ms | skin kernels %s ms | wall %s ms" % (spread(skin["device"]), spread(skin["kernels"]), spread(skin["wall"])))
+    lines.append("(b) update_geometry( V', N' ): device %s ms | copy %s ms | wall %s ms" % (spread(geo["device"]), spread(geo["copy"]), spread(geo["wall"])))
+    lines.append("(c) update_transforms, one-hot: device %s ms | transform kernels %s ms | wall %s ms" % (spread(xf["device"]), spread(xf["kernels"]), spread(xf["wall"])))
+    floor = 64 * vertices + 64 * count
+    rate = floor / (float(np.median(skin["kernels"])) * 1e-3)
+    lines.append("(d) skin kernels: traffic floor %d bytes -> %.1f GB/s = %.1f %% of 8 TB/s" % (floor, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S))
+    dev.close()
+    return lines
+
+
 def main():
     import refit_ref
     pbr = pbr_loader.load()
     name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
+    if "--skin" in sys.argv:
+        text = "\n".join(measure_skin(pbr, name, float(arg("--phong", "0.6")), int(arg("--reps", "9")))) + "\n"
+        sys.stdout.write(text)
+        if "--out" in sys.argv:
+            with open(arg("--out", ""), "a") as f:
+                f.write(text)
+        return
     if "--transforms" in sys.argv:
         text = "\n".join(measure_transforms(pbr, name, float(arg("--phong", "0.6")), reps)) + "\n"
         sys.stdout.write(text)
