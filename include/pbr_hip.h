@@ -35,10 +35,11 @@ extern "C" {
  * version 9 pbr_update_vertices and pbr_read_bvh, version 10 pbr_read_variance and pbr_denoise_guided,
  * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
  * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry, version 15 pbr_set_parts, pbr_update_transforms and
- * pbr_read_geometry, version 16 pbr_set_skin and pbr_update_skin).  A caller that loads the library at run time — or
+ * pbr_read_geometry, version 16 pbr_set_skin and pbr_update_skin,
+ * version 17 pbr_set_morph, pbr_update_morph and pbr_update_pose).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 16
+#define PBR_ABI_VERSION 17
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -424,11 +425,82 @@ int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_par
  *               kernel writes V' to the staging buffer and raises a flag word, the host reads 4 bytes, only then the pointers
  *               are swapped, and the normals are written after that check.
  * OUT OF SCOPE: more than four influences, dual-quaternion skinning, morph targets, pbr_multi.h, topology changes, and any
- * rebuild of a tree that large deformations have degraded — the refit's boxes remain what pbr_read_bvh shows. */
+ * rebuild of a tree that large deformations have degraded — the refit's boxes remain what pbr_read_bvh shows.  (Morph
+ * targets came with ABI version 17, in calls of their own: pbr_set_morph, pbr_update_morph and pbr_update_pose below.) */
 #define PBR_SKIN_INFLUENCES 4
 int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* vertex_weights, uint32_t num_vertices,
                   const uint32_t* normal_bones, const float* normal_weights, uint32_t num_normals, uint32_t num_bones );
 int pbr_update_skin( pbr_ctx* ctx, const float* matrices, uint32_t num_bones );
+/* MORPH TARGETS (BLEND SHAPES), COMPUTED ON THE DEVICE (ABI version 17).  Faces, muscle correctives, cloth caches: sparse per-vertex
+ * (and per-normal) deltas, each target scaled by one weight per update, applied BEFORE the skin.  pbr_set_morph says once which
+ * deltas and captures the REST POSE, pbr_update_morph then takes num_targets weights, computes V' and N' from the rest pose on
+ * the device and does exactly what pbr_update_geometry( V', N' ) does; pbr_update_pose takes the weights and the matrices of the
+ * skin that is set (pbr_set_skin) and is, bit for bit, the skin of the morphed rest pose.  Only weights and matrices travel.
+ *
+ * pbr_set_morph: sparse targets, target-major as exporters give them.  Target t owns entries vertex_first[t] ..
+ * vertex_first[t+1]-1 (vertex_first has num_targets + 1 words); entry e is the element index vertex_index[e] and the delta quad
+ * vertex_delta[e] (x, y, z used, w ignored and not checked).  normal_first / normal_index / normal_delta likewise for the vertex
+ * normals, which have their own indices (facesN) — all three NULL: the normals are never morphed (an update then is a
+ * pbr_update_geometry( V', NULL, 0 )); otherwise the scene must have usable vertex normals.  Empty targets and targets that touch
+ * every element are both legal.  The call captures the rest pose as pbr_set_skin does: the vertex positions as they are on the
+ * device NOW, copied device to device, and with normal targets the normals the context holds now.  num_targets == 0 with all six
+ * pointers NULL drops the morph and frees its buffers; a second call replaces the morph and the rest pose; pbr_upload_scene
+ * drops the morph; pbr_configure and the other update calls leave it alone.  A morph, a skin and parts are independent: each has
+ * its own rest pose, no set call touches another's state.
+ * Refusals, each checked before the device is touched and leaving the context and any morph that was set exactly as it was:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  no scene;
+ *   PBR_EINVAL  in this order, within one rule the vertex lists before the normal lists: num_targets == 0 with a pointer; a null
+ *               vertex_first, vertex_index or vertex_delta; the three normal pointers disagreeing about NULL; first[0] != 0 or a
+ *               `first` array that decreases; an index >= the uploaded count; an index that occurs twice within one target; an
+ *               x, y or z of a delta that is not finite (the messages name target and entry);
+ *   PBR_ESTATE  normal targets for a scene without usable vertex normals.
+ * ALL allocation happens in this call: the library transposes the lists into element-major runs — runFirst[count + 1] words and
+ * one 16-byte entry { dx, dy, dz, target } per delta, an element's run in ascending target —; with V vertices, N normals, T
+ * targets, Ev vertex entries and En normal entries it holds 16 V + 16 V + 4 ( V + 1 ) + 16 Ev bytes (rest position, staging
+ * position, runs, entries), + 16 N + 4 ( N + 1 ) + 16 En with normal targets, + 4 T + 4 (weight table, flag word;
+ * pbr_diag_morph_info, pbr_hip_diag.h) — and pbr_update_geometry's tables if the scene has patches and no update made them yet.
+ * The update calls allocate nothing.
+ *
+ * pbr_update_morph: `weights` is host memory, borrowed for the call, num_targets floats.
+ * THE DEFINITION, operation by operation in binary32, none fused; dot and sqrtf are pbr_update_geometry's.
+ *   active    the targets whose weight compares unequal to 0, taken in ascending target index.  A target of weight 0
+ *             contributes nothing, not even a +0.
+ *   position  p' = p; for every entry ( t, d ) of the element with t active, in ascending t, for each of x, y, z:
+ *             p'.c = p'.c + w_t * d.c — a product, then an addition.  p'.w = p.w bit for bit.  An element with no active entry
+ *             is the rest quad bit for bit; in particular all weights 0 give the rest pose.
+ *   normal    q = n + sum w_t d, accumulated the same way.  With no active entry n is copied.  Otherwise d = dot( q, q ); if
+ *             !( d > 0 && d < inf ) n is copied, else n'.xyz = q * ( 1.0f / sqrtf( d ) ), n'.w = n.w — the tail of
+ *             pbr_update_transforms' normal rule, so no normal word is ever NaN.
+ *   weights   used as given: negative weights and weights above 1 are legal.
+ * pbr_update_pose: per element skinPosition( B, p' ) and skinNormal( B, n' ) of pbr_update_skin's definition, p' and n' the
+ * morphed rest quads above, B the element's blend of `matrices` (num_bones x 12 floats), its identity rule and its singular-blend
+ * rule included.  Normals: morphed if the morph has normal targets, then skinned if the skin has normal influences; with
+ * neither the context's normals stay.
+ * NEVER CUMULATIVE: pbr_update_morph ignores a set skin, pbr_update_skin ignores a set morph; each of the three calls is a
+ * function of the rest pose and its own arguments only.  pbr_update_pose( 0 weights, M ) equals pbr_update_skin( M );
+ * pbr_update_pose( w, one-hot identity bones ) equals pbr_update_morph( w ).
+ * THE CONTRACT is pbr_update_skin's: after the call every call gives bit for bit what it gives after pbr_update_geometry( V', N' ),
+ * in all four traversals and under Phong tessellation; the temporal history hears of the update as it does for the skin.
+ * Refusals, in this order, each before the device is touched and leaving the context, the vertices, the normals and the tree as
+ * they were:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  no morph set (the message names pbr_set_morph; a new upload drops it);
+ *   PBR_ESTATE  pbr_update_pose: no skin set;
+ *   PBR_ESTATE  pbr_update_pose: skin and morph did not capture the same geometry — the context keeps a geometry generation,
+ *               bumped by an upload and by every successful update of any kind; both set calls record it and they must agree;
+ *   PBR_EINVAL  null `weights`; num_targets other than the set one; a weight that is not finite (the message names the target);
+ *   PBR_EINVAL  pbr_update_pose: everything pbr_update_skin refuses about `matrices` and num_bones;
+ *   then pbr_update_geometry's own refusals, in its order (a tree that is not nested, an ordered traversal without
+ *   pbr_refit_ordered_walk, ...);
+ *   PBR_EINVAL  a coordinate of V' that is not finite: finite inputs can overflow.  Found ON THE DEVICE with pbr_update_skin's
+ *               mechanism — staging buffer, flag word, 4 bytes read back, pointers swapped only then; the normals are written
+ *               after that check.
+ * OUT OF SCOPE: pbr_multi.h, morphing of anything but positions and normals, topology changes. */
+int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* vertex_index, const pbr_float4* vertex_delta,
+                   const uint32_t* normal_first, const uint32_t* normal_index, const pbr_float4* normal_delta, uint32_t num_targets );
+int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets );
+int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones );
 /* The vertex positions and the vertex normals the context holds now — as uploaded, or after any update of any of the three
  * kinds —, bit for bit, .w included.  pbr_read_bvh's count-only convention: *num_vertices and *num_normals are always set, an
  * output pointer may be NULL, else its capacity (in quads) must reach the count.  *num_normals is 0 for a scene without usable

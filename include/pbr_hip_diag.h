@@ -145,6 +145,15 @@ int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
  * kernels alone in that update; pbr_last_kernel_ms covers the whole update.  PBR_EINVAL for a null context or null out. */
 int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
 
+/* pbr_set_morph / pbr_update_morph / pbr_update_pose (pbr_hip.h): out[0] the targets (0 if no morph is set), [1] the vertex
+ * entries Ev, [2] the normal entries En, [3] the device bytes held for the morph — 16 V + 16 V + 4 ( V + 1 ) + 16 Ev (rest
+ * position, staging position, runs, entries), + 16 N + 4 ( N + 1 ) + 16 En with normal targets, + 4 T + 4 (weight table, flag
+ * word) —, [4] the successful pbr_update_morph and pbr_update_pose calls since pbr_set_morph, [5] the most recent successful
+ * update of any kind: 0 none of the two, 1 a pbr_update_morph, 2 a pbr_update_pose.  *ms (may be NULL): the device time of the
+ * morph / pose kernels alone in that update; pbr_last_kernel_ms covers the whole update.  PBR_EINVAL for a null context or null
+ * out. */
+int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms );
+
 /* The Phong patch records as they are on the device now: six quads per face, the corners, then the vertex normals, .w = 0.
  * *count = the quads; out = NULL returns the count only, else capacity >= *count quads.  PBR_ESTATE without a scene or for a
  * scene without usable vertex normals, PBR_EINVAL for a null context, null count or too little room. */

@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 16
+ABI_VERSION = 17
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -210,6 +210,10 @@ for _name, _args in (
         ("pbr_set_skin", [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),  # ABI version 16
         ("pbr_update_skin", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
         ("pbr_diag_skin_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_set_morph", [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),  # ABI version 17
+        ("pbr_update_morph", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
+        ("pbr_update_pose", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
+        ("pbr_diag_morph_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -259,6 +263,12 @@ if hasattr(host, "pbrh_pt_set_skin"):
     host.pbrh_pt_set_skin.argtypes = [_vp, _up, _fp, ctypes.c_uint32, _up, _fp, ctypes.c_uint32, ctypes.c_uint32]
 if hasattr(host, "pbrh_pt_update_skin"):
     host.pbrh_pt_update_skin.argtypes = [_vp, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_set_morph"):
+    host.pbrh_pt_set_morph.argtypes = [_vp, _up, _up, _fp, _up, _up, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_morph"):
+    host.pbrh_pt_update_morph.argtypes = [_vp, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_pose"):
+    host.pbrh_pt_update_pose.argtypes = [_vp, _fp, ctypes.c_uint32, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -287,6 +297,28 @@ def _skin_arrays(bones, weights):
     bones = None if bones is None else np.ascontiguousarray(bones, np.uint32).reshape(-1, 4)
     weights = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
     return bones, weights
+
+
+def _morph_lists(targets, what):
+    """Morph targets — a sequence of (indices, deltas) pairs, one per target, deltas (n, 3) or (n, 4) — as pbr_set_morph's
+    target-major lists: first (targets + 1, uint32), index (uint32) and delta (entries, 4) float32 with w = 0."""
+    first = np.zeros(len(targets) + 1, np.uint32)
+    indices, deltas = [], []
+    for t, (index, delta) in enumerate(targets):
+        index = np.asarray(index, np.uint32).reshape(-1)
+        delta = np.asarray(delta, np.float32)
+        delta = delta.reshape(index.shape[0], delta.shape[-1] if delta.ndim > 1 else 3)
+        if delta.shape[1] not in (3, 4):
+            raise ValueError("%s target %d: deltas must be (n, 3) or (n, 4)" % (what, t))
+        quad = np.zeros((index.shape[0], 4), np.float32)
+        quad[:, :delta.shape[1]] = delta
+        indices.append(index)
+        deltas.append(quad)
+        first[t + 1] = first[t] + index.shape[0]
+    index = np.ascontiguousarray(np.concatenate(indices) if indices else np.zeros(0, np.uint32), np.uint32)
+    delta = np.ascontiguousarray(np.concatenate(deltas) if deltas else np.zeros((0, 4), np.float32), np.float32)
+    # a list without entries still hands the library a pointer: NULL means "no such lists"
+    return first, (index if index.size else np.zeros(1, np.uint32)), (delta if delta.size else np.zeros((1, 4), np.float32))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -546,6 +578,40 @@ class Device:
         out, ms = (ctypes.c_uint64 * 4)(), ctypes.c_double()
         self._check(hip.pbr_diag_skin_info(self._ctx, out, ctypes.byref(ms)))
         return {"bones": int(out[0]), "device_bytes": int(out[1]), "updates": int(out[2]), "last_update": bool(out[3]), "ms": float(ms.value)}
+
+    def set_morph(self, vertex_targets, normal_targets=None):
+        """pbr_set_morph: sparse morph targets, one (indices, deltas) pair per target — indices uint32, deltas (n, 3) or (n, 4)
+        float32 — for the vertices and, unless None, as many pairs for the vertex normals.  Captures the rest pose — the
+        positions and normals the context holds now.  set_morph(None) drops the morph."""
+        if vertex_targets is None:
+            self._check(hip.pbr_set_morph(self._ctx, None, None, None, None, None, None, 0))
+            return
+        if normal_targets is not None and len(normal_targets) != len(vertex_targets):
+            raise ValueError("set_morph: %d vertex targets, %d normal targets" % (len(vertex_targets), len(normal_targets)))
+        v = _morph_lists(vertex_targets, "vertex")
+        n = (None, None, None) if normal_targets is None else _morph_lists(normal_targets, "normal")
+        self._check(hip.pbr_set_morph(self._ctx, *[a.ctypes.data for a in v], *[None if a is None else a.ctypes.data for a in n], len(vertex_targets)))
+
+    def update_morph(self, weights):
+        """pbr_update_morph: one float32 weight per target, used as given.  Positions and normals are morphed on the device from
+        the rest pose of set_morph; everything behind is update_geometry's."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        self._check(hip.pbr_update_morph(self._ctx, weights.ctypes.data, weights.shape[0]))
+
+    def update_pose(self, weights, matrices):
+        """pbr_update_pose: the skin of the morphed rest pose — update_morph's weights and update_skin's matrices in one call."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        self._check(hip.pbr_update_pose(self._ctx, weights.ctypes.data, weights.shape[0], matrices.ctypes.data, matrices.shape[0]))
+
+    def morph_info(self):
+        """pbr_diag_morph_info: the targets, the vertex and normal entries, the device bytes held for the morph, the update_morph
+        and update_pose calls since set_morph, the last update (0 none of the two, 1 morph, 2 pose), and the device time of its
+        morph / pose kernels alone."""
+        out, ms = (ctypes.c_uint64 * 6)(), ctypes.c_double()
+        self._check(hip.pbr_diag_morph_info(self._ctx, out, ctypes.byref(ms)))
+        return {"targets": int(out[0]), "vertex_entries": int(out[1]), "normal_entries": int(out[2]), "device_bytes": int(out[3]),
+                "updates": int(out[4]), "last_update": int(out[5]), "ms": float(ms.value)}
 
     def read_patches(self):
         """pbr_diag_read_patches: the Phong patch records on the device, (faces, 6, 4) float32 — three corners, three normals."""
@@ -1071,6 +1137,27 @@ class PathTracer:
         """PathTracer::updateSkin: Device.update_skin on the tracer's context; starts a new accumulation."""
         matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
         if host.pbrh_pt_update_skin(self._h, _as_fp(matrices), matrices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def setMorph(self, vertex_targets, normal_targets=None):
+        """PathTracer::setMorph: Device.set_morph on the tracer's context."""
+        v = _morph_lists(vertex_targets, "vertex")
+        n = (None, None, None) if normal_targets is None else _morph_lists(normal_targets, "normal")
+        if host.pbrh_pt_set_morph(self._h, v[0].ctypes.data_as(_up), v[1].ctypes.data_as(_up), _as_fp(v[2]), None if n[0] is None else n[0].ctypes.data_as(_up),
+                                  None if n[1] is None else n[1].ctypes.data_as(_up), None if n[2] is None else _as_fp(n[2]), len(vertex_targets)) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updateMorph(self, weights):
+        """PathTracer::updateMorph: Device.update_morph on the tracer's context; starts a new accumulation."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if host.pbrh_pt_update_morph(self._h, _as_fp(weights), weights.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updatePose(self, weights, matrices):
+        """PathTracer::updatePose: Device.update_pose on the tracer's context; starts a new accumulation."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        if host.pbrh_pt_update_pose(self._h, _as_fp(weights), weights.shape[0], _as_fp(matrices), matrices.shape[0]) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def refitOrderedWalk(self, on):

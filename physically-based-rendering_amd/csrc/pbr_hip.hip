@@ -36,6 +36,7 @@
 #include "pt_relink.hpp"
 #include "pt_transform.hpp"
 #include "pt_skin.hpp"
+#include "pt_morph.hpp"
 
 using ptk::DevParams;
 
@@ -241,6 +242,26 @@ struct pbr_ctx {
 	uint32_t skinUpdates = 0;      // successful pbr_update_skin calls since pbr_set_skin
 	bool lastUpdateSkin = false;   // the most recent successful update was a pbr_update_skin
 	double lastSkinMs = 0.0;       // of the last pbr_update_skin: device time of the skin kernels alone
+	// pbr_set_morph / pbr_update_morph / pbr_update_pose (pt_morph_host.hpp, pt_morph.hpp): the morph's own REST POSE, the
+	// element-major runs packMorph made — runFirst[count + 1] and one 16-byte entry per delta, for the vertices and, with normal
+	// targets, for the normals —, the weight table (num_targets floats) in pinned and in device memory, and a staging buffer and
+	// a flag word of the skin's kind.  All of it is allocated by pbr_set_morph and freed by the next one, by freeMorph and with
+	// the scene.  The events evXf* are shared: one update is one kind of move
+	uint32_t numMorphTargets = 0;
+	bool morphNormals = false;     // normal targets were given: the normals are morphed too
+	float4* dMorphRest = nullptr, * dMorphRestNormals = nullptr, * dMorphStaged = nullptr;
+	uint32_t* dMorphVertexRun = nullptr, * dMorphNormalRun = nullptr;
+	ptm::Entry* dMorphVertexEntries = nullptr, * dMorphNormalEntries = nullptr;
+	float* dMorphWeights = nullptr, * hMorphWeights = nullptr;
+	unsigned* dMorphFlag = nullptr, * hMorphFlag = nullptr;
+	uint64_t morphVertexEntries = 0, morphNormalEntries = 0;
+	uint64_t morphBytes = 0;       // device bytes of all of the above
+	uint32_t morphUpdates = 0;     // successful pbr_update_morph and pbr_update_pose calls since pbr_set_morph
+	uint32_t lastUpdateMorph = 0;  // the most recent successful update: 0 neither, 1 a pbr_update_morph, 2 a pbr_update_pose
+	double lastMorphMs = 0.0;      // of the last of them: device time of the morph / pose kernels alone
+	// which geometry a rest pose was captured from: bumped by an upload and by every successful update; pbr_set_skin and
+	// pbr_set_morph record it, pbr_update_pose needs both to have captured the same
+	uint64_t geometryGeneration = 0, skinGeneration = 0, morphGeneration = 0;
 
 	// configuration + images
 	bool configured = false;
@@ -414,11 +435,36 @@ void freeSkin( pbr_ctx* ctx ) {
 	ctx->lastSkinMs = 0.0;
 }
 
+// pbr_set_morph( 0 targets ), a second pbr_set_morph, pbr_upload_scene: the morph, its rest pose and their buffers go.
+void freeMorph( pbr_ctx* ctx ) {
+	for( void* p : { (void*) ctx->dMorphRest, (void*) ctx->dMorphRestNormals, (void*) ctx->dMorphStaged, (void*) ctx->dMorphVertexRun, (void*) ctx->dMorphNormalRun,
+	                 (void*) ctx->dMorphVertexEntries, (void*) ctx->dMorphNormalEntries, (void*) ctx->dMorphWeights, (void*) ctx->dMorphFlag } ) {
+		(void) hipFree( p );
+	}
+
+	(void) hipHostFree( ctx->hMorphWeights );
+	(void) hipHostFree( ctx->hMorphFlag );
+	ctx->dMorphRest = ctx->dMorphRestNormals = ctx->dMorphStaged = nullptr;
+	ctx->dMorphVertexRun = ctx->dMorphNormalRun = nullptr;
+	ctx->dMorphVertexEntries = ctx->dMorphNormalEntries = nullptr;
+	ctx->dMorphWeights = ctx->hMorphWeights = nullptr;
+	ctx->dMorphFlag = ctx->hMorphFlag = nullptr;
+	ctx->numMorphTargets = 0;
+	ctx->morphNormals = false;
+	ctx->morphVertexEntries = ctx->morphNormalEntries = 0;
+	ctx->morphBytes = 0;
+	ctx->morphUpdates = 0;
+	ctx->lastMorphMs = 0.0;
+}
+
 void freeScene( pbr_ctx* ctx ) {
 	freeParts( ctx );
 	ctx->lastUpdateTransforms = false;
 	freeSkin( ctx );
 	ctx->lastUpdateSkin = false;
+	freeMorph( ctx );
+	ctx->lastUpdateMorph = 0;
+	ctx->geometryGeneration++;
 	(void) hipFree( ctx->dNodes );
 	freeWalkStreams( ctx );
 	(void) hipFree( ctx->dTris );
@@ -1904,13 +1950,81 @@ int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
 	return PBR_OK;
 }
 
+// What pbr_update_morph brings (matrices == nullptr) and what pbr_update_pose brings: one weight per target, and for the pose
+// one matrix per bone of the skin that is set.
+struct MorphUpdate {
+	const float* weights;
+	uint32_t num_targets;
+	bool pose;
+	const float* matrices;
+	uint32_t num_bones;
+};
+
+// The sequence every front end that computes V' on the device goes through, once: H first (pbr_denoise_temporal under motion
+// tracking: a copy nobody reads if the call is refused), `upload` (the call's tables, asynchronous copies on the stream), the
+// flag word cleared, `launch` (the kernel that writes V' to `staged` and raises the flag word for a position that is not finite)
+// between evXfStart and evXfStop, the flag's 4 bytes read back — and only then the temporal policy hears of an update and the
+// staging buffer becomes the context's vertices (the two pointers are swapped).  A refused call leaves the context as it was.
+// The normals cannot fail; the caller writes them after this returns PBR_OK.  (A template, so it steps out of the C linkage
+// this part of the file is in.)
+extern "C++" template<class Upload, class Launch>
+int stageVertices( pbr_ctx* ctx, const char* call, unsigned* hostFlag, unsigned* deviceFlag, float4*& staged, const char* overflow, Upload upload, Launch launch ) {
+	const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
+
+	if( keepsHistory ) {
+		PBR_TRY( keepHistoryVertices( ctx, call ) );
+	}
+
+	const auto uploadStart = std::chrono::steady_clock::now();
+	*hostFlag = 0u;
+	HIP_TRY( ctx, upload() );
+	HIP_TRY( ctx, hipMemcpyAsync( deviceFlag, hostFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
+	const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
+	launch();
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( hostFlag, deviceFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+
+	if( *hostFlag != 0u ) {
+		return fail( ctx, PBR_EINVAL, "%s: %s", call, overflow );
+	}
+
+	ctx->temporal.update();   // the H it asks for is kept already
+	std::swap( ctx->dVertices, staged );
+	ctx->lastRefitUploadMs = uploadMs;
+	return PBR_OK;
+}
+
 // pbr_update_vertices (patches == nullptr), pbr_update_geometry, pbr_update_transforms (moves != nullptr: vertices is null,
-// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set) and pbr_update_skin
-// (skin != nullptr, likewise, never together with moves): the checks, the step that brings V' and N' to the device — two copies
-// from the host, the transform launches or the skin launches —, the shared launches, the state.
+// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set), pbr_update_skin
+// (skin != nullptr, likewise, never together with moves) and pbr_update_morph / pbr_update_pose (morph != nullptr, likewise, never
+// together with the other two): the checks, the step that brings V' and N' to the device — two copies from the host, the
+// transform launches, the skin launches or the morph / pose launches —, the shared launches, the state.
 int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches, const TransformUpdate* moves = nullptr,
-                 const SkinUpdate* skin = nullptr ) {
-	if( skin != nullptr ) {
+                 const SkinUpdate* skin = nullptr, const MorphUpdate* morph = nullptr ) {
+	const bool poses = ( morph != nullptr && morph->pose );
+
+	if( morph != nullptr ) {
+		if( ctx->numMorphTargets == 0 ) {
+			return fail( ctx, PBR_ESTATE, "%s without a morph: pbr_set_morph declares the targets and captures the rest pose (a new upload drops it)", call );
+		}
+		if( poses && ctx->numBones == 0 ) {
+			return fail( ctx, PBR_ESTATE, "pbr_update_pose without a skin: pbr_set_skin declares the influences (a new upload drops it)" );
+		}
+		if( poses && ctx->skinGeneration != ctx->morphGeneration ) {
+			return fail( ctx, PBR_ESTATE, "pbr_update_pose: pbr_set_skin and pbr_set_morph captured different geometry (an upload or an update lies between them): set both on the same rest pose" );
+		}
+
+		PBR_TRY( checkMorphWeights( morph->weights, morph->num_targets, ctx->numMorphTargets, ctx->hMorphWeights, &ctx->error, call ) );
+
+		if( poses ) {
+			PBR_TRY( checkSkinMatrices( morph->matrices, morph->num_bones, ctx->numBones, ctx->hSkinBones, &ctx->error, call ) );
+		}
+	}
+	else if( skin != nullptr ) {
 		if( ctx->numBones == 0 ) {
 			return fail( ctx, PBR_ESTATE, "pbr_update_skin without a skin: pbr_set_skin declares the influences and captures the rest pose (a new upload drops it)" );
 		}
@@ -1971,8 +2085,53 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 
 	const uint32_t F = ctx->numFaces;
 
-	// the step that brings V' and N' to the device: two copies from the host, the transform launches or the skin launches
-	if( skin != nullptr ) {
+	// the step that brings V' and N' to the device: two copies from the host, the transform launches, the skin launches or the
+	// morph / pose launches
+	if( morph != nullptr ) {
+		const uint32_t V = ctx->numVertices, N = ctx->numNormals;
+		const dim3 vertexGrid( ( V + 255 ) / 256 ), normalGrid( ( N + 255 ) / 256 ), group( 256 );
+
+		PBR_TRY( stageVertices( ctx, call, ctx->hMorphFlag, ctx->dMorphFlag, ctx->dMorphStaged,
+		                        poses ? "a posed position is not finite (weights, deltas and matrices are finite, the skin of the morphed rest pose overflows; found on the device)"
+		                              : "a morphed position is not finite (weights and deltas are finite, their sum with the rest pose overflows; found on the device)",
+		                        [&]() {
+			                        hipError_t err = hipMemcpyAsync( ctx->dMorphWeights, ctx->hMorphWeights, sizeof( float ) * ctx->numMorphTargets, hipMemcpyHostToDevice, ctx->stream );
+			                        return ( err != hipSuccess || !poses ) ? err : hipMemcpyAsync( ctx->dSkinBones, ctx->hSkinBones, sizeof( pbr_float4 ) * 3 * ctx->numBones, hipMemcpyHostToDevice, ctx->stream );
+		                        },
+		                        [&]() {
+			                        if( poses ) {
+				                        hipLaunchKernelGGL( ptr::poseVertices, vertexGrid, group, 0, ctx->stream, ctx->dMorphRest, ctx->dMorphVertexRun, ctx->dMorphVertexEntries,
+				                                            ctx->dMorphWeights, ctx->dSkinOfVertex, ctx->dSkinBones, ctx->dMorphStaged, ctx->dMorphFlag, (int) V );
+			                        }
+			                        else {
+				                        hipLaunchKernelGGL( ptr::morphVertices, vertexGrid, group, 0, ctx->stream, ctx->dMorphRest, ctx->dMorphVertexRun, ctx->dMorphVertexEntries,
+				                                            ctx->dMorphWeights, ctx->dMorphStaged, ctx->dMorphFlag, (int) V );
+			                        }
+		                        } ) );
+
+		// the normals: morphed if the morph has normal targets, skinned if this is a pose and the skin has normal influences
+		const bool morphs = ctx->morphNormals, skins = ( poses && ctx->skinNormals );
+
+		if( morphs || skins ) {
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
+
+			if( morphs && skins ) {
+				hipLaunchKernelGGL( ptr::poseNormals, normalGrid, group, 0, ctx->stream, ctx->dMorphRestNormals, ctx->dMorphNormalRun, ctx->dMorphNormalEntries,
+				                    ctx->dMorphWeights, ctx->dSkinOfNormal, ctx->dSkinBones, ctx->dPatchNormals, (int) N );
+			}
+			else if( morphs ) {
+				hipLaunchKernelGGL( ptr::morphNormals, normalGrid, group, 0, ctx->stream, ctx->dMorphRestNormals, ctx->dMorphNormalRun, ctx->dMorphNormalEntries,
+				                    ctx->dMorphWeights, ctx->dPatchNormals, (int) N );
+			}
+			else {
+				hipLaunchKernelGGL( ptr::skinNormals, normalGrid, group, 0, ctx->stream, ctx->dSkinRestNormals, ctx->dSkinOfNormal, ctx->dSkinBones, ctx->dPatchNormals, (int) N );
+			}
+
+			HIP_TRY( ctx, hipGetLastError() );
+			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
+		}
+	}
+	else if( skin != nullptr ) {
 		// pbr_update_transforms' mechanism below, word for word: H first, V' into the skin's staging buffer, the flag word read
 		// back, and only then the pointers are swapped; the normals are written after that check
 		const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
@@ -2074,6 +2233,7 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 		}
 	}
 
+	ctx->geometryGeneration++;   // the context's vertices are new ones from here on: a rest pose captured before is another geometry's
 	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dVertices, ctx->dTris, (int) F );
 	HIP_TRY( ctx, hipGetLastError() );
 
@@ -2145,6 +2305,20 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 
 		ctx->lastSkinMs = (double) ms + (double) normalsMs;
 		ctx->skinUpdates++;
+	}
+
+	ctx->lastUpdateMorph = ( morph == nullptr ) ? 0u : poses ? 2u : 1u;
+
+	if( morph != nullptr ) {
+		float ms = 0.0f, normalsMs = 0.0f;
+		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
+
+		if( ctx->morphNormals || ( poses && ctx->skinNormals ) ) {
+			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
+		}
+
+		ctx->lastMorphMs = (double) ms + (double) normalsMs;
+		ctx->morphUpdates++;
 	}
 
 	if( relinks ) {
@@ -2351,6 +2525,7 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 	ctx->hSkinFlag = (unsigned*) hostFlag;
 	ctx->numBones = num_bones;
 	ctx->skinNormals = ( normal_bones != nullptr );
+	ctx->skinGeneration = ctx->geometryGeneration;
 	ctx->skinBytes = ( quad + quad + record ) * V + ( ctx->skinNormals ? ( quad + record ) * N : 0 ) + bone * num_bones + sizeof( unsigned );
 	return PBR_OK;
 }
@@ -2380,6 +2555,148 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 
 	if( ms != nullptr ) {
 		*ms = ctx->lastSkinMs;
+	}
+
+	return PBR_OK;
+}
+
+int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* vertex_index, const pbr_float4* vertex_delta, const uint32_t* normal_first,
+                   const uint32_t* normal_index, const pbr_float4* normal_delta, uint32_t num_targets ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_morph before pbr_upload_scene" );
+	}
+
+	PBR_TRY( checkMorph( vertex_first, vertex_index, vertex_delta, normal_first, normal_index, normal_delta, num_targets, ctx->numVertices, ctx->numNormals, &ctx->error ) );
+
+	if( normal_first != nullptr && ctx->dTriPN == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "pbr_set_morph: normal targets for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( num_targets == 0 ) {
+		freeMorph( ctx );
+		return PBR_OK;
+	}
+
+	// the caller's target-major lists as element-major runs
+	const bool withNormals = ( normal_first != nullptr );
+	const size_t V = ctx->numVertices, N = withNormals ? ctx->numNormals : 0, T = num_targets, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
+	const size_t Ev = vertex_first[T], En = withNormals ? normal_first[T] : 0;
+	std::vector<uint32_t> vertexRun( V + 1 ), normalRun( withNormals ? N + 1 : 0 );
+	std::vector<ptm::Entry> vertexEntries( Ev ), normalEntries( En );
+	PBR_TRY( packMorph( vertex_first, vertex_index, vertex_delta, num_targets, (uint32_t) V, vertexRun.data(), vertexEntries.data(), &ctx->error ) );
+
+	if( withNormals ) {
+		PBR_TRY( packMorph( normal_first, normal_index, normal_delta, num_targets, (uint32_t) N, normalRun.data(), normalEntries.data(), &ctx->error ) );
+	}
+	if( ctx->dTriPN != nullptr ) {
+		PBR_TRY( ensurePatchTables( ctx ) );   // a morph update gathers the patches again: its tables are made here, not by an update
+	}
+
+	// everything new first: a call that cannot have its buffers leaves the morph that was set
+	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * entriesV = nullptr, * entriesN = nullptr;
+	void* weights = nullptr, * flag = nullptr, * hostWeights = nullptr, * hostFlag = nullptr;
+	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, word * ( V + 1 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &entriesV, std::max<size_t>( quad * Ev, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &weights, std::max<size_t>( sizeof( float ) * T, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostWeights, std::max<size_t>( sizeof( float ) * T, 16 ), hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, vertexRun.data(), word * ( V + 1 ), hipMemcpyHostToDevice );
+	err = ( err != hipSuccess || Ev == 0 ) ? err : hipMemcpy( entriesV, vertexEntries.data(), quad * Ev, hipMemcpyHostToDevice );
+
+	if( withNormals ) {
+		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, word * ( N + 1 ) );
+		err = ( err != hipSuccess ) ? err : hipMalloc( &entriesN, std::max<size_t>( quad * En, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, normalRun.data(), word * ( N + 1 ), hipMemcpyHostToDevice );
+		err = ( err != hipSuccess || En == 0 ) ? err : hipMemcpy( entriesN, normalEntries.data(), quad * En, hipMemcpyHostToDevice );
+	}
+
+	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
+
+	if( err != hipSuccess ) {
+		for( void* p : { rest, restNormals, staged, ofVertex, ofNormal, entriesV, entriesN, weights, flag } ) {
+			(void) hipFree( p );
+		}
+
+		(void) hipHostFree( hostWeights );
+		(void) hipHostFree( hostFlag );
+		return fail( ctx, PBR_EDEVICE, "pbr_set_morph: the rest pose and the target tables: %s", hipGetErrorString( err ) );
+	}
+
+	freeMorph( ctx );
+	ctx->dMorphRest = (float4*) rest;
+	ctx->dMorphRestNormals = (float4*) restNormals;
+	ctx->dMorphStaged = (float4*) staged;
+	ctx->dMorphVertexRun = (uint32_t*) ofVertex;
+	ctx->dMorphNormalRun = (uint32_t*) ofNormal;
+	ctx->dMorphVertexEntries = (ptm::Entry*) entriesV;
+	ctx->dMorphNormalEntries = (ptm::Entry*) entriesN;
+	ctx->dMorphWeights = (float*) weights;
+	ctx->hMorphWeights = (float*) hostWeights;
+	ctx->dMorphFlag = (unsigned*) flag;
+	ctx->hMorphFlag = (unsigned*) hostFlag;
+	ctx->numMorphTargets = num_targets;
+	ctx->morphNormals = withNormals;
+	ctx->morphVertexEntries = Ev;
+	ctx->morphNormalEntries = En;
+	ctx->morphGeneration = ctx->geometryGeneration;
+	ctx->morphBytes = quad * V + quad * V + word * ( V + 1 ) + quad * Ev + ( withNormals ? quad * N + word * ( N + 1 ) + quad * En : 0 ) + sizeof( float ) * T + sizeof( unsigned );
+	return PBR_OK;
+}
+
+int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	const PatchUpdate patches = { nullptr, 0 };
+	const MorphUpdate morph = { weights, num_targets, false, nullptr, 0 };
+	return updateScene( ctx, "pbr_update_morph", nullptr, 0, &patches, nullptr, nullptr, &morph );
+}
+
+int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	const PatchUpdate patches = { nullptr, 0 };
+	const MorphUpdate pose = { weights, num_targets, true, matrices, num_bones };
+	return updateScene( ctx, "pbr_update_pose", nullptr, 0, &patches, nullptr, nullptr, &pose );
+}
+
+int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms ) {
+	if( ctx == nullptr || out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_morph_info: null argument" );
+	}
+
+	out[0] = ctx->numMorphTargets;
+	out[1] = ctx->morphVertexEntries;
+	out[2] = ctx->morphNormalEntries;
+	out[3] = ctx->morphBytes;
+	out[4] = ctx->morphUpdates;
+	out[5] = ctx->lastUpdateMorph;
+
+	if( ms != nullptr ) {
+		*ms = ctx->lastMorphMs;
 	}
 
 	return PBR_OK;

@@ -154,19 +154,20 @@ inline void packInfluences( const uint32_t* bones, const float* weights, uint32_
 
 // What pbr_update_skin answers to these matrices before it touches the device, and the bone records that travel: `records`
 // has room for three quads per bone (its content is undefined after a refusal).  `setBones` is pbr_set_skin's count, > 0.
-// Bones are not checked for a zero determinant: the definition handles a singular blend.
-inline int checkSkinMatrices( const float* matrices, uint32_t num_bones, uint32_t setBones, pbr_float4* records, std::string* why ) {
+// Bones are not checked for a zero determinant: the definition handles a singular blend.  `call` names the caller in the
+// messages: pbr_update_pose (pt_morph_host.hpp) takes its matrices through here too.
+inline int checkSkinMatrices( const float* matrices, uint32_t num_bones, uint32_t setBones, pbr_float4* records, std::string* why, const char* call = "pbr_update_skin" ) {
 	if( matrices == nullptr ) {
-		return packFail( why, PBR_EINVAL, "pbr_update_skin: null matrices" );
+		return packFail( why, PBR_EINVAL, "%s: null matrices", call );
 	}
 	if( num_bones != setBones ) {
-		return packFail( why, PBR_EINVAL, "pbr_update_skin: %u matrices, pbr_set_skin declared %u bones", num_bones, setBones );
+		return packFail( why, PBR_EINVAL, "%s: %u matrices, pbr_set_skin declared %u bones", call, num_bones, setBones );
 	}
 
 	for( uint32_t k = 0; k < num_bones; k++ ) {
 		for( int w = 0; w < 12; w++ ) {
 			if( !std::isfinite( matrices[(size_t) k * 12 + w] ) ) {
-				return packFail( why, PBR_EINVAL, "pbr_update_skin: word %d of bone %u's matrix is not finite", w, k );
+				return packFail( why, PBR_EINVAL, "%s: word %d of bone %u's matrix is not finite", call, w, k );
 			}
 		}
 	}

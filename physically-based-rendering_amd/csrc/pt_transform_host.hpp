@@ -78,14 +78,10 @@ PATCH_FN bool finitePosition( Q p ) {
 	return finiteWord( p.x ) && finiteWord( p.y ) && finiteWord( p.z );
 }
 
+// The tail of every normal rule (transformNormal below, ptm::morphNormal in pt_morph_host.hpp): q to unit length with the rest
+// quad's .w — or the rest normal, word for word, when q's squared length is 0, infinite or NaN.
 template<class Q>
-PATCH_FN Q transformNormal( const float c[9], bool identity, Q n ) {
-	if( identity ) {
-		return n;
-	}
-
-	const ptp::V3 v = { n.x, n.y, n.z };
-	const ptp::V3 q = { ptp::dot3( { c[0], c[1], c[2] }, v ), ptp::dot3( { c[3], c[4], c[5] }, v ), ptp::dot3( { c[6], c[7], c[8] }, v ) };
+PATCH_FN Q unitOrRest( ptp::V3 q, Q n ) {
 	const float d = ptp::dot3( q, q );
 
 	if( !( d > 0.0f && d < INFINITY ) ) {
@@ -98,6 +94,17 @@ PATCH_FN Q transformNormal( const float c[9], bool identity, Q n ) {
 	out.y = unit.y;
 	out.z = unit.z;
 	return out;
+}
+
+template<class Q>
+PATCH_FN Q transformNormal( const float c[9], bool identity, Q n ) {
+	if( identity ) {
+		return n;
+	}
+
+	const ptp::V3 v = { n.x, n.y, n.z };
+	const ptp::V3 q = { ptp::dot3( { c[0], c[1], c[2] }, v ), ptp::dot3( { c[3], c[4], c[5] }, v ), ptp::dot3( { c[6], c[7], c[8] }, v ) };
+	return unitOrRest( q, n );
 }
 
 }   // namespace ptx

@@ -349,6 +349,46 @@ int pbrh_pt_update_skin( void* tracer, const float* matrices, uint32_t num_bones
 	}
 }
 
+int pbrh_pt_set_morph( void* tracer, const uint32_t* vertex_first, const uint32_t* vertex_index, const pbr_float4* vertex_delta, const uint32_t* normal_first,
+                       const uint32_t* normal_index, const pbr_float4* normal_delta, uint32_t num_targets ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.setMorph( vertex_first, vertex_index, vertex_delta, normal_first, normal_index, normal_delta, num_targets );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
+int pbrh_pt_update_morph( void* tracer, const float* weights, uint32_t num_targets ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateMorph( weights, num_targets );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
+int pbrh_pt_update_pose( void* tracer, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updatePose( weights, num_targets, matrices, num_bones );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
 	HostTracer* t = static_cast<HostTracer*>( tracer );
 

@@ -486,6 +486,33 @@ void PathTracer::updateSkin( const float* matrices, uint32_t numBones ) {
 	this->resetSampleCount();
 }
 
+void PathTracer::setMorph( const uint32_t* vertexFirst, const uint32_t* vertexIndex, const pbr_float4* vertexDelta, const uint32_t* normalFirst,
+                           const uint32_t* normalIndex, const pbr_float4* normalDelta, uint32_t numTargets ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] setMorph before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_set_morph( mCtx, vertexFirst, vertexIndex, vertexDelta, normalFirst, normalIndex, normalDelta, numTargets ), "pbr_set_morph" );
+}
+
+void PathTracer::updateMorph( const float* weights, uint32_t numTargets ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateMorph before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_morph( mCtx, weights, numTargets ), "pbr_update_morph" );
+	this->resetSampleCount();
+}
+
+void PathTracer::updatePose( const float* weights, uint32_t numTargets, const float* matrices, uint32_t numBones ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updatePose before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_pose( mCtx, weights, numTargets, matrices, numBones ), "pbr_update_pose" );
+	this->resetSampleCount();
+}
+
 void PathTracer::refitOrderedWalk( bool on ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );

@@ -100,6 +100,15 @@ class PathTracer {
 		// pbr_update_skin: one row-major 3 x 4 matrix per bone; positions and normals are blended on the device from the rest
 		// pose, then everything updateGeometry rebuilds; starts a new accumulation
 		void updateSkin( const float* matrices, uint32_t numBones );
+		// pbr_set_morph: sparse morph targets, target-major, for the vertices and (unless null) for the vertex normals; captures
+		// the rest pose the morph and pose updates start from
+		void setMorph( const uint32_t* vertexFirst, const uint32_t* vertexIndex, const pbr_float4* vertexDelta, const uint32_t* normalFirst,
+		               const uint32_t* normalIndex, const pbr_float4* normalDelta, uint32_t numTargets );
+		// pbr_update_morph: one weight per target; positions and normals are morphed on the device from the rest pose, then
+		// everything updateGeometry rebuilds; starts a new accumulation
+		void updateMorph( const float* weights, uint32_t numTargets );
+		// pbr_update_pose: the skin of the morphed rest pose — the weights and one row-major 3 x 4 matrix per bone
+		void updatePose( const float* weights, uint32_t numTargets, const float* matrices, uint32_t numBones );
 		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
 		void refitOrderedWalk( bool on );
 

@@ -51,7 +51,22 @@ One warm-up round of all three calls, then the three alternate on the same conte
   (b) pbr_update_geometry( V', N' ) with the same V', N' precomputed on the host (not timed): device, copy, wall
   (c) pbr_update_transforms with the one-hot equivalent — every element follows its own part only —: device, its transform
       kernels, wall
-  (d) the skin kernels against their traffic floor, 64 B per vertex and per normal (the bone records are not in it)"""
+  (d) the skin kernels against their traffic floor, 64 B per vertex and per normal (the bone records are not in it)
+
+  python scripts/refit_measure.py --scene ... --morph [--phong 0.6] [--reps 9] [--out FILE]
+
+pbr_update_morph and pbr_update_pose (profiles/r17/experiments/morph.txt), under the --skin leg's conditions, its skin and its
+matrices.  Four sets of targets in one run: 8 and 64 targets, each target naming either about 5 % of the vertices — one window
+of consecutive indices at a seeded offset, as a blend shape names a region of a mesh — or all of them; normal targets over the
+same indices.  Every weight is non-zero: every entry is active.  Per set, one warm-up round, then the four calls alternate on the
+same context:
+  (a) pbr_update_morph( w ): device time of the whole update, of the morph kernels alone, wall
+  (b) pbr_update_pose( w, M ): the same for the pose kernels
+  (c) pbr_update_geometry( V', N' ) with the morph's V', N' precomputed on the host (not timed): device, copy, wall
+  (d) pbr_update_skin( M ) alone: device, its skin kernels, wall
+  (e) the kernels' bytes over their time against the stated traffic: 36 B per element (rest quad, one run word, store) and 16 B
+      per entry for the morph, 32 B per element more for the pose (the influence record), 64 B per element for the skin; the
+      weight table and the bone records are not in it"""
 import os
 import sys
 import time
@@ -276,19 +291,9 @@ def measure_skin(pbr, name, alpha, reps):
     lines.append("tables: %d bytes for the skin, %d for the parts, beside the refit's %d and the patch refit's %d"
                  % (dev.skin_info()["device_bytes"], dev.transform_info()["device_bytes"], dev.refit_info()["device_bytes"], dev.patch_refit_info()["device_bytes"]))
 
-    def matrices(step):
-        """Bone 0 the identity; bone k turned about y by an angle of its own and shifted a little, another pose per step."""
-        k = np.arange(bones, dtype=np.float64)
-        angle = 0.05 * step + 0.001 * (k % 97)
-        m = np.zeros((bones, 3, 4))
-        m[:, 0, 0], m[:, 0, 2], m[:, 2, 0], m[:, 2, 2], m[:, 1, 1] = np.cos(angle), np.sin(angle), -np.sin(angle), np.cos(angle), 1.0
-        m[:, :, 3] = 0.01 * step * np.stack([np.cos(k), np.sin(k), np.cos(2.0 * k)], axis=1)
-        m[0] = np.eye(3, 4)
-        return np.ascontiguousarray(m.reshape(bones, 12), np.float32)
-
     poses = []
     for step in (1, 2):
-        M = matrices(step)
+        M = bone_matrices(bones, step)
         v, n = skin_ref.skin(a["vertices"], vb, vw, normals, nb, nw, M)
         poses.append((M, v, n))
     dev.update_skin(poses[0][0])                                     # all three paths warm
@@ -322,10 +327,113 @@ def measure_skin(pbr, name, alpha, reps):
     return lines
 
 
+def bone_matrices(bones, step):
+    """Bone 0 the identity; bone k turned about y by an angle of its own and shifted a little, another pose per step (the
+    --skin leg's matrices)."""
+    k = np.arange(bones, dtype=np.float64)
+    angle = 0.05 * step + 0.001 * (k % 97)
+    m = np.zeros((bones, 3, 4))
+    m[:, 0, 0], m[:, 0, 2], m[:, 2, 0], m[:, 2, 2], m[:, 1, 1] = np.cos(angle), np.sin(angle), -np.sin(angle), np.cos(angle), 1.0
+    m[:, :, 3] = 0.01 * step * np.stack([np.cos(k), np.sin(k), np.cos(2.0 * k)], axis=1)
+    m[0] = np.eye(3, 4)
+    return np.ascontiguousarray(m.reshape(bones, 12), np.float32)
+
+
+def measure_morph(pbr, name, alpha, reps):
+    import morph_ref
+    import skin_ref
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = {k: np.ascontiguousarray(v) for k, v in sc.arrays().items()}
+    cfg = sc.config(W, H)
+    cfg.phong_tessellation = alpha
+    faces, vertices = a["facesV"].shape[0], a["vertices"].shape[0]
+    facesN, normals = smooth_normals(a["facesV"], a["vertices"])
+    count = normals.shape[0]
+    desc = pbr.SceneDesc.from_buffer_copy(sc.desc)
+    desc.facesN, desc.normals, desc.num_normals = facesN.ctypes.data, normals.ctypes.data, count
+    vb, vw, nb, nw, bones = skin_ref.influences_for(name, a["facesV"], facesN, vertices, count)
+    extent = float(np.abs(a["vertices"][:, :3]).max())
+    lines = ["== %s by a morph, phong_tessellation %g: %d faces, %d vertices, %d smooth normals made here (facesN = facesV), %d bones"
+             % (name, alpha, faces, vertices, count, bones)]
+    dev = pbr.Device(0)
+    for targets, cover in ((8, 0.05), (8, 1.0), (64, 0.05), (64, 1.0)):
+        rng = np.random.default_rng(17 * targets + int(100 * cover))
+        vt, nt = [], []
+        for _ in range(targets):
+            for out, n, size in ((vt, vertices, 0.002 * extent), (nt, count, 0.05)):
+                window = n if cover >= 1.0 else max(1, int(cover * n))
+                index = ((int(rng.integers(0, n)) + np.arange(window)) % n).astype(np.uint32)
+                out.append((index, (rng.random((window, 3), dtype=np.float32) - np.float32(0.5)) * np.float32(2.0 * size)))
+        ev, en = sum(t[0].size for t in vt), sum(t[0].size for t in nt)
+        runs = np.bincount(np.concatenate([t[0] for t in vt]), minlength=vertices)
+        dev.upload_scene(desc)                                       # a fresh rest pose for every set
+        dev.configure(cfg)
+        dev.set_skin(vb, vw, nb, nw, bones)
+        dev.set_morph(vt, nt)
+        info = dev.morph_info()
+        assert info["device_bytes"] == morph_ref.expected_bytes(vertices, vt, count, nt) and info["vertex_entries"] == ev and info["normal_entries"] == en
+        lines.append("-- %d targets, each naming %s: %d vertex entries, %d normal entries; a vertex's run is %d .. %d entries, %.2f on average; %d bytes for the morph beside the skin's %d"
+                     % (targets, "every element" if cover >= 1.0 else "a window of %g %% of the elements" % (100.0 * cover), ev, en, runs.min(), runs.max(), runs.mean(),
+                        info["device_bytes"], dev.skin_info()["device_bytes"]))
+        poses = []
+        for step in (1, 2):
+            w = ((0.1 + 0.01 * np.arange(targets)) * np.where(np.arange(targets) % 2 == 0, 1.0, -1.0) * step).astype(np.float32)
+            v, n = morph_ref.morph(a["vertices"], vt, normals, nt, w)
+            poses.append((w, bone_matrices(bones, step), v, n))
+        w, M, v, n = poses[0]
+        dev.update_morph(w)                                          # all four paths warm
+        dev.update_pose(w, M)
+        dev.update_geometry(v, n)
+        dev.update_skin(M)
+        morph = {key: [] for key in ("device", "kernels", "wall")}
+        pose = {key: [] for key in ("device", "kernels", "wall")}
+        geo = {key: [] for key in ("device", "copy", "wall")}
+        skin = {key: [] for key in ("device", "kernels", "wall")}
+        for rep in range(reps):
+            w, M, v, n = poses[rep % 2]
+            morph["wall"].append(wall(lambda: dev.update_morph(w)))
+            morph["device"].append(dev.last_kernel_ms())
+            morph["kernels"].append(dev.morph_info()["ms"])
+            if rep == 0:
+                got_v, got_n = dev.read_geometry()
+                same = np.array_equal(got_v.view(np.uint32), v.view(np.uint32)) and np.array_equal(got_n.view(np.uint32), n.view(np.uint32))
+                lines.append("read_geometry after the first timed update_morph equals the numpy restatement bit for bit: %s" % same)
+            pose["wall"].append(wall(lambda: dev.update_pose(w, M)))
+            pose["device"].append(dev.last_kernel_ms())
+            pose["kernels"].append(dev.morph_info()["ms"])
+            geo["wall"].append(wall(lambda: dev.update_geometry(v, n)))
+            geo["device"].append(dev.last_kernel_ms())
+            geo["copy"].append(dev.refit_info()["upload_ms"])
+            skin["wall"].append(wall(lambda: dev.update_skin(M)))
+            skin["device"].append(dev.last_kernel_ms())
+            skin["kernels"].append(dev.skin_info()["ms"])
+        lines.append("(a) update_morph: device %s ms | morph kernels %s ms | wall %s ms" % (spread(morph["device"]), spread(morph["kernels"]), spread(morph["wall"])))
+        lines.append("(b) update_pose: device %s ms | pose kernels %s ms | wall %s ms" % (spread(pose["device"]), spread(pose["kernels"]), spread(pose["wall"])))
+        lines.append("(c) update_geometry( V', N' ): device %s ms | copy %s ms | wall %s ms" % (spread(geo["device"]), spread(geo["copy"]), spread(geo["wall"])))
+        lines.append("(d) update_skin alone: device %s ms | skin kernels %s ms | wall %s ms" % (spread(skin["device"]), spread(skin["kernels"]), spread(skin["wall"])))
+        elements = vertices + count
+        for label, traffic, times in (("morph", 36 * elements + 16 * (ev + en), morph["kernels"]), ("pose", 68 * elements + 16 * (ev + en), pose["kernels"]),
+                                      ("skin", 64 * elements, skin["kernels"])):
+            rate = traffic / (float(np.median(times)) * 1e-3)
+            lines.append("(e) %s kernels: stated traffic %d bytes -> %.1f GB/s = %.1f %% of 8 TB/s" % (label, traffic, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S))
+    dev.close()
+    return lines
+
+
 def main():
     import refit_ref
     pbr = pbr_loader.load()
     name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
+    if "--morph" in sys.argv:
+        text = "\n".join(measure_morph(pbr, name, float(arg("--phong", "0.6")), int(arg("--reps", "9")))) + "\n"
+        sys.stdout.write(text)
+        if "--out" in sys.argv:
+            with open(arg("--out", ""), "a") as f:
+                f.write(text)
+        return
     if "--skin" in sys.argv:
         text = "\n".join(measure_skin(pbr, name, float(arg("--phong", "0.6")), int(arg("--reps", "9")))) + "\n"
         sys.stdout.write(text)
