@@ -37,6 +37,7 @@
 #include "pt_transform.hpp"
 #include "pt_skin.hpp"
 #include "pt_morph.hpp"
+#include "pt_update_host.hpp"
 
 using ptk::DevParams;
 
@@ -135,6 +136,52 @@ struct TemporalPlanes {
 	}
 };
 
+// What every pbr_set_* captures (pbr_set_parts, pbr_set_skin, pbr_set_morph): the REST POSE — a copy of the positions and, when
+// the call was given the normals' side too, of the normals as they were when it was made —, the staging buffer V' is written to
+// before it becomes dVertices (the two pointers are swapped: nothing caches dVertices, every launch takes it from the context),
+// and the flag word of a position that is not finite with its pinned host twin.  Each kind owns one: no call touches another
+// kind's.  allocRestPose makes one, freeRestPose gives it back.
+struct RestPose {
+	float4* dRest = nullptr, * dRestNormals = nullptr, * dStaged = nullptr;
+	unsigned* dFlag = nullptr, * hFlag = nullptr;
+	bool normals = false;       // the normals are moved too
+	uint64_t bytes = 0;         // device bytes of the kind: the pose and the kind's own tables (formulas in pbr_hip_diag.h)
+	uint32_t updates = 0;       // successful updates of the kind since its pbr_set_*
+	double lastMs = 0.0;        // of the last of them: device time of the kernels that write V' and N' alone
+	uint64_t generation = 0;    // geometryGeneration when the pose was captured
+};
+
+// What pbr_set_parts adds to its rest pose: the part index of every vertex and normal, the part records in device and in pinned
+// memory.
+struct PartsState {
+	RestPose pose;
+	uint32_t count = 0;
+	unsigned* dOfVertex = nullptr, * dOfNormal = nullptr;
+	float4* dRecords = nullptr;
+	ptx::PartRecord* hRecords = nullptr;
+};
+
+// What pbr_set_skin adds: one 32-byte influence record per vertex and — with normal influences — per normal, the bone records
+// (48 bytes each) in device and in pinned memory.
+struct SkinState {
+	RestPose pose;
+	uint32_t count = 0;
+	uint4* dOfVertex = nullptr, * dOfNormal = nullptr;
+	float4* dBones = nullptr;
+	pbr_float4* hBones = nullptr;
+};
+
+// What pbr_set_morph adds: the element-major runs packMorph made — runFirst[count + 1] and one 16-byte entry per delta, for the
+// vertices and, with normal targets, for the normals — and the weight table (num_targets floats) in device and in pinned memory.
+struct MorphState {
+	RestPose pose;
+	uint32_t count = 0;
+	uint32_t* dVertexRun = nullptr, * dNormalRun = nullptr;
+	ptm::Entry* dVertexEntries = nullptr, * dNormalEntries = nullptr;
+	float* dWeights = nullptr, * hWeights = nullptr;
+	uint64_t vertexEntries = 0, normalEntries = 0;
+};
+
 struct pbr_ctx {
 	int device = -1;
 	Knobs knobs;
@@ -191,8 +238,7 @@ struct pbr_ctx {
 	uint32_t numNormals = 0;       // the upload's count, usable or not
 	uint64_t patchBytes = 0;       // device bytes of the three tables (0 until the first pbr_update_geometry)
 	uint32_t geometryUpdates = 0;  // successful pbr_update_geometry calls since the upload
-	bool lastUpdateGeometry = false;   // the most recent successful update was a pbr_update_geometry: dTriPN is current, the boxes
-	float patchAlpha = 0.0f;           // ... are thick ones for this phong_tessellation (pbr_configure's state rule)
+	float patchAlpha = 0.0f;           // the last update's boxes are thick ones for this phong_tessellation (pbr_configure's state rule)
 	double lastRefitUploadMs = 0.0;
 	// pbr_refit_ordered_walk (pt_relink_host.hpp, pt_relink.hpp): while it is on, pbr_update_vertices under a ray-ordered traversal
 	// rebuilds dNodesWalk's records on the device.  dRelink: one allocation with the static and the working tables of the layout
@@ -209,59 +255,22 @@ struct pbr_ctx {
 	double lastRelinkMs = 0.0;     // of the last pbr_update_vertices: device time of the re-link kernels alone,
 	uint32_t lastRelinkLaunches = 0;   // their number,
 	bool lastRelinked = false;     // and whether it re-linked at all
-	// pbr_set_parts / pbr_update_transforms (pt_transform_host.hpp, pt_transform.hpp): the REST POSE — a copy of the positions
-	// and, with normal parts, of the normals as they were when the parts were set —, the part index of every vertex and normal,
-	// the staging buffer V' is written to before it becomes dVertices (the two pointers are swapped: nothing caches dVertices,
-	// every launch takes it from the context), the part records and the flag word of a position that is not finite.  All of it
-	// is allocated by pbr_set_parts and freed by the next one, by freeParts and with the scene; the records and the flag have a
-	// pinned host twin, so neither copy waits for a staging copy of pageable memory
-	uint32_t numParts = 0;
-	bool partNormals = false;      // normal parts were given: the normals are transformed too
-	float4* dPartRest = nullptr, * dPartRestNormals = nullptr, * dPartStaged = nullptr, * dPartRecords = nullptr;
-	unsigned* dPartOfVertex = nullptr, * dPartOfNormal = nullptr, * dPartFlag = nullptr;
-	ptx::PartRecord* hPartRecords = nullptr;
-	unsigned* hPartFlag = nullptr;
-	uint64_t partBytes = 0;        // device bytes of all of the above
-	uint32_t transformUpdates = 0; // successful pbr_update_transforms calls since pbr_set_parts
-	bool lastUpdateTransforms = false;   // the most recent successful update was a pbr_update_transforms
+	// pbr_set_parts / pbr_update_transforms (pt_transform_host.hpp, pt_transform.hpp), pbr_set_skin / pbr_update_skin
+	// (pt_skin_host.hpp, pt_skin.hpp), pbr_set_morph / pbr_update_morph / pbr_update_pose (pt_morph_host.hpp, pt_morph.hpp): three
+	// kinds of move, independent of each other, each with a RestPose of its own and next to it the tables only that kind has
+	// (above).  All of a kind is allocated by its pbr_set_* and freed by the next one, by freeParts / freeSkin / freeMorph and with the
+	// scene.  The tables an update uploads have a pinned host twin, so no copy waits for a staging copy of pageable memory.
+	PartsState parts;
+	SkinState skin;
+	MorphState morph;
+	// the events of the step that computes V' and N' on the device; shared: one update is one kind of move
 	hipEvent_t evXfStart = nullptr, evXfStop = nullptr, evXfNormalsStart = nullptr, evXfNormalsStop = nullptr;
-	double lastTransformMs = 0.0;  // of the last pbr_update_transforms: device time of the transform kernels alone
-	// pbr_set_skin / pbr_update_skin (pt_skin_host.hpp, pt_skin.hpp): the skin's own REST POSE, one 32-byte influence record per
-	// vertex and — with normal influences — per normal, the bone records (48 bytes each) in pinned and in device memory.  The
-	// staging buffer and the flag word are of the parts' kind; a skin and parts are independent, so the skin owns a pair of its
-	// own here and neither call touches the other's state.  All of it is allocated by pbr_set_skin and freed by the next one,
-	// by freeSkin and with the scene.  The events evXf* are shared: one update is one kind of move
-	uint32_t numBones = 0;
-	bool skinNormals = false;      // normal influences were given: the normals are skinned too
-	float4* dSkinRest = nullptr, * dSkinRestNormals = nullptr, * dSkinStaged = nullptr, * dSkinBones = nullptr;
-	uint4* dSkinOfVertex = nullptr, * dSkinOfNormal = nullptr;
-	unsigned* dSkinFlag = nullptr;
-	pbr_float4* hSkinBones = nullptr;
-	unsigned* hSkinFlag = nullptr;
-	uint64_t skinBytes = 0;        // device bytes of all of the above
-	uint32_t skinUpdates = 0;      // successful pbr_update_skin calls since pbr_set_skin
-	bool lastUpdateSkin = false;   // the most recent successful update was a pbr_update_skin
-	double lastSkinMs = 0.0;       // of the last pbr_update_skin: device time of the skin kernels alone
-	// pbr_set_morph / pbr_update_morph / pbr_update_pose (pt_morph_host.hpp, pt_morph.hpp): the morph's own REST POSE, the
-	// element-major runs packMorph made — runFirst[count + 1] and one 16-byte entry per delta, for the vertices and, with normal
-	// targets, for the normals —, the weight table (num_targets floats) in pinned and in device memory, and a staging buffer and
-	// a flag word of the skin's kind.  All of it is allocated by pbr_set_morph and freed by the next one, by freeMorph and with
-	// the scene.  The events evXf* are shared: one update is one kind of move
-	uint32_t numMorphTargets = 0;
-	bool morphNormals = false;     // normal targets were given: the normals are morphed too
-	float4* dMorphRest = nullptr, * dMorphRestNormals = nullptr, * dMorphStaged = nullptr;
-	uint32_t* dMorphVertexRun = nullptr, * dMorphNormalRun = nullptr;
-	ptm::Entry* dMorphVertexEntries = nullptr, * dMorphNormalEntries = nullptr;
-	float* dMorphWeights = nullptr, * hMorphWeights = nullptr;
-	unsigned* dMorphFlag = nullptr, * hMorphFlag = nullptr;
-	uint64_t morphVertexEntries = 0, morphNormalEntries = 0;
-	uint64_t morphBytes = 0;       // device bytes of all of the above
-	uint32_t morphUpdates = 0;     // successful pbr_update_morph and pbr_update_pose calls since pbr_set_morph
-	uint32_t lastUpdateMorph = 0;  // the most recent successful update: 0 neither, 1 a pbr_update_morph, 2 a pbr_update_pose
-	double lastMorphMs = 0.0;      // of the last of them: device time of the morph / pose kernels alone
+	// the most recent successful update since the upload (pt_update_host.hpp): what pbr_configure's state rule and the four
+	// pbr_diag_*_info calls report of it is derived from this one value.  freeScene resets it, freeParts / freeSkin / freeMorph do not
+	UpdateKind lastUpdate = UpdateKind::None;
 	// which geometry a rest pose was captured from: bumped by an upload and by every successful update; pbr_set_skin and
-	// pbr_set_morph record it, pbr_update_pose needs both to have captured the same
-	uint64_t geometryGeneration = 0, skinGeneration = 0, morphGeneration = 0;
+	// pbr_set_morph record it in their pose, pbr_update_pose needs both to have captured the same
+	uint64_t geometryGeneration = 0;
 
 	// configuration + images
 	bool configured = false;
@@ -383,6 +392,18 @@ int fail( pbr_ctx* ctx, int code, const char* fmt, ... ) {
 		} \
 	} while( 0 )
 
+// What most calls ask of the context first.
+int usable( pbr_ctx* ctx ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+
+	return PBR_OK;
+}
+
 void freeWalkStreams( pbr_ctx* ctx ) {
 	(void) hipFree( ctx->dNodesWalk );
 	ctx->dNodesWalk = nullptr;
@@ -394,76 +415,54 @@ void freeWalkStreams( pbr_ctx* ctx ) {
 	ctx->relinkRuns.clear();
 }
 
-// pbr_set_parts( 0 parts ), a second pbr_set_parts, pbr_upload_scene: the parts, the rest pose and their buffers go.
-void freeParts( pbr_ctx* ctx ) {
-	for( void* p : { (void*) ctx->dPartRest, (void*) ctx->dPartRestNormals, (void*) ctx->dPartStaged, (void*) ctx->dPartRecords, (void*) ctx->dPartOfVertex,
-	                 (void*) ctx->dPartOfNormal, (void*) ctx->dPartFlag } ) {
+// A rest pose's buffers go; the record is as it was made.
+void freeRestPose( RestPose* pose ) {
+	for( void* p : { (void*) pose->dRest, (void*) pose->dRestNormals, (void*) pose->dStaged, (void*) pose->dFlag } ) {
 		(void) hipFree( p );
 	}
 
-	(void) hipHostFree( ctx->hPartRecords );
-	(void) hipHostFree( ctx->hPartFlag );
-	ctx->dPartRest = ctx->dPartRestNormals = ctx->dPartStaged = ctx->dPartRecords = nullptr;
-	ctx->dPartOfVertex = ctx->dPartOfNormal = ctx->dPartFlag = nullptr;
-	ctx->hPartRecords = nullptr;
-	ctx->hPartFlag = nullptr;
-	ctx->numParts = 0;
-	ctx->partNormals = false;
-	ctx->partBytes = 0;
-	ctx->transformUpdates = 0;
-	ctx->lastTransformMs = 0.0;
+	(void) hipHostFree( pose->hFlag );
+	*pose = RestPose();
+}
+
+// pbr_set_parts( 0 parts ), a second pbr_set_parts, pbr_upload_scene: the parts, the rest pose and their buffers go.  Like
+// freeSkin and freeMorph it knows nothing of ctx->lastUpdate: dropping a kind does not undo that its update was the last one.
+void freeParts( PartsState* parts ) {
+	freeRestPose( &parts->pose );
+	(void) hipFree( parts->dRecords );
+	(void) hipFree( parts->dOfVertex );
+	(void) hipFree( parts->dOfNormal );
+	(void) hipHostFree( parts->hRecords );
+	*parts = PartsState();
 }
 
 // pbr_set_skin( 0 bones ), a second pbr_set_skin, pbr_upload_scene: the skin, its rest pose and their buffers go.
-void freeSkin( pbr_ctx* ctx ) {
-	for( void* p : { (void*) ctx->dSkinRest, (void*) ctx->dSkinRestNormals, (void*) ctx->dSkinStaged, (void*) ctx->dSkinBones, (void*) ctx->dSkinOfVertex,
-	                 (void*) ctx->dSkinOfNormal, (void*) ctx->dSkinFlag } ) {
-		(void) hipFree( p );
-	}
-
-	(void) hipHostFree( ctx->hSkinBones );
-	(void) hipHostFree( ctx->hSkinFlag );
-	ctx->dSkinRest = ctx->dSkinRestNormals = ctx->dSkinStaged = ctx->dSkinBones = nullptr;
-	ctx->dSkinOfVertex = ctx->dSkinOfNormal = nullptr;
-	ctx->dSkinFlag = nullptr;
-	ctx->hSkinBones = nullptr;
-	ctx->hSkinFlag = nullptr;
-	ctx->numBones = 0;
-	ctx->skinNormals = false;
-	ctx->skinBytes = 0;
-	ctx->skinUpdates = 0;
-	ctx->lastSkinMs = 0.0;
+void freeSkin( SkinState* skin ) {
+	freeRestPose( &skin->pose );
+	(void) hipFree( skin->dBones );
+	(void) hipFree( skin->dOfVertex );
+	(void) hipFree( skin->dOfNormal );
+	(void) hipHostFree( skin->hBones );
+	*skin = SkinState();
 }
 
 // pbr_set_morph( 0 targets ), a second pbr_set_morph, pbr_upload_scene: the morph, its rest pose and their buffers go.
-void freeMorph( pbr_ctx* ctx ) {
-	for( void* p : { (void*) ctx->dMorphRest, (void*) ctx->dMorphRestNormals, (void*) ctx->dMorphStaged, (void*) ctx->dMorphVertexRun, (void*) ctx->dMorphNormalRun,
-	                 (void*) ctx->dMorphVertexEntries, (void*) ctx->dMorphNormalEntries, (void*) ctx->dMorphWeights, (void*) ctx->dMorphFlag } ) {
+void freeMorph( MorphState* morph ) {
+	freeRestPose( &morph->pose );
+
+	for( void* p : { (void*) morph->dVertexRun, (void*) morph->dNormalRun, (void*) morph->dVertexEntries, (void*) morph->dNormalEntries, (void*) morph->dWeights } ) {
 		(void) hipFree( p );
 	}
 
-	(void) hipHostFree( ctx->hMorphWeights );
-	(void) hipHostFree( ctx->hMorphFlag );
-	ctx->dMorphRest = ctx->dMorphRestNormals = ctx->dMorphStaged = nullptr;
-	ctx->dMorphVertexRun = ctx->dMorphNormalRun = nullptr;
-	ctx->dMorphVertexEntries = ctx->dMorphNormalEntries = nullptr;
-	ctx->dMorphWeights = ctx->hMorphWeights = nullptr;
-	ctx->dMorphFlag = ctx->hMorphFlag = nullptr;
-	ctx->numMorphTargets = 0;
-	ctx->morphNormals = false;
-	ctx->morphVertexEntries = ctx->morphNormalEntries = 0;
-	ctx->morphBytes = 0;
-	ctx->morphUpdates = 0;
-	ctx->lastMorphMs = 0.0;
+	(void) hipHostFree( morph->hWeights );
+	*morph = MorphState();
 }
 
 void freeScene( pbr_ctx* ctx ) {
-	freeParts( ctx );
-	ctx->lastUpdateTransforms = false;
-	freeSkin( ctx );
-	ctx->lastUpdateSkin = false;
-	freeMorph( ctx );
-	ctx->lastUpdateMorph = 0;
+	freeParts( &ctx->parts );
+	freeSkin( &ctx->skin );
+	freeMorph( &ctx->morph );
+	ctx->lastUpdate = UpdateKind::None;
 	ctx->geometryGeneration++;
 	(void) hipFree( ctx->dNodes );
 	freeWalkStreams( ctx );
@@ -495,7 +494,6 @@ void freeScene( pbr_ctx* ctx ) {
 	std::vector<pbr_float4>().swap( ctx->patchNormals );
 	ctx->patchBytes = 0;
 	ctx->geometryUpdates = 0;
-	ctx->lastUpdateGeometry = false;
 	ctx->patchAlpha = 0.0f;
 	ctx->dFacesV = nullptr;
 	ctx->dVertices = ctx->dRootBox = ctx->dHistVertices = nullptr;
@@ -1868,12 +1866,7 @@ int launchRelink( pbr_ctx* ctx ) {
 }  // namespace
 
 int pbr_refit_ordered_walk( pbr_ctx* ctx, int on ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
 
 	ctx->refitOrdered = ( on != 0 );
 	return PBR_OK;
@@ -1916,22 +1909,17 @@ int ensurePatchTables( pbr_ctx* ctx ) {
 	return PBR_OK;
 }
 
-// What pbr_update_geometry brings beyond the positions; pbr_update_vertices passes none.
-struct PatchUpdate {
-	const pbr_float4* normals;
+// One update call: its kind, and what that kind brings.
+struct UpdateCall {
+	UpdateKind kind;
+	const pbr_float4* vertices;   // Vertices, Geometry: V'
+	uint32_t num_vertices;
+	const pbr_float4* normals;    // Geometry: N', or NULL and 0 to keep the context's
 	uint32_t num_normals;
-};
-
-// What pbr_update_transforms brings INSTEAD of positions and normals: the matrices V' and N' are computed from on the device.
-struct TransformUpdate {
-	const float* matrices;
-	uint32_t num_parts;
-};
-
-// What pbr_update_skin brings: one matrix per bone; V' and N' are blended from them on the device.
-struct SkinUpdate {
-	const float* matrices;
-	uint32_t num_bones;
+	const float* weights;         // Morph, Pose: one per target
+	uint32_t num_targets;
+	const float* matrices;        // Transforms: one per part; Skin, Pose: one per bone
+	uint32_t num_matrices;
 };
 
 // pbr_denoise_temporal under motion tracking: H, the positions the history was made under, is a copy of dVertices taken before
@@ -1950,290 +1938,193 @@ int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
 	return PBR_OK;
 }
 
-// What pbr_update_morph brings (matrices == nullptr) and what pbr_update_pose brings: one weight per target, and for the pose
-// one matrix per bone of the skin that is set.
-struct MorphUpdate {
-	const float* weights;
-	uint32_t num_targets;
-	bool pose;
-	const float* matrices;
-	uint32_t num_bones;
-};
+// What pt_update_host.hpp's decisions read of the context.  (It returns a C++ struct, so it steps out of the C linkage.)
+extern "C++" UpdateFacts updateFacts( const pbr_ctx* ctx ) {
+	UpdateFacts f;
+	f.hasScene = ctx->hasScene;
+	f.nested = ctx->refit.nested;
+	f.why = ctx->refit.why.c_str();
+	f.configured = ctx->configured;
+	f.traversal = ctx->cfg.traversal;
+	f.phongTessellation = ctx->cfg.phong_tessellation;
+	f.refitOrdered = ctx->refitOrdered;
+	f.hasPatches = ( ctx->dTriPN != nullptr );
+	f.walkBuilt = ( ctx->dNodesWalk != nullptr && ctx->walkBuilt == ctx->cfg.traversal );
+	f.numParts = ctx->parts.count;
+	f.numBones = ctx->skin.count;
+	f.numMorphTargets = ctx->morph.count;
+	f.skinGeneration = ctx->skin.pose.generation;
+	f.morphGeneration = ctx->morph.pose.generation;
+	f.partNormals = ctx->parts.pose.normals;
+	f.skinNormals = ctx->skin.pose.normals;
+	f.morphNormals = ctx->morph.pose.normals;
+	f.tracking = ctx->temporal.tracking;
+	f.history = ctx->temporal.history;
+	f.moved = ctx->temporal.moved;
+	return f;
+}
 
-// The sequence every front end that computes V' on the device goes through, once: H first (pbr_denoise_temporal under motion
+// The kind's argument check (stage 2 of pt_update_host.hpp); it fills the pinned tables the update uploads.
+int checkUpdateArguments( pbr_ctx* ctx, const UpdateCall& u, const char* call ) {
+	switch( u.kind ) {
+		case UpdateKind::Pose:
+			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call ) );
+			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+
+		case UpdateKind::Morph:
+			return checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call );
+
+		case UpdateKind::Skin:
+			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+
+		case UpdateKind::Transforms:
+			return checkTransforms( u.matrices, u.num_matrices, ctx->parts.count, ctx->parts.hRecords, &ctx->error );
+
+		case UpdateKind::Geometry:
+			PBR_TRY( checkRefitVertices( u.vertices, u.num_vertices, ctx->numVertices, &ctx->error, call ) );
+			return checkRefitNormals( u.normals, u.num_normals, ctx->numNormals, &ctx->error );
+
+		default:
+			return checkRefitVertices( u.vertices, u.num_vertices, ctx->numVertices, &ctx->error, call );
+	}
+}
+
+// The rest pose an update of this kind starts from, and whose statistics it moves; none for the kinds that bring V' from the host.
+RestPose* restPoseOf( pbr_ctx* ctx, UpdateKind kind ) {
+	switch( kind ) {
+		case UpdateKind::Transforms: return &ctx->parts.pose;
+		case UpdateKind::Skin: return &ctx->skin.pose;
+		case UpdateKind::Morph:
+		case UpdateKind::Pose: return &ctx->morph.pose;
+		default: return nullptr;
+	}
+}
+
+// The sequence every kind that computes V' on the device goes through, once: H first (pbr_denoise_temporal under motion
 // tracking: a copy nobody reads if the call is refused), `upload` (the call's tables, asynchronous copies on the stream), the
-// flag word cleared, `launch` (the kernel that writes V' to `staged` and raises the flag word for a position that is not finite)
-// between evXfStart and evXfStop, the flag's 4 bytes read back — and only then the temporal policy hears of an update and the
-// staging buffer becomes the context's vertices (the two pointers are swapped).  A refused call leaves the context as it was.
-// The normals cannot fail; the caller writes them after this returns PBR_OK.  (A template, so it steps out of the C linkage
-// this part of the file is in.)
+// flag word cleared, `launch` (the kernel that writes V' to the pose's staging buffer and raises the flag word for a position
+// that is not finite — finite arguments can overflow, and the host never sees V') between evXfStart and evXfStop, the flag's 4
+// bytes read back — and only then the temporal policy hears of an update and the staging buffer becomes the context's vertices
+// (the two pointers are swapped).  A refused call leaves the context as it was.  The normals cannot fail; the caller writes them
+// after this returns PBR_OK.  (A template, so it steps out of the C linkage this part of the file is in.)
 extern "C++" template<class Upload, class Launch>
-int stageVertices( pbr_ctx* ctx, const char* call, unsigned* hostFlag, unsigned* deviceFlag, float4*& staged, const char* overflow, Upload upload, Launch launch ) {
-	const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
-
+int stageVertices( pbr_ctx* ctx, const char* call, RestPose* pose, bool keepsHistory, const char* overflow, Upload upload, Launch launch ) {
 	if( keepsHistory ) {
 		PBR_TRY( keepHistoryVertices( ctx, call ) );
 	}
 
 	const auto uploadStart = std::chrono::steady_clock::now();
-	*hostFlag = 0u;
+	*pose->hFlag = 0u;
 	HIP_TRY( ctx, upload() );
-	HIP_TRY( ctx, hipMemcpyAsync( deviceFlag, hostFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( pose->dFlag, pose->hFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
 	const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 	HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
 	launch();
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( hostFlag, deviceFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( pose->hFlag, pose->dFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 
-	if( *hostFlag != 0u ) {
+	if( *pose->hFlag != 0u ) {
 		return fail( ctx, PBR_EINVAL, "%s: %s", call, overflow );
 	}
 
 	ctx->temporal.update();   // the H it asks for is kept already
-	std::swap( ctx->dVertices, staged );
+	std::swap( ctx->dVertices, pose->dStaged );
 	ctx->lastRefitUploadMs = uploadMs;
 	return PBR_OK;
 }
 
-// pbr_update_vertices (patches == nullptr), pbr_update_geometry, pbr_update_transforms (moves != nullptr: vertices is null,
-// patches says "a pbr_update_geometry", and the normals come from the rest pose if normal parts were set), pbr_update_skin
-// (skin != nullptr, likewise, never together with moves) and pbr_update_morph / pbr_update_pose (morph != nullptr, likewise, never
-// together with the other two): the checks, the step that brings V' and N' to the device — two copies from the host, the
-// transform launches, the skin launches or the morph / pose launches —, the shared launches, the state.
-int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uint32_t num_vertices, const PatchUpdate* patches, const TransformUpdate* moves = nullptr,
-                 const SkinUpdate* skin = nullptr, const MorphUpdate* morph = nullptr ) {
-	const bool poses = ( morph != nullptr && morph->pose );
+// V' of a kind that computes it on the device: the kind's tables, its kernel and its overflow message through stageVertices.
+int stageKind( pbr_ctx* ctx, UpdateKind kind, const char* call, bool keepsHistory ) {
+	const uint32_t V = ctx->numVertices;
+	const dim3 grid( ( V + 255 ) / 256 ), group( 256 );
+	PartsState& parts = ctx->parts;
+	SkinState& skin = ctx->skin;
+	MorphState& morph = ctx->morph;
+	const auto uploadBones = [&]() { return hipMemcpyAsync( skin.dBones, skin.hBones, sizeof( pbr_float4 ) * 3 * skin.count, hipMemcpyHostToDevice, ctx->stream ); };
+	const auto uploadWeights = [&]() { return hipMemcpyAsync( morph.dWeights, morph.hWeights, sizeof( float ) * morph.count, hipMemcpyHostToDevice, ctx->stream ); };
 
-	if( morph != nullptr ) {
-		if( ctx->numMorphTargets == 0 ) {
-			return fail( ctx, PBR_ESTATE, "%s without a morph: pbr_set_morph declares the targets and captures the rest pose (a new upload drops it)", call );
-		}
-		if( poses && ctx->numBones == 0 ) {
-			return fail( ctx, PBR_ESTATE, "pbr_update_pose without a skin: pbr_set_skin declares the influences (a new upload drops it)" );
-		}
-		if( poses && ctx->skinGeneration != ctx->morphGeneration ) {
-			return fail( ctx, PBR_ESTATE, "pbr_update_pose: pbr_set_skin and pbr_set_morph captured different geometry (an upload or an update lies between them): set both on the same rest pose" );
-		}
+	switch( kind ) {
+		case UpdateKind::Transforms:
+			return stageVertices( ctx, call, &parts.pose, keepsHistory, "a transformed position is not finite (the matrices are finite, their product with the rest pose overflows; found on the device)",
+			                      [&]() { return hipMemcpyAsync( parts.dRecords, parts.hRecords, sizeof( ptx::PartRecord ) * parts.count, hipMemcpyHostToDevice, ctx->stream ); },
+			                      [&]() { hipLaunchKernelGGL( ptr::transformVertices, grid, group, 0, ctx->stream, parts.pose.dRest, parts.dOfVertex, parts.dRecords, parts.pose.dStaged, parts.pose.dFlag, (int) V ); } );
 
-		PBR_TRY( checkMorphWeights( morph->weights, morph->num_targets, ctx->numMorphTargets, ctx->hMorphWeights, &ctx->error, call ) );
+		case UpdateKind::Skin:
+			return stageVertices( ctx, call, &skin.pose, keepsHistory, "a skinned position is not finite (the matrices are finite, their blend's product with the rest pose overflows; found on the device)",
+			                      uploadBones,
+			                      [&]() { hipLaunchKernelGGL( ptr::skinVertices, grid, group, 0, ctx->stream, skin.pose.dRest, skin.dOfVertex, skin.dBones, skin.pose.dStaged, skin.pose.dFlag, (int) V ); } );
 
-		if( poses ) {
-			PBR_TRY( checkSkinMatrices( morph->matrices, morph->num_bones, ctx->numBones, ctx->hSkinBones, &ctx->error, call ) );
-		}
+		case UpdateKind::Morph:
+			return stageVertices( ctx, call, &morph.pose, keepsHistory, "a morphed position is not finite (weights and deltas are finite, their sum with the rest pose overflows; found on the device)",
+			                      uploadWeights,
+			                      [&]() {
+				                      hipLaunchKernelGGL( ptr::morphVertices, grid, group, 0, ctx->stream, morph.pose.dRest, morph.dVertexRun, morph.dVertexEntries, morph.dWeights,
+				                                          morph.pose.dStaged, morph.pose.dFlag, (int) V );
+			                      } );
+
+		case UpdateKind::Pose:
+			return stageVertices( ctx, call, &morph.pose, keepsHistory, "a posed position is not finite (weights, deltas and matrices are finite, the skin of the morphed rest pose overflows; found on the device)",
+			                      [&]() {
+				                      const hipError_t err = uploadWeights();
+				                      return ( err != hipSuccess ) ? err : uploadBones();
+			                      },
+			                      [&]() {
+				                      hipLaunchKernelGGL( ptr::poseVertices, grid, group, 0, ctx->stream, morph.pose.dRest, morph.dVertexRun, morph.dVertexEntries, morph.dWeights,
+				                                          skin.dOfVertex, skin.dBones, morph.pose.dStaged, morph.pose.dFlag, (int) V );
+			                      } );
+
+		default:
+			return fail( ctx, PBR_EINVAL, "%s: not a kind that is computed on the device", call );
 	}
-	else if( skin != nullptr ) {
-		if( ctx->numBones == 0 ) {
-			return fail( ctx, PBR_ESTATE, "pbr_update_skin without a skin: pbr_set_skin declares the influences and captures the rest pose (a new upload drops it)" );
-		}
+}
 
-		PBR_TRY( checkSkinMatrices( skin->matrices, skin->num_bones, ctx->numBones, ctx->hSkinBones, &ctx->error ) );
-	}
-	else if( moves != nullptr ) {
-		if( ctx->numParts == 0 ) {
-			return fail( ctx, PBR_ESTATE, "pbr_update_transforms without parts: pbr_set_parts declares them and captures the rest pose (a new upload drops them)" );
-		}
-
-		PBR_TRY( checkTransforms( moves->matrices, moves->num_parts, ctx->numParts, ctx->hPartRecords, &ctx->error ) );
-	}
-	else {
-		if( !ctx->hasScene ) {
-			return fail( ctx, PBR_ESTATE, "%s before pbr_upload_scene", call );
-		}
-
-		PBR_TRY( checkRefitVertices( vertices, num_vertices, ctx->numVertices, &ctx->error, call ) );
-
-		if( patches != nullptr ) {
-			PBR_TRY( checkRefitNormals( patches->normals, patches->num_normals, ctx->numNormals, &ctx->error ) );
-		}
-	}
-	if( !ctx->refit.nested ) {
-		return fail( ctx, PBR_ESTATE, "%s: the uploaded tree is not properly nested (%s); a refit needs the children of every container to tile its subtree", call, ctx->refit.why.c_str() );
-	}
-	const bool ordered = ( ctx->configured && ctx->cfg.traversal != 0 );
-
-	if( ordered && !ctx->refitOrdered ) {
-		return fail( ctx, PBR_ESTATE, "%s while a ray-ordered traversal (%u) is configured: its streams carry child orders built from the old boxes — configure traversal 0, update, then configure the ordered walk again", call, ctx->cfg.traversal );
-	}
-	if( patches == nullptr && ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_vertices while Phong tessellation is configured: tight boxes of the flat triangles would clip the patches" );
-	}
-	if( patches != nullptr && patches->normals != nullptr && ctx->dTriPN == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_geometry: new normals for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
+// N' behind the staged V', between evXfNormalsStart and evXfNormalsStop: the one kernel the plan names, from its kind's rest
+// normals into the context's.  Nothing when nothing moves the normals.
+int launchNormals( pbr_ctx* ctx, NormalKernel which ) {
+	if( which == NormalKernel::None ) {
+		return PBR_OK;
 	}
 
-	// the patches are gathered again whenever the scene has any; the boxes are thick ones under a configured phong_tessellation
-	// only (it cannot be configured without patches), and with alpha = 0 they are pbr_update_vertices's, kernel for kernel
-	const bool gathers = ( patches != nullptr && ctx->dTriPN != nullptr );
-	const float alpha = ( gathers && ctx->configured && ctx->cfg.phong_tessellation > 0.0f ) ? ctx->cfg.phong_tessellation : 0.0f;
+	const uint32_t N = ctx->numNormals;
+	const dim3 grid( ( N + 255 ) / 256 ), group( 256 );
+	const SkinState& skin = ctx->skin;
+	const MorphState& morph = ctx->morph;
+	HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
 
-	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	switch( which ) {
+		case NormalKernel::Transform:
+			hipLaunchKernelGGL( ptr::transformNormals, grid, group, 0, ctx->stream, ctx->parts.pose.dRestNormals, ctx->parts.dOfNormal, ctx->parts.dRecords,
+			                    ctx->dPatchNormals, (int) N );
+			break;
 
-	if( gathers ) {
-		PBR_TRY( ensurePatchTables( ctx ) );
+		case NormalKernel::Skin:
+			hipLaunchKernelGGL( ptr::skinNormals, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			break;
+
+		case NormalKernel::Morph:
+			hipLaunchKernelGGL( ptr::morphNormals, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
+			                    ctx->dPatchNormals, (int) N );
+			break;
+
+		default:
+			hipLaunchKernelGGL( ptr::poseNormals, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
+			                    skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			break;
 	}
 
-	// pbr_refit_ordered_walk: the configured layout's records are re-linked in place behind the refit.  Its tables first: a call
-	// that cannot have them changes nothing
-	const bool relinks = ( ordered && ctx->dNodesWalk != nullptr && ctx->walkBuilt == ctx->cfg.traversal );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
+	return PBR_OK;
+}
 
-	if( relinks ) {
-		PBR_TRY( ensureRelinkTables( ctx ) );
-	}
-
+// The launches every update shares, behind V' and N' in the context's buffers: the face records, the stored face normals, the
+// patches (and under Phong tessellation the faces' thick boxes for the leaf step one launch later), the subtrees, the top of
+// the tree, and the re-link of the configured layout's records.
+int refitBehind( pbr_ctx* ctx, bool gathers, float alpha, bool relinks ) {
 	const uint32_t F = ctx->numFaces;
-
-	// the step that brings V' and N' to the device: two copies from the host, the transform launches, the skin launches or the
-	// morph / pose launches
-	if( morph != nullptr ) {
-		const uint32_t V = ctx->numVertices, N = ctx->numNormals;
-		const dim3 vertexGrid( ( V + 255 ) / 256 ), normalGrid( ( N + 255 ) / 256 ), group( 256 );
-
-		PBR_TRY( stageVertices( ctx, call, ctx->hMorphFlag, ctx->dMorphFlag, ctx->dMorphStaged,
-		                        poses ? "a posed position is not finite (weights, deltas and matrices are finite, the skin of the morphed rest pose overflows; found on the device)"
-		                              : "a morphed position is not finite (weights and deltas are finite, their sum with the rest pose overflows; found on the device)",
-		                        [&]() {
-			                        hipError_t err = hipMemcpyAsync( ctx->dMorphWeights, ctx->hMorphWeights, sizeof( float ) * ctx->numMorphTargets, hipMemcpyHostToDevice, ctx->stream );
-			                        return ( err != hipSuccess || !poses ) ? err : hipMemcpyAsync( ctx->dSkinBones, ctx->hSkinBones, sizeof( pbr_float4 ) * 3 * ctx->numBones, hipMemcpyHostToDevice, ctx->stream );
-		                        },
-		                        [&]() {
-			                        if( poses ) {
-				                        hipLaunchKernelGGL( ptr::poseVertices, vertexGrid, group, 0, ctx->stream, ctx->dMorphRest, ctx->dMorphVertexRun, ctx->dMorphVertexEntries,
-				                                            ctx->dMorphWeights, ctx->dSkinOfVertex, ctx->dSkinBones, ctx->dMorphStaged, ctx->dMorphFlag, (int) V );
-			                        }
-			                        else {
-				                        hipLaunchKernelGGL( ptr::morphVertices, vertexGrid, group, 0, ctx->stream, ctx->dMorphRest, ctx->dMorphVertexRun, ctx->dMorphVertexEntries,
-				                                            ctx->dMorphWeights, ctx->dMorphStaged, ctx->dMorphFlag, (int) V );
-			                        }
-		                        } ) );
-
-		// the normals: morphed if the morph has normal targets, skinned if this is a pose and the skin has normal influences
-		const bool morphs = ctx->morphNormals, skins = ( poses && ctx->skinNormals );
-
-		if( morphs || skins ) {
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
-
-			if( morphs && skins ) {
-				hipLaunchKernelGGL( ptr::poseNormals, normalGrid, group, 0, ctx->stream, ctx->dMorphRestNormals, ctx->dMorphNormalRun, ctx->dMorphNormalEntries,
-				                    ctx->dMorphWeights, ctx->dSkinOfNormal, ctx->dSkinBones, ctx->dPatchNormals, (int) N );
-			}
-			else if( morphs ) {
-				hipLaunchKernelGGL( ptr::morphNormals, normalGrid, group, 0, ctx->stream, ctx->dMorphRestNormals, ctx->dMorphNormalRun, ctx->dMorphNormalEntries,
-				                    ctx->dMorphWeights, ctx->dPatchNormals, (int) N );
-			}
-			else {
-				hipLaunchKernelGGL( ptr::skinNormals, normalGrid, group, 0, ctx->stream, ctx->dSkinRestNormals, ctx->dSkinOfNormal, ctx->dSkinBones, ctx->dPatchNormals, (int) N );
-			}
-
-			HIP_TRY( ctx, hipGetLastError() );
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
-		}
-	}
-	else if( skin != nullptr ) {
-		// pbr_update_transforms' mechanism below, word for word: H first, V' into the skin's staging buffer, the flag word read
-		// back, and only then the pointers are swapped; the normals are written after that check
-		const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
-
-		if( keepsHistory ) {
-			PBR_TRY( keepHistoryVertices( ctx, call ) );
-		}
-
-		const uint32_t V = ctx->numVertices;
-		const auto uploadStart = std::chrono::steady_clock::now();
-		*ctx->hSkinFlag = 0u;
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->dSkinBones, ctx->hSkinBones, sizeof( pbr_float4 ) * 3 * ctx->numBones, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->dSkinFlag, ctx->hSkinFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
-		const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
-		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-		HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
-		hipLaunchKernelGGL( ptr::skinVertices, dim3( ( V + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dSkinRest, ctx->dSkinOfVertex,
-		                    ctx->dSkinBones, ctx->dSkinStaged, ctx->dSkinFlag, (int) V );
-		HIP_TRY( ctx, hipGetLastError() );
-		HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->hSkinFlag, ctx->dSkinFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-
-		if( *ctx->hSkinFlag != 0u ) {
-			return fail( ctx, PBR_EINVAL, "pbr_update_skin: a skinned position is not finite (the matrices are finite, their blend's product with the rest pose overflows; found on the device)" );
-		}
-
-		ctx->temporal.update();   // the H it asks for is kept already
-		std::swap( ctx->dVertices, ctx->dSkinStaged );
-		ctx->lastRefitUploadMs = uploadMs;
-
-		if( ctx->skinNormals ) {
-			const uint32_t N = ctx->numNormals;
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
-			hipLaunchKernelGGL( ptr::skinNormals, dim3( ( N + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dSkinRestNormals, ctx->dSkinOfNormal,
-			                    ctx->dSkinBones, ctx->dPatchNormals, (int) N );
-			HIP_TRY( ctx, hipGetLastError() );
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
-		}
-	}
-	else if( moves == nullptr ) {
-		// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
-		// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below
-		// does not: it waits for the copy
-		if( ctx->temporal.update() ) {
-			PBR_TRY( keepHistoryVertices( ctx, call ) );
-		}
-
-		const auto uploadStart = std::chrono::steady_clock::now();
-		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice ) );
-
-		if( gathers && patches->normals != nullptr ) {
-			HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, patches->normals, sizeof( pbr_float4 ) * patches->num_normals, hipMemcpyHostToDevice ) );
-		}
-
-		ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
-		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	}
-	else {
-		// V' goes to the staging buffer first: finite matrices can overflow, the host never sees V', and a refused call leaves the
-		// context as it was.  So H is copied before the temporal policy hears of an update (a copy nobody reads if the call is
-		// refused), the kernel raises a flag word, the host reads its 4 bytes, and only then the staging buffer becomes dVertices
-		const bool keepsHistory = ( ctx->temporal.tracking && ctx->temporal.history && !ctx->temporal.moved );
-
-		if( keepsHistory ) {
-			PBR_TRY( keepHistoryVertices( ctx, call ) );
-		}
-
-		const uint32_t V = ctx->numVertices;
-		const auto uploadStart = std::chrono::steady_clock::now();
-		*ctx->hPartFlag = 0u;
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->dPartRecords, ctx->hPartRecords, sizeof( ptx::PartRecord ) * ctx->numParts, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->dPartFlag, ctx->hPartFlag, sizeof( unsigned ), hipMemcpyHostToDevice, ctx->stream ) );
-		const double uploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
-		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-		HIP_TRY( ctx, hipEventRecord( ctx->evXfStart, ctx->stream ) );
-		hipLaunchKernelGGL( ptr::transformVertices, dim3( ( V + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dPartRest, ctx->dPartOfVertex,
-		                    ctx->dPartRecords, ctx->dPartStaged, ctx->dPartFlag, (int) V );
-		HIP_TRY( ctx, hipGetLastError() );
-		HIP_TRY( ctx, hipEventRecord( ctx->evXfStop, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( ctx->hPartFlag, ctx->dPartFlag, sizeof( unsigned ), hipMemcpyDeviceToHost, ctx->stream ) );
-		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-
-		if( *ctx->hPartFlag != 0u ) {
-			return fail( ctx, PBR_EINVAL, "pbr_update_transforms: a transformed position is not finite (the matrices are finite, their product with the rest pose overflows; found on the device)" );
-		}
-
-		ctx->temporal.update();   // the H it asks for is kept already
-		std::swap( ctx->dVertices, ctx->dPartStaged );
-		ctx->lastRefitUploadMs = uploadMs;
-
-		if( ctx->partNormals ) {
-			const uint32_t N = ctx->numNormals;
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
-			hipLaunchKernelGGL( ptr::transformNormals, dim3( ( N + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dPartRestNormals, ctx->dPartOfNormal,
-			                    ctx->dPartRecords, ctx->dPatchNormals, (int) N );
-			HIP_TRY( ctx, hipGetLastError() );
-			HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStop, ctx->stream ) );
-		}
-	}
-
-	ctx->geometryGeneration++;   // the context's vertices are new ones from here on: a rest pose captured before is another geometry's
 	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dVertices, ctx->dTris, (int) F );
 	HIP_TRY( ctx, hipGetLastError() );
 
@@ -2245,7 +2136,6 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
-	// the patches, and under Phong tessellation the faces' thick boxes for the leaf step one launch later
 	if( gathers ) {
 		const auto kernel = ( alpha > 0.0f ) ? ptr::refitPatches<true> : ptr::refitPatches<false>;
 		hipLaunchKernelGGL( kernel, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dPatchFacesN, ctx->dVertices,
@@ -2272,56 +2162,79 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 		PBR_TRY( launchRelink( ctx ) );
 	}
 
+	return PBR_OK;
+}
+
+// Every update call: the refusals (pt_update_host.hpp's two stages around the kind's argument check), the tables a plan needs,
+// the step that brings V' and N' to the device, the shared launches, the state.
+int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
+	const UpdateKind kind = u.kind;
+	const char* call = updateCall( kind );
+	const UpdateFacts facts = updateFacts( ctx );
+	PBR_TRY( admitKind( kind, facts, &ctx->error ) );
+	PBR_TRY( checkUpdateArguments( ctx, u, call ) );
+	PBR_TRY( admitShared( kind, u.normals != nullptr, facts, &ctx->error ) );
+	const UpdatePlan plan = planUpdate( kind, facts );
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+
+	if( plan.gathers ) {
+		PBR_TRY( ensurePatchTables( ctx ) );
+	}
+	if( plan.relinks ) {
+		PBR_TRY( ensureRelinkTables( ctx ) );   // its tables first: a call that cannot have them changes nothing
+	}
+
+	RestPose* pose = restPoseOf( ctx, kind );
+
+	if( pose != nullptr ) {
+		PBR_TRY( stageKind( ctx, kind, call, plan.keepsHistory ) );
+		PBR_TRY( launchNormals( ctx, plan.normals ) );
+	}
+	else {
+		// pbr_denoise_temporal: static geometry only — unless motion is tracked: then the history stays, and the first update
+		// after a temporal call keeps the positions the history was made under.  The copy runs on the stream, the upload below
+		// does not: it waits for the copy
+		ctx->temporal.update();
+
+		if( plan.keepsHistory ) {
+			PBR_TRY( keepHistoryVertices( ctx, call ) );
+		}
+
+		const auto uploadStart = std::chrono::steady_clock::now();
+		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, u.vertices, sizeof( pbr_float4 ) * u.num_vertices, hipMemcpyHostToDevice ) );
+
+		if( plan.gathers && u.normals != nullptr ) {
+			HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, u.normals, sizeof( pbr_float4 ) * u.num_normals, hipMemcpyHostToDevice ) );
+		}
+
+		ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
+		HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	}
+
+	ctx->geometryGeneration++;   // the context's vertices are new ones from here on: a rest pose captured before is another geometry's
+	PBR_TRY( refitBehind( ctx, plan.gathers, plan.alpha, plan.relinks ) );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	PBR_TRY( timedTail( ctx ) );
 	ctx->treeStale = true;
 	ctx->refitUpdates++;
-	ctx->lastUpdateGeometry = ( patches != nullptr );
-	ctx->patchAlpha = alpha;
-	ctx->geometryUpdates += ( patches != nullptr ) ? 1u : 0u;
-	ctx->lastUpdateTransforms = ( moves != nullptr );
+	ctx->lastUpdate = kind;
+	ctx->patchAlpha = plan.alpha;
+	ctx->geometryUpdates += updateWasGeometry( kind ) ? 1u : 0u;
 
-	if( moves != nullptr ) {
+	if( pose != nullptr ) {
 		float ms = 0.0f, normalsMs = 0.0f;
 		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
 
-		if( ctx->partNormals ) {
+		if( plan.normals != NormalKernel::None ) {
 			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
 		}
 
-		ctx->lastTransformMs = (double) ms + (double) normalsMs;
-		ctx->transformUpdates++;
+		pose->lastMs = (double) ms + (double) normalsMs;
+		pose->updates++;
 	}
 
-	ctx->lastUpdateSkin = ( skin != nullptr );
-
-	if( skin != nullptr ) {
-		float ms = 0.0f, normalsMs = 0.0f;
-		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
-
-		if( ctx->skinNormals ) {
-			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
-		}
-
-		ctx->lastSkinMs = (double) ms + (double) normalsMs;
-		ctx->skinUpdates++;
-	}
-
-	ctx->lastUpdateMorph = ( morph == nullptr ) ? 0u : poses ? 2u : 1u;
-
-	if( morph != nullptr ) {
-		float ms = 0.0f, normalsMs = 0.0f;
-		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evXfStart, ctx->evXfStop ) );
-
-		if( ctx->morphNormals || ( poses && ctx->skinNormals ) ) {
-			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
-		}
-
-		ctx->lastMorphMs = (double) ms + (double) normalsMs;
-		ctx->morphUpdates++;
-	}
-
-	if( relinks ) {
+	if( plan.relinks ) {
 		// the eight first references are the context's too (applyWalk): 32 bytes of header, no node, box or record
 		float ms = 0.0f;
 		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evRelinkStart, ctx->evRelinkStop ) );
@@ -2333,38 +2246,72 @@ int updateScene( pbr_ctx* ctx, const char* call, const pbr_float4* vertices, uin
 
 	freeWalkStreams( ctx );   // none while traversal 0 is configured; an unconfigured context may hold a previous mode's
 	// the flag is on but the configured layout's records are not there to re-link: they are built on the host, as pbr_configure does
-	return ordered ? buildWalkStreams( ctx, ctx->cfg.traversal ) : PBR_OK;
+	return plan.ordered ? buildWalkStreams( ctx, ctx->cfg.traversal ) : PBR_OK;
+}
+
+// "Everything new first" of a pbr_set_*: the rest pose's buffers — the normals' only if the call moves them —, the staging
+// buffer, the flag word and its pinned twin, and the capture of the context's vertices and normals, device to device (the
+// caller's hipDeviceSynchronize waits for it).  On failure everything is given back and *pose is an empty record; the
+// context is not touched either way.
+hipError_t allocRestPose( const pbr_ctx* ctx, bool withNormals, RestPose* pose ) {
+	const size_t vertexBytes = sizeof( pbr_float4 ) * ctx->numVertices, normalBytes = sizeof( pbr_float4 ) * ctx->numNormals;
+	*pose = RestPose();
+	hipError_t err = hipMalloc( (void**) &pose->dRest, std::max<size_t>( vertexBytes, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &pose->dStaged, std::max<size_t>( vertexBytes, 16 ) );
+	err = ( err != hipSuccess || !withNormals ) ? err : hipMalloc( (void**) &pose->dRestNormals, std::max<size_t>( normalBytes, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &pose->dFlag, 16 );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &pose->hFlag, 16, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( pose->dRest, ctx->dVertices, vertexBytes, hipMemcpyDeviceToDevice );
+	err = ( err != hipSuccess || !withNormals ) ? err : hipMemcpy( pose->dRestNormals, ctx->dPatchNormals, normalBytes, hipMemcpyDeviceToDevice );
+
+	if( err != hipSuccess ) {
+		freeRestPose( pose );
+		return err;
+	}
+
+	pose->normals = withNormals;
+	pose->generation = ctx->geometryGeneration;
+	return hipSuccess;
 }
 
 }  // namespace
 
 int pbr_update_vertices( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices ) {
 	if( ctx == nullptr || ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
+		return fail( ctx, PBR_ESTATE, "context is not usable" );   // a null context too: this call's answer since it exists
 	}
 
-	return updateScene( ctx, "pbr_update_vertices", vertices, num_vertices, nullptr );
+	return updateScene( ctx, { UpdateKind::Vertices, vertices, num_vertices, nullptr, 0, nullptr, 0, nullptr, 0 } );
 }
 
 int pbr_update_geometry( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertices, const pbr_float4* normals, uint32_t num_normals ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::Geometry, vertices, num_vertices, normals, num_normals, nullptr, 0, nullptr, 0 } );
+}
 
-	const PatchUpdate patches = { normals, num_normals };
-	return updateScene( ctx, "pbr_update_geometry", vertices, num_vertices, &patches );
+int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_parts ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::Transforms, nullptr, 0, nullptr, 0, nullptr, 0, matrices, num_parts } );
+}
+
+int pbr_update_skin( pbr_ctx* ctx, const float* matrices, uint32_t num_bones ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::Skin, nullptr, 0, nullptr, 0, nullptr, 0, matrices, num_bones } );
+}
+
+int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::Morph, nullptr, 0, nullptr, 0, weights, num_targets, nullptr, 0 } );
+}
+
+int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::Pose, nullptr, 0, nullptr, 0, weights, num_targets, matrices, num_bones } );
 }
 
 int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals, uint32_t num_parts ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
+
 	if( !ctx->hasScene ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_parts before pbr_upload_scene" );
 	}
@@ -2378,7 +2325,7 @@ int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_verti
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_parts == 0 ) {
-		freeParts( ctx );
+		freeParts( &ctx->parts );
 		return PBR_OK;
 	}
 	if( ctx->dTriPN != nullptr ) {
@@ -2387,74 +2334,36 @@ int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_verti
 
 	// everything new first: a call that cannot have its buffers leaves the parts that were set
 	const size_t V = num_vertices, N = num_normals, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
-	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * records = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * flag = nullptr;
-	void* hostRecords = nullptr, * hostFlag = nullptr;
-	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, std::max<size_t>( word * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &records, sizeof( ptx::PartRecord ) * num_parts );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostRecords, sizeof( ptx::PartRecord ) * num_parts, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, vertex_part, word * V, hipMemcpyHostToDevice );
+	PartsState fresh;
+	hipError_t err = allocRestPose( ctx, normal_part != nullptr, &fresh.pose );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfVertex, std::max<size_t>( word * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dRecords, sizeof( ptx::PartRecord ) * num_parts );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hRecords, sizeof( ptx::PartRecord ) * num_parts, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfVertex, vertex_part, word * V, hipMemcpyHostToDevice );
 
 	if( normal_part != nullptr ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, std::max<size_t>( word * N, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, normal_part, word * N, hipMemcpyHostToDevice );
+		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfNormal, std::max<size_t>( word * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfNormal, normal_part, word * N, hipMemcpyHostToDevice );
 	}
 
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		for( void* p : { rest, restNormals, staged, records, ofVertex, ofNormal, flag } ) {
-			(void) hipFree( p );
-		}
-
-		(void) hipHostFree( hostRecords );
-		(void) hipHostFree( hostFlag );
+		freeParts( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_parts: the rest pose and the part tables: %s", hipGetErrorString( err ) );
 	}
 
-	freeParts( ctx );
-	ctx->dPartRest = (float4*) rest;
-	ctx->dPartRestNormals = (float4*) restNormals;
-	ctx->dPartStaged = (float4*) staged;
-	ctx->dPartRecords = (float4*) records;
-	ctx->dPartOfVertex = (unsigned*) ofVertex;
-	ctx->dPartOfNormal = (unsigned*) ofNormal;
-	ctx->dPartFlag = (unsigned*) flag;
-	ctx->hPartRecords = (ptx::PartRecord*) hostRecords;
-	ctx->hPartFlag = (unsigned*) hostFlag;
-	ctx->numParts = num_parts;
-	ctx->partNormals = ( normal_part != nullptr );
-	ctx->partBytes = ( quad + quad + word ) * V + ( ctx->partNormals ? ( quad + word ) * N : 0 ) + sizeof( ptx::PartRecord ) * num_parts + sizeof( unsigned );
+	fresh.count = num_parts;
+	fresh.pose.bytes = ( quad + quad + word ) * V + ( fresh.pose.normals ? ( quad + word ) * N : 0 ) + sizeof( ptx::PartRecord ) * num_parts + sizeof( unsigned );
+	freeParts( &ctx->parts );
+	ctx->parts = fresh;
 	return PBR_OK;
-}
-
-int pbr_update_transforms( pbr_ctx* ctx, const float* matrices, uint32_t num_parts ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
-
-	const PatchUpdate patches = { nullptr, 0 };
-	const TransformUpdate moves = { matrices, num_parts };
-	return updateScene( ctx, "pbr_update_transforms", nullptr, 0, &patches, &moves );
 }
 
 int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* vertex_weights, uint32_t num_vertices, const uint32_t* normal_bones,
                   const float* normal_weights, uint32_t num_normals, uint32_t num_bones ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
+
 	if( !ctx->hasScene ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_skin before pbr_upload_scene" );
 	}
@@ -2468,7 +2377,7 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_bones == 0 ) {
-		freeSkin( ctx );
+		freeSkin( &ctx->skin );
 		return PBR_OK;
 	}
 	if( ctx->dTriPN != nullptr ) {
@@ -2480,67 +2389,32 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 	std::vector<pts::Influence> packed( std::max<size_t>( V, N ) );
 
 	// everything new first: a call that cannot have its buffers leaves the skin that was set
-	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * bones = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * flag = nullptr;
-	void* hostBones = nullptr, * hostFlag = nullptr;
-	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, std::max<size_t>( record * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &bones, bone * num_bones );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostBones, bone * num_bones, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
+	SkinState fresh;
+	hipError_t err = allocRestPose( ctx, normal_bones != nullptr, &fresh.pose );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfVertex, std::max<size_t>( record * V, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dBones, bone * num_bones );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hBones, bone * num_bones, hipHostMallocDefault );
 	packInfluences( vertex_bones, vertex_weights, num_vertices, packed.data() );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, packed.data(), record * V, hipMemcpyHostToDevice );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfVertex, packed.data(), record * V, hipMemcpyHostToDevice );
 
 	if( normal_bones != nullptr ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, std::max<size_t>( record * N, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
+		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfNormal, std::max<size_t>( record * N, 16 ) );
 		packInfluences( normal_bones, normal_weights, num_normals, packed.data() );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, packed.data(), record * N, hipMemcpyHostToDevice );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfNormal, packed.data(), record * N, hipMemcpyHostToDevice );
 	}
 
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		for( void* p : { rest, restNormals, staged, bones, ofVertex, ofNormal, flag } ) {
-			(void) hipFree( p );
-		}
-
-		(void) hipHostFree( hostBones );
-		(void) hipHostFree( hostFlag );
+		freeSkin( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_skin: the rest pose and the influence tables: %s", hipGetErrorString( err ) );
 	}
 
-	freeSkin( ctx );
-	ctx->dSkinRest = (float4*) rest;
-	ctx->dSkinRestNormals = (float4*) restNormals;
-	ctx->dSkinStaged = (float4*) staged;
-	ctx->dSkinBones = (float4*) bones;
-	ctx->dSkinOfVertex = (uint4*) ofVertex;
-	ctx->dSkinOfNormal = (uint4*) ofNormal;
-	ctx->dSkinFlag = (unsigned*) flag;
-	ctx->hSkinBones = (pbr_float4*) hostBones;
-	ctx->hSkinFlag = (unsigned*) hostFlag;
-	ctx->numBones = num_bones;
-	ctx->skinNormals = ( normal_bones != nullptr );
-	ctx->skinGeneration = ctx->geometryGeneration;
-	ctx->skinBytes = ( quad + quad + record ) * V + ( ctx->skinNormals ? ( quad + record ) * N : 0 ) + bone * num_bones + sizeof( unsigned );
+	fresh.count = num_bones;
+	fresh.pose.bytes = ( quad + quad + record ) * V + ( fresh.pose.normals ? ( quad + record ) * N : 0 ) + bone * num_bones + sizeof( unsigned );
+	freeSkin( &ctx->skin );
+	ctx->skin = fresh;
 	return PBR_OK;
-}
-
-int pbr_update_skin( pbr_ctx* ctx, const float* matrices, uint32_t num_bones ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
-
-	const PatchUpdate patches = { nullptr, 0 };
-	const SkinUpdate skin = { matrices, num_bones };
-	return updateScene( ctx, "pbr_update_skin", nullptr, 0, &patches, nullptr, &skin );
 }
 
 int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
@@ -2548,13 +2422,13 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_skin_info: null argument" );
 	}
 
-	out[0] = ctx->numBones;
-	out[1] = ctx->skinBytes;
-	out[2] = ctx->skinUpdates;
-	out[3] = ctx->lastUpdateSkin ? 1 : 0;
+	out[0] = ctx->skin.count;
+	out[1] = ctx->skin.pose.bytes;
+	out[2] = ctx->skin.pose.updates;
+	out[3] = ( ctx->lastUpdate == UpdateKind::Skin ) ? 1 : 0;
 
 	if( ms != nullptr ) {
-		*ms = ctx->lastSkinMs;
+		*ms = ctx->skin.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2562,12 +2436,8 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 
 int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* vertex_index, const pbr_float4* vertex_delta, const uint32_t* normal_first,
                    const uint32_t* normal_index, const pbr_float4* normal_delta, uint32_t num_targets ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
+
 	if( !ctx->hasScene ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_morph before pbr_upload_scene" );
 	}
@@ -2581,7 +2451,7 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_targets == 0 ) {
-		freeMorph( ctx );
+		freeMorph( &ctx->morph );
 		return PBR_OK;
 	}
 
@@ -2601,86 +2471,36 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 	}
 
 	// everything new first: a call that cannot have its buffers leaves the morph that was set
-	void* rest = nullptr, * restNormals = nullptr, * staged = nullptr, * ofVertex = nullptr, * ofNormal = nullptr, * entriesV = nullptr, * entriesN = nullptr;
-	void* weights = nullptr, * flag = nullptr, * hostWeights = nullptr, * hostFlag = nullptr;
-	hipError_t err = hipMalloc( &rest, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &staged, std::max<size_t>( quad * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &ofVertex, word * ( V + 1 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &entriesV, std::max<size_t>( quad * Ev, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &weights, std::max<size_t>( sizeof( float ) * T, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( &flag, 16 );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostWeights, std::max<size_t>( sizeof( float ) * T, 16 ), hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( &hostFlag, 16, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( rest, ctx->dVertices, quad * V, hipMemcpyDeviceToDevice );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( ofVertex, vertexRun.data(), word * ( V + 1 ), hipMemcpyHostToDevice );
-	err = ( err != hipSuccess || Ev == 0 ) ? err : hipMemcpy( entriesV, vertexEntries.data(), quad * Ev, hipMemcpyHostToDevice );
+	MorphState fresh;
+	hipError_t err = allocRestPose( ctx, withNormals, &fresh.pose );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dVertexRun, word * ( V + 1 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dVertexEntries, std::max<size_t>( quad * Ev, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dWeights, std::max<size_t>( sizeof( float ) * T, 16 ) );
+	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hWeights, std::max<size_t>( sizeof( float ) * T, 16 ), hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dVertexRun, vertexRun.data(), word * ( V + 1 ), hipMemcpyHostToDevice );
+	err = ( err != hipSuccess || Ev == 0 ) ? err : hipMemcpy( fresh.dVertexEntries, vertexEntries.data(), quad * Ev, hipMemcpyHostToDevice );
 
 	if( withNormals ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( &restNormals, std::max<size_t>( quad * N, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMalloc( &ofNormal, word * ( N + 1 ) );
-		err = ( err != hipSuccess ) ? err : hipMalloc( &entriesN, std::max<size_t>( quad * En, 16 ) );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( restNormals, ctx->dPatchNormals, quad * N, hipMemcpyDeviceToDevice );
-		err = ( err != hipSuccess ) ? err : hipMemcpy( ofNormal, normalRun.data(), word * ( N + 1 ), hipMemcpyHostToDevice );
-		err = ( err != hipSuccess || En == 0 ) ? err : hipMemcpy( entriesN, normalEntries.data(), quad * En, hipMemcpyHostToDevice );
+		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dNormalRun, word * ( N + 1 ) );
+		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dNormalEntries, std::max<size_t>( quad * En, 16 ) );
+		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dNormalRun, normalRun.data(), word * ( N + 1 ), hipMemcpyHostToDevice );
+		err = ( err != hipSuccess || En == 0 ) ? err : hipMemcpy( fresh.dNormalEntries, normalEntries.data(), quad * En, hipMemcpyHostToDevice );
 	}
 
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		for( void* p : { rest, restNormals, staged, ofVertex, ofNormal, entriesV, entriesN, weights, flag } ) {
-			(void) hipFree( p );
-		}
-
-		(void) hipHostFree( hostWeights );
-		(void) hipHostFree( hostFlag );
+		freeMorph( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_morph: the rest pose and the target tables: %s", hipGetErrorString( err ) );
 	}
 
-	freeMorph( ctx );
-	ctx->dMorphRest = (float4*) rest;
-	ctx->dMorphRestNormals = (float4*) restNormals;
-	ctx->dMorphStaged = (float4*) staged;
-	ctx->dMorphVertexRun = (uint32_t*) ofVertex;
-	ctx->dMorphNormalRun = (uint32_t*) ofNormal;
-	ctx->dMorphVertexEntries = (ptm::Entry*) entriesV;
-	ctx->dMorphNormalEntries = (ptm::Entry*) entriesN;
-	ctx->dMorphWeights = (float*) weights;
-	ctx->hMorphWeights = (float*) hostWeights;
-	ctx->dMorphFlag = (unsigned*) flag;
-	ctx->hMorphFlag = (unsigned*) hostFlag;
-	ctx->numMorphTargets = num_targets;
-	ctx->morphNormals = withNormals;
-	ctx->morphVertexEntries = Ev;
-	ctx->morphNormalEntries = En;
-	ctx->morphGeneration = ctx->geometryGeneration;
-	ctx->morphBytes = quad * V + quad * V + word * ( V + 1 ) + quad * Ev + ( withNormals ? quad * N + word * ( N + 1 ) + quad * En : 0 ) + sizeof( float ) * T + sizeof( unsigned );
+	fresh.count = num_targets;
+	fresh.vertexEntries = Ev;
+	fresh.normalEntries = En;
+	fresh.pose.bytes = quad * V + quad * V + word * ( V + 1 ) + quad * Ev + ( withNormals ? quad * N + word * ( N + 1 ) + quad * En : 0 ) + sizeof( float ) * T + sizeof( unsigned );
+	freeMorph( &ctx->morph );
+	ctx->morph = fresh;
 	return PBR_OK;
-}
-
-int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
-
-	const PatchUpdate patches = { nullptr, 0 };
-	const MorphUpdate morph = { weights, num_targets, false, nullptr, 0 };
-	return updateScene( ctx, "pbr_update_morph", nullptr, 0, &patches, nullptr, nullptr, &morph );
-}
-
-int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
-
-	const PatchUpdate patches = { nullptr, 0 };
-	const MorphUpdate pose = { weights, num_targets, true, matrices, num_bones };
-	return updateScene( ctx, "pbr_update_pose", nullptr, 0, &patches, nullptr, nullptr, &pose );
 }
 
 int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms ) {
@@ -2688,15 +2508,15 @@ int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_morph_info: null argument" );
 	}
 
-	out[0] = ctx->numMorphTargets;
-	out[1] = ctx->morphVertexEntries;
-	out[2] = ctx->morphNormalEntries;
-	out[3] = ctx->morphBytes;
-	out[4] = ctx->morphUpdates;
-	out[5] = ctx->lastUpdateMorph;
+	out[0] = ctx->morph.count;
+	out[1] = ctx->morph.vertexEntries;
+	out[2] = ctx->morph.normalEntries;
+	out[3] = ctx->morph.pose.bytes;
+	out[4] = ctx->morph.pose.updates;
+	out[5] = updateMorphCode( ctx->lastUpdate );
 
 	if( ms != nullptr ) {
-		*ms = ctx->lastMorphMs;
+		*ms = ctx->morph.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2745,13 +2565,13 @@ int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_transform_info: null argument" );
 	}
 
-	out[0] = ctx->numParts;
-	out[1] = ctx->partBytes;
-	out[2] = ctx->transformUpdates;
-	out[3] = ctx->lastUpdateTransforms ? 1 : 0;
+	out[0] = ctx->parts.count;
+	out[1] = ctx->parts.pose.bytes;
+	out[2] = ctx->parts.pose.updates;
+	out[3] = ( ctx->lastUpdate == UpdateKind::Transforms ) ? 1 : 0;
 
 	if( ms != nullptr ) {
-		*ms = ctx->lastTransformMs;
+		*ms = ctx->parts.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2798,7 +2618,7 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs vertex normals: the uploaded scene's facesN / normals are missing or out of range" );
 	}
-	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !ctx->lastUpdateGeometry ) {
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !updateWasGeometry( ctx->lastUpdate ) ) {
 		return fail( ctx, PBR_ESTATE, "Phong tessellation after pbr_update_vertices: the refitted boxes are tight boxes of the flat triangles and would clip the patches, and the patches' corners were not updated — upload the scene again, or call pbr_update_geometry under this phong_tessellation" );
 	}
 	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !( ctx->patchAlpha == cfg->phong_tessellation ) ) {
@@ -3371,12 +3191,7 @@ int pbr_temporal_reset( pbr_ctx* ctx ) {
 // Per-vertex motion for pbr_denoise_temporal: while it is on, pbr_update_vertices keeps the history (and the vertex positions it
 // was made under) instead of dropping it.  A flag of the context: needs no scene, survives pbr_configure and pbr_upload_scene.
 int pbr_temporal_track_motion( pbr_ctx* ctx, int on ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
 
 	ctx->temporal.track( on != 0 );
 
@@ -3391,12 +3206,7 @@ int pbr_temporal_track_motion( pbr_ctx* ctx, int on ) {
 
 // The planes of the last successful pbr_denoise_temporal's motion step: {Pprev, code} and the first-hit face per pixel.
 int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face ) {
-	if( ctx == nullptr ) {
-		return PBR_EINVAL;
-	}
-	if( ctx->stream == nullptr ) {
-		return fail( ctx, PBR_ESTATE, "context is not usable" );
-	}
+	PBR_TRY( usable( ctx ) );
 	if( !ctx->temporal.lastMotion || ctx->planes.face == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_read_temporal_motion: the last successful pbr_denoise_temporal did not take the motion path (it needs pbr_temporal_track_motion, a history and a pbr_update_vertices since that history)" );
 	}
@@ -4165,7 +3975,7 @@ int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha ) {
 	out[0] = ( ctx->dTriPN != nullptr ) ? 1 : 0;
 	out[1] = ctx->patchBytes;
 	out[2] = ctx->geometryUpdates;
-	out[3] = ctx->lastUpdateGeometry ? 1 : 0;
+	out[3] = updateWasGeometry( ctx->lastUpdate ) ? 1 : 0;
 
 	if( alpha != nullptr ) {
 		*alpha = ctx->patchAlpha;
