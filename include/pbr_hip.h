@@ -36,10 +36,11 @@ extern "C" {
  * version 11 pbr_denoise_temporal and pbr_temporal_reset, version 12 pbr_temporal_track_motion and pbr_read_temporal_motion,
  * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry, version 15 pbr_set_parts, pbr_update_transforms and
  * pbr_read_geometry, version 16 pbr_set_skin and pbr_update_skin,
- * version 17 pbr_set_morph, pbr_update_morph and pbr_update_pose).  A caller that loads the library at run time — or
+ * version 17 pbr_set_morph, pbr_update_morph and pbr_update_pose, version 18 pbr_update_skin_dq, pbr_update_pose_dq and
+ * pbr_dual_quats_from_matrices).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 17
+#define PBR_ABI_VERSION 18
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -501,6 +502,79 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
                    const uint32_t* normal_first, const uint32_t* normal_index, const pbr_float4* normal_delta, uint32_t num_targets );
 int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets );
 int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones );
+/* DUAL-QUATERNION SKINNING, COMPUTED ON THE DEVICE (ABI version 18).  Linear blending of matrices collapses twisting joints: a ring
+ * of vertices blended half and half between a bone and the same bone turned by 180 degrees about the limb's axis ends up ON the
+ * axis under pbr_update_skin.  Blending the bones as unit dual quaternions keeps the ring's radius.  This block lifts the item
+ * "dual-quaternion skinning" from the OUT OF SCOPE lists above.  pbr_update_skin_dq and pbr_update_pose_dq use the skin that
+ * pbr_set_skin set — its influences, its REST POSE, its bone count — and are pbr_update_skin and pbr_update_pose with another
+ * blend; they start from the rest pose and never accumulate.  The bones' records lie in the 48 bytes per bone pbr_set_skin
+ * allocated (32 are used): the two calls allocate nothing, and pbr_diag_skin_info's byte formula stays true.
+ *
+ * `dual_quats` is host memory, borrowed for the call, num_bones x 8 floats { rx, ry, rz, rw, dx, dy, dz, dw }: the real part r is
+ * the rotation quaternion, vector part first; the dual part is d = 1/2 t r, the quaternion product of ( t, 0 ) and r, t the
+ * translation.  A DUAL QUATERNION CARRIES NO SCALE AND NO SHEAR: a bone is a rotation and a translation.
+ * THE DEFINITION, operation by operation in binary32, none fused, sqrtf and `/` correctly rounded (the library's default build).
+ *   dot4( a, b ) = ( ( ax*bx + ay*by ) + az*bz ) + aw*bw; cross is pbr_denoise_temporal's:
+ *   cross( p, q ) = ( py*qz - pz*qy, pz*qx - px*qz, px*qy - py*qx ), each word two products and a subtraction.
+ *   1 slots       S = the slots j = 0..3 of the element whose weight compares unequal to 0, in slot order — pbr_update_skin's rule.
+ *   2 hemisphere  the pivot is the real part of the first slot of S.  For every later slot s: if dot4( r_s, pivot ) < 0 the
+ *                 slot's weight is negated (negation is exact).
+ *   3 blend       eight words k: for the first slot Q[k] = w * q_s[k]; for each later slot Q[k] = Q[k] + w * q_s[k] — a
+ *                 product, then an addition.
+ *   4 normalise   nn = dot4( Q.real, Q.real ), len = sqrtf( nn ), r = Q.real / len, d = Q.dual / len: a division per word, not a
+ *                 multiplication by a reciprocal.  Since sqrtf( fl( s*s ) ) == s in binary32, a blend of identity bones comes out
+ *                 as the identity for ANY weights.
+ *   5 identity    if r.x, r.y, r.z and all four words of d compare equal to 0 and fabsf( r.w ) == 1, the element — position or
+ *                 normal — is the rest quad bit for bit; -0 stays -0.
+ *   6 position    t = 2.0f * cross( r.xyz, p ); u = cross( r.xyz, t ); p1 = ( p + r.w * t ) + u; c = cross( r.xyz, d.xyz );
+ *                 tr = 2.0f * ( ( r.w * d.xyz - d.w * r.xyz ) + c ); p' = p1 + tr; p'.w = p.w bit for bit.
+ *   7 normal      the blend comes from the normal's own influences; q = ( n + r.w * t ) + u with t and u of rule 6 taken from n,
+ *                 then the tail every normal rule here shares: dd = dot( q, q ); if !( dd > 0 && dd < inf ) n is copied, else
+ *                 n'.xyz = q * ( 1.0f / sqrtf( dd ) ), n'.w = n.w.  If !( nn > 0 && nn < inf ) the rest normal is copied too, so no
+ *                 normal word is ever NaN.  A position under a blend with nn == 0 or a NaN comes out not finite and is caught by
+ *                 rule 8; under an nn that overflowed over finite words (real parts beyond 1.8e19) r and d are 0.
+ *   8 overflow    a position that is not finite is found ON THE DEVICE with pbr_update_skin's mechanism — staging buffer, flag
+ *                 word, 4 bytes read back, pointers swapped only then; the normals are written after that check.
+ * The bones are USED AS GIVEN: not checked for unit length — rule 4 normalises the blend, and a positive multiple of a bone is the
+ * same bone up to rounding — and not checked for r . d = 0.  The weights are used as given, as pbr_update_skin uses them.
+ * pbr_update_pose_dq is the dual-quaternion skin of the morphed rest pose: rules 1 - 8 on p' and n' of pbr_update_morph's
+ * definition, with pbr_update_pose's rules about which normals are morphed and which are skinned.
+ * FIVE PROPERTIES that follow, and that tests rest on:
+ *   1. UNMOVED ELEMENTS STAY UNMOVED.  Identity bones — ( 0, 0, 0, 1; 0, 0, 0, 0 ) or its negation — under ANY weights give the
+ *      rest quads bit for bit; such an element is unmoved for pbr_denoise_temporal.
+ *   2. THE SIGN OF A BONE DOES NOT MATTER.  Negating all eight words of any bone changes no bit of V' and N', provided no
+ *      element's hemisphere dot is exactly 0.
+ *   3. A ONE-HOT ELEMENT FOLLOWS ITS BONE as a rigid motion, whatever the one weight is (a weight that is a power of two gives
+ *      the same bits as 1.0f).
+ *   4. NOT BIT-EQUAL TO THE MATRIX SKIN.  The results are NOT bit-equal to pbr_update_skin with the equivalent matrices: the
+ *      arithmetic differs.
+ *   5. pbr_update_pose_dq( 0 weights, Q ) equals pbr_update_skin_dq( Q ) to the bit.
+ * THE CONTRACT is pbr_update_skin's: everything behind V' and N' is pbr_update_geometry's.  Boxes, patches, the thick boxes under
+ * Phong tessellation, the re-linked ordered walks, renders and the temporal motion path are bit for bit what
+ * pbr_update_geometry( V', N' ) and a fresh upload of the moved scene give.  To pbr_diag_skin_info and pbr_diag_morph_info a dq
+ * update is another kind (pbr_diag_skin_dq_info, pbr_hip_diag.h, counts them).
+ * Refusals, in this order, each leaving the context, the vertices, the normals and the tree exactly as they were:
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  pbr_update_skin_dq: no skin set (the message names pbr_set_skin).  pbr_update_pose_dq: pbr_update_pose's
+ *               admission — no morph set, no skin set, skin and morph did not capture the same geometry;
+ *   PBR_EINVAL  pbr_update_pose_dq: everything pbr_update_morph refuses about `weights` and num_targets;
+ *   PBR_EINVAL  about `dual_quats`, in this order: a null pointer; a count other than pbr_set_skin's; a word that is not finite
+ *               (the message names bone and word); a real part whose four words are all 0 (the message names the bone);
+ *   then pbr_update_geometry's own refusals, in its order;
+ *   PBR_EINVAL  rule 8.
+ *
+ * pbr_dual_quats_from_matrices: host only, no context.  `matrices` are num_bones row-major 3 x 4 matrices in
+ * pbr_update_transforms' layout, dual_quats_out has room for num_bones x 8 floats; computed in double and rounded once to float.
+ * `message` (may be NULL) receives the reason of a refusal, at most `capacity` bytes with the terminator.  PBR_EINVAL, with
+ * nothing written to dual_quats_out, for a null pointer, for a matrix word that is not finite, and for a matrix whose 3 x 3 block R
+ * is not a rotation: a word of R^T R - I or det R - 1 above PBR_DQ_RIGID_TOLERANCE in magnitude — a scaled, a sheared and a
+ * mirrored matrix are refused, the message names the bone.  The tolerance is an input rule, not a measurement.
+ * OUT OF SCOPE: more than four influences, scale or shear on top of the dual quaternions, blending between the linear and the
+ * dual-quaternion skin per vertex, pbr_multi.h, topology changes. */
+#define PBR_DQ_RIGID_TOLERANCE 1e-4
+int pbr_update_skin_dq( pbr_ctx* ctx, const float* dual_quats, uint32_t num_bones );
+int pbr_update_pose_dq( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* dual_quats, uint32_t num_bones );
+int pbr_dual_quats_from_matrices( const float* matrices, uint32_t num_bones, float* dual_quats_out, char* message, size_t capacity );
 /* The vertex positions and the vertex normals the context holds now — as uploaded, or after any update of any of the three
  * kinds —, bit for bit, .w included.  pbr_read_bvh's count-only convention: *num_vertices and *num_normals are always set, an
  * output pointer may be NULL, else its capacity (in quads) must reach the count.  *num_normals is 0 for a scene without usable

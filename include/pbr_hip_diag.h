@@ -154,6 +154,15 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms );
  * out. */
 int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms );
 
+/* pbr_update_skin_dq / pbr_update_pose_dq (pbr_hip.h): out[0] the successful calls of the two since pbr_set_skin (a new
+ * pbr_set_skin, dropping the skin and pbr_upload_scene start it again at 0), [1] the most recent successful update of any kind:
+ * 0 none of the two, 1 a pbr_update_skin_dq, 2 a pbr_update_pose_dq.  *ms (may be NULL): the device time of the dq kernels alone
+ * in the last of them; pbr_last_kernel_ms covers the whole update.  The dual quaternions lie in the 48 bytes per bone that
+ * pbr_set_skin allocated, so pbr_diag_skin_info's bytes are the same with and without them.  To pbr_diag_skin_info and
+ * pbr_diag_morph_info a dq update is another kind: their counts and times do not move, their last_update is 0 afterwards.
+ * PBR_EINVAL for a null context or null out. */
+int pbr_diag_skin_dq_info( pbr_ctx* ctx, uint64_t out[2], double* ms );
+
 /* The Phong patch records as they are on the device now: six quads per face, the corners, then the vertex normals, .w = 0.
  * *count = the quads; out = NULL returns the count only, else capacity >= *count quads.  PBR_ESTATE without a scene or for a
  * scene without usable vertex normals, PBR_EINVAL for a null context, null count or too little room. */

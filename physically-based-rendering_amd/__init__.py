@@ -122,7 +122,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 17
+ABI_VERSION = 18
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -214,6 +214,10 @@ for _name, _args in (
         ("pbr_update_morph", [_vp, ctypes.c_void_p, ctypes.c_uint32]),
         ("pbr_update_pose", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
         ("pbr_diag_morph_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_update_skin_dq", [_vp, ctypes.c_void_p, ctypes.c_uint32]),                                                # ABI version 18
+        ("pbr_update_pose_dq", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
+        ("pbr_dual_quats_from_matrices", [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
+        ("pbr_diag_skin_dq_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -269,6 +273,10 @@ if hasattr(host, "pbrh_pt_update_morph"):
     host.pbrh_pt_update_morph.argtypes = [_vp, _fp, ctypes.c_uint32]
 if hasattr(host, "pbrh_pt_update_pose"):
     host.pbrh_pt_update_pose.argtypes = [_vp, _fp, ctypes.c_uint32, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_skin_dq"):
+    host.pbrh_pt_update_skin_dq.argtypes = [_vp, _fp, ctypes.c_uint32]
+if hasattr(host, "pbrh_pt_update_pose_dq"):
+    host.pbrh_pt_update_pose_dq.argtypes = [_vp, _fp, ctypes.c_uint32, _fp, ctypes.c_uint32]
 host.pbrh_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_pfm.argtypes = [ctypes.c_char_p, _fp, ctypes.c_uint32, ctypes.c_uint32]
 host.pbrh_write_png.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
@@ -319,6 +327,18 @@ def _morph_lists(targets, what):
     delta = np.ascontiguousarray(np.concatenate(deltas) if deltas else np.zeros((0, 4), np.float32), np.float32)
     # a list without entries still hands the library a pointer: NULL means "no such lists"
     return first, (index if index.size else np.zeros(1, np.uint32)), (delta if delta.size else np.zeros((1, 4), np.float32))
+
+
+def dual_quats_from_matrices(matrices):
+    """pbr_dual_quats_from_matrices: row-major 3 x 4 matrices, (bones, 12) or (bones, 3, 4), as (bones, 8) float32 dual
+    quaternions for Device.update_skin_dq.  Host only.  A matrix that is not finite or whose 3 x 3 block is not a rotation
+    (scale, shear, a mirror) raises PbrError with the library's message."""
+    matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+    out = np.zeros((matrices.shape[0], 8), np.float32)
+    why = ctypes.create_string_buffer(512)
+    if hip.pbr_dual_quats_from_matrices(matrices.ctypes.data, matrices.shape[0], out.ctypes.data, why, len(why)) != 0:
+        raise PbrError(why.value.decode())
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
@@ -612,6 +632,27 @@ class Device:
         self._check(hip.pbr_diag_morph_info(self._ctx, out, ctypes.byref(ms)))
         return {"targets": int(out[0]), "vertex_entries": int(out[1]), "normal_entries": int(out[2]), "device_bytes": int(out[3]),
                 "updates": int(out[4]), "last_update": int(out[5]), "ms": float(ms.value)}
+
+    def update_skin_dq(self, dual_quats):
+        """pbr_update_skin_dq: one dual quaternion per bone, (bones, 8) float32 { rx, ry, rz, rw, dx, dy, dz, dw } — the rotation
+        quaternion, vector part first, and the dual part 1/2 t r (dual_quats_from_matrices makes them).  The influences and the
+        rest pose are set_skin's; everything behind is update_geometry's."""
+        dual_quats = np.ascontiguousarray(dual_quats, np.float32).reshape(-1, 8)
+        self._check(hip.pbr_update_skin_dq(self._ctx, dual_quats.ctypes.data, dual_quats.shape[0]))
+
+    def update_pose_dq(self, weights, dual_quats):
+        """pbr_update_pose_dq: the dual-quaternion skin of the morphed rest pose — update_morph's weights and update_skin_dq's
+        dual quaternions in one call."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        dual_quats = np.ascontiguousarray(dual_quats, np.float32).reshape(-1, 8)
+        self._check(hip.pbr_update_pose_dq(self._ctx, weights.ctypes.data, weights.shape[0], dual_quats.ctypes.data, dual_quats.shape[0]))
+
+    def skin_dq_info(self):
+        """pbr_diag_skin_dq_info: the update_skin_dq and update_pose_dq calls since set_skin, the last update (0 none of the two,
+        1 skin_dq, 2 pose_dq), and the device time of its dq kernels alone."""
+        out, ms = (ctypes.c_uint64 * 2)(), ctypes.c_double()
+        self._check(hip.pbr_diag_skin_dq_info(self._ctx, out, ctypes.byref(ms)))
+        return {"updates": int(out[0]), "last_update": int(out[1]), "ms": float(ms.value)}
 
     def read_patches(self):
         """pbr_diag_read_patches: the Phong patch records on the device, (faces, 6, 4) float32 — three corners, three normals."""
@@ -1158,6 +1199,19 @@ class PathTracer:
         weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
         matrices = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
         if host.pbrh_pt_update_pose(self._h, _as_fp(weights), weights.shape[0], _as_fp(matrices), matrices.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updateSkinDQ(self, dual_quats):
+        """PathTracer::updateSkinDQ: Device.update_skin_dq on the tracer's context; starts a new accumulation."""
+        dual_quats = np.ascontiguousarray(dual_quats, np.float32).reshape(-1, 8)
+        if host.pbrh_pt_update_skin_dq(self._h, _as_fp(dual_quats), dual_quats.shape[0]) != 0:
+            raise PbrError(host.pbrh_last_error().decode())
+
+    def updatePoseDQ(self, weights, dual_quats):
+        """PathTracer::updatePoseDQ: Device.update_pose_dq on the tracer's context; starts a new accumulation."""
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        dual_quats = np.ascontiguousarray(dual_quats, np.float32).reshape(-1, 8)
+        if host.pbrh_pt_update_pose_dq(self._h, _as_fp(weights), weights.shape[0], _as_fp(dual_quats), dual_quats.shape[0]) != 0:
             raise PbrError(host.pbrh_last_error().decode())
 
     def refitOrderedWalk(self, on):

@@ -37,6 +37,7 @@
 #include "pt_transform.hpp"
 #include "pt_skin.hpp"
 #include "pt_morph.hpp"
+#include "pt_skin_dq.hpp"
 #include "pt_update_host.hpp"
 
 using ptk::DevParams;
@@ -162,13 +163,17 @@ struct PartsState {
 };
 
 // What pbr_set_skin adds: one 32-byte influence record per vertex and — with normal influences — per normal, the bone records
-// (48 bytes each) in device and in pinned memory.
+// (48 bytes each) in device and in pinned memory.  pbr_update_skin_dq and pbr_update_pose_dq (pt_skin_dq_host.hpp) put their
+// dual quaternions into the same two tables, 32 of the 48 bytes per bone; pose.updates and pose.lastMs are the matrix skin's, the
+// dual-quaternion updates of both calls are counted here.
 struct SkinState {
 	RestPose pose;
 	uint32_t count = 0;
 	uint4* dOfVertex = nullptr, * dOfNormal = nullptr;
 	float4* dBones = nullptr;
 	pbr_float4* hBones = nullptr;
+	uint32_t dqUpdates = 0;     // successful pbr_update_skin_dq and pbr_update_pose_dq since pbr_set_skin
+	double dqLastMs = 0.0;      // of the last of them: device time of the dq kernels that write V' and N' alone
 };
 
 // What pbr_set_morph adds: the element-major runs packMorph made — runFirst[count + 1] and one 16-byte entry per delta, for the
@@ -1918,7 +1923,7 @@ struct UpdateCall {
 	uint32_t num_normals;
 	const float* weights;         // Morph, Pose: one per target
 	uint32_t num_targets;
-	const float* matrices;        // Transforms: one per part; Skin, Pose: one per bone
+	const float* matrices;        // Transforms: one per part; Skin, Pose: one per bone; SkinDQ, PoseDQ: one dual quaternion per bone
 	uint32_t num_matrices;
 };
 
@@ -1977,6 +1982,13 @@ int checkUpdateArguments( pbr_ctx* ctx, const UpdateCall& u, const char* call ) 
 		case UpdateKind::Skin:
 			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
 
+		case UpdateKind::PoseDQ:
+			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call ) );
+			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+
+		case UpdateKind::SkinDQ:
+			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+
 		case UpdateKind::Transforms:
 			return checkTransforms( u.matrices, u.num_matrices, ctx->parts.count, ctx->parts.hRecords, &ctx->error );
 
@@ -1993,9 +2005,11 @@ int checkUpdateArguments( pbr_ctx* ctx, const UpdateCall& u, const char* call ) 
 RestPose* restPoseOf( pbr_ctx* ctx, UpdateKind kind ) {
 	switch( kind ) {
 		case UpdateKind::Transforms: return &ctx->parts.pose;
-		case UpdateKind::Skin: return &ctx->skin.pose;
+		case UpdateKind::Skin:
+		case UpdateKind::SkinDQ: return &ctx->skin.pose;
 		case UpdateKind::Morph:
-		case UpdateKind::Pose: return &ctx->morph.pose;
+		case UpdateKind::Pose:
+		case UpdateKind::PoseDQ: return &ctx->morph.pose;
 		default: return nullptr;
 	}
 }
@@ -2044,6 +2058,8 @@ int stageKind( pbr_ctx* ctx, UpdateKind kind, const char* call, bool keepsHistor
 	SkinState& skin = ctx->skin;
 	MorphState& morph = ctx->morph;
 	const auto uploadBones = [&]() { return hipMemcpyAsync( skin.dBones, skin.hBones, sizeof( pbr_float4 ) * 3 * skin.count, hipMemcpyHostToDevice, ctx->stream ); };
+	// the dual quaternions of the two dq kinds lie in the same tables, two quads per bone
+	const auto uploadDualQuats = [&]() { return hipMemcpyAsync( skin.dBones, skin.hBones, sizeof( pbr_float4 ) * 2 * skin.count, hipMemcpyHostToDevice, ctx->stream ); };
 	const auto uploadWeights = [&]() { return hipMemcpyAsync( morph.dWeights, morph.hWeights, sizeof( float ) * morph.count, hipMemcpyHostToDevice, ctx->stream ); };
 
 	switch( kind ) {
@@ -2073,6 +2089,22 @@ int stageKind( pbr_ctx* ctx, UpdateKind kind, const char* call, bool keepsHistor
 			                      },
 			                      [&]() {
 				                      hipLaunchKernelGGL( ptr::poseVertices, grid, group, 0, ctx->stream, morph.pose.dRest, morph.dVertexRun, morph.dVertexEntries, morph.dWeights,
+				                                          skin.dOfVertex, skin.dBones, morph.pose.dStaged, morph.pose.dFlag, (int) V );
+			                      } );
+
+		case UpdateKind::SkinDQ:
+			return stageVertices( ctx, call, &skin.pose, keepsHistory, "a skinned position is not finite (the dual quaternions are finite, their blend or its product with the rest pose is not; found on the device)",
+			                      uploadDualQuats,
+			                      [&]() { hipLaunchKernelGGL( ptr::skinVerticesDQ, grid, group, 0, ctx->stream, skin.pose.dRest, skin.dOfVertex, skin.dBones, skin.pose.dStaged, skin.pose.dFlag, (int) V ); } );
+
+		case UpdateKind::PoseDQ:
+			return stageVertices( ctx, call, &morph.pose, keepsHistory, "a posed position is not finite (weights, deltas and dual quaternions are finite, the dq skin of the morphed rest pose is not; found on the device)",
+			                      [&]() {
+				                      const hipError_t err = uploadWeights();
+				                      return ( err != hipSuccess ) ? err : uploadDualQuats();
+			                      },
+			                      [&]() {
+				                      hipLaunchKernelGGL( ptr::poseVerticesDQ, grid, group, 0, ctx->stream, morph.pose.dRest, morph.dVertexRun, morph.dVertexEntries, morph.dWeights,
 				                                          skin.dOfVertex, skin.dBones, morph.pose.dStaged, morph.pose.dFlag, (int) V );
 			                      } );
 
@@ -2107,6 +2139,15 @@ int launchNormals( pbr_ctx* ctx, NormalKernel which ) {
 		case NormalKernel::Morph:
 			hipLaunchKernelGGL( ptr::morphNormals, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
 			                    ctx->dPatchNormals, (int) N );
+			break;
+
+		case NormalKernel::SkinDQ:
+			hipLaunchKernelGGL( ptr::skinNormalsDQ, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			break;
+
+		case NormalKernel::PoseDQ:
+			hipLaunchKernelGGL( ptr::poseNormalsDQ, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
+			                    skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
 			break;
 
 		default:
@@ -2230,8 +2271,15 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 			HIP_TRY( ctx, hipEventElapsedTime( &normalsMs, ctx->evXfNormalsStart, ctx->evXfNormalsStop ) );
 		}
 
-		pose->lastMs = (double) ms + (double) normalsMs;
-		pose->updates++;
+		if( updateDualQuatCode( kind ) != 0 ) {
+			// another kind to pbr_diag_skin_info and pbr_diag_morph_info: pbr_diag_skin_dq_info counts these
+			ctx->skin.dqLastMs = (double) ms + (double) normalsMs;
+			ctx->skin.dqUpdates++;
+		}
+		else {
+			pose->lastMs = (double) ms + (double) normalsMs;
+			pose->updates++;
+		}
 	}
 
 	if( plan.relinks ) {
@@ -2307,6 +2355,27 @@ int pbr_update_morph( pbr_ctx* ctx, const float* weights, uint32_t num_targets )
 int pbr_update_pose( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* matrices, uint32_t num_bones ) {
 	PBR_TRY( usable( ctx ) );
 	return updateScene( ctx, { UpdateKind::Pose, nullptr, 0, nullptr, 0, weights, num_targets, matrices, num_bones } );
+}
+
+int pbr_update_skin_dq( pbr_ctx* ctx, const float* dual_quats, uint32_t num_bones ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::SkinDQ, nullptr, 0, nullptr, 0, nullptr, 0, dual_quats, num_bones } );
+}
+
+int pbr_update_pose_dq( pbr_ctx* ctx, const float* weights, uint32_t num_targets, const float* dual_quats, uint32_t num_bones ) {
+	PBR_TRY( usable( ctx ) );
+	return updateScene( ctx, { UpdateKind::PoseDQ, nullptr, 0, nullptr, 0, weights, num_targets, dual_quats, num_bones } );
+}
+
+int pbr_dual_quats_from_matrices( const float* matrices, uint32_t num_bones, float* dual_quats_out, char* message, size_t capacity ) {
+	std::string why;
+	const int status = dualQuatsFromMatrices( matrices, num_bones, dual_quats_out, &why );
+
+	if( message != nullptr && capacity > 0 ) {
+		std::snprintf( message, capacity, "%s", why.c_str() );
+	}
+
+	return status;
 }
 
 int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_vertices, const uint32_t* normal_part, uint32_t num_normals, uint32_t num_parts ) {
@@ -2429,6 +2498,21 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 
 	if( ms != nullptr ) {
 		*ms = ctx->skin.pose.lastMs;
+	}
+
+	return PBR_OK;
+}
+
+int pbr_diag_skin_dq_info( pbr_ctx* ctx, uint64_t out[2], double* ms ) {
+	if( ctx == nullptr || out == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_skin_dq_info: null argument" );
+	}
+
+	out[0] = ctx->skin.dqUpdates;
+	out[1] = updateDualQuatCode( ctx->lastUpdate );
+
+	if( ms != nullptr ) {
+		*ms = ctx->skin.dqLastMs;
 	}
 
 	return PBR_OK;

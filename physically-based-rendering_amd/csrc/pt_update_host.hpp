@@ -1,12 +1,13 @@
-// pt_update_host.hpp — what the six update calls (pbr_update_vertices, pbr_update_geometry, pbr_update_transforms,
-// pbr_update_skin, pbr_update_morph, pbr_update_pose; include/pbr_hip.h) decide before and around their launches, and what the
-// context remembers of the last one.  Host code only, no HIP: pbr_hip.hip gathers the facts from the context and calls this
+// pt_update_host.hpp — what the eight update calls (pbr_update_vertices, pbr_update_geometry, pbr_update_transforms,
+// pbr_update_skin, pbr_update_morph, pbr_update_pose, pbr_update_skin_dq, pbr_update_pose_dq; include/pbr_hip.h) decide before and
+// around their launches, and what the context remembers of the last one.  Host code only, no HIP: pbr_hip.hip gathers the facts from the context and calls this
 // unit, tests/update_plan_driver.cpp builds it with a plain C++17 compiler.
 //
 // A call is refused in three stages, and the first refusal wins:
 //   1  admitKind     the kind's own state: no morph / no skin / two generations / no parts / no scene
-//   2                the kind's argument check (checkMorphWeights, checkSkinMatrices, checkTransforms, checkRefitVertices,
-//                    checkRefitNormals — each in its own host unit; they also fill the pinned tables), run by the caller
+//   2                the kind's argument check (checkMorphWeights, checkSkinMatrices, checkSkinDualQuats, checkTransforms,
+//                    checkRefitVertices, checkRefitNormals — each in its own host unit; they also fill the pinned tables), run
+//                    by the caller
 //   3  admitShared   what every update shares: a tree that is not nested, an ordered walk without pbr_refit_ordered_walk,
 //                    pbr_update_vertices under Phong tessellation, new normals for a scene without patches
 // planUpdate then says what the accepted call launches.
@@ -18,7 +19,8 @@
 #include "pt_scene_pack.hpp"
 
 // The kinds of update, and `None`: no update since the upload.  The context keeps the kind of the most recent successful one.
-enum class UpdateKind : uint32_t { None = 0, Vertices, Geometry, Transforms, Skin, Morph, Pose };
+// SkinDQ and PoseDQ are Skin and Pose with dual quaternions for the bones (pt_skin_dq_host.hpp); new kinds are appended.
+enum class UpdateKind : uint32_t { None = 0, Vertices, Geometry, Transforms, Skin, Morph, Pose, SkinDQ, PoseDQ };
 
 // pbr_configure's state rule and pbr_diag_patch_refit_info: the last update was "a pbr_update_geometry" — every kind but
 // pbr_update_vertices is one, it brings or computes the normals' side too
@@ -31,8 +33,14 @@ inline uint32_t updateMorphCode( UpdateKind last ) {
 	return ( last == UpdateKind::Morph ) ? 1u : ( last == UpdateKind::Pose ) ? 2u : 0u;
 }
 
+// pbr_diag_skin_dq_info: 0 none of the two, 1 a pbr_update_skin_dq, 2 a pbr_update_pose_dq
+inline uint32_t updateDualQuatCode( UpdateKind last ) {
+	return ( last == UpdateKind::SkinDQ ) ? 1u : ( last == UpdateKind::PoseDQ ) ? 2u : 0u;
+}
+
 inline const char* updateCall( UpdateKind kind ) {
-	static const char* const names[] = { "", "pbr_update_vertices", "pbr_update_geometry", "pbr_update_transforms", "pbr_update_skin", "pbr_update_morph", "pbr_update_pose" };
+	static const char* const names[] = { "", "pbr_update_vertices", "pbr_update_geometry", "pbr_update_transforms", "pbr_update_skin", "pbr_update_morph", "pbr_update_pose",
+	                                     "pbr_update_skin_dq", "pbr_update_pose_dq" };
 	return names[(uint32_t) kind];
 }
 
@@ -56,19 +64,19 @@ struct UpdateFacts {
 // Stage 1.  PBR_OK, or the status with the message in *why.
 inline int admitKind( UpdateKind kind, const UpdateFacts& f, std::string* why ) {
 	const char* call = updateCall( kind );
-	const bool pose = ( kind == UpdateKind::Pose );
+	const bool pose = ( kind == UpdateKind::Pose || kind == UpdateKind::PoseDQ );
 
 	if( ( kind == UpdateKind::Morph || pose ) && f.numMorphTargets == 0 ) {
 		return packFail( why, PBR_ESTATE, "%s without a morph: pbr_set_morph declares the targets and captures the rest pose (a new upload drops it)", call );
 	}
 	if( pose && f.numBones == 0 ) {
-		return packFail( why, PBR_ESTATE, "pbr_update_pose without a skin: pbr_set_skin declares the influences (a new upload drops it)" );
+		return packFail( why, PBR_ESTATE, "%s without a skin: pbr_set_skin declares the influences (a new upload drops it)", call );
 	}
 	if( pose && f.skinGeneration != f.morphGeneration ) {
-		return packFail( why, PBR_ESTATE, "pbr_update_pose: pbr_set_skin and pbr_set_morph captured different geometry (an upload or an update lies between them): set both on the same rest pose" );
+		return packFail( why, PBR_ESTATE, "%s: pbr_set_skin and pbr_set_morph captured different geometry (an upload or an update lies between them): set both on the same rest pose", call );
 	}
-	if( kind == UpdateKind::Skin && f.numBones == 0 ) {
-		return packFail( why, PBR_ESTATE, "pbr_update_skin without a skin: pbr_set_skin declares the influences and captures the rest pose (a new upload drops it)" );
+	if( ( kind == UpdateKind::Skin || kind == UpdateKind::SkinDQ ) && f.numBones == 0 ) {
+		return packFail( why, PBR_ESTATE, "%s without a skin: pbr_set_skin declares the influences and captures the rest pose (a new upload drops it)", call );
 	}
 	if( kind == UpdateKind::Transforms && f.numParts == 0 ) {
 		return packFail( why, PBR_ESTATE, "pbr_update_transforms without parts: pbr_set_parts declares them and captures the rest pose (a new upload drops them)" );
@@ -106,7 +114,7 @@ inline int admitShared( UpdateKind kind, bool bringsNormals, const UpdateFacts& 
 }
 
 // The kernel that writes N' behind the staged V' of a device kind.
-enum class NormalKernel : uint32_t { None = 0, Transform, Skin, Morph, Pose };
+enum class NormalKernel : uint32_t { None = 0, Transform, Skin, Morph, Pose, SkinDQ, PoseDQ };
 
 // What an admitted call does.
 struct UpdatePlan {
@@ -128,17 +136,18 @@ inline UpdatePlan planUpdate( UpdateKind kind, const UpdateFacts& f ) {
 	plan.keepsHistory = ( f.tracking && f.history && !f.moved );   // what TemporalPolicy::update() answers
 
 	// the pose: morphed if the morph has normal targets, skinned if the skin has normal influences
-	const bool morphs = ( ( kind == UpdateKind::Morph || kind == UpdateKind::Pose ) && f.morphNormals );
-	const bool skins = ( ( kind == UpdateKind::Skin || kind == UpdateKind::Pose ) && f.skinNormals );
+	const bool dq = ( kind == UpdateKind::SkinDQ || kind == UpdateKind::PoseDQ );
+	const bool morphs = ( ( kind == UpdateKind::Morph || kind == UpdateKind::Pose || kind == UpdateKind::PoseDQ ) && f.morphNormals );
+	const bool skins = ( ( kind == UpdateKind::Skin || kind == UpdateKind::Pose || dq ) && f.skinNormals );
 
 	if( kind == UpdateKind::Transforms && f.partNormals ) {
 		plan.normals = NormalKernel::Transform;
 	}
 	else if( morphs ) {
-		plan.normals = skins ? NormalKernel::Pose : NormalKernel::Morph;
+		plan.normals = !skins ? NormalKernel::Morph : dq ? NormalKernel::PoseDQ : NormalKernel::Pose;
 	}
 	else if( skins ) {
-		plan.normals = NormalKernel::Skin;
+		plan.normals = dq ? NormalKernel::SkinDQ : NormalKernel::Skin;
 	}
 
 	return plan;

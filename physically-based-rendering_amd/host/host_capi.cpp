@@ -389,6 +389,32 @@ int pbrh_pt_update_pose( void* tracer, const float* weights, uint32_t num_target
 	}
 }
 
+int pbrh_pt_update_skin_dq( void* tracer, const float* dual_quats, uint32_t num_bones ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updateSkinDQ( dual_quats, num_bones );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
+int pbrh_pt_update_pose_dq( void* tracer, const float* weights, uint32_t num_targets, const float* dual_quats, uint32_t num_bones ) {
+	HostTracer* t = static_cast<HostTracer*>( tracer );
+
+	try {
+		t->pt.updatePoseDQ( weights, num_targets, dual_quats, num_bones );
+		return 0;
+	}
+	catch( const std::exception& e ) {
+		gError = e.what();
+		return -1;
+	}
+}
+
 int pbrh_pt_refit_ordered_walk( void* tracer, int on ) {
 	HostTracer* t = static_cast<HostTracer*>( tracer );
 

@@ -513,6 +513,24 @@ void PathTracer::updatePose( const float* weights, uint32_t numTargets, const fl
 	this->resetSampleCount();
 }
 
+void PathTracer::updateSkinDQ( const float* dualQuats, uint32_t numBones ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updateSkinDQ before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_skin_dq( mCtx, dualQuats, numBones ), "pbr_update_skin_dq" );
+	this->resetSampleCount();
+}
+
+void PathTracer::updatePoseDQ( const float* weights, uint32_t numTargets, const float* dualQuats, uint32_t numBones ) {
+	if( mCtx == nullptr ) {
+		throw std::runtime_error( "[PathTracer] updatePoseDQ before initOpenCLBuffers" );
+	}
+
+	this->check( pbr_update_pose_dq( mCtx, weights, numTargets, dualQuats, numBones ), "pbr_update_pose_dq" );
+	this->resetSampleCount();
+}
+
 void PathTracer::refitOrderedWalk( bool on ) {
 	if( mCtx == nullptr ) {
 		throw std::runtime_error( "[PathTracer] refitOrderedWalk before initOpenCLBuffers" );

@@ -109,6 +109,10 @@ class PathTracer {
 		void updateMorph( const float* weights, uint32_t numTargets );
 		// pbr_update_pose: the skin of the morphed rest pose — the weights and one row-major 3 x 4 matrix per bone
 		void updatePose( const float* weights, uint32_t numTargets, const float* matrices, uint32_t numBones );
+		// pbr_update_skin_dq: one dual quaternion (eight floats) per bone of the skin setSkin set; starts a new accumulation
+		void updateSkinDQ( const float* dualQuats, uint32_t numBones );
+		// pbr_update_pose_dq: the dual-quaternion skin of the morphed rest pose — the weights and one dual quaternion per bone
+		void updatePoseDQ( const float* weights, uint32_t numTargets, const float* dualQuats, uint32_t numBones );
 		// pbr_refit_ordered_walk: while on, updateVertices works under a ray-ordered traversal (the records are re-linked on the device)
 		void refitOrderedWalk( bool on );
 

@@ -66,7 +66,20 @@ same context:
   (d) pbr_update_skin( M ) alone: device, its skin kernels, wall
   (e) the kernels' bytes over their time against the stated traffic: 36 B per element (rest quad, one run word, store) and 16 B
       per entry for the morph, 32 B per element more for the pose (the influence record), 64 B per element for the skin; the
-      weight table and the bone records are not in it"""
+      weight table and the bone records are not in it
+
+  python scripts/refit_measure.py --scene ... --skin-dq [--phong 0.6] [--reps 9] [--out FILE]
+
+pbr_update_skin_dq and pbr_update_pose_dq (profiles/r19/experiments/skin_dq.txt), next to the --skin leg's calls in the same run:
+the same scenes, influences and bones, the bones' dual quaternions made by pbr_dual_quats_from_matrices from the leg's rigid
+matrices; for the pose the --morph leg's first set of targets (8 of 5 % each).  One warm-up round, then the four calls alternate
+on the same context:
+  (a) pbr_update_skin_dq( Q ): device time of the whole update, of the dq kernels alone (pbr_diag_skin_dq_info), wall
+  (b) pbr_update_pose_dq( w, Q ): the same
+  (c) pbr_update_skin( M ) with the same bones as matrices: device, its skin kernels, wall
+  (d) pbr_update_geometry( V', N' ) with the dq skin's V', N' precomputed on the host (not timed): device, copy, wall
+  (e) (a) against (c) in percent, wall and kernels
+  (f) both kernels against the 64 B per element they share (the bone records, 32 against 48 B per active slot, are not in it)"""
 import os
 import sys
 import time
@@ -339,6 +352,93 @@ def bone_matrices(bones, step):
     return np.ascontiguousarray(m.reshape(bones, 12), np.float32)
 
 
+def measure_skin_dq(pbr, name, alpha, reps):
+    import skin_dq_ref
+    import skin_ref
+    kind, seed, triangles = SCENES[name]
+    pbr.cfg_reset()
+    pbr.cfg_set(**{"render.max_depth": 3})
+    sc = pbr.HostScene.generate(kind, seed, triangles)
+    a = {k: np.ascontiguousarray(v) for k, v in sc.arrays().items()}
+    cfg = sc.config(W, H)
+    cfg.phong_tessellation = alpha
+    faces, vertices = a["facesV"].shape[0], a["vertices"].shape[0]
+    facesN, normals = smooth_normals(a["facesV"], a["vertices"])
+    count = normals.shape[0]
+    desc = pbr.SceneDesc.from_buffer_copy(sc.desc)
+    desc.facesN, desc.normals, desc.num_normals = facesN.ctypes.data, normals.ctypes.data, count
+    vb, vw, nb, nw, bones = skin_ref.influences_for(name, a["facesV"], facesN, vertices, count)
+    extent = float(np.abs(a["vertices"][:, :3]).max())
+    # the --morph leg's first set: 8 targets, each a window of 5 % of the elements
+    rng = np.random.default_rng(17 * 8 + 5)
+    vt, nt = [], []
+    for _ in range(8):
+        for out, n, size in ((vt, vertices, 0.002 * extent), (nt, count, 0.05)):
+            window = max(1, int(0.05 * n))
+            index = ((int(rng.integers(0, n)) + np.arange(window)) % n).astype(np.uint32)
+            out.append((index, (rng.random((window, 3), dtype=np.float32) - np.float32(0.5)) * np.float32(2.0 * size)))
+    dev = pbr.Device(0)
+    dev.upload_scene(desc)
+    dev.configure(cfg)
+    dev.set_skin(vb, vw, nb, nw, bones)
+    dev.set_morph(vt, nt)
+    lines = ["== %s by a dual-quaternion skin, phong_tessellation %g: %d faces, %d vertices, %d smooth normals made here (facesN = facesV), %d bones; the --skin leg's "
+             "influences and matrices, the bones' dual quaternions by pbr_dual_quats_from_matrices; 8 morph targets of 5 %% each for the pose"
+             % (name, alpha, faces, vertices, count, bones),
+             "tables: %d bytes for the skin with or without dual quaternions, %d for the morph" % (dev.skin_info()["device_bytes"], dev.morph_info()["device_bytes"])]
+    poses = []
+    for step in (1, 2):
+        M = bone_matrices(bones, step)
+        Q = pbr.dual_quats_from_matrices(M)
+        w = ((0.1 + 0.01 * np.arange(8)) * np.where(np.arange(8) % 2 == 0, 1.0, -1.0) * step).astype(np.float32)
+        v, n = skin_dq_ref.skin(a["vertices"], vb, vw, normals, nb, nw, Q)
+        poses.append((M, Q, w, v, n))
+    M, Q, w, v, n = poses[0]
+    dev.update_skin(M)                                               # all four paths warm
+    dev.update_skin_dq(Q)
+    dev.update_pose_dq(w, Q)
+    dev.update_geometry(v, n)
+    skin = {key: [] for key in ("device", "kernels", "wall")}
+    dq = {key: [] for key in ("device", "kernels", "wall")}
+    pose = {key: [] for key in ("device", "kernels", "wall")}
+    geo = {key: [] for key in ("device", "copy", "wall")}
+    for rep in range(reps):
+        M, Q, w, v, n = poses[rep % 2]
+        skin["wall"].append(wall(lambda: dev.update_skin(M)))
+        skin["device"].append(dev.last_kernel_ms())
+        skin["kernels"].append(dev.skin_info()["ms"])
+        dq["wall"].append(wall(lambda: dev.update_skin_dq(Q)))
+        dq["device"].append(dev.last_kernel_ms())
+        dq["kernels"].append(dev.skin_dq_info()["ms"])
+        if rep == 0:
+            got_v, got_n = dev.read_geometry()
+            same = np.array_equal(got_v.view(np.uint32), v.view(np.uint32)) and np.array_equal(got_n.view(np.uint32), n.view(np.uint32))
+            lines.append("read_geometry after the first timed update_skin_dq equals the numpy restatement bit for bit: %s" % same)
+        pose["wall"].append(wall(lambda: dev.update_pose_dq(w, Q)))
+        pose["device"].append(dev.last_kernel_ms())
+        pose["kernels"].append(dev.skin_dq_info()["ms"])
+        if rep == 0:
+            got_v, got_n = dev.read_geometry()
+            want_v, want_n = skin_dq_ref.pose(a["vertices"], vt, vb, vw, normals, nt, nb, nw, w, Q)
+            same = np.array_equal(got_v.view(np.uint32), want_v.view(np.uint32)) and np.array_equal(got_n.view(np.uint32), want_n.view(np.uint32))
+            lines.append("read_geometry after the first timed update_pose_dq equals the numpy restatement bit for bit: %s" % same)
+        geo["wall"].append(wall(lambda: dev.update_geometry(v, n)))
+        geo["device"].append(dev.last_kernel_ms())
+        geo["copy"].append(dev.refit_info()["upload_ms"])
+    lines.append("(a) update_skin_dq: device %s ms | dq kernels %s ms | wall %s ms" % (spread(dq["device"]), spread(dq["kernels"]), spread(dq["wall"])))
+    lines.append("(b) update_pose_dq: device %s ms | dq kernels %s ms | wall %s ms" % (spread(pose["device"]), spread(pose["kernels"]), spread(pose["wall"])))
+    lines.append("(c) update_skin, the same bones as matrices: device %s ms | skin kernels %s ms | wall %s ms" % (spread(skin["device"]), spread(skin["kernels"]), spread(skin["wall"])))
+    lines.append("(d) update_geometry( V', N' ): device %s ms | copy %s ms | wall %s ms" % (spread(geo["device"]), spread(geo["copy"]), spread(geo["wall"])))
+    lines.append("(e) update_skin_dq against update_skin, medians: wall %+.1f %% | kernels %+.1f %%"
+                 % (100.0 * (np.median(dq["wall"]) / np.median(skin["wall"]) - 1.0), 100.0 * (np.median(dq["kernels"]) / np.median(skin["kernels"]) - 1.0)))
+    floor = 64 * vertices + 64 * count
+    for label, times in (("dq", dq["kernels"]), ("skin", skin["kernels"])):
+        rate = floor / (float(np.median(times)) * 1e-3)
+        lines.append("(f) %s kernels: traffic floor %d bytes -> %.1f GB/s = %.1f %% of 8 TB/s" % (label, floor, rate / 1e9, 100.0 * rate / HBM_BYTES_PER_S))
+    dev.close()
+    return lines
+
+
 def measure_morph(pbr, name, alpha, reps):
     import morph_ref
     import skin_ref
@@ -429,6 +529,13 @@ def main():
     name, reps, frames = arg("--scene", "sponza"), int(arg("--reps", "7")), int(arg("--frames", "16"))
     if "--morph" in sys.argv:
         text = "\n".join(measure_morph(pbr, name, float(arg("--phong", "0.6")), int(arg("--reps", "9")))) + "\n"
+        sys.stdout.write(text)
+        if "--out" in sys.argv:
+            with open(arg("--out", ""), "a") as f:
+                f.write(text)
+        return
+    if "--skin-dq" in sys.argv:
+        text = "\n".join(measure_skin_dq(pbr, name, float(arg("--phong", "0.6")), int(arg("--reps", "9")))) + "\n"
         sys.stdout.write(text)
         if "--out" in sys.argv:
             with open(arg("--out", ""), "a") as f:
