@@ -681,6 +681,10 @@ int pbr_read_debug( pbr_ctx* ctx, float* rgba );
  * first-hit distance (so sigma_world is in pixel footprints), a the first-hit diffuse colour (Kd); taps across the
  * hit / miss divide are left out; a standard deviation of 0 switches its term off.  Features come from one primary ray
  * through every pixel centre over the uploaded scene (orb lights are not in that pass).
+ * Each operation is in binary32, and what is not finite has no say: a tap whose exponent is not below inf — NaN included —
+ * is left out, and "off" is the term times 0, so a colour that is not finite (or a squared difference that overflows)
+ * removes its tap with sigma_color = 0 as well.  A pixel whose weights do not sum to a value in (0, inf) — its own colour is
+ * not finite, or ( sigma_world * 2^k * pxDim * t )^2 underflows to 0 while t > 0 — stays as it is.
  *   rgba      host, width x height x 4 floats, row 0 = bottom like pbr_read_output: filtered colour, .w = the
  *             accumulated first-hit distance, unfiltered.  The accumulation itself is not modified.
  *   features  optional (NULL): host, 3 x width x height x 4 floats — position {x, y, z, t (INFINITY: miss)},
@@ -724,7 +728,9 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
  *      hit / miss divide, with !( e < inf ), or with V_k( q ) not finite;  w = ( spline_i * spline_j ) * expf( -e )
  *   5. C_k+1( p ) = sum w C_k( q ) / sum w;   V_k+1( p ) = sum ( w * w ) V_k( q ) / ( sum w * sum w );
  *      if sum w is not in (0, inf), colour and variance stay as they were
- * With sigma_luminance = 0 the colour is bit for bit pbr_denoise's with sigma_color = 0 and the same other parameters.
+ * With sigma_luminance = 0 the colour is bit for bit pbr_denoise's with sigma_color = 0 and the same other parameters — on
+ * colours that are finite: e_l = 0 does not look at them, so here a tap that is not finite takes part and spreads, where
+ * pbr_denoise's colour term times 0 leaves it out.
  *   rgba          host, width x height x 4 floats: filtered colour, .w = the accumulated first-hit distance as pbr_denoise
  *   variance_out  optional (NULL): host, width x height floats, V after the last pass
  *   features      optional (NULL): as pbr_denoise

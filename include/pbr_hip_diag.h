@@ -85,6 +85,22 @@ int pbr_diag_intersect( pbr_ctx* ctx, int op, const float* in, int n, float* out
  * increment} (orc_surface_step). */
 int pbr_diag_surface_step( pbr_ctx* ctx, const float* in, int n, float* out );
 
+/* The a-trous filters over planes the caller supplies — kind 0: pbr_denoise's passes (ptd::atrousPass), kind 1: those of
+ * pbr_denoise_guided and pbr_denoise_temporal (ptd::atrousGuidedPass) — through the pass drivers the public calls use: same
+ * grid and block, same by-value arguments per pass, same ping-pong, same last pass (the guided filter's `original` is `image`).
+ * Needs a live context for its device and stream only: no scene, no pbr_configure; it touches none of the context's images,
+ * moments, history, counters or kernel time.
+ *   width, height  >= 1, width * height <= 1 Mi; NOT bound to multiples of 8
+ *   params         pbr_denoise_params (kind 0) / pbr_denoise_guided_params (kind 1): passes 1 .. 8, standard deviations
+ *                  finite and >= 0, as the public calls check them
+ *   image          width x height x 4: colour, .w = the first-hit distance that passes through
+ *   variance       width x height, V_0 (kind 1; ignored and may be NULL for kind 0)
+ *   features       3 x width x height x 4: position, normal, albedo as pbr_denoise returns them
+ *   rgba_out       width x height x 4;  variance_out: width x height, kind 1, may be NULL
+ * PBR_EINVAL for anything else; a refused or failed call writes nothing. */
+int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim, const void* params, const float* image, const float* variance,
+                     const float* features, float* rgba_out, float* variance_out );
+
 /* Traversal-only throughput probe: streams n rays {ox,oy,oz,-, dx,dy,dz,-} through a persistent
  * closest-hit kernel `repeats` times with `lds_slots` hot nodes staged in LDS; best kernel time in
  * *ms_out, hits {t, face bits} in out2. */

@@ -222,7 +222,8 @@ for _name, _args in (
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
         ("pbr_diag_intersect", [_vp, ctypes.c_int, _fp, ctypes.c_int, _fp]),
-        ("pbr_diag_surface_step", [_vp, _fp, ctypes.c_int, _fp])):
+        ("pbr_diag_surface_step", [_vp, _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_filter", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, _fp, _fp, _fp, _fp, _fp])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -949,6 +950,27 @@ class Device:
         out = np.empty((items.shape[0], 4), np.float32)
         self._check(hip.pbr_diag_intersect(self._ctx, self.INTERSECT_OPS[op], _as_fp(items), items.shape[0], _as_fp(out)))
         return out
+
+    def diag_filter(self, kind, image, features, params, px_dim, variance=None):
+        """pbr_diag_filter: the a-trous passes of `denoise` (kind 0, params a DenoiseParams) or of `denoise_guided` /
+        `denoise_temporal` (kind 1, params a GuidedDenoiseParams, variance (H, W) = V_0) over planes given here: image (H, W, 4),
+        features (3, H, W, 4) as `denoise` returns them; any H, W >= 1.  No scene or configuration needed.
+        -> rgba (H, W, 4) for kind 0, (rgba, variance (H, W)) for kind 1."""
+        image = np.ascontiguousarray(image, np.float32)
+        h, w = image.shape[:2]
+        features = np.ascontiguousarray(features, np.float32)
+        if image.shape != (h, w, 4) or features.shape != (3, h, w, 4):
+            raise PbrError("diag_filter: image (H, W, 4) and features (3, H, W, 4)")
+        if kind == 1:
+            variance = np.ascontiguousarray(variance, np.float32)
+            if variance.shape != (h, w):
+                raise PbrError("diag_filter: variance (H, W)")
+        out = np.empty((h, w, 4), np.float32)
+        var = np.empty((h, w), np.float32) if kind == 1 else None
+        self._check(hip.pbr_diag_filter(self._ctx, kind, w, h, px_dim, ctypes.addressof(params), _as_fp(image),
+                                        _as_fp(variance) if kind == 1 else None, _as_fp(features), _as_fp(out),
+                                        _as_fp(var) if kind == 1 else None))
+        return (out, var) if kind == 1 else out
 
     def diag_surface_step(self, items):
         """pbr_diag_surface_step: n x 24 {origin, dir, normal, t, seed, color, lit, lightDir, lightRgb, pad[3]} -> n x 12

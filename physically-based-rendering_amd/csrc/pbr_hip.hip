@@ -3145,6 +3145,19 @@ const float4* guidedPasses( pbr_ctx* ctx, const pbr_denoise_guided_params& param
 	return in;
 }
 
+// `passes` launches of ptd::atrousPass, ping-pong between `in` and `out`: the first reads `in`, the second overwrites it.
+// -> the plane that holds the result.  The caller checks hipGetLastError.
+const float4* plainPasses( pbr_ctx* ctx, const pbr_denoise_params& params, int w, int h, float pxDim, float4* in, float4* out,
+                           const float4* position, const float4* normal, const float4* albedo ) {
+	for( uint32_t pass = 0; pass < params.passes; pass++ ) {
+		hipLaunchKernelGGL( ptd::atrousPass, imageGrid( w, h ), kImageBlock, 0, ctx->stream, ptd::plainPass( params, pass, w, h, pxDim ), (const float4*) in, out,
+			position, normal, albedo );
+		std::swap( in, out );
+	}
+
+	return in;
+}
+
 }  // namespace
 
 // The denoise half of the display step (csrc/pt_denoise.hpp): first-hit features from one primary ray per pixel, then
@@ -3179,18 +3192,11 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position.p, (float4*) D.normal.p, (float4*) D.albedo.p, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	float4* in = (float4*) D.ping.p;
-	float4* out = (float4*) D.pong.p;
-
-	for( uint32_t pass = 0; pass < params->passes; pass++ ) {
-		hipLaunchKernelGGL( ptd::atrousPass, grid, kImageBlock, 0, ctx->stream, ptd::plainPass( *params, pass, w, h, pxDim ), (const float4*) in, out,
-			(const float4*) D.position.p, (const float4*) D.normal.p, (const float4*) D.albedo.p );
-		std::swap( in, out );
-	}
-
+	const float4* result = plainPasses( ctx, *params, w, h, pxDim, (float4*) D.ping.p, (float4*) D.pong.p, (const float4*) D.position.p,
+		(const float4*) D.normal.p, (const float4*) D.albedo.p );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	PBR_TRY( readBack( ctx, rgba, in, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, rgba, result, sizeof( float4 ) * pixels ) );
 	PBR_TRY( readFeatures( ctx, features, D, pixels ) );
 	return timedTail( ctx );
 }
@@ -3260,6 +3266,73 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 	PBR_TRY( readBack( ctx, variance_out, dVariance.p, sizeof( float ) * pixels ) );
 	PBR_TRY( readFeatures( ctx, features, D, pixels ) );
 	return timedTail( ctx );
+}
+
+// The filters of pbr_denoise (kind 0) and pbr_denoise_guided / pbr_denoise_temporal (kind 1) over planes the caller supplies
+// (include/pbr_hip_diag.h): the public calls' pass drivers, grid, block and ping-pong, with nothing of the context but its
+// device and stream.
+int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim, const void* params, const float* image, const float* variance,
+                     const float* features, float* rgba_out, float* variance_out ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( kind < 0 || kind > 1 || params == nullptr || image == nullptr || features == nullptr || rgba_out == nullptr || ( kind == 1 && variance == nullptr ) ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_filter: kind 0 / 1, and no null parameters, image, features, destination or (kind 1) variance" );
+	}
+	if( width < 1 || height < 1 || (uint64_t) width * (uint64_t) height > ( 1ull << 20 ) ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_filter: width, height >= 1 and width * height <= 1 Mi (got %d x %d)", width, height );
+	}
+
+	const pbr_denoise_params* plain = ( kind == 0 ) ? (const pbr_denoise_params*) params : nullptr;
+	const pbr_denoise_guided_params* guided = ( kind == 1 ) ? (const pbr_denoise_guided_params*) params : nullptr;
+	std::string why;
+	const int status = ( kind == 0 ) ? ptd::filterCheck( "pbr_diag_filter", *plain, &why ) : ptd::filterCheck( "pbr_diag_filter", *guided, &why );
+
+	if( status != PBR_OK ) {
+		return fail( ctx, status, "%s", why.c_str() );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const size_t pixels = (size_t) width * (size_t) height;
+	FilterPlanes D;
+	DevBuf dOriginal, dVariance;
+	HIP_TRY( ctx, D.alloc( pixels ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.position.p, features, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.normal.p, features + 4 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.albedo.p, features + 8 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	const float4* result = nullptr;
+	std::vector<float> working;
+
+	if( kind == 0 ) {
+		HIP_TRY( ctx, hipMemcpyAsync( D.ping.p, image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		result = plainPasses( ctx, *plain, width, height, pxDim, (float4*) D.ping.p, (float4*) D.pong.p, (const float4*) D.position.p,
+			(const float4*) D.normal.p, (const float4*) D.albedo.p );
+	} else {
+		// the filter's first input as pixelVariance builds `working`: {r, g, b, var}
+		working.assign( image, image + 4 * pixels );
+
+		for( size_t at = 0; at < pixels; at++ ) {
+			working[4 * at + 3] = variance[at];
+		}
+
+		HIP_TRY( ctx, dOriginal.alloc( sizeof( float4 ) * pixels ) );
+		HIP_TRY( ctx, dVariance.alloc( sizeof( float ) * pixels ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dOriginal.p, image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( D.ping.p, working.data(), sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		float4* const outs[2] = { (float4*) D.pong.p, (float4*) D.ping.p };
+		result = guidedPasses( ctx, *guided, width, height, pxDim, (const float4*) D.ping.p, outs, (const float4*) D.position.p,
+			(const float4*) D.normal.p, (const float4*) D.albedo.p, (const float4*) dOriginal.p, (float*) dVariance.p );
+	}
+
+	HIP_TRY( ctx, hipGetLastError() );
+	// staged, so that a call that fails on the device has written nothing
+	std::vector<float> rgba( 4 * pixels ), var( ( kind == 1 && variance_out != nullptr ) ? pixels : 0 );
+	PBR_TRY( readBack( ctx, rgba.data(), result, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, var.empty() ? nullptr : var.data(), dVariance.p, sizeof( float ) * pixels ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	std::copy( rgba.begin(), rgba.end(), rgba_out );
+	std::copy( var.begin(), var.end(), variance_out );
+	return PBR_OK;
 }
 
 // pbr_denoise_temporal's history is dropped: the next call starts every pixel at L = 1.

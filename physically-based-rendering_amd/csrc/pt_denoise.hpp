@@ -17,7 +17,10 @@
 //
 // Floating point, no reference: the test (tests/test_gpu_denoise.py) restates the filter in numpy fp32 and states its
 // tolerance; properties (a constant image is a fixed point, edges of the features are not crossed, variance drops on a
-// flat wall) are checked on rendered frames.
+// flat wall) are checked on rendered frames.  What rendered frames do not contain — colours, variances and distances that
+// are not finite, overflow or underflow, images smaller than a launch block — is planted through pbr_diag_filter and held to
+// the definition in float64 (tests/denoise_ref.py, tests/test_gpu_filter_planes.py); firstHitFeatures is held to a float64
+// brute force on every pixel of two hand-made scenes there.
 #pragma once
 
 #include "pt_kernel.hpp"

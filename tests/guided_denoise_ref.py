@@ -69,8 +69,9 @@ def world_scale(sigma_world, step, px_dim):
     return F(sigma_world) * F(step) * F(px_dim)
 
 
-def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigma_world, sigma_albedo, px_dim, exp64=False):
-    """One pass: colour (H, W, 3+), var (H, W) -> (colour' (H, W, 3), var' (H, W))."""
+def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigma_world, sigma_albedo, px_dim, exp64=False, record=None):
+    """One pass: colour (H, W, 3+), var (H, W) -> (colour' (H, W, 3), var' (H, W)).  record: a list that gets the pass's
+    decisions (denoise_ref.Record)."""
     position, normal, albedo = features
     colour, var = np.asarray(colour, F)[..., :3], np.asarray(var, F)
     h, w = var.shape
@@ -84,11 +85,17 @@ def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigm
     with np.errstate(all="ignore"):
         s_world = world_scale(sigma_world, step, px_dim) * position[..., 3]
         inv_world = np.where(hit & (s_world > 0), F(1.0) / (s_world * s_world), F(0.0)).astype(F)
-        scale = F(sigma_luminance) * np.sqrt(local_variance(var)) + F(1e-6)
+        local = local_variance(var)
+        scale = F(sigma_luminance) * np.sqrt(local) + F(1e-6)
         y0 = adaptive_ref.luminance(colour)
     acc = np.zeros((h, w, 3), F)
     wsum, vsum = np.zeros((h, w), F), np.zeros((h, w), F)
     ys, xs = np.mgrid[0:h, 0:w]
+    rec = None
+    if record is not None:
+        import denoise_ref
+        rec = denoise_ref.Record(h, w)
+        rec.g_zero = local == 0
     for j in range(-2, 3):
         for i in range(-2, 3):
             ty, tx = ys + j * step, xs + i * step
@@ -111,20 +118,27 @@ def guided_pass(colour, var, features, step, sigma_luminance, sigma_normal, sigm
                 acc += np.where(ok[..., None], wt[..., None] * c, F(0.0))
                 vsum += np.where(ok, (wt * wt) * v, F(0.0))
             wsum += wt
+            if rec is not None:
+                rec.tap(j, i, inside, n[..., 3] == normal[..., 3], e < np.inf, np.isfinite(c).all(-1) & np.isfinite(colour).all(-1),
+                        np.isfinite(v), wt)
     usable = (wsum > 0) & np.isfinite(wsum)
+    if rec is not None:
+        rec.stayed = ~usable
+        record.append(rec)
     with np.errstate(all="ignore"):
         colour_out = np.where(usable[..., None], acc / wsum[..., None], colour).astype(F)
         var_out = np.where(usable, vsum / (wsum * wsum), var).astype(F)
     return colour_out, var_out
 
 
-def guided_numpy(image, var, features, params, px_dim, exp64=False):
+def guided_numpy(image, var, features, params, px_dim, exp64=False, record=None):
     """The whole call: image (H, W, 4) the accumulation, var (H, W) = V_0, params with .passes, .sigma_luminance,
-    .sigma_normal, .sigma_world, .sigma_albedo -> (rgba (H, W, 4) with the image's .w, variance (H, W) after the last pass)."""
+    .sigma_normal, .sigma_world, .sigma_albedo -> (rgba (H, W, 4) with the image's .w, variance (H, W) after the last pass).
+    record: a list that gets one denoise_ref.Record per pass."""
     colour, v = np.asarray(image, F)[..., :3], np.asarray(var, F)
     for k in range(int(params.passes)):
         colour, v = guided_pass(colour, v, features, 1 << k, params.sigma_luminance, params.sigma_normal, params.sigma_world,
-                                params.sigma_albedo, px_dim, exp64)
+                                params.sigma_albedo, px_dim, exp64, record)
     out = np.asarray(image, F).copy()
     out[..., :3] = colour
     return out, v

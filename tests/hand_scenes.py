@@ -175,12 +175,13 @@ def make(pbr, shape, seed=SEED, brdf=1, lights=False, degenerate=False, signed_z
     return sc
 
 
-def camera(pbr, vertices, flat):
+def camera(pbr, vertices, flat, toward=(4.0, 3.0, 6.0), distance=1.3):
     """A pbr_camera whose view the faces with area fill, however few they are: rays leave the eye along w (+ u and v across
-    the image), the basis the host driver derives from eye, centre and up = y; no focus point."""
+    the image), the basis the host driver derives from eye, centre and up = y; no focus point.  toward, distance: where the
+    eye stands, seen from the middle of the faces, in units of their extent."""
     seen = vertices[np.repeat(~flat, 3), :3].astype(np.float64)
     middle, size = 0.5 * (seen.min(0) + seen.max(0)), max(float(np.linalg.norm(seen.max(0) - seen.min(0))), 1.5)
-    eye = middle + 1.3 * size * _unit(np.array([4.0, 3.0, 6.0]))               # no coordinate plane is seen edge-on
+    eye = middle + distance * size * _unit(np.array(toward, np.float64))        # (4, 3, 6): no coordinate plane is seen edge-on
     w = _unit(middle - eye)
     u = _unit(np.cross(w, [0.0, 1.0, 0.0]))
     v = _unit(np.cross(u, w))
@@ -265,6 +266,41 @@ def brute_force(facesV, vertices, rays):
     return best
 
 
+def brute_force_faces(facesV, vertices, rays):
+    """brute_force() with what it leaves out -> (t, face, gap, edge), each (n,): the closest hit and its face (-1: miss); the
+    distance in t to the runner-up among the accepted hits (inf if there is none); and how close, in barycentric units, the
+    ray passes to the boundary of ANY face whose plane it meets in front of the origin — an edge of the face it hits, or the
+    silhouette of one it just misses.  rays: (n, 6), taken to float64 as they are."""
+    tri = vertices[:, :3][facesV[:, :3].astype(np.int64)].astype(np.float64)
+    a, e1, e2 = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    n = rays.shape[0]
+    best, face, gap, edge = np.full(n, np.inf), np.full(n, -1, np.int64), np.full(n, np.inf), np.full(n, np.inf)
+    for k in range(0, n, 64):
+        o, dd = np.asarray(rays[k:k + 64, None, 0:3], np.float64), np.asarray(rays[k:k + 64, None, 3:6], np.float64)
+        p = np.cross(dd, e2)
+        det = (e1 * p).sum(2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / det
+            tv = o - a
+            u = (tv * p).sum(2) * inv
+            q = np.cross(tv, e1)
+            vv = (q * dd).sum(2) * inv
+            tt = (e2 * q).sum(2) * inv
+            ok = (u >= -1e-6) & (vv >= -1e-6) & (u + vv <= 1 + 1e-6) & (tt > 1e-4) & np.isfinite(tt)
+            ahead = (tt > 0) & np.isfinite(tt)
+            boundary = np.abs(np.minimum(np.minimum(u, vv), 1.0 - (u + vv)))
+        hits = np.sort(np.where(ok, tt, np.inf), axis=1)
+        best[k:k + 64] = hits[:, 0]
+        face[k:k + 64] = np.where(np.isfinite(hits[:, 0]), np.where(ok, tt, np.inf).argmin(1), -1)
+        if hits.shape[1] > 1:
+            with np.errstate(invalid="ignore"):
+                gap[k:k + 64] = np.where(np.isfinite(hits[:, 1]), hits[:, 1] - hits[:, 0], np.inf)
+        edge[k:k + 64] = np.where(ahead, boundary, np.inf).min(1)
+        edge_on = (np.abs(det) < 1e-12) & (np.linalg.norm(np.cross(e1, e2), axis=1) > 0)
+        edge[k:k + 64] = np.where(edge_on.any(1), 0.0, edge[k:k + 64])                    # a face with area seen edge-on is all boundary
+    return best, face, gap, edge
+
+
 def outliers(t, best):
     """The rays outside that test's tolerance, 1e-3 max( 1, t ); a ray that misses in both is inside."""
     t, best = np.asarray(t, np.float64), np.asarray(best, np.float64)
@@ -327,3 +363,43 @@ def moved(sc, seed=1):
         v = move(sc, seed)
         _cache[key] = (sc, v, with_arrays(sc, vertices=v, bvh=refit_ref.refit(sc.arrays["bvh"], sc.arrays["facesV"], v)))
     return _cache[key][1:]
+
+
+# ---- the feature pass: every pixel-centre ray of a camera, far from every edge -------------------------------------------------
+
+FEATURE_W, FEATURE_H = 64, 48
+FEATURE_KD = [[0.62, 0.58, 0.5], [0.1, 0.6, 0.2], [0.9, 0.15, 0.1]]      # face f has material f % 3
+EDGE_MARGIN = 1e-5       # barycentric: ten times brute_force's own acceptance band, which is what a binary32 ray can move a hit by
+# shape: (toward, distance) of camera() — found by trying a few eyes; tests/test_filter_planes_cpu.py holds what they are there for
+FEATURE_CAMERAS = {"wide7": ((5.0, 2.0, 4.0), 0.5), "wide40": ((6.0, 1.0, 3.0), 0.9)}
+
+
+def centre_rays64(cam, px, w, h):
+    """The rays through the pixel centres (pathtracing.cl:25-48 without jitter and lens) in float64 from the camera's binary32
+    fields and the binary32 pixel dimension: (h * w, 6), row-major, row 0 = bottom."""
+    eye, cw, cu, cv = (np.array([q.x, q.y, q.z], np.float64) for q in (cam.eye, cam.w, cam.u, cam.v))
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    inner = (cu - cu * w) + cu * (2.0 * xs[..., None]) + cv - cv * h + cv * (2.0 * ys[..., None])
+    direction = _unit(cw + inner * (float(np.float32(px)) * 0.5))
+    return np.concatenate([np.broadcast_to(eye, direction.shape), direction], axis=-1).reshape(-1, 6)
+
+
+def feature_case(pbr, shape):
+    """A scene of `shape` with three materials, flat faces and no lights at FEATURE_W x FEATURE_H under FEATURE_CAMERAS[shape]
+    -> (scene, rays64 (h * w, 6), brute_force_faces of them)."""
+    key = ("features", shape)
+    if key not in _cache:
+        base = scene(pbr, shape)
+        a = dict(base.arrays)
+        a["facesV"] = a["facesV"].copy()
+        a["facesV"][:, 3] = np.arange(a["facesV"].shape[0]) % len(FEATURE_KD)
+        a["facesN"] = a["facesV"].copy()
+        a["materials"] = np.repeat(np.array(MATERIALS[1], np.float32), len(FEATURE_KD), axis=0)
+        a["materials"][:, 8:11] = FEATURE_KD
+        toward, distance = FEATURE_CAMERAS[shape]
+        cam = camera(pbr, a["vertices"], base.flat, toward, distance)
+        sc = refit_scenes.Scene(pbr, a, base.config(width=FEATURE_W, height=FEATURE_H), cam, pbr.pixel_dimension(FEATURE_W, FEATURE_H), base.seeds)
+        sc.flat, sc.shape = base.flat, shape
+        rays = centre_rays64(cam, sc.px, FEATURE_W, FEATURE_H)
+        _cache[key] = (sc, rays, brute_force_faces(a["facesV"], a["vertices"], rays))
+    return _cache[key]

@@ -6,6 +6,8 @@ traced rays for the feature buffers, and through properties on rendered frames. 
 import numpy as np
 import pytest
 
+from denoise_ref import atrous_numpy
+
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 2e-5, 1e-6
@@ -27,59 +29,6 @@ def rendered(pbr, dev, kind="cornell", triangles=0, w=96, h=64, frames=4, **cfg)
     dev.configure(sc.config(w, h))
     dev.render(0, pbr.frame_seeds(0, frames), px, cam)
     return sc, cam, px
-
-
-def atrous_numpy(image, features, params, px_dim):
-    """The definition in include/pbr_hip.h, fp32, operation for operation as csrc/pt_denoise.hpp has it."""
-    f32 = np.float32
-    position, normal, albedo = features
-    h, w = image.shape[:2]
-    spline = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625], f32)
-    cur = image.copy()
-    hit = normal[..., 3] != 0
-
-    def inverse_square(sigma):
-        sigma = f32(sigma)
-        return f32(1.0) / (sigma * sigma) if sigma > 0 else f32(0.0)
-
-    def sqdist(a, b):
-        d = a[..., :3] - b[..., :3]
-        return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-
-    for k in range(params.passes):
-        step = 1 << k
-        inv_color = inverse_square(f32(params.sigma_color) / f32(1 << k))
-        inv_normal, inv_albedo = inverse_square(params.sigma_normal), inverse_square(params.sigma_albedo)
-        world_scale = f32(params.sigma_world) * f32(step) * f32(px_dim)
-        with np.errstate(all="ignore"):
-            sigma_world = world_scale * position[..., 3]
-            inv_world = np.where(hit & (sigma_world > 0), f32(1.0) / (sigma_world * sigma_world), f32(0.0)).astype(f32)
-        acc = np.zeros((h, w, 3), f32)
-        wsum = np.zeros((h, w), f32)
-        ys, xs = np.mgrid[0:h, 0:w]
-        for j in range(-2, 3):
-            for i in range(-2, 3):
-                ty, tx = ys + j * step, xs + i * step
-                inside = (ty >= 0) & (ty < h) & (tx >= 0) & (tx < w)
-                tyc, txc = np.clip(ty, 0, h - 1), np.clip(tx, 0, w - 1)
-                n, c = normal[tyc, txc], cur[tyc, txc]
-                ok = inside & (n[..., 3] == normal[..., 3])
-                with np.errstate(all="ignore"):
-                    e = sqdist(c, cur) * inv_color
-                    e_hit = e + sqdist(n, normal) * inv_normal
-                    e_hit = e_hit + sqdist(position[tyc, txc], position) * inv_world
-                    e_hit = e_hit + sqdist(albedo[tyc, txc], albedo) * inv_albedo
-                    e = np.where(hit, e_hit, e).astype(f32)
-                    ok &= e < np.inf
-                    wt = np.where(ok, (spline[i + 2] * spline[j + 2]) * np.exp(-e, dtype=f32), f32(0.0)).astype(f32)
-                    acc += np.where(ok[..., None], wt[..., None] * c[..., :3], f32(0.0))
-                wsum += wt
-        out = cur.copy()
-        usable = (wsum > 0) & np.isfinite(wsum)
-        with np.errstate(all="ignore"):
-            out[..., :3] = np.where(usable[..., None], acc / wsum[..., None], cur[..., :3])
-        cur = out
-    return cur
 
 
 def test_features_are_the_first_hits_of_the_pixel_centre_rays(pbr, device):
