@@ -101,6 +101,34 @@ int pbr_diag_surface_step( pbr_ctx* ctx, const float* in, int n, float* out );
 int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim, const void* params, const float* image, const float* variance,
                      const float* features, float* rgba_out, float* variance_out );
 
+/* Steps 0 to 4 of pbr_denoise_temporal (pbr_hip.h: the motion step, the candidate, the taps, the history value, the blend) over
+ * planes the caller supplies, through the driver the public call uses: same grid and block, the same by-value arguments built
+ * from the two cameras, ptd::temporalMotion in front of ptd::temporalIntegrate< true > on the motion path, else
+ * ptd::temporalIntegrate< false > alone.  No filter pass follows.  Needs a live context for its device and stream only: no
+ * scene, no pbr_configure; it touches none of the context's images, moments, history, motion policy, counters or kernel time.
+ *   width, height  >= 1, width * height <= 1 Mi; NOT bound to multiples of 8
+ *   pxDim, cam     of this call;  temporal: checked as pbr_denoise_temporal checks it
+ *   image          width x height x 4, variance: width x height — merged into {r, g, b, var} as the public call's working plane is
+ *   features       3 x width x height x 4: position, normal, albedo as pbr_denoise returns them
+ *   previous state prev_integrated (w x h x 4), prev_features (3 x w x h x 4), prev_lengths (w x h), prev_cam, prev_pxDim: all of
+ *                  the four pointers, or none (NULL) — none is the first call after a reset: every pixel copies, L = 1
+ *   motion inputs  face (w x h, -1 = miss), facesV (num_faces x 4: {a, b, c, material}), vertices and hist_vertices
+ *                  (num_vertices x 4: V and H): all four, or none.  All four: the motion path
+ *   integrated     w x h x 4;  history: w x h x 4 {fx, fy, L, valid};  lengths: w x h
+ *   motion         w x h x 4 {Pprev, code}, reference: w x h x 4 {nref, len} — step 0's two planes; written on the motion path
+ *                  only (required there, ignored otherwise)
+ * PBR_EINVAL for a null or size error, a previous state or motion inputs given in part, motion inputs without a previous
+ * state, more than 16 Mi faces or vertices, a face outside [-1, num_faces), a facesV corner >= num_vertices — the two keep the
+ * kernels' gathers in bounds — and a prev_lengths entry outside 1 .. 1024.  The last keeps Hl + 1 inside the definition: the
+ * kernel forms it in 32-bit unsigned arithmetic, the definition (and the tests' restatement, in 64-bit integers) in the
+ * integers; the two agree for every length a call of the library can have left — 1 .. max_history <= 1024 — and need not
+ * beyond 2^32 - 2.  A refused or failed call writes nothing. */
+int pbr_diag_temporal( pbr_ctx* ctx, int width, int height, float pxDim, const pbr_camera* cam, const pbr_temporal_params* temporal,
+                       const float* image, const float* variance, const float* features,
+                       const float* prev_integrated, const float* prev_features, const uint32_t* prev_lengths, const pbr_camera* prev_cam, float prev_pxDim,
+                       const int32_t* face, const uint32_t* facesV, uint32_t num_faces, const float* vertices, const float* hist_vertices, uint32_t num_vertices,
+                       float* integrated, float* history, uint32_t* lengths, float* motion, float* reference );
+
 /* Traversal-only throughput probe: streams n rays {ox,oy,oz,-, dx,dy,dz,-} through a persistent
  * closest-hit kernel `repeats` times with `lds_slots` hot nodes staged in LDS; best kernel time in
  * *ms_out, hits {t, face bits} in out2. */

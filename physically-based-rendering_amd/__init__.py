@@ -223,7 +223,11 @@ for _name, _args in (
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
         ("pbr_diag_intersect", [_vp, ctypes.c_int, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_surface_step", [_vp, _fp, ctypes.c_int, _fp]),
-        ("pbr_diag_filter", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, _fp, _fp, _fp, _fp, _fp])):
+        ("pbr_diag_filter", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, _fp, _fp, _fp, _fp, _fp]),
+        ("pbr_diag_temporal", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(TemporalParams), _fp, _fp, _fp,
+                               _fp, _fp, _up, ctypes.POINTER(Camera), ctypes.c_float,
+                               ctypes.POINTER(ctypes.c_int32), _up, ctypes.c_uint32, _fp, _fp, ctypes.c_uint32,
+                               _fp, _fp, _up, _fp, _fp])):
     if hasattr(hip, _name):
         getattr(hip, _name).argtypes = _args
 hip.pbr_diag_tune_budget.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -971,6 +975,61 @@ class Device:
                                         _as_fp(variance) if kind == 1 else None, _as_fp(features), _as_fp(out),
                                         _as_fp(var) if kind == 1 else None))
         return (out, var) if kind == 1 else out
+
+    def diag_temporal(self, image, variance, features, cam, px_dim, temporal, prev=None, motion=None, out=None):
+        """pbr_diag_temporal: steps 0 to 4 of `denoise_temporal` over planes given here — image (H, W, 4), variance (H, W),
+        features (3, H, W, 4) as `denoise` returns them, any H, W >= 1; no scene or configuration needed.  prev: None (no
+        history) or a dict integrated (H, W, 4) / features (3, H, W, 4) / lengths (H, W) / cam / px_dim; motion: None or a dict
+        face (H, W) int32 / faces_v (faces, 4) uint32 / vertices / hist_vertices (n, 4): the motion path.  out: arrays to write
+        into instead of new ones (keys as returned).  -> dict integrated, history (H, W, 4), lengths (H, W) uint32 and, on the
+        motion path, motion and reference (H, W, 4).  The library checks the values; this wrapper only the shapes."""
+        image, variance = np.ascontiguousarray(image, np.float32), np.ascontiguousarray(variance, np.float32)
+        features = np.ascontiguousarray(features, np.float32)
+        h, w = variance.shape
+        if image.shape != (h, w, 4) or features.shape != (3, h, w, 4):
+            raise PbrError("diag_temporal: image (H, W, 4), variance (H, W) and features (3, H, W, 4)")
+        keep = []   # the converted inputs must outlive the call
+
+        def held(a, dtype, shape):
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape != shape:
+                raise PbrError("diag_temporal: an input of shape %s where %s is expected" % (a.shape, shape))
+            keep.append(a)
+            return a
+
+        p_int = p_feat = p_len = p_cam = None
+        p_px = 0.0
+        if prev is not None:
+            p_int = _as_fp(held(prev["integrated"], np.float32, (h, w, 4)))
+            p_feat = _as_fp(held(prev["features"], np.float32, (3, h, w, 4)))
+            p_len = held(prev["lengths"], np.uint32, (h, w)).ctypes.data_as(_up)
+            p_cam, p_px = ctypes.byref(prev["cam"]), prev["px_dim"]
+        m_face = m_faces = m_v = m_h = None
+        nf = nv = 0
+        if motion is not None:
+            faces_v = np.ascontiguousarray(motion["faces_v"], np.uint32).reshape(-1, 4)
+            vertices = np.ascontiguousarray(motion["vertices"], np.float32).reshape(-1, 4)
+            nf, nv = faces_v.shape[0], vertices.shape[0]
+            m_face = held(motion["face"], np.int32, (h, w)).ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            m_faces = held(faces_v, np.uint32, (nf, 4)).ctypes.data_as(_up)
+            m_v = _as_fp(held(vertices, np.float32, (nv, 4)))
+            m_h = _as_fp(held(motion["hist_vertices"], np.float32, (nv, 4)))
+        res = dict(out) if out is not None else {}
+        for key, dtype, shape in (("integrated", np.float32, (h, w, 4)), ("history", np.float32, (h, w, 4)), ("lengths", np.uint32, (h, w)),
+                                  ("motion", np.float32, (h, w, 4)), ("reference", np.float32, (h, w, 4))):
+            if key in ("motion", "reference") and motion is None:
+                res.pop(key, None)
+                continue
+            if key not in res:
+                res[key] = np.empty(shape, dtype)
+            elif res[key].dtype != dtype or res[key].shape != shape or not res[key].flags.c_contiguous:
+                raise PbrError("diag_temporal: out[%r] must be a contiguous %s array of shape %s" % (key, np.dtype(dtype).name, shape))
+        self._check(hip.pbr_diag_temporal(self._ctx, w, h, px_dim, ctypes.byref(cam), ctypes.byref(temporal), _as_fp(image), _as_fp(variance),
+                                          _as_fp(features), p_int, p_feat, p_len, p_cam, p_px, m_face, m_faces, nf, m_v, m_h, nv,
+                                          _as_fp(res["integrated"]), _as_fp(res["history"]), res["lengths"].ctypes.data_as(_up),
+                                          _as_fp(res["motion"]) if motion is not None else None,
+                                          _as_fp(res["reference"]) if motion is not None else None))
+        return res
 
     def diag_surface_step(self, items):
         """pbr_diag_surface_step: n x 24 {origin, dir, normal, t, seed, color, lit, lightDir, lightRgb, pad[3]} -> n x 12

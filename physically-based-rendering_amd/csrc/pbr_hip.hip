@@ -3158,6 +3158,36 @@ const float4* plainPasses( pbr_ctx* ctx, const pbr_denoise_params& params, int w
 	return in;
 }
 
+// Steps 0 to 4 of pbr_denoise_temporal (pt_temporal.hpp) over device planes: temporalMotion in front when `motion`, then
+// temporalIntegrate< motion >.  working holds {C, V} and receives I; info may be null.  Without `motion` the planes from
+// `face` on are not touched.  The caller checks hipGetLastError.
+struct TemporalStepPlanes {
+	float4* working;
+	const float4* position, * normal, * albedo;
+	const float4* prevI, * prevPosition, * prevNormal, * prevAlbedo;
+	const unsigned* prevLengths;
+	unsigned* lengths;
+	float4* info;
+	const int* face;
+	const uint4* facesV;
+	const float4* vertices, * histVertices;
+	float4* motion, * reference;
+};
+
+void temporalSteps( pbr_ctx* ctx, const ptd::TemporalArgs& A, int w, int h, bool motion, const TemporalStepPlanes& S ) {
+	const dim3 grid = imageGrid( w, h );
+
+	if( motion ) {
+		hipLaunchKernelGGL( ptd::temporalMotion, grid, kImageBlock, 0, ctx->stream, w, h, S.face, S.position, S.normal,
+			S.facesV, S.vertices, S.histVertices, S.motion, S.reference );
+	}
+
+	const auto integrate = motion ? ptd::temporalIntegrate<true> : ptd::temporalIntegrate<false>;
+	hipLaunchKernelGGL( integrate, grid, kImageBlock, 0, ctx->stream, A, S.working, S.position, S.normal, S.albedo,
+		S.prevI, S.prevPosition, S.prevNormal, S.prevAlbedo, S.prevLengths, S.lengths, S.info,
+		(const float4*) ( motion ? S.motion : nullptr ), (const float4*) ( motion ? S.reference : nullptr ) );
+}
+
 }  // namespace
 
 // The denoise half of the display step (csrc/pt_denoise.hpp): first-hit features from one primary ray per pixel, then
@@ -3335,6 +3365,138 @@ int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim,
 	return PBR_OK;
 }
 
+// Steps 0 to 4 of pbr_denoise_temporal over planes the caller supplies (include/pbr_hip_diag.h): the public call's driver, grid,
+// block and by-value arguments, with nothing of the context but its device and stream.
+int pbr_diag_temporal( pbr_ctx* ctx, int width, int height, float pxDim, const pbr_camera* cam, const pbr_temporal_params* temporal,
+                       const float* image, const float* variance, const float* features,
+                       const float* prev_integrated, const float* prev_features, const uint32_t* prev_lengths, const pbr_camera* prev_cam, float prev_pxDim,
+                       const int32_t* face, const uint32_t* facesV, uint32_t num_faces, const float* vertices, const float* hist_vertices, uint32_t num_vertices,
+                       float* integrated, float* history, uint32_t* lengths, float* motion, float* reference ) {
+	if( ctx == nullptr || ctx->stream == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( cam == nullptr || temporal == nullptr || image == nullptr || variance == nullptr || features == nullptr || integrated == nullptr
+	        || history == nullptr || lengths == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: no null camera, parameters, image, variance, features, integrated, history or lengths" );
+	}
+	if( width < 1 || height < 1 || (uint64_t) width * (uint64_t) height > ( 1ull << 20 ) ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: width, height >= 1 and width * height <= 1 Mi (got %d x %d)", width, height );
+	}
+
+	std::string why;
+	const int status = ptd::temporalCheck( "pbr_diag_temporal", *temporal, &why );
+
+	if( status != PBR_OK ) {
+		return fail( ctx, status, "%s", why.c_str() );
+	}
+
+	const int prevGiven = ( prev_integrated != nullptr ) + ( prev_features != nullptr ) + ( prev_lengths != nullptr ) + ( prev_cam != nullptr );
+	const int motionGiven = ( face != nullptr ) + ( facesV != nullptr ) + ( vertices != nullptr ) + ( hist_vertices != nullptr );
+
+	if( ( prevGiven != 0 && prevGiven != 4 ) || ( motionGiven != 0 && motionGiven != 4 ) ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: the previous state, and the motion inputs, are given whole or not at all" );
+	}
+
+	const bool hasHistory = ( prevGiven == 4 ), moving = ( motionGiven == 4 );
+
+	if( moving && !hasHistory ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: motion inputs without a previous state" );
+	}
+	if( moving && ( motion == nullptr || reference == nullptr || num_faces < 1 || num_vertices < 1 || num_faces > ( 1u << 24 ) || num_vertices > ( 1u << 24 ) ) ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: the motion path needs motion and reference destinations and 1 .. 16 Mi faces and vertices" );
+	}
+
+	const size_t pixels = (size_t) width * (size_t) height;
+
+	// what keeps the kernels' gathers in bounds, and Hl + 1 inside the definition
+	if( hasHistory ) {
+		for( size_t at = 0; at < pixels; at++ ) {
+			if( prev_lengths[at] < 1u || prev_lengths[at] > 1024u ) {
+				return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: prev_lengths must be in 1 .. 1024 (pixel %zu: %u)", at, prev_lengths[at] );
+			}
+		}
+	}
+	if( moving ) {
+		for( size_t at = 0; at < pixels; at++ ) {
+			if( face[at] < -1 || (int64_t) face[at] >= (int64_t) num_faces ) {
+				return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: face must be in [-1, num_faces) (pixel %zu: %d)", at, face[at] );
+			}
+		}
+		for( size_t f = 0; f < num_faces; f++ ) {
+			for( int k = 0; k < 3; k++ ) {
+				if( facesV[4 * f + k] >= num_vertices ) {
+					return fail( ctx, PBR_EINVAL, "pbr_diag_temporal: facesV corner >= num_vertices (face %zu)", f );
+				}
+			}
+		}
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	const size_t plane = sizeof( float4 ) * pixels;
+	DevBuf dWorking, dFeatures, dPrevI, dPrevFeatures, dPrevLengths, dLengths, dInfo, dFace, dFacesV, dVertices, dHistVertices, dMotion, dReference;
+	HIP_TRY( ctx, dWorking.alloc( plane ) );
+	HIP_TRY( ctx, dFeatures.alloc( 3 * plane ) );
+	HIP_TRY( ctx, dLengths.alloc( sizeof( unsigned ) * pixels ) );
+	HIP_TRY( ctx, dInfo.alloc( plane ) );
+	// the working plane as pixelVariance builds it: {r, g, b, var}
+	std::vector<float> working( image, image + 4 * pixels );
+
+	for( size_t at = 0; at < pixels; at++ ) {
+		working[4 * at + 3] = variance[at];
+	}
+
+	HIP_TRY( ctx, hipMemcpyAsync( dWorking.p, working.data(), plane, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dFeatures.p, features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
+
+	if( hasHistory ) {
+		HIP_TRY( ctx, dPrevI.alloc( plane ) );
+		HIP_TRY( ctx, dPrevFeatures.alloc( 3 * plane ) );
+		HIP_TRY( ctx, dPrevLengths.alloc( sizeof( unsigned ) * pixels ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevI.p, prev_integrated, plane, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevFeatures.p, prev_features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevLengths.p, prev_lengths, sizeof( unsigned ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	}
+	if( moving ) {
+		HIP_TRY( ctx, dFace.alloc( sizeof( int ) * pixels ) );
+		HIP_TRY( ctx, dFacesV.alloc( sizeof( uint4 ) * num_faces ) );
+		HIP_TRY( ctx, dVertices.alloc( sizeof( float4 ) * num_vertices ) );
+		HIP_TRY( ctx, dHistVertices.alloc( sizeof( float4 ) * num_vertices ) );
+		HIP_TRY( ctx, dMotion.alloc( plane ) );
+		HIP_TRY( ctx, dReference.alloc( plane ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dFace.p, face, sizeof( int ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dFacesV.p, facesV, sizeof( uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dVertices.p, vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dHistVertices.p, hist_vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
+	}
+
+	// without a previous state the old camera is never read by a pixel: this call's stands in
+	const ptd::TemporalArgs A = ptd::temporalArgs( *temporal, width, height, pxDim, hasHistory, hasHistory ? *prev_cam : *cam,
+		hasHistory ? prev_pxDim : pxDim, ptd::cameraTerms( *cam, width, height, pxDim ) );
+	const float4* dF = (const float4*) dFeatures.p;
+	const float4* dPF = (const float4*) dPrevFeatures.p;
+	const TemporalStepPlanes S = { (float4*) dWorking.p, dF, dF + pixels, dF + 2 * pixels,
+		(const float4*) dPrevI.p, dPF, hasHistory ? dPF + pixels : nullptr, hasHistory ? dPF + 2 * pixels : nullptr,
+		(const unsigned*) dPrevLengths.p, (unsigned*) dLengths.p, (float4*) dInfo.p, (const int*) dFace.p, (const uint4*) dFacesV.p,
+		(const float4*) dVertices.p, (const float4*) dHistVertices.p, (float4*) dMotion.p, (float4*) dReference.p };
+	temporalSteps( ctx, A, width, height, moving, S );
+	HIP_TRY( ctx, hipGetLastError() );
+	// staged, so that a call that fails on the device has written nothing
+	std::vector<float> outI( 4 * pixels ), outInfo( 4 * pixels ), outMotion( moving ? 4 * pixels : 0 ), outReference( moving ? 4 * pixels : 0 );
+	std::vector<uint32_t> outLengths( pixels );
+	PBR_TRY( readBack( ctx, outI.data(), dWorking.p, plane ) );
+	PBR_TRY( readBack( ctx, outInfo.data(), dInfo.p, plane ) );
+	PBR_TRY( readBack( ctx, outLengths.data(), dLengths.p, sizeof( uint32_t ) * pixels ) );
+	PBR_TRY( readBack( ctx, moving ? outMotion.data() : nullptr, dMotion.p, plane ) );
+	PBR_TRY( readBack( ctx, moving ? outReference.data() : nullptr, dReference.p, plane ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	std::copy( outI.begin(), outI.end(), integrated );
+	std::copy( outInfo.begin(), outInfo.end(), history );
+	std::copy( outLengths.begin(), outLengths.end(), lengths );
+	std::copy( outMotion.begin(), outMotion.end(), motion );
+	std::copy( outReference.begin(), outReference.end(), reference );
+	return PBR_OK;
+}
+
 // pbr_denoise_temporal's history is dropped: the next call starts every pixel at L = 1.
 int pbr_temporal_reset( pbr_ctx* ctx ) {
 	if( ctx == nullptr ) {
@@ -3431,16 +3593,10 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 		ctx->varianceFirstCount, (const float4*) dOriginal, (float*) nullptr, dI, w, h, ctx->tilesX );
 	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, T.position[cur], T.normal[cur], T.albedo[cur], motion ? T.face : (int*) nullptr );
 
-	if( motion ) {
-		hipLaunchKernelGGL( ptd::temporalMotion, grid, kImageBlock, 0, ctx->stream, w, h, (const int*) T.face, dPosition, dNormal,
-			(const uint4*) ctx->dFacesV, (const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, T.motion, T.reference );
-	}
-
-	const auto integrate = motion ? ptd::temporalIntegrate<true> : ptd::temporalIntegrate<false>;
-	hipLaunchKernelGGL( integrate, grid, kImageBlock, 0, ctx->stream, A, dI, dPosition, dNormal, dAlbedo,
-		(const float4*) T.integrated[prev], (const float4*) T.position[prev], (const float4*) T.normal[prev],
-		(const float4*) T.albedo[prev], (const unsigned*) T.length[prev], T.length[cur], ( history != nullptr ) ? T.info : (float4*) nullptr,
-		(const float4*) ( motion ? T.motion : nullptr ), (const float4*) ( motion ? T.reference : nullptr ) );
+	const TemporalStepPlanes S = { dI, dPosition, dNormal, dAlbedo, T.integrated[prev], T.position[prev], T.normal[prev], T.albedo[prev],
+		T.length[prev], T.length[cur], ( history != nullptr ) ? T.info : (float4*) nullptr, T.face, (const uint4*) ctx->dFacesV,
+		(const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, T.motion, T.reference };
+	temporalSteps( ctx, A, w, h, motion, S );
 	HIP_TRY( ctx, hipGetLastError() );
 
 	// the first pass reads I and leaves it as it is: it is the next call's history

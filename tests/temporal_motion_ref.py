@@ -21,7 +21,7 @@ def cross(a, b):
                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
 
 
-def motion(features, face, vertices, hist_vertices, faces_v):
+def motion(features, face, vertices, hist_vertices, faces_v, record=None):
     """Step 0 -> (motion (H, W, 4) = {Pprev, code}, reference (H, W, 4) = {nref, len}).  code 1: the face has not moved (Pprev = P
     and nref = N bit for bit, len = 1); 2: moved; 3: moved and u, v or Pprev not finite; a miss pixel is all zeros."""
     position, normal, _ = features
@@ -53,23 +53,30 @@ def motion(features, face, vertices, hist_vertices, faces_v):
     out = np.where(unmoved[..., None], still, moved)
     out_ref = np.where(unmoved[..., None], still_ref, moved_ref)
     zero = np.zeros(4, F)
+    if record is not None:
+        record.code = np.where(hit, out[..., 3], 0).astype(np.uint8)
     return np.where(hit[..., None], out, zero).astype(F), np.where(hit[..., None], out_ref, zero).astype(F)
 
 
-def integrate(image, var, features, face, vertices, hist_vertices, faces_v, cam, px_dim, prev, params):
+def integrate(image, var, features, face, vertices, hist_vertices, faces_v, cam, px_dim, prev, params, record=None, planes=None):
     """Steps 0 to 4 on the motion path -> (integrated, history, motion) — the first two as temporal_ref.integrate gives them,
     motion (H, W, 4) as pbr_read_temporal_motion does.  prev = temporal_ref.previous( ... ) of the call before: the motion path
-    is not taken without a history."""
+    is not taken without a history.  record: a temporal_ref.Record that gets the decisions; planes: a dict that gets step 0's
+    `reference` plane {nref, len}, which the three results do not hold."""
     image, var = np.asarray(image, F), np.asarray(var, F)
     position, normal, albedo = features
     h, w = var.shape
     given = np.concatenate([image[..., :3], var[..., None]], axis=-1).astype(F)
-    moved, reference = motion(features, face, vertices, hist_vertices, faces_v)
+    moved, reference = motion(features, face, vertices, hist_vertices, faces_v, record)
+    if planes is not None:
+        planes["reference"] = reference
     hit = normal[..., 3] != 0
 
     # step 1: the candidate of a hit pixel starts from Pprev; miss pixels as they were
-    fx, fy = ref.candidate((moved, normal, albedo), cam, px_dim, prev.cam, prev.px_dim)
+    fx, fy = ref.candidate((moved, normal, albedo), cam, px_dim, prev.cam, prev.px_dim, record)
     lost = hit & (moved[..., 3] == 3)
+    if record is not None:
+        record.candidate[lost] = ref.LOST
     nan = F(np.nan)
     fx, fy = np.where(lost, nan, fx).astype(F), np.where(lost, nan, fy).astype(F)
 
@@ -102,6 +109,10 @@ def integrate(image, var, features, face, vertices, hist_vertices, faces_v, cam,
                     on_surface &= ref.sqdist(p, moved) <= radius2
                 ok &= np.where(hit, on_surface, True)
                 ok &= np.isfinite(old).all(-1)
+                if record is not None:
+                    record.set_tap(j, i, has, inside, bw > 0, n[..., 3] == normal[..., 3], hit, a[..., 3] == albedo[..., 3],
+                                   ref.dot(n, reference) >= bound, (F(params.sigma_world) == 0) | (ref.sqdist(p, moved) <= radius2),
+                                   np.isfinite(old).all(-1))
                 acc = acc + np.where(ok[..., None], bw[..., None] * old[..., :3], F(0.0)).astype(F)
                 vsum = vsum + np.where(ok, (bw * bw) * old[..., 3], F(0.0)).astype(F)
                 wsum = wsum + np.where(ok, bw, F(0.0)).astype(F)
@@ -109,10 +120,14 @@ def integrate(image, var, features, face, vertices, hist_vertices, faces_v, cam,
             better = ok & (bw > best)
             best = np.where(better, bw, best).astype(F)
             length = np.where(better, prev.lengths[yi, xi], length)
+            if record is not None:
+                record.source[better] = j * 2 + i
 
     # steps 3 and 4, unchanged
     blend = (wsum > 0) & (int(params.max_history) > 1) & np.isfinite(given).all(-1)
     new_length = np.where(blend, np.minimum(length + 1, int(params.max_history)), 1)
+    if record is not None:
+        record.set_blend(wsum > 0, int(params.max_history) > 1, np.isfinite(given).all(-1), new_length)
     with np.errstate(all="ignore"):
         hc = acc / wsum[..., None]
         hv = vsum / (wsum * wsum)

@@ -5,7 +5,11 @@ tests/temporal_kernel_shim_head.inc (what it needs from HIP and from the headers
 (a loop over the pixels), built with g++ and the library's -ffp-contract=off, and run on the synthetic quad of
 test_temporal_motion_cpu.py.  < false > must give tests/temporal_ref.py and temporalMotion + < true >
 tests/temporal_motion_ref.py, bit for bit.  This pins the SOURCE to the definition; that the GPU's compiler and its sqrt and
-division keep it is what tests/test_gpu_temporal_motion.py checks on the device."""
+division keep it is what tests/test_gpu_temporal_motion.py checks on the device.
+
+The same build then runs over every planted case of tests/temporal_planes.py — thresholds hit exactly, candidates off the scale,
+histories that are not finite, degenerate and overflowing faces, images of 1 x 1 to 70 x 9 — against the restatements, bit for
+bit, `reference` included: what tests/test_gpu_temporal_planes.py asks of the device, asked of the source."""
 import ctypes
 import os
 import subprocess
@@ -14,6 +18,7 @@ import numpy as np
 import pytest
 
 import temporal_motion_ref as mref
+import temporal_planes
 import temporal_ref as ref
 import test_temporal_motion_cpu as quad
 from conftest import ROOT, same_values
@@ -51,22 +56,26 @@ def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def run(lib, image, var, feat, face, V, Hv, cam, prev, p, motion_path):
-    """What pbr_denoise_temporal launches behind pixelVariance and the feature pass -> (integrated, history, motion)"""
+def run(lib, image, var, feat, face, V, Hv, cam, prev, p, motion_path, px_dim=quad.PX, faces=quad.FACES, planes=None):
+    """What pbr_denoise_temporal launches behind pixelVariance and the feature pass -> (integrated, history, motion).  prev = None:
+    no history, as the first call after a reset launches it.  planes: a dict that gets `reference`."""
     h, w = var.shape
     A = Args()
     A.width, A.height, A.hasHistory, A.maxHistory, A.normalCos = w, h, 1, p.max_history, p.normal_cos
-    A.worldTerm, A.worldScale = (1 if p.sigma_world != 0 else 0), F(p.sigma_world) * F(quad.PX)
+    A.worldTerm, A.worldScale = (1 if p.sigma_world != 0 else 0), F(p.sigma_world) * F(px_dim)
+    if prev is None:
+        A.hasHistory = 0
+        prev = ref.previous(np.zeros((h, w, 4), F), tuple(np.zeros((h, w, 4), F) for _ in range(3)), np.ones((h, w)), cam, px_dim)
     old, cur = ref.camera_vectors(prev.cam), ref.camera_vectors(cam)
     cam_a, cv_h = cur["u"] - cur["u"] * F(w), cur["v"] * F(h)                      # setCamera's camA and cvH
     for k in range(3):
         A.eye[k], A.cu[k], A.cv[k], A.cw[k] = old["eye"][k], old["u"][k], old["v"][k], old["w"][k]
         A.curCu[k], A.curCv[k], A.curCw[k], A.curCamA[k], A.curCvH[k] = cur["u"][k], cur["v"][k], cur["w"][k], cam_a[k], cv_h[k]
-    A.halfPx, A.curHalfPx = F(prev.px_dim) * F(0.5), F(quad.PX) * F(0.5)
+    A.halfPx, A.curHalfPx = F(prev.px_dim) * F(0.5), F(px_dim) * F(0.5)
     position, normal, albedo = (np.ascontiguousarray(f, F) for f in feat)
     working = np.ascontiguousarray(np.concatenate([image[..., :3], var[..., None]], -1), F)
     motion, reference = np.zeros((h, w, 4), F), np.zeros((h, w, 4), F)
-    face, faces = np.ascontiguousarray(face, np.int32), np.ascontiguousarray(quad.FACES, np.uint32)
+    face, faces = np.ascontiguousarray(face, np.int32), np.ascontiguousarray(faces, np.uint32)
     V, Hv = np.ascontiguousarray(V, F), np.ascontiguousarray(Hv, F)
     if motion_path:
         lib.run_motion(w, h, _vp(face), _vp(position), _vp(normal), _vp(faces), _vp(V), _vp(Hv), _vp(motion), _vp(reference))
@@ -77,6 +86,8 @@ def run(lib, image, var, feat, face, V, Hv, cam, prev, p, motion_path):
                       *[_vp(a) for a in old_planes], _vp(old_lengths), _vp(lengths), _vp(info),
                       _vp(motion) if motion_path else None, _vp(reference) if motion_path else None)
     assert same_values(lengths.astype(F), info[..., 2])
+    if planes is not None:
+        planes["reference"] = reference
     return working, info, motion
 
 
@@ -117,3 +128,18 @@ def test_the_kernels_source_is_the_restatement_s_bit_for_bit(kernels, name):
         got = run(kernels, image, var, feat, face, V, Hv, cam, prev, p, False)
         assert same_values(got[0], want[0]) and same_values(got[1], want[1]), "%s, static path" % name
     assert seen == {"unmoved": {0.0, 1.0}, "collapsed": {0.0, 2.0, 3.0}}.get(name, {0.0, 2.0})
+
+
+@pytest.mark.parametrize("case", [pytest.param(c, id=c.name) for c in temporal_planes.cases()])
+def test_the_kernels_source_is_the_restatement_s_on_every_planted_case(kernels, case):
+    want = temporal_planes.evaluate(case).rest
+    m, planes = case.motion, {}
+    none = np.zeros((1, 4), F)
+    got = run(kernels, case.image, case.variance, case.features, m.face if m else np.zeros((case.h, case.w), np.int32), m.vertices if m else none,
+              m.hist_vertices if m else none, case.cam, case.prev, case.params, m is not None, px_dim=case.px_dim,
+              faces=m.faces_v if m else np.zeros((1, 4), np.uint32), planes=planes)
+    assert same_values(got[0], want.integrated), "integrated"
+    assert same_values(got[1], want.history), "history"
+    if m is not None:
+        assert same_values(got[2], want.motion), "motion"
+        assert same_values(planes["reference"], want.reference), "reference"
