@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/pt_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg.  The product never imports this module.  PARITY UNPINNED (see pt_oracle.h).
+cpu_baseline leg.  The product never imports this module.  Held bit for bit to the reference's own
+kernel text as compiled for the CPU (oracle/refkernel.py, tests/test_refkernel_cpu.py), given the builtin table of pt_oracle.c.
 
 The oracle's structs are layout-identical to the C ABI's wire formats (both are the
 reference's host structs, source/PathTracer.h:25-73), so a pbr_scene_desc / pbr_camera built

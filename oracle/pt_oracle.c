@@ -1,7 +1,7 @@
 /*
  * pt_oracle.c — CPU restatement of the reference path-tracing kernel.
  *
- * TEST INFRASTRUCTURE ONLY (see pt_oracle.h).  PARITY UNPINNED (see pt_oracle.h).
+ * TEST INFRASTRUCTURE ONLY (see pt_oracle.h).  Held to the reference's compiled kernel text (see pt_oracle.h).
  *
  * Follows /root/reference/source/opencl/{pathtracing,pt_utils,pt_rgb,pt_brdf,
  * pt_intersect,pt_bvh}.cl one function at a time; every function cites the

@@ -6,16 +6,21 @@
  * tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, and
  * only as the checker / the reported CPU baseline.
  *
- * PARITY UNPINNED: the reference (sebadorn/Physically-based-Rendering) ships no
- * tests, golden images or known-answer vectors for this path, and its kernels
- * (OpenCL C, source/opencl/ *.cl) cannot be built in the build container without
- * writing stand-ins for an OpenCL runtime/builtin library (no POCL, no libclc,
- * amdocl64 has 0 devices; the sources also fail to compile under clang because
- * of two writes through `const Scene*`, pt_bvh.cl:23 and :89).  This oracle is
- * therefore a line-by-line restatement of the reference algorithm, each
- * function citing the file:line it follows; the only in-tree known answer
- * (1082 faces -> 1265 flat BVH nodes, pathtracing.cl:75-76) pins the host-side
- * BVH flattening, not this file.
+ * PARITY: held to the reference's own kernel text as a compiler reads it.  The
+ * reference (sebadorn/Physically-based-Rendering) ships no tests, golden images
+ * or known-answer vectors for this path, and its kernels (OpenCL C,
+ * source/opencl/ *.cl) cannot run as OpenCL in the build container.  But their
+ * text compiles unmodified for the CPU (oracle/refkernel.py: -Dconst= for two
+ * writes through `const Scene*`, pt_bvh.cl:23 and :89, -Dinline= so that C99
+ * inline functions get bodies) behind a shim of the builtins, and
+ * tests/test_refkernel_cpu.py requires this file to equal that build bit for
+ * bit over the recorded configurations.  Pinned that way: control flow,
+ * operation order, int / double promotions, the order of the RNG draws, which
+ * value goes where, the accumulation.  This project's own choice, still: the
+ * bits of the implementation-defined builtins ("deterministic math" below,
+ * which the shim follows), the shim's image stand-ins, and the two -D flags.
+ * This file stays a line-by-line restatement, each function citing the
+ * file:line it follows.
  *
  * All arithmetic is IEEE-754 binary32 with NO implicit contraction
  * (-ffp-contract=off); fused multiply-adds appear only where written as fmaf().

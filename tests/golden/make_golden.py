@@ -3,8 +3,8 @@
 These are REGRESSION fixtures: outputs of this repository's own oracle on this repository's own
 procedural scenes, frozen so that a toolchain, libm or CPU change that moves a single bit is
 noticed — on the build container and on the GPU box alike.  They are NOT reference-derived
-pins: the reference ships no golden vectors and its kernels cannot be built here (see
-oracle/pt_oracle.h, "PARITY UNPINNED").
+pins: the reference ships no golden vectors (what IS recorded from its compiled kernel text is
+tests/golden/refkernel_*.npz, see make_refkernel.py and oracle/pt_oracle.h, "PARITY").
 """
 import os
 import sys

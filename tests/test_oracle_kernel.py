@@ -1,6 +1,7 @@
 """The oracle against first principles and against the reference's documented quirks
 (SURVEY.md Appendix A).  CPU only.  The reference has no tests or golden vectors for this path
-(parity unpinned), so these are known-answer checks derived from the kernel sources."""
+(what holds the oracle to the reference's compiled kernel text is tests/test_refkernel_cpu.py), so these are known-answer
+checks derived from the kernel sources."""
 import ctypes
 
 import numpy as np
