@@ -39,8 +39,13 @@
 #include "pt_morph.hpp"
 #include "pt_skin_dq.hpp"
 #include "pt_update_host.hpp"
+#include "pt_device_memory.hpp"
 
 using ptk::DevParams;
+using ptmem::Owned;
+using ptmem::Pinned;
+using ptmem::allocAll;
+using ptmem::want;
 
 typedef void ( *KernelFn )( const ptk::DevParams );
 
@@ -77,7 +82,7 @@ struct Knobs {
 struct DealTable {
 	std::vector<unsigned> host;
 	unsigned first[PT_BANDS + 1] = {};
-	unsigned* dev = nullptr;
+	Owned<unsigned> dev;
 };
 
 // pbr_denoise_temporal's device planes (pt_temporal.hpp), row-major W x H.  Two sets {integrated colour | variance, position,
@@ -85,66 +90,45 @@ struct DealTable {
 // call and becomes the history by flipping `set` — nothing is copied.  Behind them the filter's working planes, and the
 // planes of the motion path (pbr_temporal_track_motion): first-hit face, {Pprev, code}, {nref, len}.
 struct TemporalPlanes {
-	float4* integrated[2] = {}, * position[2] = {}, * normal[2] = {}, * albedo[2] = {};
-	unsigned* length[2] = {};
-	float4* ping = nullptr, * pong = nullptr;
-	float4* info = nullptr;       // {fx, fy, L, valid} of a call that asks for it
-	float* variance = nullptr;
-	float4* motion = nullptr, * reference = nullptr;
-	int* face = nullptr;
+	Owned<float4> integrated[2], position[2], normal[2], albedo[2];
+	Owned<unsigned> length[2];
+	Owned<float4> ping, pong;
+	Owned<float4> info;           // {fx, fy, L, valid} of a call that asks for it
+	Owned<float> variance;
+	Owned<float4> motion, reference;
+	Owned<int> face;
 	int set = 0;
-
-	// visit( slot, bytes per pixel, is it a plane of the motion path )
-	template <class Visit>
-	void each( Visit visit ) {
-		for( float4** plane : { &integrated[0], &integrated[1], &position[0], &position[1], &normal[0], &normal[1], &albedo[0], &albedo[1], &ping, &pong, &info } ) {
-			visit( (void**) plane, sizeof( float4 ), false );
-		}
-
-		visit( (void**) &length[0], sizeof( unsigned ), false );
-		visit( (void**) &length[1], sizeof( unsigned ), false );
-		visit( (void**) &variance, sizeof( float ), false );
-		visit( (void**) &motion, sizeof( float4 ), true );
-		visit( (void**) &reference, sizeof( float4 ), true );
-		visit( (void**) &face, sizeof( int ), true );
-	}
 
 	// The planes that are not there yet — the motion path's only if needMotion.  All or nothing: a call that fails gives back
 	// what it got, and leaves the planes of earlier calls (a history) alone.
-	hipError_t alloc( size_t pixels, bool needMotion ) {
-		const bool hadHistory = ( variance != nullptr );   // all or nothing: one stands for all
-		hipError_t err = hipSuccess;
-		each( [&]( void** slot, size_t bytes, bool ofMotion ) {
-			if( err == hipSuccess && *slot == nullptr && ( needMotion || !ofMotion ) ) {
-				err = hipMalloc( slot, bytes * pixels );
-			}
-		} );
+	int alloc( size_t pixels, bool needMotion ) {
+		const bool hadHistory = !variance.empty();   // all or nothing: one stands for all
+		int err = hadHistory ? 0 : allocAll( { want( integrated[0], pixels ), want( integrated[1], pixels ), want( position[0], pixels ), want( position[1], pixels ),
+		                                       want( normal[0], pixels ), want( normal[1], pixels ), want( albedo[0], pixels ), want( albedo[1], pixels ),
+		                                       want( ping, pixels ), want( pong, pixels ), want( info, pixels ), want( length[0], pixels ), want( length[1], pixels ),
+		                                       want( variance, pixels ) } );
 
-		if( err != hipSuccess ) {
-			free( hadHistory );
+		if( err == 0 && needMotion && face.empty() ) {
+			err = allocAll( { want( motion, pixels ), want( reference, pixels ), want( face, pixels ) } );
+		}
+
+		if( err != 0 && !hadHistory ) {
+			*this = TemporalPlanes();
 		}
 
 		return err;
-	}
-
-	void free( bool motionOnly = false ) {
-		each( [motionOnly]( void** slot, size_t, bool ofMotion ) {
-			if( ofMotion || !motionOnly ) {
-				(void) hipFree( *slot );
-				*slot = nullptr;
-			}
-		} );
 	}
 };
 
 // What every pbr_set_* captures (pbr_set_parts, pbr_set_skin, pbr_set_morph): the REST POSE — a copy of the positions and, when
 // the call was given the normals' side too, of the normals as they were when it was made —, the staging buffer V' is written to
-// before it becomes dVertices (the two pointers are swapped: nothing caches dVertices, every launch takes it from the context),
+// before it becomes dVertices (the two buffers are swapped: nothing caches dVertices, every launch takes it from the context),
 // and the flag word of a position that is not finite with its pinned host twin.  Each kind owns one: no call touches another
-// kind's.  allocRestPose makes one, freeRestPose gives it back.
+// kind's.  allocRestPose makes one; like the records below it is given back by assigning an empty one.
 struct RestPose {
-	float4* dRest = nullptr, * dRestNormals = nullptr, * dStaged = nullptr;
-	unsigned* dFlag = nullptr, * hFlag = nullptr;
+	Owned<float4> dRest, dRestNormals, dStaged;
+	Owned<unsigned> dFlag;
+	Owned<unsigned, Pinned> hFlag;
 	bool normals = false;       // the normals are moved too
 	uint64_t bytes = 0;         // device bytes of the kind: the pose and the kind's own tables (formulas in pbr_hip_diag.h)
 	uint32_t updates = 0;       // successful updates of the kind since its pbr_set_*
@@ -153,13 +137,14 @@ struct RestPose {
 };
 
 // What pbr_set_parts adds to its rest pose: the part index of every vertex and normal, the part records in device and in pinned
-// memory.
+// memory.  pbr_set_parts( 0 parts ), a second pbr_set_parts and pbr_upload_scene assign an empty record.  Like the skin's and the
+// morph's it knows nothing of ctx->lastUpdate: dropping a kind does not undo that its update was the last one.
 struct PartsState {
 	RestPose pose;
 	uint32_t count = 0;
-	unsigned* dOfVertex = nullptr, * dOfNormal = nullptr;
-	float4* dRecords = nullptr;
-	ptx::PartRecord* hRecords = nullptr;
+	Owned<unsigned> dOfVertex, dOfNormal;
+	Owned<float4> dRecords;     // six quads per part
+	Owned<ptx::PartRecord, Pinned> hRecords;
 };
 
 // What pbr_set_skin adds: one 32-byte influence record per vertex and — with normal influences — per normal, the bone records
@@ -169,9 +154,9 @@ struct PartsState {
 struct SkinState {
 	RestPose pose;
 	uint32_t count = 0;
-	uint4* dOfVertex = nullptr, * dOfNormal = nullptr;
-	float4* dBones = nullptr;
-	pbr_float4* hBones = nullptr;
+	Owned<uint4> dOfVertex, dOfNormal;   // two quads per element
+	Owned<float4> dBones;       // three quads per bone
+	Owned<pbr_float4, Pinned> hBones;
 	uint32_t dqUpdates = 0;     // successful pbr_update_skin_dq and pbr_update_pose_dq since pbr_set_skin
 	double dqLastMs = 0.0;      // of the last of them: device time of the dq kernels that write V' and N' alone
 };
@@ -181,97 +166,163 @@ struct SkinState {
 struct MorphState {
 	RestPose pose;
 	uint32_t count = 0;
-	uint32_t* dVertexRun = nullptr, * dNormalRun = nullptr;
-	ptm::Entry* dVertexEntries = nullptr, * dNormalEntries = nullptr;
-	float* dWeights = nullptr, * hWeights = nullptr;
+	Owned<uint32_t> dVertexRun, dNormalRun;
+	Owned<ptm::Entry> dVertexEntries, dNormalEntries;
+	Owned<float> dWeights;
+	Owned<float, Pinned> hWeights;
 	uint64_t vertexEntries = 0, normalEntries = 0;
 };
 
-struct pbr_ctx {
-	int device = -1;
-	Knobs knobs;
-	hipStream_t stream = nullptr;
-	hipEvent_t evStart = nullptr, evStop = nullptr, evTraceStart = nullptr, evTraceStop = nullptr, evChainStart = nullptr;
-	std::string error;
-	double lastKernelMs = 0.0;
-	int numCUs = 0;
-
-	// scene
-	bool hasScene = false;
-	float4* dNodes = nullptr;
-	float4* dTris = nullptr;
-	float4* dTriPN = nullptr;      // exact vertices + vertex normals per face (Phong tessellation); null if the normal indices are unusable
-	float4* dMats = nullptr;
-	float4* dFaceN = nullptr;      // per-face unit normal + material, prepareFaceNormals
-	float4* dLights = nullptr;
-	uint32_t numHotAvail = 0;      // records at the head of the node stream that are ranked for LDS staging
-	int firstRef = 0;              // record of node 1
-	// ray-ordered walk (pbr_config.traversal != 0): the records of the configured layout, packed from a host copy of the flat tree
-	SceneTree tree;
-	float4* dNodesWalk = nullptr;
+// The ray-ordered walk (pbr_config.traversal != 0): the records of the configured layout, packed from a host copy of the flat
+// tree, and what pbr_refit_ordered_walk's re-link keeps for them (pt_relink_host.hpp, pt_relink.hpp): while that flag is on,
+// pbr_update_vertices under a ray-ordered traversal rebuilds dNodesWalk's records on the device.  dRelink: one allocation with
+// the static and the working tables of the layout dNodesWalk holds, made by the first such update; relinkView and the two level
+// tables point into it.  The tables are a layout's: they go with its records (freeWalkStreams) — with the scene, with a
+// pbr_configure of another traversal and with an update that does not re-link.
+struct WalkStreams {
+	Owned<float4> dNodesWalk;
 	uint32_t walkBuilt = 0;        // the scheme dNodesWalk holds (0: none)
 	uint32_t walkHotAvail = 0;     // records at the head of dNodesWalk that are ranked for LDS staging (all orders interleaved)
 	int walkFirst[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-	uint64_t nodeBytes = 0, walkBytes = 0, triBytes = 0;   // device bytes of the reference-order stream, the ordered streams, the face records
+	Owned<unsigned char> dRelink;
+	RelinkView relinkView = {};
+	unsigned* dRelinkLevelNodes = nullptr;   // inside dRelink
+	unsigned* dRelinkLevelFirst = nullptr;
+	std::vector<RelinkRun> relinkRuns;
+	uint32_t relinkLevels = 0, relinkContainers = 0;
+};
+
+// What lives and dies with the uploaded scene: freeScene assigns an empty one.
+struct Scene {
+	Owned<float4> dNodes;
+	Owned<float4> dTris;
+	Owned<float4> dTriPN;          // exact vertices + vertex normals per face (Phong tessellation); null if the normal indices are unusable
+	Owned<float4> dMats;
+	Owned<float4> dFaceN;          // per-face unit normal + material, prepareFaceNormals
+	Owned<float4> dLights;
+	uint32_t numHotAvail = 0;      // records at the head of the node stream that are ranked for LDS staging
+	int firstRef = 0;              // record of node 1
+	SceneTree tree;
+	WalkStreams walk;
 	uint32_t numNodes = 0, numFaces = 0, numMaterials = 0, numLights = 0;
 	uint32_t sceneBrdf = 1;
 	// pbr_update_vertices (pt_refit_host.hpp, pt_refit.hpp): kept from the upload — the faces' vertex indices, a buffer for the
 	// vertices, node 0's box (it has no record), and the refit's tables: thread slots, per-node words and heights, node ->
 	// record, the nodes above the cut by level.  refit keeps the verdict, recordOf and the partition's sizes on the host
 	RefitPlan refit;
-	uint4* dFacesV = nullptr;
-	float4* dVertices = nullptr;
-	float4* dRootBox = nullptr;
-	unsigned* dRefitSlots = nullptr;
-	unsigned* dRefitInfo = nullptr;
-	unsigned short* dRefitHeights = nullptr;
-	int* dRefitRecordOf = nullptr;
-	unsigned* dRefitTop = nullptr;
-	unsigned* dRefitLevelFirst = nullptr;
+	Owned<uint4> dFacesV;
+	Owned<float4> dVertices;
+	Owned<float4> dRootBox;
+	Owned<unsigned> dRefitSlots;
+	Owned<unsigned> dRefitInfo;
+	Owned<unsigned short> dRefitHeights;
+	Owned<int> dRefitRecordOf;
+	Owned<unsigned> dRefitTop;
+	Owned<unsigned> dRefitLevelFirst;
 	uint32_t numVertices = 0, refitGroups = 0, refitLevels = 0, refitTopNodes = 0, refitSubtrees = 0;
-	uint64_t refitBytes = 0;       // device bytes of all of the above
 	uint32_t refitUpdates = 0;     // pbr_update_vertices / pbr_update_geometry calls since the upload: > 0 = the boxes are refitted ones
 	bool treeStale = false;        // tree.bvh's boxes are older than the device's (refreshTree)
 	// pbr_update_geometry (pt_patch_refit_host.hpp, pt_patch_refit.hpp): the faces' normal indices and the vertex normals, kept
 	// on the host by the upload (only when dTriPN is there) and moved to the device by the first such update together with the
-	// per-face scratch table of thick boxes — no allocation per call; freed with the scene
+	// per-face scratch table of thick boxes — no allocation per call
 	std::vector<pbr_uint4> patchFacesN;
 	std::vector<pbr_float4> patchNormals;
-	uint4* dPatchFacesN = nullptr;
-	float4* dPatchNormals = nullptr;
-	float2* dFaceBoxes = nullptr;  // 24 bytes per face: lo.xyz, hi.xyz
+	Owned<uint4> dPatchFacesN;
+	Owned<float4> dPatchNormals;
+	Owned<float2> dFaceBoxes;      // 24 bytes per face: lo.xyz, hi.xyz
 	uint32_t numNormals = 0;       // the upload's count, usable or not
-	uint64_t patchBytes = 0;       // device bytes of the three tables (0 until the first pbr_update_geometry)
 	uint32_t geometryUpdates = 0;  // successful pbr_update_geometry calls since the upload
-	float patchAlpha = 0.0f;           // the last update's boxes are thick ones for this phong_tessellation (pbr_configure's state rule)
-	double lastRefitUploadMs = 0.0;
-	// pbr_refit_ordered_walk (pt_relink_host.hpp, pt_relink.hpp): while it is on, pbr_update_vertices under a ray-ordered traversal
-	// rebuilds dNodesWalk's records on the device.  dRelink: one allocation with the static and the working tables of the layout
-	// dNodesWalk holds, made by the first such update and freed with the streams (freeWalkStreams); relinkView points into it
-	bool refitOrdered = false;     // the flag: survives pbr_configure and pbr_upload_scene
-	void* dRelink = nullptr;
-	uint64_t relinkBytes = 0;
-	RelinkView relinkView = {};
-	unsigned* dRelinkLevelNodes = nullptr;   // inside dRelink
-	unsigned* dRelinkLevelFirst = nullptr;
-	std::vector<RelinkRun> relinkRuns;
-	uint32_t relinkLevels = 0, relinkContainers = 0;
-	hipEvent_t evRelinkStart = nullptr, evRelinkStop = nullptr;
-	double lastRelinkMs = 0.0;     // of the last pbr_update_vertices: device time of the re-link kernels alone,
-	uint32_t lastRelinkLaunches = 0;   // their number,
-	bool lastRelinked = false;     // and whether it re-linked at all
+	float patchAlpha = 0.0f;       // the last update's boxes are thick ones for this phong_tessellation (pbr_configure's state rule)
 	// pbr_set_parts / pbr_update_transforms (pt_transform_host.hpp, pt_transform.hpp), pbr_set_skin / pbr_update_skin
 	// (pt_skin_host.hpp, pt_skin.hpp), pbr_set_morph / pbr_update_morph / pbr_update_pose (pt_morph_host.hpp, pt_morph.hpp): three
 	// kinds of move, independent of each other, each with a RestPose of its own and next to it the tables only that kind has
-	// (above).  All of a kind is allocated by its pbr_set_* and freed by the next one, by freeParts / freeSkin / freeMorph and with the
-	// scene.  The tables an update uploads have a pinned host twin, so no copy waits for a staging copy of pageable memory.
+	// (above).  All of a kind is allocated by its pbr_set_* and given back by the next one and with the scene.  The tables an
+	// update uploads have a pinned host twin, so no copy waits for a staging copy of pageable memory.
 	PartsState parts;
 	SkinState skin;
 	MorphState morph;
+	// pbr_temporal_track_motion: H, the vertex positions the history was made under — a copy of dVertices taken by the first
+	// pbr_update_vertices after a temporal call, allocated then, given back when tracking is turned off (not part of refitBytes)
+	Owned<float4> dHistVertices;
+
+	// device bytes of what the upload keeps for updates (pbr_diag_refit_info): nothing for a tree that cannot be refitted
+	uint64_t refitBytes() const {
+		return !refit.nested ? 0 : dFacesV.bytes() + dVertices.bytes() + dRootBox.bytes() + dRefitSlots.bytes() + dRefitInfo.bytes() + dRefitHeights.bytes()
+		                           + dRefitRecordOf.bytes() + dRefitTop.bytes() + dRefitLevelFirst.bytes();
+	}
+};
+
+// What lives and dies with the configuration: freeImages assigns an empty one.
+struct Images {
+	Owned<float4> dImgIn;
+	Owned<float4> dImgOut;
+	Owned<float4> dImgDbg;
+	Owned<float4> dRows;           // W x H row-major staging for read-back / write_input
+	Owned<float4> dFull;           // all tiles of the frame, filled by pbr_import_tiles
+	// the banded queue's dealing orders (pt_deal.hpp; pt_kernel.hpp, nextSlot): the local tiles as a grid cut into PT_BANDS bands
+	// of rows, and per order (DealOrder) a table that names, per band, its tiles in the order they are dealt.  deal[kDealSpatial]
+	// is the spatial table, or a pinned one; the two cost orders are learnt from the debug image (node visits per pixel of a
+	// launch's last frame, learnTileCosts) and keep the spatial bands
+	DealTable deal[kDealOrders];
+	Owned<float> dTileCost;        // node visits per local tile
+	Owned<float4> dFrameBuf;       // frame-parallel launches: {finalColor, focus} per frame and local pixel slot
+	// pbr_render_dof: the focus chain's table (pt_chain.hpp) — per frame of a launch and local pixel slot the previous
+	// first-hit distance, behind them the focus pixel's per frame
+	Owned<float> dChain;
+	// pbr_render_adaptive (launchAdaptive, pt_adaptive.hpp): allocated by the first adaptive call after pbr_configure.  Per local
+	// tile the frames it rendered, its error estimate at its last test and whether it is still active; per pixel slot the
+	// luminance's {mean, M2}; the dealing table of the round (the active tiles only) — the context's own tables stay as they are
+	Owned<unsigned> dTileFrames;
+	Owned<float> dTileError;
+	Owned<unsigned> dTileActive;
+	Owned<float2> dMoments;
+	Owned<unsigned> dAdaptiveOrder;
+	// pbr_denoise_temporal (pt_temporal.hpp): the history's planes, allocated by the first temporal call after pbr_configure
+	TemporalPlanes planes;
+};
+
+// The context's stream and events: declared ahead of every buffer, so that they go after the buffers when the context does.
+struct Stream {
+	hipStream_t s = nullptr;
+	Stream() = default;
+	Stream( const Stream& ) = delete;
+	Stream& operator=( const Stream& ) = delete;
+	~Stream() { if( s != nullptr ) { (void) hipStreamDestroy( s ); } }
+	operator hipStream_t() const { return s; }
+};
+
+struct Event {
+	hipEvent_t e = nullptr;
+	Event() = default;
+	Event( const Event& ) = delete;
+	Event& operator=( const Event& ) = delete;
+	~Event() { if( e != nullptr ) { (void) hipEventDestroy( e ); } }
+	operator hipEvent_t() const { return e; }
+};
+
+struct pbr_ctx {
+	int device = -1;
+	Knobs knobs;
+	Stream stream;
+	Event evStart, evStop, evTraceStart, evTraceStop, evChainStart;
+	Event evRelinkStart, evRelinkStop;
 	// the events of the step that computes V' and N' on the device; shared: one update is one kind of move
-	hipEvent_t evXfStart = nullptr, evXfStop = nullptr, evXfNormalsStart = nullptr, evXfNormalsStop = nullptr;
+	Event evXfStart, evXfStop, evXfNormalsStart, evXfNormalsStop;
+	Event evFoldStart, evFoldStop;
+	std::string error;
+	double lastKernelMs = 0.0;
+	int numCUs = 0;
+
+	// scene
+	bool hasScene = false;
+	Scene scene;
+	double lastRefitUploadMs = 0.0;
+	bool refitOrdered = false;     // pbr_refit_ordered_walk's flag: survives pbr_configure and pbr_upload_scene
+	double lastRelinkMs = 0.0;     // of the last pbr_update_vertices: device time of the re-link kernels alone,
+	uint32_t lastRelinkLaunches = 0;   // their number,
+	bool lastRelinked = false;     // and whether it re-linked at all
 	// the most recent successful update since the upload (pt_update_host.hpp): what pbr_configure's state rule and the four
-	// pbr_diag_*_info calls report of it is derived from this one value.  freeScene resets it, freeParts / freeSkin / freeMorph do not
+	// pbr_diag_*_info calls report of it is derived from this one value.  freeScene resets it, dropping a kind does not
 	UpdateKind lastUpdate = UpdateKind::None;
 	// which geometry a rest pose was captured from: bumped by an upload and by every successful update; pbr_set_skin and
 	// pbr_set_morph record it in their pose, pbr_update_pose needs both to have captured the same
@@ -281,19 +332,9 @@ struct pbr_ctx {
 	bool configured = false;
 	pbr_config cfg;
 	int tilesX = 0, tilesY = 0, numTiles = 0, numLocalTiles = 0;
-	float4* dImgIn = nullptr;
-	float4* dImgOut = nullptr;
-	float4* dImgDbg = nullptr;
-	float4* dRows = nullptr;       // W x H row-major staging for read-back / write_input
-	float4* dFull = nullptr;       // all tiles of the frame, filled by pbr_import_tiles
-	// the banded queue's dealing orders (pt_deal.hpp; pt_kernel.hpp, nextSlot): the local tiles as a grid cut into PT_BANDS bands
-	// of rows, and per order (DealOrder) a table that names, per band, its tiles in the order they are dealt.  deal[kDealSpatial]
-	// is the spatial table, or a pinned one; the two cost orders are learnt from the debug image (node visits per pixel of a
-	// launch's last frame, learnTileCosts) and keep the spatial bands
+	Images images;
 	DealGrid queueGrid;
-	DealTable deal[kDealOrders];
 	bool orderPinned = false;      // pbr_diag_set_tile_order: the caller's order stays (tests, A/B runs)
-	float* dTileCost = nullptr;    // node visits per local tile
 	std::vector<float> hTileCost;
 	bool costLearnt = false;       // the two cost tables hold orders learnt for costCam
 	pbr_camera costCam = {};       // the camera (and pixel size) the costs were measured with
@@ -303,13 +344,7 @@ struct pbr_ctx {
 	int lastBvhRadius = 0;         // pbr_build_bvh: the clustering's search radius of the last build (0: none yet / the radix-tree builder)
 	bool focusGiven = false;       // pbr_set_focus_depth: the focus pixel's previous-frame distance for the next frame
 	float focusDepth = 0.0f;
-	float4* dFrameBuf = nullptr;   // frame-parallel launches: {finalColor, focus} per frame and local pixel slot
-	size_t frameBufFrames = 0;
-	// pbr_render_dof: the focus chain's table (pt_chain.hpp) — per frame of a launch and local pixel slot the previous
-	// first-hit distance, behind them the focus pixel's per frame — and the focus pixel's distance after the last launch
-	float* dChain = nullptr;
-	size_t chainFloats = 0;
-	float* dChainCarry = nullptr;
+	Owned<float> dChainCarry;      // pbr_render_dof: the focus pixel's distance after the last launch
 	double lastChainMs = 0.0;      // of the last render: time inside the focus chain's launches
 	// schedule auto-tuning (launch(), pt_tuner.hpp): per scene + configuration, the candidates are timed on the first
 	// frames that are rendered anyway, then the fastest one is kept
@@ -320,27 +355,16 @@ struct pbr_ctx {
 	Plan chainPlans[ScheduleTuner::kPlans];         // the same candidates in the chained build of their kernels (pbr_render_dof; pt_flavour.hpp)
 	bool plansBuilt = false, phongPlanBuilt = false, chainPlansBuilt = false;
 	bool workClean = false;                         // the queue heads are zero (foldFrames leaves them so)
-	float* hSeeds = nullptr;                        // pinned staging for the seeds of a launch
-	size_t hSeedCapacity = 0;
+	Owned<float, Pinned> hSeeds;                    // pinned staging for the seeds of a launch
 	int pinnedPlan = -1;                            // pbr_diag_pin_plan: >= 0 renders with this plan, no tuning (ranks of a multi-GPU run: all the same)
 	char lastPlan[48] = "";        // name of the plan that rendered the largest chunk of the last render
 	char lastKernel[96] = "";      // ... and its kernel
 	double lastTraceMs = 0.0;      // of the last render: time inside the path-tracing launches only ...
 	uint32_t lastTraceLaunches = 0; // ... and how many there were (frame-parallel renders are chunked)
-	float* dSeeds = nullptr;
-	size_t seedCapacity = 0;
-	unsigned long long* dCounters = nullptr;
-	unsigned int* dWork = nullptr;
-	unsigned int* dGuard = nullptr;
-	// pbr_render_adaptive (launchAdaptive, pt_adaptive.hpp): allocated by the first adaptive call after pbr_configure.  Per local
-	// tile the frames it rendered, its error estimate at its last test and whether it is still active; per pixel slot the
-	// luminance's {mean, M2}; the dealing table of the round (the active tiles only) — the context's own tables stay as they are
-	unsigned* dTileFrames = nullptr;
-	float* dTileError = nullptr;
-	unsigned* dTileActive = nullptr;
-	float2* dMoments = nullptr;
-	unsigned* dAdaptiveOrder = nullptr;
-	hipEvent_t evFoldStart = nullptr, evFoldStop = nullptr;
+	Owned<float> dSeeds;
+	Owned<unsigned long long> dCounters;
+	Owned<unsigned int> dWork;
+	unsigned int* dGuard = nullptr;                 // mapped pinned memory: by hand, pbr_create / pbr_destroy
 	bool adaptiveStats = false;          // dTileFrames / dTileError hold the last adaptive call's
 	// pbr_read_variance, pbr_denoise_guided: dMoments / dTileFrames describe the accumulated image as it is now — set by a successful
 	// adaptive call, cleared by whatever writes or swaps imageIn / imageOut — and that call's first_sample_count
@@ -349,20 +373,23 @@ struct pbr_ctx {
 	uint32_t lastAdaptiveRounds = 0;     // of the last adaptive call: rounds (= convergence tests per tile that reached the end),
 	uint64_t lastAdaptiveUnits = 0;      // (pixel, frame) units traced,
 	double lastAdaptiveFoldMs = 0.0;     // time inside foldFramesAdaptive
-	// pbr_denoise_temporal (pt_temporal.hpp): the history's planes, allocated by the first temporal call after pbr_configure,
-	// freed with the images
-	TemporalPlanes planes;
 	// is set planes.set a history, has the geometry moved since it was made, which path does a call take: pt_temporal_host.hpp.
 	// The history is dropped by pbr_temporal_reset, pbr_configure, pbr_upload_scene and — without motion tracking — pbr_update_vertices
 	TemporalPolicy temporal;
-	// pbr_temporal_track_motion: H, the vertex positions the history was made under — a copy of dVertices taken by the first
-	// pbr_update_vertices after a temporal call, allocated then, freed with the scene and when tracking is turned off (not part
-	// of refitBytes)
-	float4* dHistVertices = nullptr;
 	bool temporalFresh = false;          // a pbr_render_adaptive succeeded since the last successful temporal call
 	pbr_camera temporalCam = {};         // the history's camera and pixel size
 	float temporalPxDim = 0.0f;
 };
+
+// pt_device_memory.hpp's four primitives over the HIP runtime
+namespace ptmem {
+
+int deviceAlloc( void** p, size_t bytes ) { return (int) hipMalloc( p, bytes ); }
+void deviceFree( void* p ) { (void) hipFree( p ); }
+int pinnedAlloc( void** p, size_t bytes ) { return (int) hipHostMalloc( p, bytes, hipHostMallocDefault ); }
+void pinnedFree( void* p ) { (void) hipHostFree( p ); }
+
+}  // namespace ptmem
 
 namespace {
 
@@ -382,7 +409,7 @@ int fail( pbr_ctx* ctx, int code, const char* fmt, ... ) {
 
 #define HIP_TRY( ctx, call ) \
 	do { \
-		const hipError_t err__ = ( call ); \
+		const hipError_t err__ = (hipError_t) ( call ); \
 		if( err__ != hipSuccess ) { \
 			return fail( ctx, PBR_EDEVICE, "%s: %s", #call, hipGetErrorString( err__ ) ); \
 		} \
@@ -410,104 +437,13 @@ int usable( pbr_ctx* ctx ) {
 }
 
 void freeWalkStreams( pbr_ctx* ctx ) {
-	(void) hipFree( ctx->dNodesWalk );
-	ctx->dNodesWalk = nullptr;
-	ctx->walkBuilt = 0;
-	ctx->walkBytes = 0;
-	(void) hipFree( ctx->dRelink );   // the re-link's tables are a layout's: they go with its records
-	ctx->dRelink = nullptr;
-	ctx->relinkBytes = 0;
-	ctx->relinkRuns.clear();
-}
-
-// A rest pose's buffers go; the record is as it was made.
-void freeRestPose( RestPose* pose ) {
-	for( void* p : { (void*) pose->dRest, (void*) pose->dRestNormals, (void*) pose->dStaged, (void*) pose->dFlag } ) {
-		(void) hipFree( p );
-	}
-
-	(void) hipHostFree( pose->hFlag );
-	*pose = RestPose();
-}
-
-// pbr_set_parts( 0 parts ), a second pbr_set_parts, pbr_upload_scene: the parts, the rest pose and their buffers go.  Like
-// freeSkin and freeMorph it knows nothing of ctx->lastUpdate: dropping a kind does not undo that its update was the last one.
-void freeParts( PartsState* parts ) {
-	freeRestPose( &parts->pose );
-	(void) hipFree( parts->dRecords );
-	(void) hipFree( parts->dOfVertex );
-	(void) hipFree( parts->dOfNormal );
-	(void) hipHostFree( parts->hRecords );
-	*parts = PartsState();
-}
-
-// pbr_set_skin( 0 bones ), a second pbr_set_skin, pbr_upload_scene: the skin, its rest pose and their buffers go.
-void freeSkin( SkinState* skin ) {
-	freeRestPose( &skin->pose );
-	(void) hipFree( skin->dBones );
-	(void) hipFree( skin->dOfVertex );
-	(void) hipFree( skin->dOfNormal );
-	(void) hipHostFree( skin->hBones );
-	*skin = SkinState();
-}
-
-// pbr_set_morph( 0 targets ), a second pbr_set_morph, pbr_upload_scene: the morph, its rest pose and their buffers go.
-void freeMorph( MorphState* morph ) {
-	freeRestPose( &morph->pose );
-
-	for( void* p : { (void*) morph->dVertexRun, (void*) morph->dNormalRun, (void*) morph->dVertexEntries, (void*) morph->dNormalEntries, (void*) morph->dWeights } ) {
-		(void) hipFree( p );
-	}
-
-	(void) hipHostFree( morph->hWeights );
-	*morph = MorphState();
+	ctx->scene.walk = WalkStreams();
 }
 
 void freeScene( pbr_ctx* ctx ) {
-	freeParts( &ctx->parts );
-	freeSkin( &ctx->skin );
-	freeMorph( &ctx->morph );
+	ctx->scene = Scene();
 	ctx->lastUpdate = UpdateKind::None;
 	ctx->geometryGeneration++;
-	(void) hipFree( ctx->dNodes );
-	freeWalkStreams( ctx );
-	(void) hipFree( ctx->dTris );
-	(void) hipFree( ctx->dTriPN );
-	ctx->dTriPN = nullptr;
-	(void) hipFree( ctx->dFaceN );
-	ctx->dFaceN = nullptr;
-	(void) hipFree( ctx->dMats );
-	(void) hipFree( ctx->dLights );
-	ctx->dNodes = ctx->dTris = ctx->dMats = ctx->dLights = nullptr;
-	(void) hipFree( ctx->dFacesV );
-	(void) hipFree( ctx->dVertices );
-	(void) hipFree( ctx->dRootBox );
-	(void) hipFree( ctx->dRefitSlots );
-	(void) hipFree( ctx->dRefitInfo );
-	(void) hipFree( ctx->dRefitHeights );
-	(void) hipFree( ctx->dRefitRecordOf );
-	(void) hipFree( ctx->dRefitTop );
-	(void) hipFree( ctx->dRefitLevelFirst );
-	(void) hipFree( ctx->dHistVertices );
-	(void) hipFree( ctx->dPatchFacesN );
-	(void) hipFree( ctx->dPatchNormals );
-	(void) hipFree( ctx->dFaceBoxes );
-	ctx->dPatchFacesN = nullptr;
-	ctx->dPatchNormals = nullptr;
-	ctx->dFaceBoxes = nullptr;
-	std::vector<pbr_uint4>().swap( ctx->patchFacesN );
-	std::vector<pbr_float4>().swap( ctx->patchNormals );
-	ctx->patchBytes = 0;
-	ctx->geometryUpdates = 0;
-	ctx->patchAlpha = 0.0f;
-	ctx->dFacesV = nullptr;
-	ctx->dVertices = ctx->dRootBox = ctx->dHistVertices = nullptr;
-	ctx->dRefitSlots = ctx->dRefitInfo = ctx->dRefitTop = ctx->dRefitLevelFirst = nullptr;
-	ctx->dRefitHeights = nullptr;
-	ctx->dRefitRecordOf = nullptr;
-	ctx->refitBytes = 0;
-	ctx->refitUpdates = 0;
-	ctx->treeStale = false;
 	ctx->hasScene = false;
 }
 
@@ -521,43 +457,13 @@ void replan( pbr_ctx* ctx ) {
 }
 
 void freeImages( pbr_ctx* ctx ) {
-	(void) hipFree( ctx->dImgIn );
-	(void) hipFree( ctx->dImgOut );
-	(void) hipFree( ctx->dImgDbg );
-	(void) hipFree( ctx->dRows );
-	(void) hipFree( ctx->dFull );
-	(void) hipFree( ctx->dFrameBuf );
-	ctx->dFrameBuf = nullptr;
-	ctx->frameBufFrames = 0;
-	(void) hipFree( ctx->dChain );
-	ctx->dChain = nullptr;
-	ctx->chainFloats = 0;
-
-	for( DealTable& table : ctx->deal ) {
-		(void) hipFree( table.dev );
-		table.dev = nullptr;
-		table.host.clear();
-	}
-
-	(void) hipFree( ctx->dTileCost );
-	(void) hipFree( ctx->dTileFrames );
-	(void) hipFree( ctx->dTileError );
-	(void) hipFree( ctx->dTileActive );
-	(void) hipFree( ctx->dMoments );
-	(void) hipFree( ctx->dAdaptiveOrder );
-	ctx->dTileFrames = ctx->dTileActive = ctx->dAdaptiveOrder = nullptr;
-	ctx->dTileError = nullptr;
-	ctx->dMoments = nullptr;
+	ctx->images = Images();
 	ctx->adaptiveStats = false;
 	ctx->varianceCurrent = false;
-
-	ctx->planes.free();
 	ctx->temporal.configure();
 	ctx->temporalFresh = false;
-	ctx->dTileCost = nullptr;
 	ctx->costLearnt = false;
 	ctx->orderPinned = false;
-	ctx->dImgIn = ctx->dImgOut = ctx->dImgDbg = ctx->dRows = ctx->dFull = nullptr;
 	ctx->configured = false;
 }
 
@@ -664,69 +570,68 @@ void invariantDivisor( unsigned d, unsigned out[2] ) {
 int uploadWalkStreams( pbr_ctx* ctx, const PackedWalk& walk, uint32_t layout ) {
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeWalkStreams( ctx );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dNodesWalk, sizeof( Quad ) * walk.storage.size() ) );
-	HIP_TRY( ctx, hipMemcpy( ctx->dNodesWalk, walk.storage.data(), sizeof( Quad ) * walk.storage.size(), hipMemcpyHostToDevice ) );
-	std::memcpy( ctx->walkFirst, walk.first, sizeof( ctx->walkFirst ) );
-	ctx->walkHotAvail = walk.hotSlots;
-	ctx->walkBytes = sizeof( Quad ) * walk.storage.size();
-	ctx->walkBuilt = layout;
+	HIP_TRY( ctx, ctx->scene.walk.dNodesWalk.alloc( walk.storage.size() ) );
+	HIP_TRY( ctx, hipMemcpy( ctx->scene.walk.dNodesWalk, walk.storage.data(), sizeof( Quad ) * walk.storage.size(), hipMemcpyHostToDevice ) );
+	std::memcpy( ctx->scene.walk.walkFirst, walk.first, sizeof( ctx->scene.walk.walkFirst ) );
+	ctx->scene.walk.walkHotAvail = walk.hotSlots;
+	ctx->scene.walk.walkBuilt = layout;
 	return PBR_OK;
 }
 
 // The host copy of the tree after pbr_update_vertices: the boxes come back from the device when somebody asks for them
 // (pbr_read_bvh, a ray-ordered walk to build) — an update itself copies nothing back.
 int refreshTree( pbr_ctx* ctx ) {
-	if( !ctx->treeStale ) {
+	if( !ctx->scene.treeStale ) {
 		return PBR_OK;
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	std::vector<Quad> records( ctx->nodeBytes / sizeof( Quad ) );
+	std::vector<Quad> records( ctx->scene.dNodes.count() );
 	Quad root[2];
-	HIP_TRY( ctx, hipMemcpy( records.data(), ctx->dNodes, ctx->nodeBytes, hipMemcpyDeviceToHost ) );
-	HIP_TRY( ctx, hipMemcpy( root, ctx->dRootBox, sizeof( root ), hipMemcpyDeviceToHost ) );
-	std::vector<pbr_bvh_node>& bvh = ctx->tree.bvh;
+	HIP_TRY( ctx, hipMemcpy( records.data(), ctx->scene.dNodes, ctx->scene.dNodes.bytes(), hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( root, ctx->scene.dRootBox, sizeof( root ), hipMemcpyDeviceToHost ) );
+	std::vector<pbr_bvh_node>& bvh = ctx->scene.tree.bvh;
 	bvh[0].bbMin = pbr_float4 { root[0].x, root[0].y, root[0].z, bvh[0].bbMin.w };
 	bvh[0].bbMax = pbr_float4 { root[1].x, root[1].y, root[1].z, bvh[0].bbMax.w };
 
-	for( uint32_t i = 1; i < ctx->tree.size(); i++ ) {
-		const Quad* rec = records.data() + (size_t) ctx->refit.recordOf[i] * 2;
+	for( uint32_t i = 1; i < ctx->scene.tree.size(); i++ ) {
+		const Quad* rec = records.data() + (size_t) ctx->scene.refit.recordOf[i] * 2;
 		bvh[i].bbMin = pbr_float4 { rec[0].x, rec[0].y, rec[1].x, bvh[i].bbMin.w };
 		bvh[i].bbMax = pbr_float4 { rec[0].z, rec[0].w, rec[1].y, bvh[i].bbMax.w };
 	}
 
-	ctx->treeStale = false;
+	ctx->scene.treeStale = false;
 	return PBR_OK;
 }
 
 int buildWalkStreams( pbr_ctx* ctx, uint32_t layout ) {
 	PBR_TRY( refreshTree( ctx ) );
 	PackedWalk walk;
-	PBR_TRY( packWalk( ctx->tree, layout, &walk, &ctx->error ) );
+	PBR_TRY( packWalk( ctx->scene.tree, layout, &walk, &ctx->error ) );
 	return uploadWalkStreams( ctx, walk, layout );
 }
 
 // The node stream, its ranked prefix and the first record(s) for the configured traversal.
 int applyWalk( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail ) {
 	const uint32_t scheme = ctx->configured ? ctx->cfg.traversal : 0u;
-	P->nodes = ctx->dNodes;
-	P->firstRef = ctx->firstRef;
+	P->nodes = ctx->scene.dNodes;
+	P->firstRef = ctx->scene.firstRef;
 	P->walkScheme = 0;
-	*hotAvail = ctx->numHotAvail;
+	*hotAvail = ctx->scene.numHotAvail;
 
 	if( scheme == 0 ) {
 		return PBR_OK;
 	}
 
-	if( ctx->walkBuilt != scheme ) {
+	if( ctx->scene.walk.walkBuilt != scheme ) {
 		PBR_TRY( buildWalkStreams( ctx, scheme ) );
 	}
 
-	P->nodes = ctx->dNodesWalk + 2;   // behind the 32-byte header ...
-	P->walkTable = (const int*) ctx->dNodesWalk;   // ... which the kernels read through a pointer of its own (DevParams)
-	P->firstRef = ctx->walkFirst[0];
+	P->nodes = ctx->scene.walk.dNodesWalk + 2;   // behind the 32-byte header ...
+	P->walkTable = (const int*) ctx->scene.walk.dNodesWalk.get();   // ... which the kernels read through a pointer of its own (DevParams)
+	P->firstRef = ctx->scene.walk.walkFirst[0];
 	P->walkScheme = (int) scheme;
-	*hotAvail = ctx->walkHotAvail;
+	*hotAvail = ctx->scene.walk.walkHotAvail;
 	return PBR_OK;
 }
 
@@ -748,7 +653,7 @@ int packConfiguredWalk( pbr_ctx* ctx, const pbr_config& cfg, const SceneTree* tr
 
 // ---- the dealing orders of the banded queue: the device side (the orders themselves, and which one a call gets: pt_deal.hpp) ----
 int uploadTileOrder( pbr_ctx* ctx ) {
-	const DealTable& table = ctx->deal[kDealSpatial];
+	const DealTable& table = ctx->images.deal[kDealSpatial];
 	HIP_TRY( ctx, hipMemcpyAsync( table.dev, table.host.data(), sizeof( unsigned ) * table.host.size(), hipMemcpyHostToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // the source is pageable: do not let it change under the copy
 	return PBR_OK;
@@ -758,7 +663,7 @@ int uploadTileOrder( pbr_ctx* ctx ) {
 // there is no order yet or the camera has moved since it was learnt (then at most every 16th launch: an order learnt a few
 // frames ago is nearly as good, and the read-back is a synchronisation a frame-by-frame caller should not pay per frame).
 int learnTileCosts( pbr_ctx* ctx, const pbr_camera* cam, float pxDim ) {
-	if( ctx->orderPinned || ctx->knobs.dealOrder == 0 || ctx->deal[kDealCostClasses].dev == nullptr ) {
+	if( ctx->orderPinned || ctx->knobs.dealOrder == 0 || ctx->images.deal[kDealCostClasses].dev == nullptr ) {
 		return PBR_OK;
 	}
 
@@ -769,14 +674,14 @@ int learnTileCosts( pbr_ctx* ctx, const pbr_camera* cam, float pxDim ) {
 	}
 
 	const unsigned tiles = (unsigned) ctx->numLocalTiles;
-	hipLaunchKernelGGL( ptk::tileCosts, dim3( ( tiles + 3u ) / 4u ), dim3( 256 ), 0, ctx->stream, (const float4*) ctx->dImgDbg, ctx->dTileCost, tiles );
+	hipLaunchKernelGGL( ptk::tileCosts, dim3( ( tiles + 3u ) / 4u ), dim3( 256 ), 0, ctx->stream, (const float4*) ctx->images.dImgDbg, ctx->images.dTileCost, tiles );
 	HIP_TRY( ctx, hipGetLastError() );
 	ctx->hTileCost.resize( tiles );
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->hTileCost.data(), ctx->dTileCost, sizeof( float ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->hTileCost.data(), ctx->images.dTileCost, sizeof( float ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	std::vector<unsigned> spatial;
-	DealTable& classes = ctx->deal[kDealCostClasses];
-	DealTable& last = ctx->deal[kDealExpensiveLast];
+	DealTable& classes = ctx->images.deal[kDealCostClasses];
+	DealTable& last = ctx->images.deal[kDealExpensiveLast];
 	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &spatial, classes.first );
 	std::copy( classes.first, classes.first + PT_BANDS + 1, last.first );
 	costTileOrder( classes.first, PT_BANDS, spatial, ctx->hTileCost, &classes.host );
@@ -804,13 +709,13 @@ int sceneParams( pbr_ctx* ctx, DevParams* P, uint32_t* hotAvail = nullptr ) {
 	}
 
 	P->parkEighths = 4;
-	P->tris = ctx->dTris;
-	P->faceN = ctx->dFaceN;
-	P->mats = ctx->dMats;
-	P->lights = ctx->dLights;
+	P->tris = ctx->scene.dTris;
+	P->faceN = ctx->scene.dFaceN;
+	P->mats = ctx->scene.dMats;
+	P->lights = ctx->scene.dLights;
 	P->guard = ctx->dGuard;
-	P->numNodes = (int) ctx->numNodes;
-	P->numLights = (int) ctx->numLights;
+	P->numNodes = (int) ctx->scene.numNodes;
+	P->numLights = (int) ctx->scene.numLights;
 	return walk;
 }
 
@@ -865,7 +770,7 @@ struct PlanSpec {
 int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan, bool chained = false ) {
 	const Knobs& knobs = ctx->knobs;
 	const int flavour = flavourOf( ctx->cfg ) | ( chained ? PTI_CHAINED : 0 );
-	const bool lights = ( ctx->numLights > 0 );
+	const bool lights = ( ctx->scene.numLights > 0 );
 	const bool shadow = ( ctx->cfg.shadow_rays == 1 ) && lights;
 	const KernelFn kernel = pickKernel( flavour, spec.group, ctx->cfg.brdf, shadow, lights );
 
@@ -913,8 +818,8 @@ int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan,
 	plan->ldsBytes = slots * 32 + slotBytes;
 	plan->park = spec.park;
 	plan->shade = spec.shade;
-	plan->parkEighths = ( ctx->numNodes >= kWideMinNodes ) ? 4 : 6;   // see traverse(), pt_kernel.hpp
-	plan->refillBatch = ( knobs.refillBatch >= 1 ) ? std::min( 64, knobs.refillBatch ) : ( ( ctx->numNodes >= kWideMinNodes ) ? kRefillBatchLarge : kRefillBatchSmall );
+	plan->parkEighths = ( ctx->scene.numNodes >= kWideMinNodes ) ? 4 : 6;   // see traverse(), pt_kernel.hpp
+	plan->refillBatch = ( knobs.refillBatch >= 1 ) ? std::min( 64, knobs.refillBatch ) : ( ( ctx->scene.numNodes >= kWideMinNodes ) ? kRefillBatchLarge : kRefillBatchSmall );
 	// pathTracingPhased once lanes are DONE, 1: measured (single-frame 1080p launches): park share scaled, shade threshold as is:
 	// Dragon-class 2.99 -> 2.47 ms, hairball 4.26 -> 4.02 ms, Sponza- / Cornell-class unchanged; scaling the shade threshold too
 	// helps the first two further (2.26 / 3.56 ms) and costs the others 10 - 20 %
@@ -1019,22 +924,8 @@ int runPlan( pbr_ctx* ctx, const Plan& plan, DevParams* P, size_t waveUnits ) {
 // The caller's seeds go to the device through a pinned staging buffer: a copy from pageable memory is staged synchronously
 // by the runtime.
 int stageSeeds( pbr_ctx* ctx, const float* seeds, uint32_t nFrames ) {
-	if( ctx->seedCapacity < nFrames ) {
-		(void) hipFree( ctx->dSeeds );
-		ctx->dSeeds = nullptr;
-		ctx->seedCapacity = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dSeeds, sizeof( float ) * nFrames ) );
-		ctx->seedCapacity = nFrames;
-	}
-
-	if( ctx->hSeedCapacity < nFrames ) {
-		(void) hipHostFree( ctx->hSeeds );
-		ctx->hSeeds = nullptr;
-		ctx->hSeedCapacity = 0;
-		HIP_TRY( ctx, hipHostMalloc( (void**) &ctx->hSeeds, sizeof( float ) * std::max<size_t>( nFrames, 64 ), hipHostMallocDefault ) );
-		ctx->hSeedCapacity = std::max<size_t>( nFrames, 64 );
-	}
-
+	HIP_TRY( ctx, ctx->dSeeds.grow( nFrames ) );
+	HIP_TRY( ctx, ctx->hSeeds.grow( std::max<size_t>( nFrames, 64 ) ) );
 	std::memcpy( ctx->hSeeds, seeds, sizeof( float ) * nFrames );
 	HIP_TRY( ctx, hipMemcpyAsync( ctx->dSeeds, ctx->hSeeds, sizeof( float ) * nFrames, hipMemcpyHostToDevice, ctx->stream ) );
 	return PBR_OK;
@@ -1060,17 +951,13 @@ int growFrameBuf( pbr_ctx* ctx, uint32_t nFrames, size_t* chunkCap ) {
 
 	*chunkCap = cap;
 
-	if( ctx->frameBufFrames < cap ) {
+	if( ctx->images.dFrameBuf.count() < pixelSlots * cap ) {
 		// grown geometrically, never beyond the cap: at least 256 frames, then twice what is asked for.  A longer render
 		// after a shorter one must not pay for a multi-GB reallocation inside every call (measured: 432 -> 512 frames at
 		// 1080p, hipFree + hipMalloc of 16 GiB = 0.4 - 0.7 s when the pages have had other owners), and a small image must
 		// not take 16 GiB because one render was longer than 256 frames (64 x 64 pixels, 300 frames: 39 MB).
 		const size_t frames = std::min<size_t>( capFrames, std::max<size_t>( 256, ( cap <= 256 ) ? cap : 2 * cap ) );
-		(void) hipFree( ctx->dFrameBuf );
-		ctx->dFrameBuf = nullptr;
-		ctx->frameBufFrames = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFrameBuf, frameBytes * frames ) );
-		ctx->frameBufFrames = frames;
+		HIP_TRY( ctx, ctx->images.dFrameBuf.grow( pixelSlots * frames ) );
 	}
 
 	return PBR_OK;
@@ -1091,7 +978,7 @@ void pointAtTable( DevParams* P, const unsigned* order, const unsigned* first ) 
 const DealTable& dealOrder( pbr_ctx* ctx, size_t tiles, uint32_t frames, bool settled ) {
 	const DealOrder dealt = dealRule( ctx->orderPinned, ctx->costLearnt, ctx->knobs.dealOrder, settled, ctx->cfg.tile_world > 1u, tiles, frames );
 	std::snprintf( ctx->lastDeal, sizeof( ctx->lastDeal ), "%s", dealName( ctx->orderPinned, dealt ) );
-	return ctx->deal[dealt];
+	return ctx->images.deal[dealt];
 }
 
 // [1] the path loop (or a record slot of the asynchronous node phase that never filled), [2] a traversal that took more
@@ -1127,14 +1014,10 @@ int runFocusChain( pbr_ctx* ctx, DevParams* P, const float4* prev, bool first ) 
 		return fail( ctx, PBR_EINVAL, "focus chain: %zu pixel slots x %zu frames do not fit a 32-bit table index", pixelSlots, n );
 	}
 
-	if( ctx->chainFloats < floats ) {
+	if( ctx->images.dChain.count() < floats ) {
 		// grown like the frame buffer whose quarter it is: at least 64 frames' worth, then twice what is asked for
 		const size_t want = std::max<size_t>( ( pixelSlots + 1 ) * 64, ( n <= 64 ) ? floats : 2 * floats );
-		(void) hipFree( ctx->dChain );
-		ctx->dChain = nullptr;
-		ctx->chainFloats = 0;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChain, sizeof( float ) * want ) );
-		ctx->chainFloats = want;
+		HIP_TRY( ctx, ctx->images.dChain.grow( want ) );
 	}
 
 	// The main launch reads a pixel's 64 frames per wave (nextSlot), the chain writes a frame's 64 pixels per wave: layout 1
@@ -1143,7 +1026,7 @@ int runFocusChain( pbr_ctx* ctx, DevParams* P, const float4* prev, bool first ) 
 	// frames in 116.8 ms against 121.1 ms (the chain alone 11.3 against 13.3 ms), the Sponza-class scene's 64 frames within
 	// the spread of each other (chain 17.1 against 18.0 ms) — layout 0 it is.
 	const bool slotMajor = ( ctx->knobs.chainLayout == 1 );
-	P->chain = ctx->dChain;
+	P->chain = ctx->images.dChain;
 	P->chainSlotStride = slotMajor ? (unsigned) n : 1u;
 	P->chainFrameStride = slotMajor ? 1u : (unsigned) pixelSlots;
 	P->chainFocusAt = (unsigned) ( pixelSlots * n );
@@ -1155,14 +1038,14 @@ int runFocusChain( pbr_ctx* ctx, DevParams* P, const float4* prev, bool first ) 
 		return fail( ctx, PBR_ESTATE, "this library was built without the focus chain of flavour %d", flavour );
 	}
 
-	const int lights = ( ctx->numLights > 0 ) ? 1 : 0;
+	const int lights = ( ctx->scene.numLights > 0 ) ? 1 : 0;
 	const ChainPixelFn pixelKernel = (ChainPixelFn) pick( 0, 0, lights );
 	const ChainSlotsFn slotsKernel = (ChainSlotsFn) pick( 1, 0, lights );
 	DevParams C = *P;
-	C.parkEighths = ( ctx->numNodes >= kWideMinNodes ) ? 4 : 6;
-	hipLaunchKernelGGL( pixelKernel, dim3( 1 ), dim3( 64 ), 0, ctx->stream, C, prev, ctx->dChain, ctx->dChainCarry, first ? 0 : 1 );
+	C.parkEighths = ( ctx->scene.numNodes >= kWideMinNodes ) ? 4 : 6;
+	hipLaunchKernelGGL( pixelKernel, dim3( 1 ), dim3( 64 ), 0, ctx->stream, C, prev, ctx->images.dChain, ctx->dChainCarry, first ? 0 : 1 );
 	HIP_TRY( ctx, hipGetLastError() );
-	hipLaunchKernelGGL( slotsKernel, dim3( (unsigned) ( ( pixelSlots + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream, C, prev, ctx->dChain );
+	hipLaunchKernelGGL( slotsKernel, dim3( (unsigned) ( ( pixelSlots + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream, C, prev, ctx->images.dChain );
 	HIP_TRY( ctx, hipGetLastError() );
 	return PBR_OK;
 }
@@ -1189,11 +1072,11 @@ int beginRender( pbr_ctx* ctx, const float* seeds, uint32_t nSeeds, const pbr_ca
 
 	DevParams& P = *out;
 	PBR_TRY( sceneParams( ctx, &P, hotAvail ) );   // P.nodes, P.firstRef / walkFirst for the configured traversal
-	P.triPN = ctx->dTriPN;
+	P.triPN = ctx->scene.dTriPN;
 	P.phongAlpha = ctx->cfg.phong_tessellation;
-	P.imgIn = ctx->dImgIn;
-	P.imgOut = ctx->dImgOut;
-	P.imgDbg = ctx->dImgDbg;
+	P.imgIn = ctx->images.dImgIn;
+	P.imgOut = ctx->images.dImgOut;
+	P.imgDbg = ctx->images.dImgDbg;
 	P.counters = ctx->dCounters;
 	P.workCounter = ctx->dWork;
 	setCamera( &P, cam, (int) ctx->cfg.width, (int) ctx->cfg.height, pxDim );
@@ -1241,8 +1124,8 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	if( cam == nullptr || seeds == nullptr || nFrames == 0 ) {
 		return fail( ctx, PBR_EINVAL, "render: null camera / seeds or zero frames" );
 	}
-	if( ctx->cfg.brdf != ctx->sceneBrdf ) {
-		return fail( ctx, PBR_EINVAL, "configured BRDF %u does not match the uploaded materials (BRDF %u)", ctx->cfg.brdf, ctx->sceneBrdf );
+	if( ctx->cfg.brdf != ctx->scene.sceneBrdf ) {
+		return fail( ctx, PBR_EINVAL, "configured BRDF %u does not match the uploaded materials (BRDF %u)", ctx->cfg.brdf, ctx->scene.sceneBrdf );
 	}
 
 	const bool dof = ( cam->focusPoint[0] >= 0 && cam->focusPoint[1] >= 0 );
@@ -1270,7 +1153,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	if( phong && chain ) {
 		return fail( ctx, PBR_EINVAL, "pbr_render_dof does not render Phong tessellation with a focus point (its plan has an intersection of its own); call pbr_render_frame + pbr_accumulate per frame" );
 	}
-	if( phong && ctx->dTriPN == nullptr ) {
+	if( phong && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs a scene with usable vertex normals" );
 	}
 
@@ -1284,7 +1167,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 	const Plan* forced = phong ? &ctx->phongPlan : ( ctx->pinnedPlan >= 0 ) ? &plans[std::min( ScheduleTuner::kPlans - 1, ctx->pinnedPlan )] : nullptr;
 	const DealTable& table = dealOrder( ctx, (size_t) ctx->numLocalTiles, nFrames, forced != nullptr || ctx->tuner.settled() );
 	pointAtTable( &P, table.dev, table.first );
-	P.frameBuf = ctx->dFrameBuf;
+	P.frameBuf = ctx->images.dFrameBuf;
 	const size_t pixelSlots = (size_t) ctx->numLocalTiles * 64;
 	P.frameStride = (unsigned) pixelSlots;
 	const unsigned foldBlocks = (unsigned) ( ( pixelSlots + 255 ) / 256 );
@@ -1306,7 +1189,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		if( chain ) {
 			// imageIn.w before the first launch, the last fold's .w — the previous launch's last first-hit distances — after it
 			HIP_TRY( ctx, hipEventRecord( ctx->evChainStart, ctx->stream ) );
-			PBR_TRY( runFocusChain( ctx, &P, done == 0 ? ctx->dImgIn : ctx->dImgOut, done == 0 ) );
+			PBR_TRY( runFocusChain( ctx, &P, done == 0 ? ctx->images.dImgIn : ctx->images.dImgOut, done == 0 ) );
 		}
 
 		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStart, ctx->stream ) );
@@ -1314,7 +1197,7 @@ int launch( pbr_ctx* ctx, uint32_t firstCount, uint32_t nFrames, const float* se
 		HIP_TRY( ctx, hipEventRecord( ctx->evTraceStop, ctx->stream ) );
 		// the running mean so far: the input image for the first chunk, imageOut after that
 		hipLaunchKernelGGL( ptk::foldFrames, dim3( foldBlocks ), dim3( 256 ), 0, ctx->stream, P,
-			(const float4*) ( done == 0 ? ctx->dImgIn : ctx->dImgOut ), ctx->dImgOut );
+			(const float4*) ( done == 0 ? ctx->images.dImgIn : ctx->images.dImgOut ), ctx->images.dImgOut );
 		HIP_TRY( ctx, hipGetLastError() );
 		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // one chunk for all but very long renders
 
@@ -1357,13 +1240,13 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 	if( !ctx->hasScene || !ctx->configured ) {
 		return fail( ctx, PBR_ESTATE, "render before pbr_upload_scene / pbr_configure" );
 	}
-	if( ctx->cfg.brdf != ctx->sceneBrdf ) {
-		return fail( ctx, PBR_EINVAL, "configured BRDF %u does not match the uploaded materials (BRDF %u)", ctx->cfg.brdf, ctx->sceneBrdf );
+	if( ctx->cfg.brdf != ctx->scene.sceneBrdf ) {
+		return fail( ctx, PBR_EINVAL, "configured BRDF %u does not match the uploaded materials (BRDF %u)", ctx->cfg.brdf, ctx->scene.sceneBrdf );
 	}
 
 	const bool phong = ( ctx->cfg.phong_tessellation > 0.0f );
 
-	if( phong && ctx->dTriPN == nullptr ) {
+	if( phong && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs a scene with usable vertex normals" );
 	}
 
@@ -1371,12 +1254,11 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 	const size_t tiles = (size_t) ctx->numLocalTiles;
 	const size_t pixelSlots = tiles * 64;
 
-	if( ctx->dMoments == nullptr ) {
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileFrames, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileError, sizeof( float ) * std::max<size_t>( 1, tiles ) ) );
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileActive, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dAdaptiveOrder, sizeof( unsigned ) * std::max<size_t>( 1, tiles ) ) );
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dMoments, sizeof( float2 ) * std::max<size_t>( 1, pixelSlots ) ) );
+	if( ctx->images.dMoments == nullptr ) {
+		Images& I = ctx->images;
+		const size_t perTile = std::max<size_t>( 1, tiles );
+		HIP_TRY( ctx, allocAll( { want( I.dTileFrames, perTile ), want( I.dTileError, perTile ), want( I.dTileActive, perTile ), want( I.dAdaptiveOrder, perTile ),
+		                          want( I.dMoments, std::max<size_t>( 1, pixelSlots ) ) } ) );
 	}
 
 	ctx->adaptiveStats = false;
@@ -1401,7 +1283,7 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 	std::snprintf( ctx->lastPlan, sizeof( ctx->lastPlan ), "%s", plan.name );
 	std::snprintf( ctx->lastKernel, sizeof( ctx->lastKernel ), "%s", plan.kernelName );
 
-	P.frameBuf = ctx->dFrameBuf;
+	P.frameBuf = ctx->images.dFrameBuf;
 	P.frameStride = (unsigned) pixelSlots;
 
 	const std::vector<AdaptivePair> pairs = adaptiveSchedule( A.min_frames, A.round_frames, A.max_frames, (uint32_t) chunkCap );
@@ -1438,9 +1320,9 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 			}
 			else {
 				filterOrder( table.host, table.first, active.data(), PT_BANDS, &order, first );
-				HIP_TRY( ctx, hipMemcpyAsync( ctx->dAdaptiveOrder, order.data(), sizeof( unsigned ) * order.size(), hipMemcpyHostToDevice, ctx->stream ) );
+				HIP_TRY( ctx, hipMemcpyAsync( ctx->images.dAdaptiveOrder, order.data(), sizeof( unsigned ) * order.size(), hipMemcpyHostToDevice, ctx->stream ) );
 				HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );   // the source is pageable
-				dTable = ctx->dAdaptiveOrder;
+				dTable = ctx->images.dAdaptiveOrder;
 			}
 
 			if( (size_t) first[PT_BANDS] != activeTiles ) {
@@ -1463,13 +1345,13 @@ int launchAdaptive( pbr_ctx* ctx, uint32_t firstCount, const float* seeds, float
 		// the running mean so far: the input image for the first pair (every tile is in it), imageOut after that
 		HIP_TRY( ctx, hipEventRecord( ctx->evFoldStart, ctx->stream ) );
 		hipLaunchKernelGGL( ptk::foldFramesAdaptive, dim3( (unsigned) ( ( activeTiles + 3 ) / 4 ) ), dim3( 256 ), 0, ctx->stream, P,
-			(const float4*) ( pair.first == 0 ? ctx->dImgIn : ctx->dImgOut ), ctx->dImgOut, dTable, (unsigned) activeTiles,
-			ctx->dMoments, pair.first, pair.endsRound ? 1 : 0, A.threshold, ctx->dTileFrames, ctx->dTileError, ctx->dTileActive );
+			(const float4*) ( pair.first == 0 ? ctx->images.dImgIn : ctx->images.dImgOut ), ctx->images.dImgOut, dTable, (unsigned) activeTiles,
+			ctx->images.dMoments, pair.first, pair.endsRound ? 1 : 0, A.threshold, ctx->images.dTileFrames, ctx->images.dTileError, ctx->images.dTileActive );
 		HIP_TRY( ctx, hipGetLastError() );
 		HIP_TRY( ctx, hipEventRecord( ctx->evFoldStop, ctx->stream ) );
 
 		if( pair.endsRound ) {
-			HIP_TRY( ctx, hipMemcpyAsync( active.data(), ctx->dTileActive, sizeof( unsigned ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
+			HIP_TRY( ctx, hipMemcpyAsync( active.data(), ctx->images.dTileActive, sizeof( unsigned ) * tiles, hipMemcpyDeviceToHost, ctx->stream ) );
 		}
 
 		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
@@ -1511,10 +1393,10 @@ int readTiled( pbr_ctx* ctx, const float4* tiles, float* rgba, int tileWorld, in
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	hipLaunchKernelGGL( ptk::untile, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, tiles, ctx->dRows,
+	hipLaunchKernelGGL( ptk::untile, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, tiles, ctx->images.dRows,
 		(int) ctx->cfg.width, (int) ctx->cfg.height, ctx->tilesX, tileWorld, tileRank );
 	HIP_TRY( ctx, hipGetLastError() );
-	HIP_TRY( ctx, hipMemcpyAsync( rgba, ctx->dRows, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( rgba, ctx->images.dRows, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -1574,23 +1456,16 @@ int pbr_create( int device, pbr_ctx** out ) {
 	hipDeviceProp_t prop;
 	HIP_TRY( ctx, hipGetDeviceProperties( &prop, device ) );
 	ctx->numCUs = prop.multiProcessorCount;
-	HIP_TRY( ctx, hipStreamCreateWithFlags( &ctx->stream, hipStreamNonBlocking ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evTraceStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evTraceStop ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evStop ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evChainStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evFoldStop ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evRelinkStop ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evXfStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evXfStop ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evXfNormalsStart ) );
-	HIP_TRY( ctx, hipEventCreate( &ctx->evXfNormalsStop ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dChainCarry, sizeof( float ) ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dCounters, sizeof( unsigned long long ) * kCounterSlots ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dWork, kWorkBytes ) );
+	HIP_TRY( ctx, hipStreamCreateWithFlags( &ctx->stream.s, hipStreamNonBlocking ) );
+
+	for( Event* event : { &ctx->evStart, &ctx->evTraceStart, &ctx->evTraceStop, &ctx->evStop, &ctx->evChainStart, &ctx->evFoldStart, &ctx->evFoldStop,
+	                      &ctx->evRelinkStart, &ctx->evRelinkStop, &ctx->evXfStart, &ctx->evXfStop, &ctx->evXfNormalsStart, &ctx->evXfNormalsStop } ) {
+		HIP_TRY( ctx, hipEventCreate( &event->e ) );
+	}
+
+	HIP_TRY( ctx, ctx->dChainCarry.alloc( 1 ) );
+	HIP_TRY( ctx, ctx->dCounters.alloc( kCounterSlots ) );
+	HIP_TRY( ctx, ctx->dWork.alloc( kWorkBytes / sizeof( unsigned int ) ) );
 	// host-visible so that it can be read while a kernel is still running
 	HIP_TRY( ctx, hipHostMalloc( (void**) &ctx->dGuard, sizeof( unsigned int ) * 4, hipHostMallocMapped ) );
 	std::memset( ctx->dGuard, 0, sizeof( unsigned int ) * 4 );
@@ -1607,30 +1482,10 @@ void pbr_destroy( pbr_ctx* ctx ) {
 	if( ctx->stream != nullptr ) {
 		(void) hipSetDevice( ctx->device );
 		(void) hipStreamSynchronize( ctx->stream );
-		freeScene( ctx );
-		freeImages( ctx );
-		(void) hipFree( ctx->dSeeds );
-		(void) hipHostFree( ctx->hSeeds );
-		(void) hipFree( ctx->dCounters );
-		(void) hipFree( ctx->dWork );
 		(void) hipHostFree( ctx->dGuard );
-		(void) hipEventDestroy( ctx->evStart );
-		(void) hipEventDestroy( ctx->evTraceStart );
-		(void) hipEventDestroy( ctx->evTraceStop );
-		(void) hipEventDestroy( ctx->evStop );
-		(void) hipEventDestroy( ctx->evChainStart );
-		(void) hipEventDestroy( ctx->evFoldStart );
-		(void) hipEventDestroy( ctx->evFoldStop );
-		(void) hipEventDestroy( ctx->evRelinkStart );
-		(void) hipEventDestroy( ctx->evRelinkStop );
-		(void) hipEventDestroy( ctx->evXfStart );
-		(void) hipEventDestroy( ctx->evXfStop );
-		(void) hipEventDestroy( ctx->evXfNormalsStart );
-		(void) hipEventDestroy( ctx->evXfNormalsStop );
-		(void) hipFree( ctx->dChainCarry );
-		(void) hipStreamDestroy( ctx->stream );
 	}
 
+	// the buffers, then the events, then the stream: the order the context declares them in, backwards
 	delete ctx;
 }
 
@@ -1672,91 +1527,83 @@ int pbr_upload_scene( pbr_ctx* ctx, const pbr_scene_desc* s ) {
 	freeScene( ctx );
 	ctx->temporal.drop();   // pbr_denoise_temporal: the history's features are the old scene's
 
-	auto toDevice = [ctx]( float4** dst, const std::vector<Quad>& src ) {
-		HIP_TRY( ctx, hipMalloc( (void**) dst, sizeof( Quad ) * src.size() ) );
-		HIP_TRY( ctx, hipMemcpy( *dst, src.data(), sizeof( Quad ) * src.size(), hipMemcpyHostToDevice ) );
+	auto toDevice = [ctx]( Owned<float4>* dst, const std::vector<Quad>& src ) {
+		HIP_TRY( ctx, dst->alloc( src.size() ) );
+		HIP_TRY( ctx, hipMemcpy( dst->get(), src.data(), sizeof( Quad ) * src.size(), hipMemcpyHostToDevice ) );
 		return PBR_OK;
 	};
 
-	PBR_TRY( toDevice( &ctx->dNodes, packed.nodes.storage ) );
-	PBR_TRY( toDevice( &ctx->dTris, packed.tris ) );
+	PBR_TRY( toDevice( &ctx->scene.dNodes, packed.nodes.storage ) );
+	PBR_TRY( toDevice( &ctx->scene.dTris, packed.tris ) );
 
 	if( !packed.triPN.empty() ) {
-		PBR_TRY( toDevice( &ctx->dTriPN, packed.triPN ) );
+		PBR_TRY( toDevice( &ctx->scene.dTriPN, packed.triPN ) );
 		// pbr_update_geometry gathers the patches again: the indices and the normals wait on the host for its first call
-		ctx->patchFacesN.assign( s->facesN, s->facesN + s->num_faces );
-		ctx->patchNormals.assign( s->normals, s->normals + s->num_normals );
+		ctx->scene.patchFacesN.assign( s->facesN, s->facesN + s->num_faces );
+		ctx->scene.patchNormals.assign( s->normals, s->normals + s->num_normals );
 	}
 
-	ctx->numNormals = s->num_normals;
+	ctx->scene.numNormals = s->num_normals;
 
-	PBR_TRY( toDevice( &ctx->dMats, packed.mats ) );
-	PBR_TRY( toDevice( &ctx->dLights, packed.lights ) );
-	ctx->nodeBytes = sizeof( Quad ) * packed.nodes.storage.size();
-	ctx->triBytes = sizeof( Quad ) * packed.tris.size();
+	PBR_TRY( toDevice( &ctx->scene.dMats, packed.mats ) );
+	PBR_TRY( toDevice( &ctx->scene.dLights, packed.lights ) );
 
 	// the face normals the shading would recompute on every hit, evaluated once by the shading's own device function
 	if( s->num_faces > 0 && ctx->knobs.faceNormals != 0 ) {
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFaceN, sizeof( float4 ) * s->num_faces ) );
+		HIP_TRY( ctx, ctx->scene.dFaceN.alloc( s->num_faces ) );
 		DevParams P;
 		std::memset( &P, 0, sizeof( P ) );
-		P.tris = ctx->dTris;
-		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( s->num_faces + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->dFaceN, (int) s->num_faces );
+		P.tris = ctx->scene.dTris;
+		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( s->num_faces + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->scene.dFaceN, (int) s->num_faces );
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
-	// what pbr_update_vertices needs on the device
-	ctx->refitBytes = 0;
+	// what pbr_update_vertices needs on the device (its bytes: Scene::refitBytes)
+	auto keep = [ctx]( auto* dst, const void* src, size_t count ) {
+		HIP_TRY( ctx, dst->alloc( count ) );
+
+		if( src != nullptr && count > 0 ) {
+			HIP_TRY( ctx, hipMemcpy( dst->get(), src, dst->bytes(), hipMemcpyHostToDevice ) );
+		}
+
+		return PBR_OK;
+	};
+	Scene& S = ctx->scene;
+	PBR_TRY( keep( &S.dVertices, s->vertices, s->num_vertices ) );   // the positions a first update's motion starts from; pbr_read_geometry's, refit or not
 
 	if( refit.nested ) {
-		auto keep = [ctx]( void** dst, const void* src, size_t bytes ) {
-			HIP_TRY( ctx, hipMalloc( dst, std::max<size_t>( bytes, 16 ) ) );
-
-			if( src != nullptr && bytes > 0 ) {
-				HIP_TRY( ctx, hipMemcpy( *dst, src, bytes, hipMemcpyHostToDevice ) );
-			}
-
-			ctx->refitBytes += bytes;
-			return PBR_OK;
-		};
 		const Quad rootBox[2] = { { s->bvh[0].bbMin.x, s->bvh[0].bbMin.y, s->bvh[0].bbMin.z, -1.0f }, { s->bvh[0].bbMax.x, s->bvh[0].bbMax.y, s->bvh[0].bbMax.z, -1.0f } };
-		PBR_TRY( keep( (void**) &ctx->dFacesV, s->facesV, sizeof( pbr_uint4 ) * s->num_faces ) );
-		PBR_TRY( keep( (void**) &ctx->dVertices, s->vertices, sizeof( pbr_float4 ) * s->num_vertices ) );   // the positions a first update's motion starts from
-		PBR_TRY( keep( (void**) &ctx->dRootBox, rootBox, sizeof( rootBox ) ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitSlots, refit.slots.data(), sizeof( uint32_t ) * refit.slots.size() ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitInfo, refit.info.data(), sizeof( uint32_t ) * refit.info.size() ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitHeights, refit.height16.data(), sizeof( uint16_t ) * refit.height16.size() ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitRecordOf, refit.recordOf.data(), sizeof( int ) * refit.recordOf.size() ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitTop, refit.topNodes.data(), sizeof( uint32_t ) * refit.topNodes.size() ) );
-		PBR_TRY( keep( (void**) &ctx->dRefitLevelFirst, refit.topLevelFirst.data(), sizeof( uint32_t ) * refit.topLevelFirst.size() ) );
-	}
-	else {
-		// no refit, but pbr_read_geometry still answers: the positions alone, outside refitBytes
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dVertices, std::max<size_t>( sizeof( pbr_float4 ) * s->num_vertices, 16 ) ) );
-		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, s->vertices, sizeof( pbr_float4 ) * s->num_vertices, hipMemcpyHostToDevice ) );
+		PBR_TRY( keep( &S.dFacesV, s->facesV, s->num_faces ) );
+		PBR_TRY( keep( &S.dRootBox, rootBox, 2 ) );
+		PBR_TRY( keep( &S.dRefitSlots, refit.slots.data(), refit.slots.size() ) );
+		PBR_TRY( keep( &S.dRefitInfo, refit.info.data(), refit.info.size() ) );
+		PBR_TRY( keep( &S.dRefitHeights, refit.height16.data(), refit.height16.size() ) );
+		PBR_TRY( keep( &S.dRefitRecordOf, refit.recordOf.data(), refit.recordOf.size() ) );
+		PBR_TRY( keep( &S.dRefitTop, refit.topNodes.data(), refit.topNodes.size() ) );
+		PBR_TRY( keep( &S.dRefitLevelFirst, refit.topLevelFirst.data(), refit.topLevelFirst.size() ) );
 	}
 
-	ctx->refitGroups = refit.numGroups();
-	ctx->refitLevels = refit.numLevels();
-	ctx->refitTopNodes = (uint32_t) refit.topNodes.size();
-	ctx->refitSubtrees = (uint32_t) refit.subtreeRoots.size();
-	ctx->numVertices = s->num_vertices;
+	S.refitGroups = refit.numGroups();
+	S.refitLevels = refit.numLevels();
+	S.refitTopNodes = (uint32_t) refit.topNodes.size();
+	S.refitSubtrees = (uint32_t) refit.subtreeRoots.size();
+	S.numVertices = s->num_vertices;
 	// the host keeps the verdict and node -> record; the rest is on the device now
 	for( std::vector<uint32_t>* v : { &refit.parent, &refit.end, &refit.height, &refit.subtreeRoots, &refit.groupFirst, &refit.slots, &refit.topNodes, &refit.topLevelFirst, &refit.info } ) {
 		std::vector<uint32_t>().swap( *v );
 	}
 	std::vector<uint16_t>().swap( refit.height16 );
-	ctx->refit = std::move( refit );
+	ctx->scene.refit = std::move( refit );
 
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	ctx->numHotAvail = packed.nodes.hotSlots;
-	ctx->firstRef = packed.nodes.first[0];
-	ctx->tree = std::move( tree );
-	ctx->numNodes = s->num_nodes;
-	ctx->numFaces = s->num_faces;
-	ctx->numMaterials = s->num_materials;
-	ctx->numLights = s->num_lights;
-	ctx->sceneBrdf = s->brdf;
+	ctx->scene.numHotAvail = packed.nodes.hotSlots;
+	ctx->scene.firstRef = packed.nodes.first[0];
+	ctx->scene.tree = std::move( tree );
+	ctx->scene.numNodes = s->num_nodes;
+	ctx->scene.numFaces = s->num_faces;
+	ctx->scene.numMaterials = s->num_materials;
+	ctx->scene.numLights = s->num_lights;
+	ctx->scene.sceneBrdf = s->brdf;
 	replan( ctx );   // a new scene / configuration is tuned afresh
 	ctx->hasScene = true;
 
@@ -1769,17 +1616,17 @@ namespace {
 // its shape and the ranking of the upload; the boxes are not read — on the first re-linked update after the streams were built,
 // kept until the streams go.  Nothing of the context changes when this fails.
 int ensureRelinkTables( pbr_ctx* ctx ) {
-	if( ctx->dRelink != nullptr ) {
+	if( ctx->scene.walk.dRelink != nullptr ) {
 		return PBR_OK;
 	}
 
 	RefitPlan shape;
 	RelinkTables t;
-	refitNesting( ctx->tree, &shape );
-	PBR_TRY( relinkTables( ctx->tree, shape, ctx->walkBuilt, &t, &ctx->error ) );
+	refitNesting( ctx->scene.tree, &shape );
+	PBR_TRY( relinkTables( ctx->scene.tree, shape, ctx->scene.walk.walkBuilt, &t, &ctx->error ) );
 
-	if( sizeof( Quad ) * t.storageQuads != ctx->walkBytes ) {
-		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the re-link expects %zu bytes of records, the streams hold %llu", sizeof( Quad ) * t.storageQuads, (unsigned long long) ctx->walkBytes );
+	if( sizeof( Quad ) * t.storageQuads != ctx->scene.walk.dNodesWalk.bytes() ) {
+		return fail( ctx, PBR_ESTATE, "pbr_update_vertices: the re-link expects %zu bytes of records, the streams hold %llu", sizeof( Quad ) * t.storageQuads, (unsigned long long) ctx->scene.walk.dNodesWalk.bytes() );
 	}
 
 	// one allocation, every table on a 256-byte boundary
@@ -1795,8 +1642,9 @@ int ensureRelinkTables( pbr_ctx* ctx ) {
 	const size_t atAxis = place( N ), atPerm = place( sizeof( uint32_t ) * t.permEntries() );
 	const size_t atNext = place( sizeof( int ) * t.nextEntries() ), atPos = place( sizeof( uint32_t ) * t.posEntries() );
 
-	char* slab = nullptr;
-	HIP_TRY( ctx, hipMalloc( (void**) &slab, bytes ) );
+	Owned<unsigned char> owner;
+	HIP_TRY( ctx, owner.alloc( bytes ) );
+	unsigned char* const slab = owner.get();
 	hipError_t err = hipMemset( slab, 0, bytes );
 	auto put = [&]( size_t at, const std::vector<uint32_t>& src ) {
 		err = ( err != hipSuccess ) ? err : hipMemcpy( slab + at, src.data(), sizeof( uint32_t ) * src.size(), hipMemcpyHostToDevice );
@@ -1809,11 +1657,10 @@ int ensureRelinkTables( pbr_ctx* ctx ) {
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();   // the memset ran on the null stream; launches use ctx->stream
 
 	if( err != hipSuccess ) {
-		(void) hipFree( slab );
 		return fail( ctx, PBR_EDEVICE, "pbr_update_vertices: the re-link's tables: %s", hipGetErrorString( err ) );
 	}
 
-	RelinkView& v = ctx->relinkView;
+	RelinkView& v = ctx->scene.walk.relinkView;
 	v.N = t.N;
 	v.scheme = t.scheme;
 	v.compact = t.compact;
@@ -1828,34 +1675,33 @@ int ensureRelinkTables( pbr_ctx* ctx ) {
 	v.perm = (uint32_t*) ( slab + atPerm );
 	v.next = (int*) ( slab + atNext );
 	v.pos = (uint32_t*) ( slab + atPos );
-	ctx->dRelinkLevelNodes = (unsigned*) ( slab + atNodes );
-	ctx->dRelinkLevelFirst = (unsigned*) ( slab + atFirst );
-	ctx->relinkRuns = t.runs;
-	ctx->relinkLevels = t.numLevels();
-	ctx->relinkContainers = (uint32_t) t.levelNodes.size();
-	ctx->relinkBytes = bytes;
-	ctx->dRelink = slab;
+	ctx->scene.walk.dRelinkLevelNodes = (unsigned*) ( slab + atNodes );
+	ctx->scene.walk.dRelinkLevelFirst = (unsigned*) ( slab + atFirst );
+	ctx->scene.walk.relinkRuns = t.runs;
+	ctx->scene.walk.relinkLevels = t.numLevels();
+	ctx->scene.walk.relinkContainers = (uint32_t) t.levelNodes.size();
+	ctx->scene.walk.dRelink = std::move( owner );
 	return PBR_OK;
 }
 
 // The re-link's launches on the context's stream, behind the refit's: sort, the levels top-down, the records.
 int launchRelink( pbr_ctx* ctx ) {
-	RelinkView v = ctx->relinkView;
-	v.refNodes = (const RelinkQuad*) ctx->dNodes;
-	v.refRecordOf = ctx->dRefitRecordOf;
-	v.info = ctx->dRefitInfo;
-	v.header = (int*) ctx->dNodesWalk;
-	v.records = (RelinkQuad*) ( ctx->dNodesWalk + 2 );
+	RelinkView v = ctx->scene.walk.relinkView;
+	v.refNodes = (const RelinkQuad*) ctx->scene.dNodes.get();
+	v.refRecordOf = ctx->scene.dRefitRecordOf;
+	v.info = ctx->scene.dRefitInfo;
+	v.header = (int*) ctx->scene.walk.dNodesWalk.get();
+	v.records = (RelinkQuad*) ( ctx->scene.walk.dNodesWalk + 2 );
 	uint32_t launches = 0;
 	HIP_TRY( ctx, hipEventRecord( ctx->evRelinkStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptl::relinkSortKernel, dim3( ( ctx->relinkContainers + RELINK_THREADS - 1 ) / RELINK_THREADS ), dim3( RELINK_THREADS ), 0, ctx->stream,
-	                    v, ctx->dRelinkLevelNodes, ctx->relinkContainers );
+	hipLaunchKernelGGL( ptl::relinkSortKernel, dim3( ( ctx->scene.walk.relinkContainers + RELINK_THREADS - 1 ) / RELINK_THREADS ), dim3( RELINK_THREADS ), 0, ctx->stream,
+	                    v, ctx->scene.walk.dRelinkLevelNodes, ctx->scene.walk.relinkContainers );
 	HIP_TRY( ctx, hipGetLastError() );
 	launches++;
 
-	for( const RelinkRun& run : ctx->relinkRuns ) {
+	for( const RelinkRun& run : ctx->scene.walk.relinkRuns ) {
 		hipLaunchKernelGGL( ptl::relinkLevelsKernel, dim3( run.blocks ), dim3( run.threads ), 0, ctx->stream,
-		                    v, ctx->dRelinkLevelNodes, ctx->dRelinkLevelFirst, run.firstLevel, run.numLevels );
+		                    v, ctx->scene.walk.dRelinkLevelNodes, ctx->scene.walk.dRelinkLevelFirst, run.firstLevel, run.numLevels );
 		HIP_TRY( ctx, hipGetLastError() );
 		launches++;
 	}
@@ -1883,34 +1729,27 @@ namespace {
 // the faces' normal indices, the vertex normals, and the scratch table of the faces' thick boxes.  Nothing of the context
 // changes when this fails.
 int ensurePatchTables( pbr_ctx* ctx ) {
-	if( ctx->dFaceBoxes != nullptr ) {
+	if( ctx->scene.dFaceBoxes != nullptr ) {
 		return PBR_OK;
 	}
 
-	const size_t indexBytes = sizeof( pbr_uint4 ) * ctx->patchFacesN.size(), normalBytes = sizeof( pbr_float4 ) * ctx->patchNormals.size();
-	const size_t boxBytes = sizeof( float ) * 6 * (size_t) ctx->numFaces;
-	uint4* indices = nullptr;
-	float4* normals = nullptr;
-	float2* boxes = nullptr;
-	hipError_t err = hipMalloc( (void**) &indices, std::max<size_t>( indexBytes, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &normals, std::max<size_t>( normalBytes, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &boxes, std::max<size_t>( boxBytes, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( indices, ctx->patchFacesN.data(), indexBytes, hipMemcpyHostToDevice );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( normals, ctx->patchNormals.data(), normalBytes, hipMemcpyHostToDevice );
+	Scene& S = ctx->scene;
+	Owned<uint4> indices;
+	Owned<float4> normals;
+	Owned<float2> boxes;   // six floats per face
+	hipError_t err = (hipError_t) allocAll( { want( indices, S.patchFacesN.size() ), want( normals, S.patchNormals.size() ), want( boxes, 3 * (size_t) S.numFaces ) } );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( indices, S.patchFacesN.data(), indices.bytes(), hipMemcpyHostToDevice );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( normals, S.patchNormals.data(), normals.bytes(), hipMemcpyHostToDevice );
 
 	if( err != hipSuccess ) {
-		(void) hipFree( indices );
-		(void) hipFree( normals );
-		(void) hipFree( boxes );
 		return fail( ctx, PBR_EDEVICE, "pbr_update_geometry: the patch refit's tables: %s", hipGetErrorString( err ) );
 	}
 
-	ctx->dPatchFacesN = indices;
-	ctx->dPatchNormals = normals;
-	ctx->dFaceBoxes = boxes;
-	ctx->patchBytes = indexBytes + normalBytes + boxBytes;
-	std::vector<pbr_uint4>().swap( ctx->patchFacesN );   // the device holds them now
-	std::vector<pbr_float4>().swap( ctx->patchNormals );
+	S.dPatchFacesN = std::move( indices );
+	S.dPatchNormals = std::move( normals );
+	S.dFaceBoxes = std::move( boxes );
+	std::vector<pbr_uint4>().swap( S.patchFacesN );   // the device holds them now
+	std::vector<pbr_float4>().swap( S.patchNormals );
 	return PBR_OK;
 }
 
@@ -1930,9 +1769,8 @@ struct UpdateCall {
 // pbr_denoise_temporal under motion tracking: H, the positions the history was made under, is a copy of dVertices taken before
 // an update replaces them.  The copy runs on the stream and is waited for.
 int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
-	const size_t bytes = std::max<size_t>( sizeof( pbr_float4 ) * ctx->numVertices, 16 );
-	hipError_t kept = ( ctx->dHistVertices != nullptr ) ? hipSuccess : hipMalloc( (void**) &ctx->dHistVertices, bytes );
-	kept = ( kept != hipSuccess ) ? kept : hipMemcpyAsync( ctx->dHistVertices, ctx->dVertices, sizeof( pbr_float4 ) * ctx->numVertices, hipMemcpyDeviceToDevice, ctx->stream );
+	hipError_t kept = (hipError_t) ctx->scene.dHistVertices.grow( ctx->scene.numVertices );
+	kept = ( kept != hipSuccess ) ? kept : hipMemcpyAsync( ctx->scene.dHistVertices, ctx->scene.dVertices, sizeof( pbr_float4 ) * ctx->scene.numVertices, hipMemcpyDeviceToDevice, ctx->stream );
 	kept = ( kept != hipSuccess ) ? kept : hipStreamSynchronize( ctx->stream );
 
 	if( kept != hipSuccess ) {
@@ -1947,22 +1785,22 @@ int keepHistoryVertices( pbr_ctx* ctx, const char* call ) {
 extern "C++" UpdateFacts updateFacts( const pbr_ctx* ctx ) {
 	UpdateFacts f;
 	f.hasScene = ctx->hasScene;
-	f.nested = ctx->refit.nested;
-	f.why = ctx->refit.why.c_str();
+	f.nested = ctx->scene.refit.nested;
+	f.why = ctx->scene.refit.why.c_str();
 	f.configured = ctx->configured;
 	f.traversal = ctx->cfg.traversal;
 	f.phongTessellation = ctx->cfg.phong_tessellation;
 	f.refitOrdered = ctx->refitOrdered;
-	f.hasPatches = ( ctx->dTriPN != nullptr );
-	f.walkBuilt = ( ctx->dNodesWalk != nullptr && ctx->walkBuilt == ctx->cfg.traversal );
-	f.numParts = ctx->parts.count;
-	f.numBones = ctx->skin.count;
-	f.numMorphTargets = ctx->morph.count;
-	f.skinGeneration = ctx->skin.pose.generation;
-	f.morphGeneration = ctx->morph.pose.generation;
-	f.partNormals = ctx->parts.pose.normals;
-	f.skinNormals = ctx->skin.pose.normals;
-	f.morphNormals = ctx->morph.pose.normals;
+	f.hasPatches = ( ctx->scene.dTriPN != nullptr );
+	f.walkBuilt = ( ctx->scene.walk.dNodesWalk != nullptr && ctx->scene.walk.walkBuilt == ctx->cfg.traversal );
+	f.numParts = ctx->scene.parts.count;
+	f.numBones = ctx->scene.skin.count;
+	f.numMorphTargets = ctx->scene.morph.count;
+	f.skinGeneration = ctx->scene.skin.pose.generation;
+	f.morphGeneration = ctx->scene.morph.pose.generation;
+	f.partNormals = ctx->scene.parts.pose.normals;
+	f.skinNormals = ctx->scene.skin.pose.normals;
+	f.morphNormals = ctx->scene.morph.pose.normals;
 	f.tracking = ctx->temporal.tracking;
 	f.history = ctx->temporal.history;
 	f.moved = ctx->temporal.moved;
@@ -1973,43 +1811,43 @@ extern "C++" UpdateFacts updateFacts( const pbr_ctx* ctx ) {
 int checkUpdateArguments( pbr_ctx* ctx, const UpdateCall& u, const char* call ) {
 	switch( u.kind ) {
 		case UpdateKind::Pose:
-			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call ) );
-			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->scene.morph.count, ctx->scene.morph.hWeights, &ctx->error, call ) );
+			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->scene.skin.count, ctx->scene.skin.hBones, &ctx->error, call );
 
 		case UpdateKind::Morph:
-			return checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call );
+			return checkMorphWeights( u.weights, u.num_targets, ctx->scene.morph.count, ctx->scene.morph.hWeights, &ctx->error, call );
 
 		case UpdateKind::Skin:
-			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+			return checkSkinMatrices( u.matrices, u.num_matrices, ctx->scene.skin.count, ctx->scene.skin.hBones, &ctx->error, call );
 
 		case UpdateKind::PoseDQ:
-			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->morph.count, ctx->morph.hWeights, &ctx->error, call ) );
-			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+			PBR_TRY( checkMorphWeights( u.weights, u.num_targets, ctx->scene.morph.count, ctx->scene.morph.hWeights, &ctx->error, call ) );
+			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->scene.skin.count, ctx->scene.skin.hBones, &ctx->error, call );
 
 		case UpdateKind::SkinDQ:
-			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->skin.count, ctx->skin.hBones, &ctx->error, call );
+			return checkSkinDualQuats( u.matrices, u.num_matrices, ctx->scene.skin.count, ctx->scene.skin.hBones, &ctx->error, call );
 
 		case UpdateKind::Transforms:
-			return checkTransforms( u.matrices, u.num_matrices, ctx->parts.count, ctx->parts.hRecords, &ctx->error );
+			return checkTransforms( u.matrices, u.num_matrices, ctx->scene.parts.count, ctx->scene.parts.hRecords, &ctx->error );
 
 		case UpdateKind::Geometry:
-			PBR_TRY( checkRefitVertices( u.vertices, u.num_vertices, ctx->numVertices, &ctx->error, call ) );
-			return checkRefitNormals( u.normals, u.num_normals, ctx->numNormals, &ctx->error );
+			PBR_TRY( checkRefitVertices( u.vertices, u.num_vertices, ctx->scene.numVertices, &ctx->error, call ) );
+			return checkRefitNormals( u.normals, u.num_normals, ctx->scene.numNormals, &ctx->error );
 
 		default:
-			return checkRefitVertices( u.vertices, u.num_vertices, ctx->numVertices, &ctx->error, call );
+			return checkRefitVertices( u.vertices, u.num_vertices, ctx->scene.numVertices, &ctx->error, call );
 	}
 }
 
 // The rest pose an update of this kind starts from, and whose statistics it moves; none for the kinds that bring V' from the host.
 RestPose* restPoseOf( pbr_ctx* ctx, UpdateKind kind ) {
 	switch( kind ) {
-		case UpdateKind::Transforms: return &ctx->parts.pose;
+		case UpdateKind::Transforms: return &ctx->scene.parts.pose;
 		case UpdateKind::Skin:
-		case UpdateKind::SkinDQ: return &ctx->skin.pose;
+		case UpdateKind::SkinDQ: return &ctx->scene.skin.pose;
 		case UpdateKind::Morph:
 		case UpdateKind::Pose:
-		case UpdateKind::PoseDQ: return &ctx->morph.pose;
+		case UpdateKind::PoseDQ: return &ctx->scene.morph.pose;
 		default: return nullptr;
 	}
 }
@@ -2045,18 +1883,18 @@ int stageVertices( pbr_ctx* ctx, const char* call, RestPose* pose, bool keepsHis
 	}
 
 	ctx->temporal.update();   // the H it asks for is kept already
-	std::swap( ctx->dVertices, pose->dStaged );
+	ctx->scene.dVertices.swap( pose->dStaged );
 	ctx->lastRefitUploadMs = uploadMs;
 	return PBR_OK;
 }
 
 // V' of a kind that computes it on the device: the kind's tables, its kernel and its overflow message through stageVertices.
 int stageKind( pbr_ctx* ctx, UpdateKind kind, const char* call, bool keepsHistory ) {
-	const uint32_t V = ctx->numVertices;
+	const uint32_t V = ctx->scene.numVertices;
 	const dim3 grid( ( V + 255 ) / 256 ), group( 256 );
-	PartsState& parts = ctx->parts;
-	SkinState& skin = ctx->skin;
-	MorphState& morph = ctx->morph;
+	PartsState& parts = ctx->scene.parts;
+	SkinState& skin = ctx->scene.skin;
+	MorphState& morph = ctx->scene.morph;
 	const auto uploadBones = [&]() { return hipMemcpyAsync( skin.dBones, skin.hBones, sizeof( pbr_float4 ) * 3 * skin.count, hipMemcpyHostToDevice, ctx->stream ); };
 	// the dual quaternions of the two dq kinds lie in the same tables, two quads per bone
 	const auto uploadDualQuats = [&]() { return hipMemcpyAsync( skin.dBones, skin.hBones, sizeof( pbr_float4 ) * 2 * skin.count, hipMemcpyHostToDevice, ctx->stream ); };
@@ -2120,39 +1958,39 @@ int launchNormals( pbr_ctx* ctx, NormalKernel which ) {
 		return PBR_OK;
 	}
 
-	const uint32_t N = ctx->numNormals;
+	const uint32_t N = ctx->scene.numNormals;
 	const dim3 grid( ( N + 255 ) / 256 ), group( 256 );
-	const SkinState& skin = ctx->skin;
-	const MorphState& morph = ctx->morph;
+	const SkinState& skin = ctx->scene.skin;
+	const MorphState& morph = ctx->scene.morph;
 	HIP_TRY( ctx, hipEventRecord( ctx->evXfNormalsStart, ctx->stream ) );
 
 	switch( which ) {
 		case NormalKernel::Transform:
-			hipLaunchKernelGGL( ptr::transformNormals, grid, group, 0, ctx->stream, ctx->parts.pose.dRestNormals, ctx->parts.dOfNormal, ctx->parts.dRecords,
-			                    ctx->dPatchNormals, (int) N );
+			hipLaunchKernelGGL( ptr::transformNormals, grid, group, 0, ctx->stream, ctx->scene.parts.pose.dRestNormals, ctx->scene.parts.dOfNormal, ctx->scene.parts.dRecords,
+			                    ctx->scene.dPatchNormals, (int) N );
 			break;
 
 		case NormalKernel::Skin:
-			hipLaunchKernelGGL( ptr::skinNormals, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			hipLaunchKernelGGL( ptr::skinNormals, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->scene.dPatchNormals, (int) N );
 			break;
 
 		case NormalKernel::Morph:
 			hipLaunchKernelGGL( ptr::morphNormals, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
-			                    ctx->dPatchNormals, (int) N );
+			                    ctx->scene.dPatchNormals, (int) N );
 			break;
 
 		case NormalKernel::SkinDQ:
-			hipLaunchKernelGGL( ptr::skinNormalsDQ, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			hipLaunchKernelGGL( ptr::skinNormalsDQ, grid, group, 0, ctx->stream, skin.pose.dRestNormals, skin.dOfNormal, skin.dBones, ctx->scene.dPatchNormals, (int) N );
 			break;
 
 		case NormalKernel::PoseDQ:
 			hipLaunchKernelGGL( ptr::poseNormalsDQ, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
-			                    skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			                    skin.dOfNormal, skin.dBones, ctx->scene.dPatchNormals, (int) N );
 			break;
 
 		default:
 			hipLaunchKernelGGL( ptr::poseNormals, grid, group, 0, ctx->stream, morph.pose.dRestNormals, morph.dNormalRun, morph.dNormalEntries, morph.dWeights,
-			                    skin.dOfNormal, skin.dBones, ctx->dPatchNormals, (int) N );
+			                    skin.dOfNormal, skin.dBones, ctx->scene.dPatchNormals, (int) N );
 			break;
 	}
 
@@ -2165,33 +2003,33 @@ int launchNormals( pbr_ctx* ctx, NormalKernel which ) {
 // patches (and under Phong tessellation the faces' thick boxes for the leaf step one launch later), the subtrees, the top of
 // the tree, and the re-link of the configured layout's records.
 int refitBehind( pbr_ctx* ctx, bool gathers, float alpha, bool relinks ) {
-	const uint32_t F = ctx->numFaces;
-	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dVertices, ctx->dTris, (int) F );
+	const uint32_t F = ctx->scene.numFaces;
+	hipLaunchKernelGGL( ptr::refitFaces, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->scene.dFacesV, ctx->scene.dVertices, ctx->scene.dTris, (int) F );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	if( ctx->dFaceN != nullptr ) {
+	if( ctx->scene.dFaceN != nullptr ) {
 		DevParams P;
 		std::memset( &P, 0, sizeof( P ) );
-		P.tris = ctx->dTris;
-		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->dFaceN, (int) F );
+		P.tris = ctx->scene.dTris;
+		hipLaunchKernelGGL( ptk::prepareFaceNormals, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, P, ctx->scene.dFaceN, (int) F );
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
 	if( gathers ) {
 		const auto kernel = ( alpha > 0.0f ) ? ptr::refitPatches<true> : ptr::refitPatches<false>;
-		hipLaunchKernelGGL( kernel, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->dFacesV, ctx->dPatchFacesN, ctx->dVertices,
-		                    ctx->dPatchNormals, ctx->dTriPN, ctx->dFaceBoxes, alpha, (int) F );
+		hipLaunchKernelGGL( kernel, dim3( ( F + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, ctx->scene.dFacesV, ctx->scene.dPatchFacesN, ctx->scene.dVertices,
+		                    ctx->scene.dPatchNormals, ctx->scene.dTriPN, ctx->scene.dFaceBoxes, alpha, (int) F );
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
 	const auto subtrees = ( alpha > 0.0f ) ? ptr::refitSubtrees<true> : ptr::refitSubtrees<false>;
-	hipLaunchKernelGGL( subtrees, dim3( ctx->refitGroups ), dim3( REFIT_SUBTREE ), 0, ctx->stream, ctx->dRefitSlots, ctx->dRefitInfo,
-	                    ctx->dRefitHeights, ctx->dRefitRecordOf, ctx->dFacesV, ctx->dVertices, ctx->dFaceBoxes, ctx->dNodes, ctx->dRootBox );
+	hipLaunchKernelGGL( subtrees, dim3( ctx->scene.refitGroups ), dim3( REFIT_SUBTREE ), 0, ctx->stream, ctx->scene.dRefitSlots, ctx->scene.dRefitInfo,
+	                    ctx->scene.dRefitHeights, ctx->scene.dRefitRecordOf, ctx->scene.dFacesV, ctx->scene.dVertices, ctx->scene.dFaceBoxes, ctx->scene.dNodes, ctx->scene.dRootBox );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	if( ctx->refitLevels > 0 ) {
-		hipLaunchKernelGGL( ptr::refitTop, dim3( 1 ), dim3( REFIT_TOP_THREADS ), 0, ctx->stream, ctx->dRefitTop, ctx->dRefitLevelFirst, (int) ctx->refitLevels,
-		                    ctx->dRefitInfo, ctx->dRefitRecordOf, ctx->dNodes, ctx->dRootBox );
+	if( ctx->scene.refitLevels > 0 ) {
+		hipLaunchKernelGGL( ptr::refitTop, dim3( 1 ), dim3( REFIT_TOP_THREADS ), 0, ctx->stream, ctx->scene.dRefitTop, ctx->scene.dRefitLevelFirst, (int) ctx->scene.refitLevels,
+		                    ctx->scene.dRefitInfo, ctx->scene.dRefitRecordOf, ctx->scene.dNodes, ctx->scene.dRootBox );
 		HIP_TRY( ctx, hipGetLastError() );
 	}
 
@@ -2243,10 +2081,10 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 		}
 
 		const auto uploadStart = std::chrono::steady_clock::now();
-		HIP_TRY( ctx, hipMemcpy( ctx->dVertices, u.vertices, sizeof( pbr_float4 ) * u.num_vertices, hipMemcpyHostToDevice ) );
+		HIP_TRY( ctx, hipMemcpy( ctx->scene.dVertices, u.vertices, sizeof( pbr_float4 ) * u.num_vertices, hipMemcpyHostToDevice ) );
 
 		if( plan.gathers && u.normals != nullptr ) {
-			HIP_TRY( ctx, hipMemcpy( ctx->dPatchNormals, u.normals, sizeof( pbr_float4 ) * u.num_normals, hipMemcpyHostToDevice ) );
+			HIP_TRY( ctx, hipMemcpy( ctx->scene.dPatchNormals, u.normals, sizeof( pbr_float4 ) * u.num_normals, hipMemcpyHostToDevice ) );
 		}
 
 		ctx->lastRefitUploadMs = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - uploadStart ).count();
@@ -2257,11 +2095,11 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 	PBR_TRY( refitBehind( ctx, plan.gathers, plan.alpha, plan.relinks ) );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	PBR_TRY( timedTail( ctx ) );
-	ctx->treeStale = true;
-	ctx->refitUpdates++;
+	ctx->scene.treeStale = true;
+	ctx->scene.refitUpdates++;
 	ctx->lastUpdate = kind;
-	ctx->patchAlpha = plan.alpha;
-	ctx->geometryUpdates += updateWasGeometry( kind ) ? 1u : 0u;
+	ctx->scene.patchAlpha = plan.alpha;
+	ctx->scene.geometryUpdates += updateWasGeometry( kind ) ? 1u : 0u;
 
 	if( pose != nullptr ) {
 		float ms = 0.0f, normalsMs = 0.0f;
@@ -2273,8 +2111,8 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 
 		if( updateDualQuatCode( kind ) != 0 ) {
 			// another kind to pbr_diag_skin_info and pbr_diag_morph_info: pbr_diag_skin_dq_info counts these
-			ctx->skin.dqLastMs = (double) ms + (double) normalsMs;
-			ctx->skin.dqUpdates++;
+			ctx->scene.skin.dqLastMs = (double) ms + (double) normalsMs;
+			ctx->scene.skin.dqUpdates++;
 		}
 		else {
 			pose->lastMs = (double) ms + (double) normalsMs;
@@ -2286,7 +2124,7 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 		// the eight first references are the context's too (applyWalk): 32 bytes of header, no node, box or record
 		float ms = 0.0f;
 		HIP_TRY( ctx, hipEventElapsedTime( &ms, ctx->evRelinkStart, ctx->evRelinkStop ) );
-		HIP_TRY( ctx, hipMemcpy( ctx->walkFirst, ctx->dNodesWalk, sizeof( ctx->walkFirst ), hipMemcpyDeviceToHost ) );
+		HIP_TRY( ctx, hipMemcpy( ctx->scene.walk.walkFirst, ctx->scene.walk.dNodesWalk, sizeof( ctx->scene.walk.walkFirst ), hipMemcpyDeviceToHost ) );
 		ctx->lastRelinkMs = (double) ms;
 		ctx->lastRelinked = true;
 		return PBR_OK;
@@ -2299,26 +2137,23 @@ int updateScene( pbr_ctx* ctx, const UpdateCall& u ) {
 
 // "Everything new first" of a pbr_set_*: the rest pose's buffers — the normals' only if the call moves them —, the staging
 // buffer, the flag word and its pinned twin, and the capture of the context's vertices and normals, device to device (the
-// caller's hipDeviceSynchronize waits for it).  On failure everything is given back and *pose is an empty record; the
-// context is not touched either way.
+// caller's hipDeviceSynchronize waits for it).  On failure *pose is an empty record; the context is not touched either way.
 hipError_t allocRestPose( const pbr_ctx* ctx, bool withNormals, RestPose* pose ) {
-	const size_t vertexBytes = sizeof( pbr_float4 ) * ctx->numVertices, normalBytes = sizeof( pbr_float4 ) * ctx->numNormals;
-	*pose = RestPose();
-	hipError_t err = hipMalloc( (void**) &pose->dRest, std::max<size_t>( vertexBytes, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &pose->dStaged, std::max<size_t>( vertexBytes, 16 ) );
-	err = ( err != hipSuccess || !withNormals ) ? err : hipMalloc( (void**) &pose->dRestNormals, std::max<size_t>( normalBytes, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &pose->dFlag, 16 );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &pose->hFlag, 16, hipHostMallocDefault );
-	err = ( err != hipSuccess ) ? err : hipMemcpy( pose->dRest, ctx->dVertices, vertexBytes, hipMemcpyDeviceToDevice );
-	err = ( err != hipSuccess || !withNormals ) ? err : hipMemcpy( pose->dRestNormals, ctx->dPatchNormals, normalBytes, hipMemcpyDeviceToDevice );
+	const size_t V = ctx->scene.numVertices, N = withNormals ? ctx->scene.numNormals : 0;
+	RestPose fresh;
+	hipError_t err = (hipError_t) allocAll( { want( fresh.dRest, V ), want( fresh.dStaged, V ), want( fresh.dFlag, 1 ), want( fresh.hFlag, 1 ) } );
+	err = ( err != hipSuccess || !withNormals ) ? err : (hipError_t) fresh.dRestNormals.alloc( N );
+	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dRest, ctx->scene.dVertices, fresh.dRest.bytes(), hipMemcpyDeviceToDevice );
+	err = ( err != hipSuccess || !withNormals ) ? err : hipMemcpy( fresh.dRestNormals, ctx->scene.dPatchNormals, fresh.dRestNormals.bytes(), hipMemcpyDeviceToDevice );
 
 	if( err != hipSuccess ) {
-		freeRestPose( pose );
+		*pose = RestPose();
 		return err;
 	}
 
-	pose->normals = withNormals;
-	pose->generation = ctx->geometryGeneration;
+	fresh.normals = withNormals;
+	fresh.generation = ctx->geometryGeneration;
+	*pose = std::move( fresh );
 	return hipSuccess;
 }
 
@@ -2385,19 +2220,19 @@ int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_verti
 		return fail( ctx, PBR_ESTATE, "pbr_set_parts before pbr_upload_scene" );
 	}
 
-	PBR_TRY( checkParts( vertex_part, num_vertices, ctx->numVertices, normal_part, num_normals, ctx->numNormals, num_parts, &ctx->error ) );
+	PBR_TRY( checkParts( vertex_part, num_vertices, ctx->scene.numVertices, normal_part, num_normals, ctx->scene.numNormals, num_parts, &ctx->error ) );
 
-	if( normal_part != nullptr && ctx->dTriPN == nullptr ) {
+	if( normal_part != nullptr && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_parts: normal parts for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_parts == 0 ) {
-		freeParts( &ctx->parts );
+		ctx->scene.parts = PartsState();
 		return PBR_OK;
 	}
-	if( ctx->dTriPN != nullptr ) {
+	if( ctx->scene.dTriPN != nullptr ) {
 		PBR_TRY( ensurePatchTables( ctx ) );   // a transform gathers the patches again: its tables are made here, not by an update
 	}
 
@@ -2405,27 +2240,23 @@ int pbr_set_parts( pbr_ctx* ctx, const uint32_t* vertex_part, uint32_t num_verti
 	const size_t V = num_vertices, N = num_normals, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
 	PartsState fresh;
 	hipError_t err = allocRestPose( ctx, normal_part != nullptr, &fresh.pose );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfVertex, std::max<size_t>( word * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dRecords, sizeof( ptx::PartRecord ) * num_parts );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hRecords, sizeof( ptx::PartRecord ) * num_parts, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : (hipError_t) allocAll( { want( fresh.dOfVertex, V ), want( fresh.dRecords, 6 * (size_t) num_parts ), want( fresh.hRecords, num_parts ) } );
 	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfVertex, vertex_part, word * V, hipMemcpyHostToDevice );
 
 	if( normal_part != nullptr ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfNormal, std::max<size_t>( word * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : (hipError_t) fresh.dOfNormal.alloc( N );
 		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfNormal, normal_part, word * N, hipMemcpyHostToDevice );
 	}
 
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		freeParts( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_parts: the rest pose and the part tables: %s", hipGetErrorString( err ) );
 	}
 
 	fresh.count = num_parts;
 	fresh.pose.bytes = ( quad + quad + word ) * V + ( fresh.pose.normals ? ( quad + word ) * N : 0 ) + sizeof( ptx::PartRecord ) * num_parts + sizeof( unsigned );
-	freeParts( &ctx->parts );
-	ctx->parts = fresh;
+	ctx->scene.parts = std::move( fresh );
 	return PBR_OK;
 }
 
@@ -2437,19 +2268,19 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 		return fail( ctx, PBR_ESTATE, "pbr_set_skin before pbr_upload_scene" );
 	}
 
-	PBR_TRY( checkSkin( vertex_bones, vertex_weights, num_vertices, ctx->numVertices, normal_bones, normal_weights, num_normals, ctx->numNormals, num_bones, &ctx->error ) );
+	PBR_TRY( checkSkin( vertex_bones, vertex_weights, num_vertices, ctx->scene.numVertices, normal_bones, normal_weights, num_normals, ctx->scene.numNormals, num_bones, &ctx->error ) );
 
-	if( normal_bones != nullptr && ctx->dTriPN == nullptr ) {
+	if( normal_bones != nullptr && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_skin: normal influences for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_bones == 0 ) {
-		freeSkin( &ctx->skin );
+		ctx->scene.skin = SkinState();
 		return PBR_OK;
 	}
-	if( ctx->dTriPN != nullptr ) {
+	if( ctx->scene.dTriPN != nullptr ) {
 		PBR_TRY( ensurePatchTables( ctx ) );   // a skin update gathers the patches again: its tables are made here, not by an update
 	}
 
@@ -2460,14 +2291,12 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 	// everything new first: a call that cannot have its buffers leaves the skin that was set
 	SkinState fresh;
 	hipError_t err = allocRestPose( ctx, normal_bones != nullptr, &fresh.pose );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfVertex, std::max<size_t>( record * V, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dBones, bone * num_bones );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hBones, bone * num_bones, hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : (hipError_t) allocAll( { want( fresh.dOfVertex, 2 * V ), want( fresh.dBones, 3 * (size_t) num_bones ), want( fresh.hBones, 3 * (size_t) num_bones ) } );
 	packInfluences( vertex_bones, vertex_weights, num_vertices, packed.data() );
 	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfVertex, packed.data(), record * V, hipMemcpyHostToDevice );
 
 	if( normal_bones != nullptr ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dOfNormal, std::max<size_t>( record * N, 16 ) );
+		err = ( err != hipSuccess ) ? err : (hipError_t) fresh.dOfNormal.alloc( 2 * N );
 		packInfluences( normal_bones, normal_weights, num_normals, packed.data() );
 		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dOfNormal, packed.data(), record * N, hipMemcpyHostToDevice );
 	}
@@ -2475,14 +2304,12 @@ int pbr_set_skin( pbr_ctx* ctx, const uint32_t* vertex_bones, const float* verte
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		freeSkin( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_skin: the rest pose and the influence tables: %s", hipGetErrorString( err ) );
 	}
 
 	fresh.count = num_bones;
 	fresh.pose.bytes = ( quad + quad + record ) * V + ( fresh.pose.normals ? ( quad + record ) * N : 0 ) + bone * num_bones + sizeof( unsigned );
-	freeSkin( &ctx->skin );
-	ctx->skin = fresh;
+	ctx->scene.skin = std::move( fresh );
 	return PBR_OK;
 }
 
@@ -2491,13 +2318,13 @@ int pbr_diag_skin_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_skin_info: null argument" );
 	}
 
-	out[0] = ctx->skin.count;
-	out[1] = ctx->skin.pose.bytes;
-	out[2] = ctx->skin.pose.updates;
+	out[0] = ctx->scene.skin.count;
+	out[1] = ctx->scene.skin.pose.bytes;
+	out[2] = ctx->scene.skin.pose.updates;
 	out[3] = ( ctx->lastUpdate == UpdateKind::Skin ) ? 1 : 0;
 
 	if( ms != nullptr ) {
-		*ms = ctx->skin.pose.lastMs;
+		*ms = ctx->scene.skin.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2508,11 +2335,11 @@ int pbr_diag_skin_dq_info( pbr_ctx* ctx, uint64_t out[2], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_skin_dq_info: null argument" );
 	}
 
-	out[0] = ctx->skin.dqUpdates;
+	out[0] = ctx->scene.skin.dqUpdates;
 	out[1] = updateDualQuatCode( ctx->lastUpdate );
 
 	if( ms != nullptr ) {
-		*ms = ctx->skin.dqLastMs;
+		*ms = ctx->scene.skin.dqLastMs;
 	}
 
 	return PBR_OK;
@@ -2526,22 +2353,22 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 		return fail( ctx, PBR_ESTATE, "pbr_set_morph before pbr_upload_scene" );
 	}
 
-	PBR_TRY( checkMorph( vertex_first, vertex_index, vertex_delta, normal_first, normal_index, normal_delta, num_targets, ctx->numVertices, ctx->numNormals, &ctx->error ) );
+	PBR_TRY( checkMorph( vertex_first, vertex_index, vertex_delta, normal_first, normal_index, normal_delta, num_targets, ctx->scene.numVertices, ctx->scene.numNormals, &ctx->error ) );
 
-	if( normal_first != nullptr && ctx->dTriPN == nullptr ) {
+	if( normal_first != nullptr && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_set_morph: normal targets for a scene that was uploaded without usable vertex normals (its facesN / normals were missing or out of range, it has no Phong patches)" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( num_targets == 0 ) {
-		freeMorph( &ctx->morph );
+		ctx->scene.morph = MorphState();
 		return PBR_OK;
 	}
 
 	// the caller's target-major lists as element-major runs
 	const bool withNormals = ( normal_first != nullptr );
-	const size_t V = ctx->numVertices, N = withNormals ? ctx->numNormals : 0, T = num_targets, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
+	const size_t V = ctx->scene.numVertices, N = withNormals ? ctx->scene.numNormals : 0, T = num_targets, quad = sizeof( pbr_float4 ), word = sizeof( uint32_t );
 	const size_t Ev = vertex_first[T], En = withNormals ? normal_first[T] : 0;
 	std::vector<uint32_t> vertexRun( V + 1 ), normalRun( withNormals ? N + 1 : 0 );
 	std::vector<ptm::Entry> vertexEntries( Ev ), normalEntries( En );
@@ -2550,23 +2377,19 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 	if( withNormals ) {
 		PBR_TRY( packMorph( normal_first, normal_index, normal_delta, num_targets, (uint32_t) N, normalRun.data(), normalEntries.data(), &ctx->error ) );
 	}
-	if( ctx->dTriPN != nullptr ) {
+	if( ctx->scene.dTriPN != nullptr ) {
 		PBR_TRY( ensurePatchTables( ctx ) );   // a morph update gathers the patches again: its tables are made here, not by an update
 	}
 
 	// everything new first: a call that cannot have its buffers leaves the morph that was set
 	MorphState fresh;
 	hipError_t err = allocRestPose( ctx, withNormals, &fresh.pose );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dVertexRun, word * ( V + 1 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dVertexEntries, std::max<size_t>( quad * Ev, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dWeights, std::max<size_t>( sizeof( float ) * T, 16 ) );
-	err = ( err != hipSuccess ) ? err : hipHostMalloc( (void**) &fresh.hWeights, std::max<size_t>( sizeof( float ) * T, 16 ), hipHostMallocDefault );
+	err = ( err != hipSuccess ) ? err : (hipError_t) allocAll( { want( fresh.dVertexRun, V + 1 ), want( fresh.dVertexEntries, Ev ), want( fresh.dWeights, T ), want( fresh.hWeights, T ) } );
 	err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dVertexRun, vertexRun.data(), word * ( V + 1 ), hipMemcpyHostToDevice );
 	err = ( err != hipSuccess || Ev == 0 ) ? err : hipMemcpy( fresh.dVertexEntries, vertexEntries.data(), quad * Ev, hipMemcpyHostToDevice );
 
 	if( withNormals ) {
-		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dNormalRun, word * ( N + 1 ) );
-		err = ( err != hipSuccess ) ? err : hipMalloc( (void**) &fresh.dNormalEntries, std::max<size_t>( quad * En, 16 ) );
+		err = ( err != hipSuccess ) ? err : (hipError_t) allocAll( { want( fresh.dNormalRun, N + 1 ), want( fresh.dNormalEntries, En ) } );
 		err = ( err != hipSuccess ) ? err : hipMemcpy( fresh.dNormalRun, normalRun.data(), word * ( N + 1 ), hipMemcpyHostToDevice );
 		err = ( err != hipSuccess || En == 0 ) ? err : hipMemcpy( fresh.dNormalEntries, normalEntries.data(), quad * En, hipMemcpyHostToDevice );
 	}
@@ -2574,7 +2397,6 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 	err = ( err != hipSuccess ) ? err : hipDeviceSynchronize();
 
 	if( err != hipSuccess ) {
-		freeMorph( &fresh );
 		return fail( ctx, PBR_EDEVICE, "pbr_set_morph: the rest pose and the target tables: %s", hipGetErrorString( err ) );
 	}
 
@@ -2582,8 +2404,7 @@ int pbr_set_morph( pbr_ctx* ctx, const uint32_t* vertex_first, const uint32_t* v
 	fresh.vertexEntries = Ev;
 	fresh.normalEntries = En;
 	fresh.pose.bytes = quad * V + quad * V + word * ( V + 1 ) + quad * Ev + ( withNormals ? quad * N + word * ( N + 1 ) + quad * En : 0 ) + sizeof( float ) * T + sizeof( unsigned );
-	freeMorph( &ctx->morph );
-	ctx->morph = fresh;
+	ctx->scene.morph = std::move( fresh );
 	return PBR_OK;
 }
 
@@ -2592,15 +2413,15 @@ int pbr_diag_morph_info( pbr_ctx* ctx, uint64_t out[6], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_morph_info: null argument" );
 	}
 
-	out[0] = ctx->morph.count;
-	out[1] = ctx->morph.vertexEntries;
-	out[2] = ctx->morph.normalEntries;
-	out[3] = ctx->morph.pose.bytes;
-	out[4] = ctx->morph.pose.updates;
+	out[0] = ctx->scene.morph.count;
+	out[1] = ctx->scene.morph.vertexEntries;
+	out[2] = ctx->scene.morph.normalEntries;
+	out[3] = ctx->scene.morph.pose.bytes;
+	out[4] = ctx->scene.morph.pose.updates;
 	out[5] = updateMorphCode( ctx->lastUpdate );
 
 	if( ms != nullptr ) {
-		*ms = ctx->morph.pose.lastMs;
+		*ms = ctx->scene.morph.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2617,8 +2438,8 @@ int pbr_read_geometry( pbr_ctx* ctx, pbr_float4* vertices_out, uint32_t vcap, ui
 		return fail( ctx, PBR_EINVAL, "pbr_read_geometry: null num_vertices or num_normals" );
 	}
 
-	*num_vertices = ctx->numVertices;
-	*num_normals = ( ctx->dTriPN != nullptr ) ? ctx->numNormals : 0;   // normals nobody can use were not kept
+	*num_vertices = ctx->scene.numVertices;
+	*num_normals = ( ctx->scene.dTriPN != nullptr ) ? ctx->scene.numNormals : 0;   // normals nobody can use were not kept
 
 	if( vertices_out != nullptr && vcap < *num_vertices ) {
 		return fail( ctx, PBR_EINVAL, "pbr_read_geometry: room for %u vertices, the scene has %u", vcap, *num_vertices );
@@ -2630,14 +2451,14 @@ int pbr_read_geometry( pbr_ctx* ctx, pbr_float4* vertices_out, uint32_t vcap, ui
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( vertices_out != nullptr && *num_vertices > 0 ) {
-		HIP_TRY( ctx, hipMemcpy( vertices_out, ctx->dVertices, sizeof( pbr_float4 ) * *num_vertices, hipMemcpyDeviceToHost ) );
+		HIP_TRY( ctx, hipMemcpy( vertices_out, ctx->scene.dVertices, sizeof( pbr_float4 ) * *num_vertices, hipMemcpyDeviceToHost ) );
 	}
 	if( normals_out != nullptr && *num_normals > 0 ) {
-		if( ctx->dPatchNormals != nullptr ) {
-			HIP_TRY( ctx, hipMemcpy( normals_out, ctx->dPatchNormals, sizeof( pbr_float4 ) * *num_normals, hipMemcpyDeviceToHost ) );
+		if( ctx->scene.dPatchNormals != nullptr ) {
+			HIP_TRY( ctx, hipMemcpy( normals_out, ctx->scene.dPatchNormals, sizeof( pbr_float4 ) * *num_normals, hipMemcpyDeviceToHost ) );
 		}
 		else {
-			std::memcpy( normals_out, ctx->patchNormals.data(), sizeof( pbr_float4 ) * *num_normals );   // still the upload's host copy
+			std::memcpy( normals_out, ctx->scene.patchNormals.data(), sizeof( pbr_float4 ) * *num_normals );   // still the upload's host copy
 		}
 	}
 
@@ -2649,13 +2470,13 @@ int pbr_diag_transform_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "pbr_diag_transform_info: null argument" );
 	}
 
-	out[0] = ctx->parts.count;
-	out[1] = ctx->parts.pose.bytes;
-	out[2] = ctx->parts.pose.updates;
+	out[0] = ctx->scene.parts.count;
+	out[1] = ctx->scene.parts.pose.bytes;
+	out[2] = ctx->scene.parts.pose.updates;
 	out[3] = ( ctx->lastUpdate == UpdateKind::Transforms ) ? 1 : 0;
 
 	if( ms != nullptr ) {
-		*ms = ctx->parts.pose.lastMs;
+		*ms = ctx->scene.parts.pose.lastMs;
 	}
 
 	return PBR_OK;
@@ -2669,17 +2490,17 @@ int pbr_read_bvh( pbr_ctx* ctx, pbr_bvh_node* nodes_out, uint32_t capacity, uint
 		return fail( ctx, PBR_EINVAL, "pbr_read_bvh: null num_nodes" );
 	}
 
-	*num_nodes = ctx->tree.size();
+	*num_nodes = ctx->scene.tree.size();
 
 	if( nodes_out == nullptr ) {
 		return PBR_OK;
 	}
-	if( capacity < ctx->tree.size() ) {
-		return fail( ctx, PBR_EINVAL, "pbr_read_bvh: room for %u nodes, the tree has %u", capacity, ctx->tree.size() );
+	if( capacity < ctx->scene.tree.size() ) {
+		return fail( ctx, PBR_EINVAL, "pbr_read_bvh: room for %u nodes, the tree has %u", capacity, ctx->scene.tree.size() );
 	}
 
 	PBR_TRY( refreshTree( ctx ) );
-	std::memcpy( nodes_out, ctx->tree.bvh.data(), sizeof( pbr_bvh_node ) * ctx->tree.size() );
+	std::memcpy( nodes_out, ctx->scene.tree.bvh.data(), sizeof( pbr_bvh_node ) * ctx->scene.tree.size() );
 	return PBR_OK;
 }
 
@@ -2699,14 +2520,14 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( cfg->max_depth == 0 || cfg->samples == 0 ) {
 		return fail( ctx, PBR_EINVAL, "max_depth and samples must be >= 1" );
 	}
-	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->dTriPN == nullptr ) {
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "Phong tessellation needs vertex normals: the uploaded scene's facesN / normals are missing or out of range" );
 	}
-	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !updateWasGeometry( ctx->lastUpdate ) ) {
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->scene.refitUpdates > 0 && !updateWasGeometry( ctx->lastUpdate ) ) {
 		return fail( ctx, PBR_ESTATE, "Phong tessellation after pbr_update_vertices: the refitted boxes are tight boxes of the flat triangles and would clip the patches, and the patches' corners were not updated — upload the scene again, or call pbr_update_geometry under this phong_tessellation" );
 	}
-	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->refitUpdates > 0 && !( ctx->patchAlpha == cfg->phong_tessellation ) ) {
-		return fail( ctx, PBR_ESTATE, "Phong tessellation %g after a pbr_update_geometry under %g: the boxes were thickened for that value and could clip these patches — configure %g, or upload the scene again", (double) cfg->phong_tessellation, (double) ctx->patchAlpha, (double) ctx->patchAlpha );
+	if( cfg->phong_tessellation > 0.0f && ctx->hasScene && ctx->scene.refitUpdates > 0 && !( ctx->scene.patchAlpha == cfg->phong_tessellation ) ) {
+		return fail( ctx, PBR_ESTATE, "Phong tessellation %g after a pbr_update_geometry under %g: the boxes were thickened for that value and could clip these patches — configure %g, or upload the scene again", (double) cfg->phong_tessellation, (double) ctx->scene.patchAlpha, (double) ctx->scene.patchAlpha );
 	}
 	if( cfg->traversal > 3 || cfg->arith > 1 ) {
 		return fail( ctx, PBR_EINVAL, "traversal must be 0 (the reference's walk), 1 (six orders), 2 (eight orders) or 3 (eight orders, compact records); arith 0 (exact) or 1 (native)" );
@@ -2717,13 +2538,13 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 
 	// the records of the configured walk for the scene there is, unless they are there already: packed before anything changes
 	PackedWalk walk;
-	const bool packsWalk = ( ctx->hasScene && ctx->walkBuilt != cfg->traversal );
+	const bool packsWalk = ( ctx->hasScene && ctx->scene.walk.walkBuilt != cfg->traversal );
 
 	if( packsWalk && cfg->traversal != 0 ) {
 		PBR_TRY( refreshTree( ctx ) );   // after pbr_update_vertices: the orders are built from the refitted boxes
 	}
 
-	PBR_TRY( packConfiguredWalk( ctx, *cfg, packsWalk ? &ctx->tree : nullptr, &walk ) );
+	PBR_TRY( packConfiguredWalk( ctx, *cfg, packsWalk ? &ctx->scene.tree : nullptr, &walk ) );
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	freeImages( ctx );
@@ -2737,28 +2558,30 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 
 	// Every context can hold the full image (import_tiles scatters all ranks' tiles into imgOut).
 	const size_t fullBytes = sizeof( float4 ) * 64 * (size_t) ctx->numTiles;
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dImgIn, fullBytes ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dImgOut, fullBytes ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dImgDbg, fullBytes ) );
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dRows, fullBytes ) );
-	HIP_TRY( ctx, hipMemset( ctx->dImgIn, 0, fullBytes ) );
-	HIP_TRY( ctx, hipMemset( ctx->dImgOut, 0, fullBytes ) );
-	HIP_TRY( ctx, hipMemset( ctx->dImgDbg, 0, fullBytes ) );
+	Images& I = ctx->images;
+	const size_t fullSlots = 64 * (size_t) ctx->numTiles;
+	HIP_TRY( ctx, allocAll( { want( I.dImgIn, fullSlots ), want( I.dImgOut, fullSlots ), want( I.dImgDbg, fullSlots ), want( I.dRows, fullSlots ) } ) );
+	HIP_TRY( ctx, hipMemset( ctx->images.dImgIn, 0, fullBytes ) );
+	HIP_TRY( ctx, hipMemset( ctx->images.dImgOut, 0, fullBytes ) );
+	HIP_TRY( ctx, hipMemset( ctx->images.dImgDbg, 0, fullBytes ) );
 	HIP_TRY( ctx, hipMemset( ctx->dCounters, 0, sizeof( unsigned long long ) * kCounterSlots ) );
 	HIP_TRY( ctx, hipDeviceSynchronize() );   // the memsets ran on the null stream; launches use ctx->stream
 
 	// the local tiles as a grid for the banded queue: its true shape when unsharded, about that when sharded
 	ctx->queueGrid = dealGrid( ctx->tilesX, ctx->numLocalTiles, (int) cfg->tile_world );
-	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &ctx->deal[kDealSpatial].host, ctx->deal[kDealSpatial].first );
-	const size_t tiles = ctx->deal[kDealSpatial].host.size();
+	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &ctx->images.deal[kDealSpatial].host, ctx->images.deal[kDealSpatial].first );
+	const size_t tiles = ctx->images.deal[kDealSpatial].host.size();
 
 	for( int order = 0; order < kDealOrders; order++ ) {
 		// a context without local tiles gets no table of the first two orders (a null pointer: learnTileCosts then learns nothing)
 		const size_t entries = ( order == kDealExpensiveLast ) ? std::max<size_t>( 1, tiles ) : tiles;
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->deal[order].dev, sizeof( unsigned ) * entries ) );
+
+		if( entries > 0 ) {
+			HIP_TRY( ctx, I.deal[order].dev.alloc( entries ) );
+		}
 	}
 
-	HIP_TRY( ctx, hipMalloc( (void**) &ctx->dTileCost, sizeof( float ) * std::max<size_t>( 1, tiles ) ) );
+	HIP_TRY( ctx, I.dTileCost.alloc( std::max<size_t>( 1, tiles ) ) );
 	ctx->costLearnt = false;
 	ctx->launchesSinceLearn = 0;
 	PBR_TRY( uploadTileOrder( ctx ) );
@@ -2768,7 +2591,7 @@ int pbr_configure( pbr_ctx* ctx, const pbr_config* cfg ) {
 	if( !walk.storage.empty() ) {
 		return uploadWalkStreams( ctx, walk, cfg->traversal );
 	}
-	if( ctx->walkBuilt != cfg->traversal ) {
+	if( ctx->scene.walk.walkBuilt != cfg->traversal ) {
 		freeWalkStreams( ctx );   // the records of a traversal that is no longer configured
 	}
 
@@ -2785,10 +2608,10 @@ int pbr_write_input( pbr_ctx* ctx, const float* rgba ) {
 
 	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dRows, rgba, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->images.dRows, rgba, sizeof( float4 ) * ctx->cfg.width * ctx->cfg.height, hipMemcpyHostToDevice, ctx->stream ) );
 	const size_t n = (size_t) ctx->numLocalTiles * 64;
 	hipLaunchKernelGGL( ptk::retile, dim3( (unsigned) ( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream,
-		ctx->dRows, ctx->dImgIn, (int) ctx->cfg.width, ctx->numLocalTiles, ctx->tilesX, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
+		ctx->images.dRows, ctx->images.dImgIn, (int) ctx->cfg.width, ctx->numLocalTiles, ctx->tilesX, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
@@ -2802,7 +2625,7 @@ int pbr_reset_accum( pbr_ctx* ctx ) {
 	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const size_t fullBytes = sizeof( float4 ) * 64 * (size_t) ctx->numTiles;
-	HIP_TRY( ctx, hipMemsetAsync( ctx->dImgIn, 0, fullBytes, ctx->stream ) );
+	HIP_TRY( ctx, hipMemsetAsync( ctx->images.dImgIn, 0, fullBytes, ctx->stream ) );
 	HIP_TRY( ctx, hipMemsetAsync( ctx->dCounters, 0, sizeof( unsigned long long ) * kCounterSlots, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
@@ -2822,9 +2645,7 @@ int pbr_accumulate( pbr_ctx* ctx ) {
 	}
 
 	ctx->varianceCurrent = false;
-	float4* tmp = ctx->dImgIn;
-	ctx->dImgIn = ctx->dImgOut;
-	ctx->dImgOut = tmp;
+	ctx->images.dImgIn.swap( ctx->images.dImgOut );
 	return PBR_OK;
 }
 
@@ -2840,7 +2661,7 @@ int pbr_render( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames, co
 
 	// result in imageOut AND imageIn
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->images.dImgIn, ctx->images.dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -2854,7 +2675,7 @@ int pbr_render_dof( pbr_ctx* ctx, uint32_t first_sample_count, uint32_t n_frames
 
 	// result in imageOut AND imageIn
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->images.dImgIn, ctx->images.dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -2874,7 +2695,7 @@ int pbr_render_adaptive( pbr_ctx* ctx, uint32_t first_sample_count, const float*
 
 	// result in imageOut AND imageIn, as pbr_render leaves it
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
-	HIP_TRY( ctx, hipMemcpyAsync( ctx->dImgIn, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( ctx->images.dImgIn, ctx->images.dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	ctx->varianceFirstCount = first_sample_count;
 	ctx->varianceCurrent = true;   // the moments and the frame counts are those of the image as it stands
@@ -2902,10 +2723,10 @@ int pbr_read_tile_stats( pbr_ctx* ctx, uint32_t* frames, float* error, uint32_t 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
 	if( frames != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( frames, ctx->dTileFrames, sizeof( uint32_t ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( frames, ctx->images.dTileFrames, sizeof( uint32_t ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
 	}
 	if( error != nullptr ) {
-		HIP_TRY( ctx, hipMemcpyAsync( error, ctx->dTileError, sizeof( float ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( error, ctx->images.dTileError, sizeof( float ) * *count, hipMemcpyDeviceToHost, ctx->stream ) );
 	}
 
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
@@ -2916,7 +2737,7 @@ int pbr_read_output( pbr_ctx* ctx, float* rgba ) {
 	if( ctx == nullptr ) {
 		return PBR_EINVAL;
 	}
-	return readTiled( ctx, ctx->dImgOut, rgba, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
+	return readTiled( ctx, ctx->images.dImgOut, rgba, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
 }
 
 int pbr_get_focus_depth( pbr_ctx* ctx, int x, int y, float* t, int* owned ) {
@@ -2939,7 +2760,7 @@ int pbr_get_focus_depth( pbr_ctx* ctx, int x, int y, float* t, int* owned ) {
 		const size_t slot = (size_t) ( position / (int) ctx->cfg.tile_world ) * 64 + (size_t) ( ( fy & 7 ) * 8 + ( fx & 7 ) );
 		float4 pixel;
 		HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-		HIP_TRY( ctx, hipMemcpyAsync( &pixel, ctx->dImgIn + slot, sizeof( pixel ), hipMemcpyDeviceToHost, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( &pixel, ctx->images.dImgIn + slot, sizeof( pixel ), hipMemcpyDeviceToHost, ctx->stream ) );
 		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 		*t = pixel.w;
 	}
@@ -2970,10 +2791,10 @@ int pbr_read_display( pbr_ctx* ctx, uint8_t* rgba8, int top_row_first ) {
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	// dRows (16 B per pixel) doubles as the 4-B-per-pixel staging buffer
-	hipLaunchKernelGGL( ptk::displayRGBA8, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, (uchar4*) ctx->dRows,
+	hipLaunchKernelGGL( ptk::displayRGBA8, imageGrid( (int) ctx->cfg.width, (int) ctx->cfg.height ), kImageBlock, 0, ctx->stream, (const float4*) ctx->images.dImgOut, (uchar4*) ctx->images.dRows.get(),
 		(int) ctx->cfg.width, (int) ctx->cfg.height, ctx->tilesX, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank, top_row_first ? 1 : 0 );
 	HIP_TRY( ctx, hipGetLastError() );
-	HIP_TRY( ctx, hipMemcpyAsync( rgba8, ctx->dRows, (size_t) 4 * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( rgba8, ctx->images.dRows, (size_t) 4 * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -2982,7 +2803,7 @@ int pbr_read_debug( pbr_ctx* ctx, float* rgba ) {
 	if( ctx == nullptr ) {
 		return PBR_EINVAL;
 	}
-	return readTiled( ctx, ctx->dImgDbg, rgba, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
+	return readTiled( ctx, ctx->images.dImgDbg, rgba, (int) ctx->cfg.tile_world, (int) ctx->cfg.tile_rank );
 }
 
 int pbr_get_counters( pbr_ctx* ctx, pbr_counters* out ) {
@@ -3024,7 +2845,7 @@ int pbr_export_tiles( pbr_ctx* ctx, void* d_dst ) {
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const size_t bytes = sizeof( float4 ) * 64 * (size_t) ctx->numLocalTiles;
 	HIP_TRY( ctx, hipMemsetAsync( d_dst, 0, (size_t) pbr_tile_bytes( ctx ), ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( d_dst, ctx->dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( d_dst, ctx->images.dImgOut, bytes, hipMemcpyDeviceToDevice, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -3040,14 +2861,12 @@ int pbr_import_tiles( pbr_ctx* ctx, const void* d_all ) {
 	ctx->varianceCurrent = false;
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 
-	if( ctx->dFull == nullptr ) {
-		HIP_TRY( ctx, hipMalloc( (void**) &ctx->dFull, sizeof( float4 ) * 64 * (size_t) ctx->numTiles ) );
-	}
+	HIP_TRY( ctx, ctx->images.dFull.grow( 64 * (size_t) ctx->numTiles ) );
 
 	const int perRank = ( ctx->numTiles + (int) ctx->cfg.tile_world - 1 ) / (int) ctx->cfg.tile_world;
 	const size_t n = (size_t) ctx->numTiles * 64;
 	hipLaunchKernelGGL( ptk::scatterGathered, dim3( (unsigned) ( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream,
-		(const float4*) d_all, ctx->dFull, ctx->numTiles, perRank, (int) ctx->cfg.tile_world, ctx->tilesX );
+		(const float4*) d_all, ctx->images.dFull, ctx->numTiles, perRank, (int) ctx->cfg.tile_world, ctx->tilesX );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
@@ -3057,7 +2876,7 @@ int pbr_read_full( pbr_ctx* ctx, float* rgba ) {
 	if( ctx == nullptr ) {
 		return PBR_EINVAL;
 	}
-	return readTiled( ctx, ctx->dFull, rgba, 1, 0 );
+	return readTiled( ctx, ctx->images.dFull, rgba, 1, 0 );
 }
 
 
@@ -3066,24 +2885,15 @@ int pbr_read_full( pbr_ctx* ctx, float* rgba ) {
 
 namespace {
 
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf() { (void) hipFree( p ); }
-	hipError_t alloc( size_t bytes ) { return hipMalloc( &p, bytes ? bytes : 4 ); }
-};
+// a per-call buffer of bytes: the diagnostics and the builders cast it to what their kernels take
+typedef Owned<unsigned char> DevBuf;
 
 // The planes pbr_denoise and pbr_denoise_guided allocate per call: the first-hit features and the filter's two working planes.
 struct FilterPlanes {
-	DevBuf position, normal, albedo, ping, pong;
+	Owned<float4> position, normal, albedo, ping, pong;
 
-	hipError_t alloc( size_t pixels ) {
-		hipError_t err = hipSuccess;
-
-		for( DevBuf* plane : { &position, &normal, &albedo, &ping, &pong } ) {
-			err = ( err == hipSuccess ) ? plane->alloc( sizeof( float4 ) * pixels ) : err;
-		}
-
-		return err;
+	int alloc( size_t pixels ) {
+		return allocAll( { want( position, pixels ), want( normal, pixels ), want( albedo, pixels ), want( ping, pixels ), want( pong, pixels ) } );
 	}
 };
 
@@ -3102,7 +2912,7 @@ int varianceUsable( pbr_ctx* ctx, const char* who ) {
 	if( ctx->cfg.tile_world > 1 ) {
 		return fail( ctx, PBR_ESTATE, "%s with tile sharding: the variance pbr_render_adaptive keeps of other ranks' tiles is not gathered", who );
 	}
-	if( !ctx->varianceCurrent || ctx->dMoments == nullptr ) {
+	if( !ctx->varianceCurrent || ctx->images.dMoments == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "%s needs the accumulated image as the last pbr_render_adaptive left it: no adaptive call yet, or the image was written since", who );
 	}
 
@@ -3121,9 +2931,9 @@ int readBack( pbr_ctx* ctx, void* dst, const void* src, size_t bytes ) {
 // {position, normal, albedo} into the caller's `features` (may be null)
 int readFeatures( pbr_ctx* ctx, float* features, const FilterPlanes& D, size_t pixels ) {
 	if( features != nullptr ) {
-		PBR_TRY( readBack( ctx, features, D.position.p, sizeof( float4 ) * pixels ) );
-		PBR_TRY( readBack( ctx, features + 4 * pixels, D.normal.p, sizeof( float4 ) * pixels ) );
-		PBR_TRY( readBack( ctx, features + 8 * pixels, D.albedo.p, sizeof( float4 ) * pixels ) );
+		PBR_TRY( readBack( ctx, features, D.position, sizeof( float4 ) * pixels ) );
+		PBR_TRY( readBack( ctx, features + 4 * pixels, D.normal, sizeof( float4 ) * pixels ) );
+		PBR_TRY( readBack( ctx, features + 8 * pixels, D.albedo, sizeof( float4 ) * pixels ) );
 	}
 
 	return PBR_OK;
@@ -3201,7 +3011,7 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 	PBR_TRY( admit( ctx, "pbr_denoise", ptd::denoiseCheck( "pbr_denoise", cam, params, rgba, &why ), why ) );
 	const bool sharded = ctx->cfg.tile_world > 1;
 
-	if( sharded && ctx->dFull == nullptr ) {
+	if( sharded && ctx->images.dFull == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_denoise with tile sharding filters the gathered frame: call pbr_import_tiles first" );
 	}
 
@@ -3217,13 +3027,13 @@ int pbr_denoise( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const pbr_den
 
 	const dim3 grid = imageGrid( w, h );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ( sharded ? ctx->dFull : ctx->dImgOut ), (float4*) D.ping.p,
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ( sharded ? ctx->images.dFull : ctx->images.dImgOut ), (float4*) D.ping,
 		w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position.p, (float4*) D.normal.p, (float4*) D.albedo.p, (int*) nullptr );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position, (float4*) D.normal, (float4*) D.albedo, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	const float4* result = plainPasses( ctx, *params, w, h, pxDim, (float4*) D.ping.p, (float4*) D.pong.p, (const float4*) D.position.p,
-		(const float4*) D.normal.p, (const float4*) D.albedo.p );
+	const float4* result = plainPasses( ctx, *params, w, h, pxDim, (float4*) D.ping, (float4*) D.pong, (const float4*) D.position,
+		(const float4*) D.normal, (const float4*) D.albedo );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	PBR_TRY( readBack( ctx, rgba, result, sizeof( float4 ) * pixels ) );
@@ -3246,11 +3056,11 @@ int pbr_read_variance( pbr_ctx* ctx, float* variance ) {
 	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 	// dRows (W x H float4) is the staging of every read-back: its first quarter holds the floats
-	hipLaunchKernelGGL( ptd::pixelVariance, imageGrid( w, h ), kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
-		ctx->varianceFirstCount, (const float4*) nullptr, (float*) ctx->dRows, (float4*) nullptr, w, h, ctx->tilesX );
+	hipLaunchKernelGGL( ptd::pixelVariance, imageGrid( w, h ), kImageBlock, 0, ctx->stream, (const float2*) ctx->images.dMoments, (const unsigned*) ctx->images.dTileFrames,
+		ctx->varianceFirstCount, (const float4*) nullptr, (float*) ctx->images.dRows.get(), (float4*) nullptr, w, h, ctx->tilesX );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( variance, ctx->dRows, sizeof( float ) * (size_t) w * (size_t) h, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( variance, ctx->images.dRows, sizeof( float ) * (size_t) w * (size_t) h, hipMemcpyDeviceToHost, ctx->stream ) );
 	return timedTail( ctx );
 }
 
@@ -3281,19 +3091,19 @@ int pbr_denoise_guided( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const 
 
 	const dim3 grid = imageGrid( w, h );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, (float4*) dOriginal.p, w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
-		ctx->varianceFirstCount, (const float4*) dOriginal.p, (float*) nullptr, (float4*) D.ping.p, w, h, ctx->tilesX );
-	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position.p, (float4*) D.normal.p, (float4*) D.albedo.p, (int*) nullptr );
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->images.dImgOut, (float4*) dOriginal.get(), w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->images.dMoments, (const unsigned*) ctx->images.dTileFrames,
+		ctx->varianceFirstCount, (const float4*) dOriginal.get(), (float*) nullptr, (float4*) D.ping, w, h, ctx->tilesX );
+	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, (float4*) D.position, (float4*) D.normal, (float4*) D.albedo, (int*) nullptr );
 	HIP_TRY( ctx, hipGetLastError() );
 
-	float4* const outs[2] = { (float4*) D.pong.p, (float4*) D.ping.p };
-	const float4* result = guidedPasses( ctx, *params, w, h, pxDim, (const float4*) D.ping.p, outs, (const float4*) D.position.p, (const float4*) D.normal.p,
-		(const float4*) D.albedo.p, (const float4*) dOriginal.p, (float*) dVariance.p );
+	float4* const outs[2] = { (float4*) D.pong, (float4*) D.ping };
+	const float4* result = guidedPasses( ctx, *params, w, h, pxDim, (const float4*) D.ping, outs, (const float4*) D.position, (const float4*) D.normal,
+		(const float4*) D.albedo, (const float4*) dOriginal.get(), (float*) dVariance.get() );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
 	PBR_TRY( readBack( ctx, rgba, result, sizeof( float4 ) * pixels ) );
-	PBR_TRY( readBack( ctx, variance_out, dVariance.p, sizeof( float ) * pixels ) );
+	PBR_TRY( readBack( ctx, variance_out, dVariance.get(), sizeof( float ) * pixels ) );
 	PBR_TRY( readFeatures( ctx, features, D, pixels ) );
 	return timedTail( ctx );
 }
@@ -3327,16 +3137,16 @@ int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim,
 	FilterPlanes D;
 	DevBuf dOriginal, dVariance;
 	HIP_TRY( ctx, D.alloc( pixels ) );
-	HIP_TRY( ctx, hipMemcpyAsync( D.position.p, features, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( D.normal.p, features + 4 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( D.albedo.p, features + 8 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.position, features, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.normal, features + 4 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( D.albedo, features + 8 * pixels, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
 	const float4* result = nullptr;
 	std::vector<float> working;
 
 	if( kind == 0 ) {
-		HIP_TRY( ctx, hipMemcpyAsync( D.ping.p, image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-		result = plainPasses( ctx, *plain, width, height, pxDim, (float4*) D.ping.p, (float4*) D.pong.p, (const float4*) D.position.p,
-			(const float4*) D.normal.p, (const float4*) D.albedo.p );
+		HIP_TRY( ctx, hipMemcpyAsync( D.ping, image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		result = plainPasses( ctx, *plain, width, height, pxDim, (float4*) D.ping, (float4*) D.pong, (const float4*) D.position,
+			(const float4*) D.normal, (const float4*) D.albedo );
 	} else {
 		// the filter's first input as pixelVariance builds `working`: {r, g, b, var}
 		working.assign( image, image + 4 * pixels );
@@ -3347,18 +3157,18 @@ int pbr_diag_filter( pbr_ctx* ctx, int kind, int width, int height, float pxDim,
 
 		HIP_TRY( ctx, dOriginal.alloc( sizeof( float4 ) * pixels ) );
 		HIP_TRY( ctx, dVariance.alloc( sizeof( float ) * pixels ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dOriginal.p, image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( D.ping.p, working.data(), sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-		float4* const outs[2] = { (float4*) D.pong.p, (float4*) D.ping.p };
-		result = guidedPasses( ctx, *guided, width, height, pxDim, (const float4*) D.ping.p, outs, (const float4*) D.position.p,
-			(const float4*) D.normal.p, (const float4*) D.albedo.p, (const float4*) dOriginal.p, (float*) dVariance.p );
+		HIP_TRY( ctx, hipMemcpyAsync( dOriginal.get(), image, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( D.ping, working.data(), sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		float4* const outs[2] = { (float4*) D.pong, (float4*) D.ping };
+		result = guidedPasses( ctx, *guided, width, height, pxDim, (const float4*) D.ping, outs, (const float4*) D.position,
+			(const float4*) D.normal, (const float4*) D.albedo, (const float4*) dOriginal.get(), (float*) dVariance.get() );
 	}
 
 	HIP_TRY( ctx, hipGetLastError() );
 	// staged, so that a call that fails on the device has written nothing
 	std::vector<float> rgba( 4 * pixels ), var( ( kind == 1 && variance_out != nullptr ) ? pixels : 0 );
 	PBR_TRY( readBack( ctx, rgba.data(), result, sizeof( float4 ) * pixels ) );
-	PBR_TRY( readBack( ctx, var.empty() ? nullptr : var.data(), dVariance.p, sizeof( float ) * pixels ) );
+	PBR_TRY( readBack( ctx, var.empty() ? nullptr : var.data(), dVariance.get(), sizeof( float ) * pixels ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	std::copy( rgba.begin(), rgba.end(), rgba_out );
 	std::copy( var.begin(), var.end(), variance_out );
@@ -3445,16 +3255,16 @@ int pbr_diag_temporal( pbr_ctx* ctx, int width, int height, float pxDim, const p
 		working[4 * at + 3] = variance[at];
 	}
 
-	HIP_TRY( ctx, hipMemcpyAsync( dWorking.p, working.data(), plane, hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( dFeatures.p, features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dWorking.get(), working.data(), plane, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dFeatures.get(), features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
 
 	if( hasHistory ) {
 		HIP_TRY( ctx, dPrevI.alloc( plane ) );
 		HIP_TRY( ctx, dPrevFeatures.alloc( 3 * plane ) );
 		HIP_TRY( ctx, dPrevLengths.alloc( sizeof( unsigned ) * pixels ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dPrevI.p, prev_integrated, plane, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dPrevFeatures.p, prev_features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dPrevLengths.p, prev_lengths, sizeof( unsigned ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevI.get(), prev_integrated, plane, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevFeatures.get(), prev_features, 3 * plane, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dPrevLengths.get(), prev_lengths, sizeof( unsigned ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
 	}
 	if( moving ) {
 		HIP_TRY( ctx, dFace.alloc( sizeof( int ) * pixels ) );
@@ -3463,31 +3273,31 @@ int pbr_diag_temporal( pbr_ctx* ctx, int width, int height, float pxDim, const p
 		HIP_TRY( ctx, dHistVertices.alloc( sizeof( float4 ) * num_vertices ) );
 		HIP_TRY( ctx, dMotion.alloc( plane ) );
 		HIP_TRY( ctx, dReference.alloc( plane ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dFace.p, face, sizeof( int ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dFacesV.p, facesV, sizeof( uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dVertices.p, vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
-		HIP_TRY( ctx, hipMemcpyAsync( dHistVertices.p, hist_vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dFace.get(), face, sizeof( int ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dFacesV.get(), facesV, sizeof( uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dVertices.get(), vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( dHistVertices.get(), hist_vertices, sizeof( float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
 	}
 
 	// without a previous state the old camera is never read by a pixel: this call's stands in
 	const ptd::TemporalArgs A = ptd::temporalArgs( *temporal, width, height, pxDim, hasHistory, hasHistory ? *prev_cam : *cam,
 		hasHistory ? prev_pxDim : pxDim, ptd::cameraTerms( *cam, width, height, pxDim ) );
-	const float4* dF = (const float4*) dFeatures.p;
-	const float4* dPF = (const float4*) dPrevFeatures.p;
-	const TemporalStepPlanes S = { (float4*) dWorking.p, dF, dF + pixels, dF + 2 * pixels,
-		(const float4*) dPrevI.p, dPF, hasHistory ? dPF + pixels : nullptr, hasHistory ? dPF + 2 * pixels : nullptr,
-		(const unsigned*) dPrevLengths.p, (unsigned*) dLengths.p, (float4*) dInfo.p, (const int*) dFace.p, (const uint4*) dFacesV.p,
-		(const float4*) dVertices.p, (const float4*) dHistVertices.p, (float4*) dMotion.p, (float4*) dReference.p };
+	const float4* dF = (const float4*) dFeatures.get();
+	const float4* dPF = (const float4*) dPrevFeatures.get();
+	const TemporalStepPlanes S = { (float4*) dWorking.get(), dF, dF + pixels, dF + 2 * pixels,
+		(const float4*) dPrevI.get(), dPF, hasHistory ? dPF + pixels : nullptr, hasHistory ? dPF + 2 * pixels : nullptr,
+		(const unsigned*) dPrevLengths.get(), (unsigned*) dLengths.get(), (float4*) dInfo.get(), (const int*) dFace.get(), (const uint4*) dFacesV.get(),
+		(const float4*) dVertices.get(), (const float4*) dHistVertices.get(), (float4*) dMotion.get(), (float4*) dReference.get() };
 	temporalSteps( ctx, A, width, height, moving, S );
 	HIP_TRY( ctx, hipGetLastError() );
 	// staged, so that a call that fails on the device has written nothing
 	std::vector<float> outI( 4 * pixels ), outInfo( 4 * pixels ), outMotion( moving ? 4 * pixels : 0 ), outReference( moving ? 4 * pixels : 0 );
 	std::vector<uint32_t> outLengths( pixels );
-	PBR_TRY( readBack( ctx, outI.data(), dWorking.p, plane ) );
-	PBR_TRY( readBack( ctx, outInfo.data(), dInfo.p, plane ) );
-	PBR_TRY( readBack( ctx, outLengths.data(), dLengths.p, sizeof( uint32_t ) * pixels ) );
-	PBR_TRY( readBack( ctx, moving ? outMotion.data() : nullptr, dMotion.p, plane ) );
-	PBR_TRY( readBack( ctx, moving ? outReference.data() : nullptr, dReference.p, plane ) );
+	PBR_TRY( readBack( ctx, outI.data(), dWorking.get(), plane ) );
+	PBR_TRY( readBack( ctx, outInfo.data(), dInfo.get(), plane ) );
+	PBR_TRY( readBack( ctx, outLengths.data(), dLengths.get(), sizeof( uint32_t ) * pixels ) );
+	PBR_TRY( readBack( ctx, moving ? outMotion.data() : nullptr, dMotion.get(), plane ) );
+	PBR_TRY( readBack( ctx, moving ? outReference.data() : nullptr, dReference.get(), plane ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	std::copy( outI.begin(), outI.end(), integrated );
 	std::copy( outInfo.begin(), outInfo.end(), history );
@@ -3514,10 +3324,9 @@ int pbr_temporal_track_motion( pbr_ctx* ctx, int on ) {
 
 	ctx->temporal.track( on != 0 );
 
-	if( on == 0 && ctx->dHistVertices != nullptr ) {
+	if( on == 0 && ctx->scene.dHistVertices != nullptr ) {
 		HIP_TRY( ctx, hipSetDevice( ctx->device ) );
-		HIP_TRY( ctx, hipFree( ctx->dHistVertices ) );
-		ctx->dHistVertices = nullptr;
+		ctx->scene.dHistVertices.reset();
 	}
 
 	return PBR_OK;
@@ -3526,14 +3335,14 @@ int pbr_temporal_track_motion( pbr_ctx* ctx, int on ) {
 // The planes of the last successful pbr_denoise_temporal's motion step: {Pprev, code} and the first-hit face per pixel.
 int pbr_read_temporal_motion( pbr_ctx* ctx, float* motion, int32_t* face ) {
 	PBR_TRY( usable( ctx ) );
-	if( !ctx->temporal.lastMotion || ctx->planes.face == nullptr ) {
+	if( !ctx->temporal.lastMotion || ctx->images.planes.face == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "pbr_read_temporal_motion: the last successful pbr_denoise_temporal did not take the motion path (it needs pbr_temporal_track_motion, a history and a pbr_update_vertices since that history)" );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const size_t pixels = (size_t) ctx->cfg.width * (size_t) ctx->cfg.height;
-	PBR_TRY( readBack( ctx, motion, ctx->planes.motion, sizeof( float4 ) * pixels ) );
-	PBR_TRY( readBack( ctx, face, ctx->planes.face, sizeof( int32_t ) * pixels ) );
+	PBR_TRY( readBack( ctx, motion, ctx->images.planes.motion, sizeof( float4 ) * pixels ) );
+	PBR_TRY( readBack( ctx, face, ctx->images.planes.face, sizeof( int32_t ) * pixels ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 	return PBR_OK;
 }
@@ -3558,19 +3367,19 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	const int w = (int) ctx->cfg.width, h = (int) ctx->cfg.height;
 	const size_t pixels = (size_t) w * (size_t) h;
-	TemporalPlanes& T = ctx->planes;
+	TemporalPlanes& T = ctx->images.planes;
 	// static geometry, or per-vertex motion in front of the integration (pt_temporal_host.hpp decides).  The planes come with
 	// the first call since pbr_configure, the motion path's with the first call that takes it; new planes are no history
 	const TemporalPolicy::Path path = ctx->temporal.path();
-	const bool motion = ( path == TemporalPolicy::MOTION ), first = ( T.variance == nullptr );
+	const bool motion = ( path == TemporalPolicy::MOTION ), first = T.variance.empty();
 
-	if( T.alloc( pixels, motion ) != hipSuccess ) {
+	if( T.alloc( pixels, motion ) != 0 ) {
 		return fail( ctx, PBR_EDEVICE, "pbr_denoise_temporal: no device memory for the history" );
 	}
 	if( first ) {
 		ctx->temporal.drop();
 	}
-	if( motion && ( ctx->dHistVertices == nullptr || ctx->dFacesV == nullptr ) ) {
+	if( motion && ( ctx->scene.dHistVertices == nullptr || ctx->scene.dFacesV == nullptr ) ) {
 		return fail( ctx, PBR_ESTATE, "pbr_denoise_temporal: the history's vertex positions are missing" );   // cannot happen: `moved` implies the copy
 	}
 
@@ -3579,7 +3388,7 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 	const float4* dPosition = T.position[cur];
 	const float4* dNormal = T.normal[cur];
 	const float4* dAlbedo = T.albedo[cur];
-	float4* dOriginal = ctx->dRows;   // the staging of every read-back: free between calls
+	float4* dOriginal = ctx->images.dRows;   // the staging of every read-back: free between calls
 
 	DevParams P;
 	PBR_TRY( sceneParams( ctx, &P ) );
@@ -3588,14 +3397,14 @@ int pbr_denoise_temporal( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, cons
 
 	const dim3 grid = imageGrid( w, h );
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
-	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
-	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->dMoments, (const unsigned*) ctx->dTileFrames,
+	hipLaunchKernelGGL( ptk::untile, grid, kImageBlock, 0, ctx->stream, (const float4*) ctx->images.dImgOut, dOriginal, w, h, ctx->tilesX, 1, 0 );
+	hipLaunchKernelGGL( ptd::pixelVariance, grid, kImageBlock, 0, ctx->stream, (const float2*) ctx->images.dMoments, (const unsigned*) ctx->images.dTileFrames,
 		ctx->varianceFirstCount, (const float4*) dOriginal, (float*) nullptr, dI, w, h, ctx->tilesX );
 	hipLaunchKernelGGL( ptd::firstHitFeatures, grid, kImageBlock, 0, ctx->stream, P, T.position[cur], T.normal[cur], T.albedo[cur], motion ? T.face : (int*) nullptr );
 
 	const TemporalStepPlanes S = { dI, dPosition, dNormal, dAlbedo, T.integrated[prev], T.position[prev], T.normal[prev], T.albedo[prev],
-		T.length[prev], T.length[cur], ( history != nullptr ) ? T.info : (float4*) nullptr, T.face, (const uint4*) ctx->dFacesV,
-		(const float4*) ctx->dVertices, (const float4*) ctx->dHistVertices, T.motion, T.reference };
+		T.length[prev], T.length[cur], ( history != nullptr ) ? T.info : (float4*) nullptr, T.face, (const uint4*) ctx->scene.dFacesV,
+		(const float4*) ctx->scene.dVertices, (const float4*) ctx->scene.dHistVertices, T.motion, T.reference };
 	temporalSteps( ctx, A, w, h, motion, S );
 	HIP_TRY( ctx, hipGetLastError() );
 
@@ -3637,16 +3446,16 @@ int buildRadixTree( pbr_ctx* ctx, ptb::BuildArrays B, uint32_t num_faces, uint32
 	HIP_TRY( ctx, dArrived.alloc( sizeof( unsigned ) * treeNodes ) );
 	HIP_TRY( ctx, dBoxMin.alloc( sizeof( float4 ) * treeNodes ) );
 	HIP_TRY( ctx, dBoxMax.alloc( sizeof( float4 ) * treeNodes ) );
-	HIP_TRY( ctx, hipMemsetAsync( dParent.p, 0xFF, sizeof( int ) * treeNodes, ctx->stream ) );
-	HIP_TRY( ctx, hipMemsetAsync( dArrived.p, 0, sizeof( unsigned ) * treeNodes, ctx->stream ) );
+	HIP_TRY( ctx, hipMemsetAsync( dParent.get(), 0xFF, sizeof( int ) * treeNodes, ctx->stream ) );
+	HIP_TRY( ctx, hipMemsetAsync( dArrived.get(), 0, sizeof( unsigned ) * treeNodes, ctx->stream ) );
 	B.numLeaves = leaves;
-	B.left = (int*) dLeft.p;
-	B.right = (int*) dRight.p;
-	B.parent = (int*) dParent.p;
-	B.size = (unsigned*) dSize.p;
-	B.arrived = (unsigned*) dArrived.p;
-	B.boxMin = (float4*) dBoxMin.p;
-	B.boxMax = (float4*) dBoxMax.p;
+	B.left = (int*) dLeft.get();
+	B.right = (int*) dRight.get();
+	B.parent = (int*) dParent.get();
+	B.size = (unsigned*) dSize.get();
+	B.arrived = (unsigned*) dArrived.get();
+	B.boxMin = (float4*) dBoxMin.get();
+	B.boxMax = (float4*) dBoxMax.get();
 	const unsigned threads = 256;
 	const unsigned leafBlocks = ( leaves + threads - 1 ) / threads;
 	const unsigned nodeBlocks = ( treeNodes + threads - 1 ) / threads;
@@ -3687,19 +3496,19 @@ int buildClustered( pbr_ctx* ctx, const ptb::BuildArrays& A, uint32_t num_faces,
 	B.facesN = A.facesN;
 	B.numFaces = num_faces;
 	B.keysSorted = A.keysSorted;
-	B.left = (int*) dLeft.p;
-	B.right = (int*) dRight.p;
-	B.parent = (int*) dParent.p;
-	B.size = (unsigned*) dSize.p;
-	B.faces = (unsigned*) dFaces.p;
-	B.boxMin = (float4*) dBoxMin.p;
-	B.boxMax = (float4*) dBoxMax.p;
-	B.clusters = (int*) dClusters.p;
-	B.clustersNext = (int*) dClustersNext.p;
-	B.nearest = (int*) dNearest.p;
-	B.flags = (unsigned long long*) dFlags.p;
-	B.scan = (unsigned long long*) dScan.p;
-	B.totals = (unsigned long long*) dTotals.p;
+	B.left = (int*) dLeft.get();
+	B.right = (int*) dRight.get();
+	B.parent = (int*) dParent.get();
+	B.size = (unsigned*) dSize.get();
+	B.faces = (unsigned*) dFaces.get();
+	B.boxMin = (float4*) dBoxMin.get();
+	B.boxMax = (float4*) dBoxMax.get();
+	B.clusters = (int*) dClusters.get();
+	B.clustersNext = (int*) dClustersNext.get();
+	B.nearest = (int*) dNearest.get();
+	B.flags = (unsigned long long*) dFlags.get();
+	B.scan = (unsigned long long*) dScan.get();
+	B.totals = (unsigned long long*) dTotals.get();
 	B.nodesOut = A.nodesOut;
 	B.facesVOut = A.facesVOut;
 	B.facesNOut = A.facesNOut;
@@ -3730,7 +3539,7 @@ int buildClustered( pbr_ctx* ctx, const ptb::BuildArrays& A, uint32_t num_faces,
 		const dim3 grid( ( count + threads - 1 ) / threads );
 		hipLaunchKernelGGL( ptb::plocNearest, grid, dim3( threads ), 0, ctx->stream, B, count, radius );
 		hipLaunchKernelGGL( ptb::plocFlags, grid, dim3( threads ), 0, ctx->stream, B, count );
-		HIP_TRY( ctx, hipcub::DeviceScan::ExclusiveSum( dTemp.p, tempBytes, B.flags, B.scan, (int) count, ctx->stream ) );
+		HIP_TRY( ctx, hipcub::DeviceScan::ExclusiveSum( dTemp.get(), tempBytes, B.flags, B.scan, (int) count, ctx->stream ) );
 		hipLaunchKernelGGL( ptb::plocMerge, grid, dim3( threads ), 0, ctx->stream, B, count, nextNode );
 		HIP_TRY( ctx, hipGetLastError() );
 		unsigned long long totals = 0;
@@ -3802,26 +3611,26 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 	HIP_TRY( ctx, dFacesVOut.alloc( sizeof( pbr_uint4 ) * num_faces ) );
 	HIP_TRY( ctx, dFacesNOut.alloc( sizeof( pbr_uint4 ) * num_faces ) );
 
-	HIP_TRY( ctx, hipMemcpyAsync( dVertices.p, vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( dFacesV.p, facesV, sizeof( pbr_uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( dFacesN.p, facesN, sizeof( pbr_uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dVertices.get(), vertices, sizeof( pbr_float4 ) * num_vertices, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dFacesV.get(), facesV, sizeof( pbr_uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dFacesN.get(), facesN, sizeof( pbr_uint4 ) * num_faces, hipMemcpyHostToDevice, ctx->stream ) );
 	// order-preserving unsigned images of +inf (minima) and -inf (maxima), see ptb::atomicMinFloat
 	const unsigned bounds[8] = { 0xFF800000u, 0xFF800000u, 0xFF800000u, 0u, 0x007FFFFFu, 0x007FFFFFu, 0x007FFFFFu, 0u };
-	HIP_TRY( ctx, hipMemcpyAsync( dBounds.p, bounds, sizeof( bounds ), hipMemcpyHostToDevice, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( dBounds.get(), bounds, sizeof( bounds ), hipMemcpyHostToDevice, ctx->stream ) );
 
 	ptb::BuildArrays B;
 	std::memset( &B, 0, sizeof( B ) );
-	B.vertices = (const pbr_float4*) dVertices.p;
-	B.facesV = (const pbr_uint4*) dFacesV.p;
-	B.facesN = (const pbr_uint4*) dFacesN.p;
+	B.vertices = (const pbr_float4*) dVertices.get();
+	B.facesV = (const pbr_uint4*) dFacesV.get();
+	B.facesN = (const pbr_uint4*) dFacesN.get();
 	B.numFaces = num_faces;
-	B.keys = (unsigned long long*) dKeys.p;
-	B.keysSorted = (unsigned long long*) dKeysSorted.p;
-	B.sceneMin = (float*) dBounds.p;
-	B.sceneMax = (float*) dBounds.p + 4;
-	B.nodesOut = (pbr_bvh_node*) dNodes.p;
-	B.facesVOut = (pbr_uint4*) dFacesVOut.p;
-	B.facesNOut = (pbr_uint4*) dFacesNOut.p;
+	B.keys = (unsigned long long*) dKeys.get();
+	B.keysSorted = (unsigned long long*) dKeysSorted.get();
+	B.sceneMin = (float*) dBounds.get();
+	B.sceneMax = (float*) dBounds.get() + 4;
+	B.nodesOut = (pbr_bvh_node*) dNodes.get();
+	B.facesVOut = (pbr_uint4*) dFacesVOut.get();
+	B.facesNOut = (pbr_uint4*) dFacesNOut.get();
 
 	const unsigned threads = 256;
 	const unsigned faceBlocks = ( num_faces + threads - 1 ) / threads;
@@ -3834,7 +3643,7 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 	size_t tempBytes = 0;
 	HIP_TRY( ctx, hipcub::DeviceRadixSort::SortKeys( nullptr, tempBytes, B.keys, B.keysSorted, (int) num_faces, 0, 64, ctx->stream ) );
 	HIP_TRY( ctx, dTemp.alloc( tempBytes ) );
-	HIP_TRY( ctx, hipcub::DeviceRadixSort::SortKeys( dTemp.p, tempBytes, B.keys, B.keysSorted, (int) num_faces, 0, 64, ctx->stream ) );
+	HIP_TRY( ctx, hipcub::DeviceRadixSort::SortKeys( dTemp.get(), tempBytes, B.keys, B.keysSorted, (int) num_faces, 0, 64, ctx->stream ) );
 
 	uint32_t treeNodes = 0;
 	PBR_TRY( radix ? buildRadixTree( ctx, B, num_faces, &treeNodes ) : buildClustered( ctx, B, num_faces, &treeNodes ) );
@@ -3843,9 +3652,9 @@ int pbr_build_bvh( pbr_ctx* ctx, const pbr_float4* vertices, uint32_t num_vertic
 
 	// a tree that is a single leaf has no container above it, but the walk starts at node 1 (pt_bvh.cl:84): give it a root
 	pbr_bvh_node* firstTreeNode = ( treeNodes == 1 ) ? nodes_out + 1 : nodes_out;
-	HIP_TRY( ctx, hipMemcpyAsync( firstTreeNode, dNodes.p, sizeof( pbr_bvh_node ) * treeNodes, hipMemcpyDeviceToHost, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( facesV_out, dFacesVOut.p, sizeof( pbr_uint4 ) * num_faces, hipMemcpyDeviceToHost, ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpyAsync( facesN_out, dFacesNOut.p, sizeof( pbr_uint4 ) * num_faces, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( firstTreeNode, dNodes.get(), sizeof( pbr_bvh_node ) * treeNodes, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( facesV_out, dFacesVOut.get(), sizeof( pbr_uint4 ) * num_faces, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( facesN_out, dFacesNOut.get(), sizeof( pbr_uint4 ) * num_faces, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
 
 	if( treeNodes == 1 ) {
@@ -3911,13 +3720,13 @@ int pbr_diag_math( pbr_ctx* ctx, int op, const float* x, const float* y, int n, 
 	HIP_TRY( ctx, dx.alloc( bytes ) );
 	HIP_TRY( ctx, dy.alloc( bytes ) );
 	HIP_TRY( ctx, dout.alloc( bytes ) );
-	HIP_TRY( ctx, hipMemcpy( dx.p, x, bytes, hipMemcpyHostToDevice ) );
-	HIP_TRY( ctx, hipMemcpy( dy.p, ( y != nullptr ) ? y : x, bytes, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dx.get(), x, bytes, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dy.get(), ( y != nullptr ) ? y : x, bytes, hipMemcpyHostToDevice ) );
 	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream,
-		op, (const float*) dx.p, (const float*) dy.p, n, (float*) dout.p );
+		op, (const float*) dx.get(), (const float*) dy.get(), n, (float*) dout.get() );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, dout.p, bytes, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, dout.get(), bytes, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -3936,30 +3745,30 @@ int pbr_diag_trace( pbr_ctx* ctx, const float* rays, int n, float* out_t, int32_
 	HIP_TRY( ctx, dFace.alloc( sizeof( int ) * (size_t) n ) );
 	HIP_TRY( ctx, dNormal.alloc( sizeof( float ) * 3 * (size_t) n ) );
 	HIP_TRY( ctx, dCounts.alloc( sizeof( unsigned ) * 2 * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dRays.p, rays, sizeof( float ) * 6 * (size_t) n, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dRays.get(), rays, sizeof( float ) * 6 * (size_t) n, hipMemcpyHostToDevice ) );
 
 	DevParams P;
 	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
 	// Phong tessellation configured and the vertex-normal records uploaded: the PHONG build of the walk, as a render takes it
-	const bool phong = ctx->configured && ctx->cfg.phong_tessellation > 0.0f && ctx->dTriPN != nullptr;
-	P.triPN = ctx->dTriPN;
+	const bool phong = ctx->configured && ctx->cfg.phong_tessellation > 0.0f && ctx->scene.dTriPN != nullptr;
+	P.triPN = ctx->scene.dTriPN;
 	P.phongAlpha = phong ? ctx->cfg.phong_tessellation : 0.0f;
-	const void* kernel = ( ctx->numLights > 0 )
+	const void* kernel = ( ctx->scene.numLights > 0 )
 		? ( phong ? (const void*) ptk::diagTrace<true, true> : (const void*) ptk::diagTrace<true, false> )
 		: ( phong ? (const void*) ptk::diagTrace<false, true> : (const void*) ptk::diagTrace<false, false> );
 	typedef void ( *DiagTraceFn )( const ptk::DevParams, const float*, int, float*, int*, float*, unsigned* );
 
-	hipLaunchKernelGGL( (DiagTraceFn) kernel, grid, block, 0, ctx->stream, P, (const float*) dRays.p, n,
-		(float*) dT.p, (int*) dFace.p, (float*) dNormal.p, (unsigned*) dCounts.p );
+	hipLaunchKernelGGL( (DiagTraceFn) kernel, grid, block, 0, ctx->stream, P, (const float*) dRays.get(), n,
+		(float*) dT.get(), (int*) dFace.get(), (float*) dNormal.get(), (unsigned*) dCounts.get() );
 
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out_t, dT.p, sizeof( float ) * (size_t) n, hipMemcpyDeviceToHost ) );
-	HIP_TRY( ctx, hipMemcpy( out_face, dFace.p, sizeof( int ) * (size_t) n, hipMemcpyDeviceToHost ) );
-	HIP_TRY( ctx, hipMemcpy( out_normal, dNormal.p, sizeof( float ) * 3 * (size_t) n, hipMemcpyDeviceToHost ) );
-	HIP_TRY( ctx, hipMemcpy( out_counts, dCounts.p, sizeof( unsigned ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_t, dT.get(), sizeof( float ) * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_face, dFace.get(), sizeof( int ) * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_normal, dNormal.get(), sizeof( float ) * 3 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_counts, dCounts.get(), sizeof( unsigned ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -3972,7 +3781,7 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	if( in == nullptr || out == nullptr || n <= 0 ) {
 		return fail( ctx, PBR_EINVAL, "diag: bad argument" );
 	}
-	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, stage, ctx->sceneBrdf );
+	const DiagItemFn kernel = (DiagItemFn) diagKernel( ctx, stage, ctx->scene.sceneBrdf );
 	if( kernel == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "diag: this library was built without the native-arithmetic diagnostics" );
 	}
@@ -3981,17 +3790,17 @@ int diagPerItem( pbr_ctx* ctx, const float* in, int n, float* out, int inWidth, 
 	DevBuf dIn, dOut;
 	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * inWidth * (size_t) n ) );
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * outWidth * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dIn.get(), in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
 
 	DevParams P;
 	PBR_TRY( sceneParams( ctx, &P ) );
 	const dim3 grid( (unsigned) ( ( n + 63 ) / 64 ) ), block( 64 );
 
-	hipLaunchKernelGGL( kernel, grid, block, 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
+	hipLaunchKernelGGL( kernel, grid, block, 0, ctx->stream, P, (const float*) dIn.get(), n, (float*) dOut.get() );
 
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * outWidth * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.get(), sizeof( float ) * outWidth * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4009,11 +3818,11 @@ int diagPlain( pbr_ctx* ctx, const char* what, int stage, const float* in, int n
 	DevBuf dIn, dOut;
 	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * inWidth * (size_t) n ) );
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * outWidth * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
-	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, (const float*) dIn.p, n, (float*) dOut.p );
+	HIP_TRY( ctx, hipMemcpy( dIn.get(), in, sizeof( float ) * inWidth * (size_t) n, hipMemcpyHostToDevice ) );
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, (const float*) dIn.get(), n, (float*) dOut.get() );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * outWidth * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.get(), sizeof( float ) * outWidth * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4055,7 +3864,7 @@ int pbr_diag_camera_ray( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const
 	DevBuf dIn, dOut;
 	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * 8 * (size_t) n ) );
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * 8 * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dIn.get(), in, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
 
 	// the camera as beginRender hands it to a render's kernels; initRay reads nothing else of P
 	DevParams P;
@@ -4064,10 +3873,10 @@ int pbr_diag_camera_ray( pbr_ctx* ctx, float pxDim, const pbr_camera* cam, const
 	P.aperture = cam->lense[0] / cam->lense[1];
 	P.antiAliasing = ctx->cfg.anti_aliasing;
 
-	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, P, (const float*) dIn.p, n, (float*) dOut.p );
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, P, (const float*) dIn.get(), n, (float*) dOut.get() );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * 8 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.get(), sizeof( float ) * 8 * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4085,11 +3894,11 @@ int pbr_diag_intersect( pbr_ctx* ctx, int op, const float* in, int n, float* out
 	DevBuf dIn, dOut;
 	HIP_TRY( ctx, dIn.alloc( sizeof( float ) * 24 * (size_t) n ) );
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * 4 * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dIn.p, in, sizeof( float ) * 24 * (size_t) n, hipMemcpyHostToDevice ) );
-	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, op, (const float*) dIn.p, n, (float*) dOut.p );
+	HIP_TRY( ctx, hipMemcpy( dIn.get(), in, sizeof( float ) * 24 * (size_t) n, hipMemcpyHostToDevice ) );
+	hipLaunchKernelGGL( kernel, dim3( (unsigned) ( ( n + 63 ) / 64 ) ), dim3( 64 ), 0, ctx->stream, op, (const float*) dIn.get(), n, (float*) dOut.get() );
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, dOut.p, sizeof( float ) * 4 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, dOut.get(), sizeof( float ) * 4 * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4104,7 +3913,7 @@ int pbr_diag_trace_stream( pbr_ctx* ctx, int mode, const float* rays8, uint32_t 
 	DevBuf dRays, dOut;
 	HIP_TRY( ctx, dRays.alloc( sizeof( float ) * 8 * (size_t) n ) );
 	HIP_TRY( ctx, dOut.alloc( sizeof( float ) * 2 * (size_t) n ) );
-	HIP_TRY( ctx, hipMemcpy( dRays.p, rays8, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
+	HIP_TRY( ctx, hipMemcpy( dRays.get(), rays8, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
 
 	uint32_t hotAvail = 0;
 	DevParams P;
@@ -4128,11 +3937,11 @@ int pbr_diag_trace_stream( pbr_ctx* ctx, int mode, const float* rays8, uint32_t 
 		const dim3 grid( (unsigned) ( ctx->numCUs * blocksPerCU ) ), block( PBR_BLOCK );
 
 		if( slots == 0 ) {
-			hipLaunchKernelGGL( ptk::diagTraceStream<false>, grid, block, 0, ctx->stream, P, (const float4*) dRays.p, n, (float2*) dOut.p );
+			hipLaunchKernelGGL( ptk::diagTraceStream<false>, grid, block, 0, ctx->stream, P, (const float4*) dRays.get(), n, (float2*) dOut.get() );
 		}
 		else {
 			HIP_TRY( ctx, hipFuncSetAttribute( (const void*) ptk::diagTraceStream<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ( slots * 32 ) ) );
-			hipLaunchKernelGGL( ptk::diagTraceStream<true>, grid, block, slots * 32, ctx->stream, P, (const float4*) dRays.p, n, (float2*) dOut.p );
+			hipLaunchKernelGGL( ptk::diagTraceStream<true>, grid, block, slots * 32, ctx->stream, P, (const float4*) dRays.get(), n, (float2*) dOut.get() );
 		}
 
 		HIP_TRY( ctx, hipGetLastError() );
@@ -4143,7 +3952,7 @@ int pbr_diag_trace_stream( pbr_ctx* ctx, int mode, const float* rays8, uint32_t 
 		best = ( ms < best ) ? ms : best;
 	}
 
-	HIP_TRY( ctx, hipMemcpy( out2, dOut.p, sizeof( float ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out2, dOut.get(), sizeof( float ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
 	*ms_out = best;
 	return PBR_OK;
 }
@@ -4161,7 +3970,7 @@ int pbr_diag_calibrate( pbr_ctx* ctx, int mode, uint64_t table_bytes, uint64_t r
 	DevBuf table, sink;
 	HIP_TRY( ctx, table.alloc( (size_t) table_bytes ) );
 	HIP_TRY( ctx, sink.alloc( 64 ) );
-	HIP_TRY( ctx, hipMemset( table.p, 0, (size_t) table_bytes ) );
+	HIP_TRY( ctx, hipMemset( table.get(), 0, (size_t) table_bytes ) );
 	HIP_TRY( ctx, hipDeviceSynchronize() );
 
 	const unsigned long long count = table_bytes / 16;
@@ -4172,13 +3981,13 @@ int pbr_diag_calibrate( pbr_ctx* ctx, int mode, uint64_t table_bytes, uint64_t r
 	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
 
 	if( mode == 0 ) {
-		hipLaunchKernelGGL( ptk::diagCalibrate<0>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.p, count, steps, (float*) sink.p );
+		hipLaunchKernelGGL( ptk::diagCalibrate<0>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.get(), count, steps, (float*) sink.get() );
 	}
 	else if( mode == 1 ) {
-		hipLaunchKernelGGL( ptk::diagCalibrate<1>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.p, count, steps, (float*) sink.p );
+		hipLaunchKernelGGL( ptk::diagCalibrate<1>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.get(), count, steps, (float*) sink.get() );
 	}
 	else {
-		hipLaunchKernelGGL( ptk::diagCalibrate<2>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.p, count, steps, (float*) sink.p );
+		hipLaunchKernelGGL( ptk::diagCalibrate<2>, dim3( blocks ), dim3( 256 ), 0, ctx->stream, (const float4*) table.get(), count, steps, (float*) sink.get() );
 	}
 
 	HIP_TRY( ctx, hipGetLastError() );
@@ -4244,9 +4053,9 @@ int pbr_diag_scene_bytes( pbr_ctx* ctx, uint64_t out[3] ) {
 		return fail( ctx, PBR_ESTATE, "diag_scene_bytes: no scene" );
 	}
 
-	out[0] = ctx->nodeBytes;
-	out[1] = ctx->walkBytes;
-	out[2] = ctx->triBytes;
+	out[0] = ctx->scene.dNodes.bytes();
+	out[1] = ctx->scene.walk.dNodesWalk.bytes();
+	out[2] = ctx->scene.dTris.bytes();
 	return PBR_OK;
 }
 
@@ -4255,20 +4064,20 @@ int pbr_diag_refit_info( pbr_ctx* ctx, uint64_t out[8], double* upload_ms, char*
 		return fail( ctx, PBR_ESTATE, "diag_refit_info: no scene" );
 	}
 
-	out[0] = ctx->refit.nested ? 1 : 0;
-	out[1] = ctx->refit.subtreeCap;
-	out[2] = ctx->refitGroups;
-	out[3] = ctx->refitSubtrees;
-	out[4] = ctx->refitTopNodes;
-	out[5] = ctx->refitLevels;
-	out[6] = ctx->refitBytes;
-	out[7] = ctx->refitUpdates;
+	out[0] = ctx->scene.refit.nested ? 1 : 0;
+	out[1] = ctx->scene.refit.subtreeCap;
+	out[2] = ctx->scene.refitGroups;
+	out[3] = ctx->scene.refitSubtrees;
+	out[4] = ctx->scene.refitTopNodes;
+	out[5] = ctx->scene.refitLevels;
+	out[6] = ctx->scene.refitBytes();
+	out[7] = ctx->scene.refitUpdates;
 
 	if( upload_ms != nullptr ) {
 		*upload_ms = ctx->lastRefitUploadMs;
 	}
 	if( why != nullptr && capacity > 0 ) {
-		std::snprintf( why, capacity, "%s", ctx->refit.why.c_str() );
+		std::snprintf( why, capacity, "%s", ctx->scene.refit.why.c_str() );
 	}
 
 	return PBR_OK;
@@ -4285,13 +4094,13 @@ int pbr_diag_patch_refit_info( pbr_ctx* ctx, uint64_t out[4], float* alpha ) {
 		return fail( ctx, PBR_ESTATE, "diag_patch_refit_info: no scene" );
 	}
 
-	out[0] = ( ctx->dTriPN != nullptr ) ? 1 : 0;
-	out[1] = ctx->patchBytes;
-	out[2] = ctx->geometryUpdates;
+	out[0] = ( ctx->scene.dTriPN != nullptr ) ? 1 : 0;
+	out[1] = ctx->scene.dPatchFacesN.bytes() + ctx->scene.dPatchNormals.bytes() + ctx->scene.dFaceBoxes.bytes();
+	out[2] = ctx->scene.geometryUpdates;
 	out[3] = updateWasGeometry( ctx->lastUpdate ) ? 1 : 0;
 
 	if( alpha != nullptr ) {
-		*alpha = ctx->patchAlpha;
+		*alpha = ctx->scene.patchAlpha;
 	}
 
 	return PBR_OK;
@@ -4301,14 +4110,14 @@ int pbr_diag_read_patches( pbr_ctx* ctx, pbr_float4* out, uint32_t capacity, uin
 	if( ctx == nullptr ) {
 		return PBR_EINVAL;
 	}
-	if( !ctx->hasScene || ctx->dTriPN == nullptr ) {
+	if( !ctx->hasScene || ctx->scene.dTriPN == nullptr ) {
 		return fail( ctx, PBR_ESTATE, "diag_read_patches: no scene, or one without usable vertex normals (no Phong patches)" );
 	}
 	if( count == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "diag_read_patches: null count" );
 	}
 
-	*count = ctx->numFaces * 6u;
+	*count = ctx->scene.numFaces * 6u;
 
 	if( out == nullptr ) {
 		return PBR_OK;
@@ -4319,7 +4128,7 @@ int pbr_diag_read_patches( pbr_ctx* ctx, pbr_float4* out, uint32_t capacity, uin
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, ctx->dTriPN, sizeof( pbr_float4 ) * (size_t) *count, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, ctx->scene.dTriPN, sizeof( pbr_float4 ) * (size_t) *count, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4327,31 +4136,31 @@ int pbr_diag_read_walk( pbr_ctx* ctx, void* out, uint64_t capacity, uint64_t* by
 	if( ctx == nullptr ) {
 		return PBR_EINVAL;
 	}
-	if( !ctx->hasScene || ctx->dNodesWalk == nullptr || ctx->walkBuilt == 0 ) {
+	if( !ctx->hasScene || ctx->scene.walk.dNodesWalk == nullptr || ctx->scene.walk.walkBuilt == 0 ) {
 		return fail( ctx, PBR_ESTATE, "diag_read_walk: no ray-ordered stream is built" );
 	}
 	if( bytes == nullptr ) {
 		return fail( ctx, PBR_EINVAL, "diag_read_walk: null bytes" );
 	}
 
-	*bytes = ctx->walkBytes;
+	*bytes = ctx->scene.walk.dNodesWalk.bytes();
 
 	if( first != nullptr ) {
-		std::memcpy( first, ctx->walkFirst, sizeof( ctx->walkFirst ) );
+		std::memcpy( first, ctx->scene.walk.walkFirst, sizeof( ctx->scene.walk.walkFirst ) );
 	}
 	if( hot_slots != nullptr ) {
-		*hot_slots = ctx->walkHotAvail;
+		*hot_slots = ctx->scene.walk.walkHotAvail;
 	}
 	if( out == nullptr ) {
 		return PBR_OK;
 	}
-	if( capacity < ctx->walkBytes ) {
-		return fail( ctx, PBR_EINVAL, "diag_read_walk: room for %llu bytes, the streams hold %llu", (unsigned long long) capacity, (unsigned long long) ctx->walkBytes );
+	if( capacity < ctx->scene.walk.dNodesWalk.bytes() ) {
+		return fail( ctx, PBR_EINVAL, "diag_read_walk: room for %llu bytes, the streams hold %llu", (unsigned long long) capacity, (unsigned long long) ctx->scene.walk.dNodesWalk.bytes() );
 	}
 
 	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
-	HIP_TRY( ctx, hipMemcpy( out, ctx->dNodesWalk, ctx->walkBytes, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out, ctx->scene.walk.dNodesWalk, ctx->scene.walk.dNodesWalk.bytes(), hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 
@@ -4360,8 +4169,8 @@ int pbr_diag_relink_info( pbr_ctx* ctx, uint64_t out[4], double* ms ) {
 		return fail( ctx, PBR_EINVAL, "diag_relink_info: null argument" );
 	}
 
-	out[0] = ctx->relinkBytes;
-	out[1] = ( ctx->dRelink != nullptr ) ? ctx->relinkLevels : 0;
+	out[0] = ctx->scene.walk.dRelink.bytes();
+	out[1] = ( ctx->scene.walk.dRelink != nullptr ) ? ctx->scene.walk.relinkLevels : 0;
 	out[2] = ctx->lastRelinkLaunches;
 	out[3] = ctx->lastRelinked ? 1 : 0;
 
@@ -4422,7 +4231,7 @@ int pbr_diag_get_tile_order( pbr_ctx* ctx, int which, uint32_t* order, uint32_t 
 		return fail( ctx, PBR_ESTATE, "diag_get_tile_order: no cost order has been learnt yet (it is built after the first render)" );
 	}
 
-	const DealTable& table = ctx->deal[( which == kDealCostClasses || which == kDealExpensiveLast ) ? which : kDealSpatial];
+	const DealTable& table = ctx->images.deal[( which == kDealCostClasses || which == kDealExpensiveLast ) ? which : kDealSpatial];
 	const uint32_t n = (uint32_t) table.host.size();
 
 	if( count != nullptr ) {
@@ -4455,7 +4264,7 @@ int pbr_diag_set_tile_order( pbr_ctx* ctx, const uint32_t* order, uint32_t count
 	std::vector<unsigned> spatial;
 	unsigned spatialFirst[PT_BANDS + 1];
 	spatialTileOrder( ctx->queueGrid, ctx->numLocalTiles, PT_BANDS, &spatial, spatialFirst );
-	DealTable& table = ctx->deal[kDealSpatial];
+	DealTable& table = ctx->images.deal[kDealSpatial];
 
 	if( order == nullptr ) {
 		table.host = spatial;
