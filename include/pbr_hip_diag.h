@@ -134,6 +134,31 @@ int pbr_diag_temporal( pbr_ctx* ctx, int width, int height, float pxDim, const p
  * *ms_out, hits {t, face bits} in out2. */
 int pbr_diag_trace_stream( pbr_ctx* ctx, int lds_slots, const float* rays8, uint32_t n, int repeats, float* out2, double* ms_out );
 
+/* One chosen ray per thread through the walk the lock-step render kernels run (csrc/pt_walk_diag.hpp): traverse() of the
+ * context's build flavour — the configured traversal AND arithmetic, unlike pbr_diag_trace — behind the staged prefix, the
+ * closest-hit walk (anyhit = 0) or the shadow walk of the shade step (anyhit = 1), which no other entry reaches.  With
+ * lds_slots > 0 a product build walks through the hand-scheduled node phases (nodePhaseAsm / nodePhaseAsmCompact), a
+ * PBR_GUARD build through the C++ loop over LDS; with 0 both walk the C++ loop on the stream in memory.
+ *   rays8       n x { origin.xyz, t0 }{ dir.xyz, - } — pbr_diag_trace_stream's layout.  t0 is what hit.t starts from: the
+ *               distance of the light for the any-hit walk; +inf for the closest-hit walk, or a finite bound (a box whose
+ *               tNear is not below it is culled)
+ *   lds_slots   the 32-byte slots of the node stream a block stages, clamped as pbr_diag_trace_stream clamps them: to the
+ *               ranked prefix, to a block's share of LDS, to whole records of the compact layout (traversal 3: even)
+ *   out_t, out_face, out_normal, out_counts   as pbr_diag_trace.  The any-hit walk reports the ray as traverse() leaves it:
+ *               t < t0 blocked, t >= t0 lit (t may exceed t0: an orb light in front of t0 sets it to inf, faces behind the
+ *               light are then recorded and do not stop the walk); its normal is 0 and its node visits are 0 — the shadow
+ *               walk does not count them, as in the reference.  A closest-hit ray that found nothing below a finite t0
+ *               returns t = t0, face 0, normal 0.
+ * One launch, thread i walks ray i in blocks of 1024: rays 64 w .. 64 w + 63 share wave w and its node phases, so the caller
+ * decides who parks with whom; the last wave runs with n % 64 lanes.  Lights, Phong tessellation: as pbr_diag_trace.  The park
+ * share is a render's (knob "park_eighths").  PBR_EDEVICE if the staged prefix was not at LDS address 0. */
+int pbr_diag_trace_walk( pbr_ctx* ctx, int anyhit, int lds_slots, const float* rays8, uint32_t n,
+                         float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts );
+
+/* What pbr_diag_trace_walk makes of a request of lds_slots under the uploaded scene and the configured traversal: *slots = the
+ * 32-byte slots a block would stage, *hot_slots (may be NULL) = the ranked prefix of the node stream that bounds them.  No launch. */
+int pbr_diag_trace_walk_slots( pbr_ctx* ctx, int lds_slots, uint32_t* slots, uint32_t* hot_slots );
+
 /* Memory-counter calibration: reads `reads` elements of a zero-filled table of table_bytes in a
  * known pattern (mode 0 coalesced 16 B / lane stream, 1 random 16-B elements, 2 random 32-B
  * records) so that rocprofv3's FETCH_SIZE / TCC_EA0_RDREQ_* can be interpreted. */

@@ -129,10 +129,11 @@ def lib():
             ctypes.c_float, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OrcCounters)]
         _lib.orc_render_frame.restype = None
-        _lib.orc_trace_rays.argtypes = [
-            ctypes.POINTER(OrcScene), ctypes.POINTER(OrcConfig), _fp, ctypes.c_int,
-            _fp, ctypes.POINTER(ctypes.c_int32), _fp, ctypes.POINTER(ctypes.c_uint32)]
-        _lib.orc_trace_rays.restype = None
+        for fn in (_lib.orc_trace_rays, _lib.orc_trace_shadow_rays):
+            fn.argtypes = [
+                ctypes.POINTER(OrcScene), ctypes.POINTER(OrcConfig), _fp, _fp, ctypes.c_int,
+                _fp, ctypes.POINTER(ctypes.c_int32), _fp, ctypes.POINTER(ctypes.c_uint32)]
+            fn.restype = None
         _lib.orc_math.argtypes = [ctypes.c_int, _fp, _fp, ctypes.c_int, _fp]
         _lib.orc_math.restype = None
         _lib.orc_brdf_eval.argtypes = [ctypes.c_int, ctypes.c_void_p, _fp, ctypes.c_int, _fp]
@@ -298,16 +299,28 @@ class Renderer:
         return {"nodes": int(c.nodes), "tris": int(c.tris), "hits": int(c.hits), "paths": int(c.paths)}
 
 
-def trace_rays(desc, cfg, rays):
+def _trace(fn, desc, cfg, rays, t0):
     s, c = scene_and_config(desc, cfg)
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
     n = rays.shape[0]
+    start = None if t0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float32), (n,)))
     t = np.empty(n, np.float32)
     face = np.empty(n, np.int32)
     normal = np.empty((n, 3), np.float32)
     counts = np.empty((n, 2), np.uint32)
-    lib().orc_trace_rays(
-        ctypes.byref(s), ctypes.byref(c), _ptr(rays), n, _ptr(t),
-        face.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(normal),
-        counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    fn(ctypes.byref(s), ctypes.byref(c), _ptr(rays), None if start is None else _ptr(start), n, _ptr(t),
+       face.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(normal),
+       counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
     return t, face, normal, counts
+
+
+def trace_rays(desc, cfg, rays, t0=None):
+    """orc_trace_rays: the closest-hit walk of the configured traversal.  t0: what ray.t starts from, one value or per ray;
+    None hands the library no array, and it starts every ray from +inf."""
+    return _trace(lib().orc_trace_rays, desc, cfg, rays, t0)
+
+
+def trace_shadow_rays(desc, cfg, rays, t_light):
+    """orc_trace_shadow_rays: traverseShadows of the configured traversal; t_light per ray (or one value).  (t, face, normal,
+    counts): t < t_light blocked, else lit; counts[:, 0] is 0 — the shadow walk counts no node visits."""
+    return _trace(lib().orc_trace_shadow_rays, desc, cfg, rays, t_light)

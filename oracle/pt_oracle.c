@@ -1938,10 +1938,10 @@ void orc_render_frame(
 	}
 }
 
-void orc_trace_rays(
-	const orc_scene* scene, const orc_config* cfg, const float* rays, int n,
-	float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts
-) {
+/* walk 0: traverse, 1: traverseShadows — each as it stands, in the configured traversal mode.  t0 (NULL: +inf) is what ray.t
+ * starts from: tLight of the shadow walk */
+static void trace_rays( const orc_scene* scene, const orc_config* cfg, int walk, const float* rays, const float* t0, int n,
+                        float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts ) {
 	ctx_t c;
 	c.scene = scene;
 	c.cfg = cfg;
@@ -1952,12 +1952,17 @@ void orc_trace_rays(
 		ray.origin = V3( rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2] );
 		ray.dir = V3( rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5] );
 		ray.normal = V3( 0.0f, 0.0f, 0.0f );
-		ray.t = ORC_INF;
+		ray.t = t0 ? t0[i] : ORC_INF;
 		ray.hitFace = 0;
 		c.dbg_faces = 0.0f;
 		c.dbg_nodes = 0.0f;
 
-		traverse( &c, &ray );
+		if( walk == 1 ) {
+			traverseShadows( &c, &ray );
+		}
+		else {
+			traverse( &c, &ray );
+		}
 
 		out_t[i] = ray.t;
 		out_face[i] = ray.hitFace;
@@ -1967,6 +1972,20 @@ void orc_trace_rays(
 		out_counts[i * 2 + 0] = (uint32_t) c.dbg_nodes;
 		out_counts[i * 2 + 1] = (uint32_t) c.dbg_faces;
 	}
+}
+
+void orc_trace_rays(
+	const orc_scene* scene, const orc_config* cfg, const float* rays, const float* t0, int n,
+	float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts
+) {
+	trace_rays( scene, cfg, 0, rays, t0, n, out_t, out_face, out_normal, out_counts );
+}
+
+void orc_trace_shadow_rays(
+	const orc_scene* scene, const orc_config* cfg, const float* rays, const float* tLight, int n,
+	float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts
+) {
+	trace_rays( scene, cfg, 1, rays, tLight, n, out_t, out_face, out_normal, out_counts );
 }
 
 void orc_math( int op, const float* x, const float* y, int n, float* out ) {

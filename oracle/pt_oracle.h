@@ -116,9 +116,22 @@ void orc_render_frame(
 	int y0, int y1, int threads, orc_counters* counters );
 
 /* Closest-hit traversal of a ray batch (pt_bvh.cl:82-123).  rays: n x {ox,oy,oz,dx,dy,dz};
- * out_t[n], out_face[n], out_normal[3n], out_counts[2n] = {nodes,tris}. */
+ * out_t[n], out_face[n], out_normal[3n], out_counts[2n] = {nodes,tris}.
+ * t0[n]: the value ray.t starts from, per ray; NULL: +inf, a camera ray's.  A box whose tNear is not below it is culled
+ * (`ray->t > tNear`, pt_bvh.cl:109), a face at or beyond it is not recorded.  A ray that finds nothing nearer comes back with
+ * t = t0, face 0, normal 0. */
 void orc_trace_rays(
-	const orc_scene* scene, const orc_config* cfg, const float* rays, int n,
+	const orc_scene* scene, const orc_config* cfg, const float* rays, const float* t0, int n,
+	float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts );
+
+/* The shadow walk of a ray batch: traverseShadows (pt_bvh.cl:133-177) as it stands — traverseShadowsOrdered in a ray-ordered
+ * mode —, lights and Phong tessellation included.  tLight[n]: what ray.t starts from, the distance of the light.  The ray as
+ * the walk leaves it: out_t < tLight blocked (the walk stopped there), out_t >= tLight lit — above tLight when an orb light in
+ * front of it set t to inf and a face behind the light was recorded, which does not stop the walk.  out_face, out_normal: the
+ * last face recorded (0 / 0 if none; a negative face: an orb light and nothing after it).  out_counts = {0, face tests}: the
+ * shadow walk does not count its node visits, intersectFace counts in both walks. */
+void orc_trace_shadow_rays(
+	const orc_scene* scene, const orc_config* cfg, const float* rays, const float* tLight, int n,
 	float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts );
 
 /* The product's opt-in ray-ordered walk (NOT the reference's algorithm — the reference has one fixed order): successor

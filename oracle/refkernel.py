@@ -211,7 +211,7 @@ def build_recorded_cases(force=False):
     quiet, sys.dont_write_bytecode = sys.dont_write_bytecode, True       # a build leaves nothing under tests/
     try:
         spec.loader.exec_module(mod)
-        configs = [mod.values_of(mod.case_inputs(name)) for name in mod.CASES]
+        configs = [mod.values_of(mod.case_inputs(name)) for name in mod.CASES] + [mod.walk_values_of(name) for name in mod.WALK_CASES]
     finally:
         sys.dont_write_bytecode = quiet
     return build_many(configs, force=force)
@@ -228,9 +228,11 @@ def write_records(path, arrays):
             f.write(np.uint32(a.ndim).tobytes() + np.array(a.shape, "<u4").tobytes() + a.astype(a.dtype.newbyteorder("<")).tobytes())
 
 
-def run(values, data, seeds, first, px_dim, camera, rays, scratch):
+def run(values, data, seeds, first, px_dim, camera, rays, scratch, t0=None, shadow_rays=None):
     """One child process of the configuration's binary.  data: the seven wire arrays; camera: the 80 bytes of a pbr_camera;
-    returns {image, debug, ray_t, ray_face, ray_normal, ray_counts}."""
+    returns {image, debug, ray_t, ray_face, ray_normal, ray_counts}.  t0: what each closest-hit ray's t starts from (+inf
+    without it); shadow_rays (n x 7: origin, dir, tLight): the reference's traverseShadows per ray — shadow_t, shadow_face,
+    shadow_tests are returned too."""
     binary = build(values)
     lights = np.asarray(data["lights"], np.float32).reshape(-1, 12)
     records = {k: data[k] for k in ("bvh", "facesV", "facesN", "vertices", "normals", "materials")}
@@ -238,6 +240,10 @@ def run(values, data, seeds, first, px_dim, camera, rays, scratch):
     records.update(lights=lights, camera=np.frombuffer(bytes(camera), np.uint32).copy(), seeds=np.asarray(seeds, np.float32).reshape(-1),
                    first=np.array([first], np.uint32), px_dim=np.array([px_dim], np.float32),
                    rays=np.asarray(rays, np.float32).reshape(-1, 6))
+    if t0 is not None:
+        records["t0"] = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float32), (records["rays"].shape[0],)))
+    if shadow_rays is not None:
+        records["shadow_rays"] = np.asarray(shadow_rays, np.float32).reshape(-1, 7)
     tag = "%s.%d" % (key_of(values), os.getpid())
     src, out = os.path.join(scratch, "refkernel_%s.in" % tag), os.path.join(scratch, "refkernel_%s.out" % tag)
     write_records(src, records)

@@ -7,6 +7,9 @@
  * u32 rank, u32 dims[rank], data.  Read: the seven wire arrays (bvh, facesV, facesN, vertices, normals, materials,
  * lights), camera (20 words), seeds, first (the first sample count), px_dim, rays (n x 6, may be empty).  Written:
  * image, debug (H x W x 4), frame_counts (frames x {node visits, face tests}: the sums of each frame's debug image), ray_t, ray_face, ray_normal, ray_counts {node visits, face tests}.
+ * Optional: t0 (one value per ray of `rays`: what its t starts from, +inf without the record) and shadow_rays (n x 7:
+ * origin, dir, tLight) — with the latter shadow_t, shadow_face, shadow_tests are written too: each ray as the reference's
+ * traverseShadows leaves it, and its face tests.
  *
  * Frames follow the reference's host loop: the last output becomes the next input, the weight of frame n is
  * n / ( n + 1 ) in float32, the debug image is the last frame's.  Every index the kernel is handed is checked against the
@@ -35,7 +38,10 @@ void rk_pixel(
 	const void* materials, const void* lights, rk_image* imageIn, rk_image* imageOut, rk_image* imageDebug );
 void rk_ray(
 	const void* bvh, const void* facesV, const void* facesN, const void* vertices, const void* normals,
-	const void* lights, const float* ray6, float* out7, int32_t* outFace );
+	const void* lights, const float* ray6, const float* t0, float* out7, int32_t* outFace );
+void rk_shadow_ray(
+	const void* bvh, const void* facesV, const void* facesN, const void* vertices, const void* normals,
+	const void* lights, const float* ray7, float* out2, int32_t* outFace );
 }
 
 struct Record {
@@ -120,6 +126,9 @@ int main( int argc, char** argv ) {
 	const Record& first = need( in, "first", 'u', 1 );
 	const Record& pxDim = need( in, "px_dim", 'f', 1 );
 	const Record& rays = need( in, "rays", 'f', 6 );
+	const Record* t0 = in.count( "t0" ) ? &need( in, "t0", 'f', 1 ) : nullptr;
+	const Record* shadowRays = in.count( "shadow_rays" ) ? &need( in, "shadow_rays", 'f', 7 ) : nullptr;
+	if( t0 && t0->words.size() != rays.rows() ) fail( "t0 does not fit rays" );
 
 	if( (int) bvh.rows() != numNodes || (int) lights.rows() != numLights ) fail( "node or light count differs from the compiled one" );
 	if( numNodes < 2 || camera.words.size() != 20 || first.words.size() != 1 || pxDim.words.size() != 1 ) fail( "bad scalar records" );
@@ -182,11 +191,24 @@ int main( int argc, char** argv ) {
 	std::vector<uint32_t> rayCounts( 2 * (size_t) nr );
 	for( uint32_t k = 0; k < nr; k++ ) {
 		float out7[7] = { 0 };
-		rk_ray( dBvh, dFacesV, dFacesN, dVertices, dNormals, dLights, (const float*) &rays.words[6 * (size_t) k], out7, &rayFace[k] );
+		const float inf = INFINITY;
+		rk_ray( dBvh, dFacesV, dFacesN, dVertices, dNormals, dLights, (const float*) &rays.words[6 * (size_t) k],
+		        t0 ? (const float*) &t0->words[k] : &inf, out7, &rayFace[k] );
 		rayT[k] = out7[0];
 		memcpy( &rayNormal[3 * (size_t) k], out7 + 1, 12 );
 		rayCounts[2 * (size_t) k] = (uint32_t) out7[4];
 		rayCounts[2 * (size_t) k + 1] = (uint32_t) out7[5];
+	}
+
+	const uint32_t ns = shadowRays ? (uint32_t) shadowRays->rows() : 0;
+	std::vector<float> shadowT( ns );
+	std::vector<int32_t> shadowFace( ns );
+	std::vector<uint32_t> shadowTests( ns );
+	for( uint32_t k = 0; k < ns; k++ ) {
+		float out2[2] = { 0 };
+		rk_shadow_ray( dBvh, dFacesV, dFacesN, dVertices, dNormals, dLights, (const float*) &shadowRays->words[7 * (size_t) k], out2, &shadowFace[k] );
+		shadowT[k] = out2[0];
+		shadowTests[k] = (uint32_t) out2[1];
 	}
 
 	FILE* f = fopen( outPath, "wb" );
@@ -198,6 +220,11 @@ int main( int argc, char** argv ) {
 	writeRecord( f, "ray_face", 'i', { nr }, rayFace.data() );
 	writeRecord( f, "ray_normal", 'f', { nr, 3 }, rayNormal.data() );
 	writeRecord( f, "ray_counts", 'u', { nr, 2 }, rayCounts.data() );
+	if( shadowRays ) {
+		writeRecord( f, "shadow_t", 'f', { ns }, shadowT.data() );
+		writeRecord( f, "shadow_face", 'i', { ns }, shadowFace.data() );
+		writeRecord( f, "shadow_tests", 'u', { ns }, shadowTests.data() );
+	}
 	fclose( f );
 	return 0;
 }

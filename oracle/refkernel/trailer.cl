@@ -31,17 +31,18 @@ void rk_pixel(
 	pathTracing( seed, pixelWeight, pxDim, *cam, bvh, facesV, facesN, vertices, normals, materials, lights, imageIn, imageOut, imageDebug );
 }
 
-/* closest hit of one ray: out = { t, hitFace, normal.xyz, node visits, face tests } */
+/* closest hit of one ray: out = { t, hitFace, normal.xyz, node visits, face tests }; *t0 is what ray.t starts from */
 void rk_ray(
 	global const bvhNode* bvh, global const uint4* facesV, global const uint4* facesN, global const float4* vertices,
-	global const float4* normals, global const light_t* lights, global const float* ray6, global float* out7, global int* outFace
+	global const float4* normals, global const light_t* lights, global const float* ray6, global const float* t0,
+	global float* out7, global int* outFace
 ) {
 	Scene scene = { bvh, lights, facesV, facesN, vertices, normals, (float4)( 0.0f ) };
 	ray4 ray;
 	ray.origin = (float3)( ray6[0], ray6[1], ray6[2] );
 	ray.dir = (float3)( ray6[3], ray6[4], ray6[5] );
 	ray.normal = (float3)( 0.0f );
-	ray.t = INFINITY;
+	ray.t = *t0;
 	ray.hitFace = 0;
 
 	traverse( &scene, &ray );
@@ -52,5 +53,26 @@ void rk_ray(
 	out7[3] = ray.normal.z;
 	out7[4] = scene.debugColor.y;
 	out7[5] = scene.debugColor.x;
+	*outFace = ray.hitFace;
+}
+
+/* the shadow walk of one ray, ray7 = { origin, dir, tLight }: out = { t, face tests } as traverseShadows leaves the ray
+ * (intersectFace counts its tests in debugColor.x in both walks; the shadow walk counts no node visits) */
+void rk_shadow_ray(
+	global const bvhNode* bvh, global const uint4* facesV, global const uint4* facesN, global const float4* vertices,
+	global const float4* normals, global const light_t* lights, global const float* ray7, global float* out2, global int* outFace
+) {
+	Scene scene = { bvh, lights, facesV, facesN, vertices, normals, (float4)( 0.0f ) };
+	ray4 ray;
+	ray.origin = (float3)( ray7[0], ray7[1], ray7[2] );
+	ray.dir = (float3)( ray7[3], ray7[4], ray7[5] );
+	ray.normal = (float3)( 0.0f );
+	ray.t = ray7[6];
+	ray.hitFace = 0;
+
+	traverseShadows( &scene, &ray );
+
+	out2[0] = ray.t;
+	out2[1] = scene.debugColor.x;
 	*outFace = ray.hitFace;
 }

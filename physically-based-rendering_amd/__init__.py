@@ -223,6 +223,8 @@ for _name, _args in (
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
         ("pbr_diag_intersect", [_vp, ctypes.c_int, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_surface_step", [_vp, _fp, ctypes.c_int, _fp]),
+        ("pbr_diag_trace_walk", [_vp, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_uint32, _fp, _ip, _fp, _up]),
+        ("pbr_diag_trace_walk_slots", [_vp, ctypes.c_int, _up, _up]),
         ("pbr_diag_filter", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, _fp, _fp, _fp, _fp, _fp]),
         ("pbr_diag_temporal", [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.POINTER(Camera), ctypes.POINTER(TemporalParams), _fp, _fp, _fp,
                                _fp, _fp, _up, ctypes.POINTER(Camera), ctypes.c_float,
@@ -912,6 +914,30 @@ class Device:
         self._check(hip.pbr_diag_trace(self._ctx, _as_fp(rays), n, _as_fp(t), face.ctypes.data_as(_ip),
                                        _as_fp(normal), counts.ctypes.data_as(_up)))
         return t, face, normal, counts
+
+    def diag_trace_walk(self, rays, t0=None, anyhit=False, lds_slots=0):
+        """pbr_diag_trace_walk: ray i on thread i of one launch through the walk of the configured traversal AND arithmetic as
+        the lock-step render kernels run it — the closest-hit walk, or with anyhit the shadow walk — behind lds_slots staged
+        slots.  rays: n x 6 {origin, dir}; t0: what hit.t starts from, per ray or one value (default +inf; the light's
+        distance for the shadow walk).  Returns (t, face, normal, counts) as diag_trace."""
+        rays = np.asarray(rays, np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        rays8 = np.zeros((n, 8), np.float32)
+        rays8[:, 0:3], rays8[:, 4:7] = rays[:, 0:3], rays[:, 3:6]
+        rays8[:, 3] = np.inf if t0 is None else np.asarray(t0, np.float32)
+        t = np.empty(n, np.float32)
+        face = np.empty(n, np.int32)
+        normal = np.empty((n, 3), np.float32)
+        counts = np.empty((n, 2), np.uint32)
+        self._check(hip.pbr_diag_trace_walk(self._ctx, 1 if anyhit else 0, int(lds_slots), _as_fp(rays8), n, _as_fp(t),
+                                            face.ctypes.data_as(_ip), _as_fp(normal), counts.ctypes.data_as(_up)))
+        return t, face, normal, counts
+
+    def diag_trace_walk_slots(self, lds_slots):
+        """pbr_diag_trace_walk_slots: (the slots diag_trace_walk stages for this request, the ranked prefix that bounds them)."""
+        slots, hot = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(hip.pbr_diag_trace_walk_slots(self._ctx, int(lds_slots), ctypes.byref(slots), ctypes.byref(hot)))
+        return int(slots.value), int(hot.value)
 
     def diag_brdf(self, items):
         items = np.ascontiguousarray(items, np.float32).reshape(-1, 16)

@@ -140,11 +140,12 @@ def build_hip(force=False, guard=False):
 # host side of the launches and every other kernel), in parallel, and linked into one shared library.
 #   flavour bit 0: ray-ordered walk (pbr_config.traversal)     bit 1: native arithmetic (pbr_config.arith)
 #   groups 0-2 pathTracing<.., 4 | 6 | 8>, 3 its Phong-tessellation build (every flavour since round 6), 4-6 pathTracingPhased<.., 4 | 6 | 8>,
-#   7 pathTracingDual (not in PBR_GUARD builds: it has no C++ node phase), 8 the focus chain of pbr_render_dof (pt_chain.hpp)
+#   7 pathTracingDual (not in PBR_GUARD builds: it has no C++ node phase), 8 the focus chain of pbr_render_dof (pt_chain.hpp),
+#   9 the per-ray entry into the walk, pbr_diag_trace_walk (pt_walk_diag.hpp)
 #   flavour bit 2 (with bit 0): the compact record of the eight-order walk — flavours 5 and 7 (no two-paths kernel: group 7)
 FLAVOURS = (0, 1, 2, 3, 5, 7)
 CHAINED = 8   # flavour bit 3: the plans' kernels once more for pbr_render_dof (groups 0-2, 4-7), reading the focus chain's table
-GROUPS = (0, 1, 2, 3, 4, 5, 6, 7, 8)
+GROUPS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)
 # what native arithmetic means to the compiler: `/` and sqrtf() become v_rcp_f32 / v_sqrt_f32 sequences without the
 # correction steps (the reference asks for native_divide / native_recip / native_sqrt); everything else is in pt_math.hpp
 NATIVE_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt"]
@@ -157,7 +158,7 @@ def instance_units(guard):
             if g == 7 and (guard or f & 4):
                 continue
             units.append((f, g))
-            if g not in (3, 8):
+            if g not in (3, 8, 9):
                 units.append((f | CHAINED, g))
     return units
 

@@ -484,21 +484,21 @@ const size_t kCounterSlots = 16;
 #define PTI_DECLARE( f, g ) extern "C" const void* PTI_NAME( f, g )( uint32_t, int, int ) __attribute__( ( weak ) );
 #define PTI_DECLARE_FLAVOUR( f ) \
 	PTI_DECLARE( f, 0 ) PTI_DECLARE( f, 1 ) PTI_DECLARE( f, 2 ) PTI_DECLARE( f, 3 ) PTI_DECLARE( f, 4 ) PTI_DECLARE( f, 5 ) PTI_DECLARE( f, 6 ) PTI_DECLARE( f, 7 ) \
-	PTI_DECLARE( f, 8 )
+	PTI_DECLARE( f, 8 ) PTI_DECLARE( f, 9 )
 PTI_DECLARE_FLAVOUR( 0 )
 PTI_DECLARE_FLAVOUR( 1 )
 PTI_DECLARE_FLAVOUR( 2 )
 PTI_DECLARE_FLAVOUR( 3 )
 PTI_DECLARE_FLAVOUR( 5 )     // the compact record of the eight-order walk (flavour bit 2; only together with bit 0)
 PTI_DECLARE_FLAVOUR( 7 )
-PTI_DECLARE_FLAVOUR( 8 )     // the chained builds (flavour bit 3, pbr_render_dof): groups 3 and 8 stay null
+PTI_DECLARE_FLAVOUR( 8 )     // the chained builds (flavour bit 3, pbr_render_dof): groups 3, 8 and 9 stay null
 PTI_DECLARE_FLAVOUR( 9 )
 PTI_DECLARE_FLAVOUR( 10 )
 PTI_DECLARE_FLAVOUR( 11 )
 PTI_DECLARE_FLAVOUR( 13 )
 PTI_DECLARE_FLAVOUR( 15 )
-#define PTI_ROW( f ) { PTI_NAME( f, 0 ), PTI_NAME( f, 1 ), PTI_NAME( f, 2 ), PTI_NAME( f, 3 ), PTI_NAME( f, 4 ), PTI_NAME( f, 5 ), PTI_NAME( f, 6 ), PTI_NAME( f, 7 ), PTI_NAME( f, 8 ) }
-#define PTI_NO_ROW { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }
+#define PTI_ROW( f ) { PTI_NAME( f, 0 ), PTI_NAME( f, 1 ), PTI_NAME( f, 2 ), PTI_NAME( f, 3 ), PTI_NAME( f, 4 ), PTI_NAME( f, 5 ), PTI_NAME( f, 6 ), PTI_NAME( f, 7 ), PTI_NAME( f, 8 ), PTI_NAME( f, 9 ) }
+#define PTI_NO_ROW { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }
 const pti_picker kPickers[PTI_FLAVOURS][PTI_GROUPS] = { PTI_ROW( 0 ), PTI_ROW( 1 ), PTI_ROW( 2 ), PTI_ROW( 3 ), PTI_NO_ROW, PTI_ROW( 5 ), PTI_NO_ROW, PTI_ROW( 7 ),
                                                        PTI_ROW( 8 ), PTI_ROW( 9 ), PTI_ROW( 10 ), PTI_ROW( 11 ), PTI_NO_ROW, PTI_ROW( 13 ), PTI_NO_ROW, PTI_ROW( 15 ) };
 
@@ -838,7 +838,7 @@ int makePlan( pbr_ctx* ctx, const PlanSpec& spec, uint32_t hotAvail, Plan* plan,
 	plan->name = spec.name;
 	// the symbol as rocprofv3 prints it (pt_instance.hip instantiates exactly these; namespaces: pt_flavour.hpp)
 	const char* const tf[2] = { "false", "true" };
-	const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0, 0 };
+	const int minw[PTI_GROUPS] = { 4, 6, 8, 4, 4, 6, 8, 0, 0, 0 };
 
 	if( spec.group == PTI_DUAL ) {
 		std::snprintf( plan->kernelName, sizeof( plan->kernelName ), "ptk_f%d::pathTracingDual<%u, %s, %s>", flavour, ctx->cfg.brdf, tf[shadow], tf[lights] );
@@ -1425,7 +1425,7 @@ int pbr_mode_built( uint32_t traversal, uint32_t arith ) {
 		if( kPickers[flavour][group] == nullptr ) {
 			return 0;
 		}
-		if( group != PTI_REFILL_PHONG && group != PTI_CHAIN && kPickers[flavour | PTI_CHAINED][group] == nullptr ) {
+		if( group != PTI_REFILL_PHONG && group != PTI_CHAIN && group != PTI_WALK && kPickers[flavour | PTI_CHAINED][group] == nullptr ) {
 			return 0;
 		}
 	}
@@ -3954,6 +3954,114 @@ int pbr_diag_trace_stream( pbr_ctx* ctx, int mode, const float* rays8, uint32_t 
 
 	HIP_TRY( ctx, hipMemcpy( out2, dOut.get(), sizeof( float ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
 	*ms_out = best;
+	return PBR_OK;
+}
+
+namespace {
+
+// pbr_diag_trace_walk's staged prefix, clamped as pbr_diag_trace_stream clamps its own: the ranked prefix, a block's share of LDS
+// at two blocks per CU, whole compact records
+size_t walkSlots( int lds_slots, uint32_t hotAvail, int walkScheme ) {
+	const int blocksPerCU = 2048 / PBR_BLOCK;
+	size_t slots = std::min<size_t>( (size_t) lds_slots, hotAvail );
+	slots = std::min<size_t>( slots, ( 160 * 1024 / (size_t) blocksPerCU - 256 ) / 32 );
+	slots &= ( walkScheme == 3 ) ? ~(size_t) 1 : ~(size_t) 0;
+	return slots;
+}
+
+}  // namespace
+
+int pbr_diag_trace_walk_slots( pbr_ctx* ctx, int lds_slots, uint32_t* slots, uint32_t* hot_slots ) {
+	if( ctx == nullptr || !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "diag_trace_walk_slots before pbr_upload_scene" );
+	}
+	if( lds_slots < 0 || slots == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_trace_walk_slots: bad argument" );
+	}
+
+	uint32_t hotAvail = 0;
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );
+	*slots = (uint32_t) walkSlots( lds_slots, hotAvail, P.walkScheme );
+
+	if( hot_slots != nullptr ) {
+		*hot_slots = hotAvail;
+	}
+
+	return PBR_OK;
+}
+
+// One chosen ray per thread through the walk a lock-step render runs (pt_walk_diag.hpp): the kernel of the context's build
+// flavour, the staged prefix clamped as above, the park share of a render's plan.
+int pbr_diag_trace_walk( pbr_ctx* ctx, int anyhit, int lds_slots, const float* rays8, uint32_t n,
+                         float* out_t, int32_t* out_face, float* out_normal, uint32_t* out_counts ) {
+	if( ctx == nullptr || !ctx->hasScene ) {
+		return fail( ctx, PBR_ESTATE, "diag_trace_walk before pbr_upload_scene" );
+	}
+	if( rays8 == nullptr || n == 0 || n > ( 1u << 24 ) || lds_slots < 0 || out_t == nullptr || out_face == nullptr || out_normal == nullptr || out_counts == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "diag_trace_walk: bad argument" );
+	}
+
+	const int flavour = ctx->configured ? flavourOf( ctx->cfg ) : 0;
+	const pti_picker pick = kPickers[flavour][PTI_WALK];
+
+	if( pick == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "diag_trace_walk: this library was built without the per-ray walk of flavour %d", flavour );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	DevBuf dRays, dT, dFace, dNormal, dCounts;
+	HIP_TRY( ctx, dRays.alloc( sizeof( float ) * 8 * (size_t) n ) );
+	HIP_TRY( ctx, dT.alloc( sizeof( float ) * (size_t) n ) );
+	HIP_TRY( ctx, dFace.alloc( sizeof( int ) * (size_t) n ) );
+	HIP_TRY( ctx, dNormal.alloc( sizeof( float ) * 3 * (size_t) n ) );
+	HIP_TRY( ctx, dCounts.alloc( sizeof( unsigned ) * 2 * (size_t) n ) );
+	HIP_TRY( ctx, hipMemcpy( dRays.get(), rays8, sizeof( float ) * 8 * (size_t) n, hipMemcpyHostToDevice ) );
+
+	uint32_t hotAvail = 0;
+	DevParams P;
+	PBR_TRY( sceneParams( ctx, &P, &hotAvail ) );
+
+	// Phong tessellation and lights as pbr_diag_trace takes them
+	const bool phong = ctx->configured && ctx->cfg.phong_tessellation > 0.0f && ctx->scene.dTriPN != nullptr;
+	P.triPN = ctx->scene.dTriPN;
+	P.phongAlpha = phong ? ctx->cfg.phong_tessellation : 0.0f;
+	// the park share of a render's plan (makePlan)
+	P.parkEighths = ( ctx->scene.numNodes >= kWideMinNodes ) ? 4 : 6;
+
+	if( ctx->knobs.parkEighths >= 0 ) {
+		P.parkEighths = std::min( 8, ctx->knobs.parkEighths );
+	}
+
+	// the staged prefix as pbr_diag_trace_stream clamps it: the ranked prefix, a block's share of LDS, whole compact records
+	const size_t slots = walkSlots( lds_slots, hotAvail, P.walkScheme );
+	P.numHot = (int) slots;
+	P.numHotBytes = (int) slots * 32;
+
+	typedef void ( *WalkFn )( const ptk::DevParams, const float4*, unsigned, float*, int*, float*, unsigned* );
+	const WalkFn kernel = (WalkFn) pick( ( anyhit ? 1u : 0u ) | ( slots > 0 ? 2u : 0u ), phong ? 1 : 0, ( ctx->scene.numLights > 0 ) ? 1 : 0 );
+
+	if( slots > 0 ) {
+		HIP_TRY( ctx, hipFuncSetAttribute( (const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ( slots * 32 ) ) );
+	}
+
+	// the kernels' error flags are of this launch (host-mapped memory; no launch of this context is in flight here)
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+
+	for( int k = 0; k < 4; k++ ) {
+		( (volatile unsigned*) ctx->dGuard )[k] = 0u;
+	}
+
+	const dim3 grid( ( n + PBR_BLOCK - 1 ) / PBR_BLOCK ), block( PBR_BLOCK );
+	hipLaunchKernelGGL( kernel, grid, block, slots * 32, ctx->stream, P, (const float4*) dRays.get(), n,
+		(float*) dT.get(), (int*) dFace.get(), (float*) dNormal.get(), (unsigned*) dCounts.get() );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	PBR_TRY( checkGuard( ctx ) );
+	HIP_TRY( ctx, hipMemcpy( out_t, dT.get(), sizeof( float ) * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_face, dFace.get(), sizeof( int ) * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_normal, dNormal.get(), sizeof( float ) * 3 * (size_t) n, hipMemcpyDeviceToHost ) );
+	HIP_TRY( ctx, hipMemcpy( out_counts, dCounts.get(), sizeof( unsigned ) * 2 * (size_t) n, hipMemcpyDeviceToHost ) );
 	return PBR_OK;
 }
 

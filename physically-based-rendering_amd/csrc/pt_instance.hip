@@ -1,5 +1,5 @@
 // One group of path-tracing kernels in one build flavour (pt_instances.hpp, pt_flavour.hpp):
-//   hipcc -c -DPT_FLAVOUR=<0..3 | 5 | 7, + 8: chained> -DPT_GROUP=<0..8> pt_instance.hip
+//   hipcc -c -DPT_FLAVOUR=<0..3 | 5 | 7, + 8: chained> -DPT_GROUP=<0..9> pt_instance.hip
 #if !defined( PT_FLAVOUR ) || !defined( PT_GROUP )
 #error "pt_instance.hip is compiled once per (PT_FLAVOUR, PT_GROUP) pair: see build.py"
 #endif
@@ -7,7 +7,7 @@
 #include "pt_kernel.hpp"
 #include "pt_instances.hpp"
 
-#if PT_CHAINED && ( PT_GROUP == PTI_CHAIN || PT_GROUP == PTI_REFILL_PHONG )
+#if PT_CHAINED && ( PT_GROUP == PTI_CHAIN || PT_GROUP == PTI_REFILL_PHONG || PT_GROUP == PTI_WALK )
 #error "the chained flavours hold the seven plans' kernels only"
 #endif
 
@@ -21,6 +21,33 @@ extern "C" const void* PTI_NAME( PT_FLAVOUR, PT_GROUP )( uint32_t stage, int, in
 	}
 
 	return lights ? (const void*) ptk::focusChainSlots<true> : (const void*) ptk::focusChainSlots<false>;
+}
+#elif PT_GROUP == PTI_WALK
+// the per-ray entry into the walk of this flavour (pbr_diag_trace_walk): both walks, with and without the staged prefix,
+// flat and Phong-tessellated faces, with or without orb lights
+#include "pt_walk_diag.hpp"
+
+namespace {
+
+template<bool ANYHIT, bool USE_LDS>
+const void* pickWalk( int phong, int lights ) {
+	if( phong ) {
+		return lights ? (const void*) ptk::diagTraceWalk<ANYHIT, true, USE_LDS, true> : (const void*) ptk::diagTraceWalk<ANYHIT, false, USE_LDS, true>;
+	}
+
+	return lights ? (const void*) ptk::diagTraceWalk<ANYHIT, true, USE_LDS, false> : (const void*) ptk::diagTraceWalk<ANYHIT, false, USE_LDS, false>;
+}
+
+}  // namespace
+
+// ( walk, phong, lights ): walk bit 0 = the any-hit walk, bit 1 = through the staged prefix
+extern "C" const void* PTI_NAME( PT_FLAVOUR, PT_GROUP )( uint32_t walk, int phong, int lights ) {
+	switch( walk & 3u ) {
+		case 0: return pickWalk<false, false>( phong, lights );
+		case 1: return pickWalk<true, false>( phong, lights );
+		case 2: return pickWalk<false, true>( phong, lights );
+		default: return pickWalk<true, true>( phong, lights );
+	}
 }
 #else
 
@@ -70,4 +97,4 @@ extern "C" const void* PTI_NAME( PT_FLAVOUR, PT_GROUP )( uint32_t brdf, int shad
 	return (const void*) k;
 }
 
-#endif   // PT_GROUP != PTI_CHAIN
+#endif   // PT_GROUP != PTI_CHAIN, PTI_WALK

@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 #define PTI_FLAVOURS 16  // bit 0: ray-ordered walk, bit 1: native arithmetic, bit 2: compact record of the eight-order walk (only with bit 0: flavours 5 and 7),
-                         // bit 3: the chained build of the plans' kernels for pbr_render_dof (no Phong group, no focus chain of its own)
+                         // bit 3: the chained build of the plans' kernels for pbr_render_dof (no Phong group, no focus chain and no per-ray entry of its own)
 #define PTI_CHAINED 8
 #define PTI_REFILL_LEAN 0    // pathTracing<.., 4>            lock step per bounce, <= 128 VGPRs
 #define PTI_REFILL_MID 1     // pathTracing<.., 6>            <= 80
@@ -18,11 +18,13 @@
 #define PTI_PHASED_WIDE 6    // pathTracingPhased<.., 8>
 #define PTI_DUAL 7           // pathTracingDual               two paths per lane (not in PBR_GUARD builds)
 #define PTI_CHAIN 8          // focusChainPixel / focusChainSlots  the focus chain of pbr_render_dof (pt_chain.hpp): no plan, a pre-pass
-#define PTI_GROUPS 9
+#define PTI_WALK 9           // diagTraceWalk                 pbr_diag_trace_walk's per-ray entry into traverse() (pt_walk_diag.hpp): no plan
+#define PTI_GROUPS 10
 
 // the address of the kernel's host stub (a void (*)( const DevParams ) of that flavour's namespace; all flavours share
 // DevParams' layout), or NULL.  Group PTI_CHAIN reads its arguments as ( stage, -, lights ): stage 0 focusChainPixel, 1
-// focusChainSlots, whose stubs take the arguments pt_chain.hpp gives them.
+// focusChainSlots, whose stubs take the arguments pt_chain.hpp gives them; group PTI_WALK as ( walk, phong, lights ): walk bit 0
+// the any-hit walk, bit 1 through the staged prefix (pt_walk_diag.hpp).
 typedef const void* ( *pti_picker )( uint32_t brdf, int shadow, int lights );
 
 #define PTI_NAME2( f, g ) pti_pick_f##f##_g##g

@@ -1,6 +1,7 @@
 """Regenerates tests/golden/refkernel_*.npz (container only: needs the reference's tree; oracle/refkernel.py builds the binaries).
 
-    python tests/golden/make_refkernel.py
+    python tests/golden/make_refkernel.py             every recording
+    python tests/golden/make_refkernel.py --walk      refkernel_walk_<case>.npz alone (WALK_CASES below: the two walks per ray)
 
 What is stored is DATA the reference's own compiled KERNEL text produced (oracle/refkernel.py: the OpenCL C assembled as its
 host assembles it, built unmodified for the CPU behind this repository's builtin shim and driver): per case
@@ -244,6 +245,88 @@ def recorded(name):
     return _golden("refkernel_" + name)
 
 
+# ---- the walks per ray: refkernel_walk_<case>.npz -------------------------------------------------------------------------
+# The reference's traverse (with a starting t) and traverseShadows on chosen rays (tests/walk_rays.py), through the trailer's
+# rk_ray / rk_shadow_ray.  Stored per case: c_rays (n, 6), c_t0, c_t, c_face, c_counts {node visits, face tests} of the
+# closest-hit walk; s_rays (m, 6), s_tlight, s_t, s_face, s_tests of the shadow walk; values_keys / values_values.  The rays ARE
+# stored: the recordings are what the device is held to with nothing restated in between, and tests/test_walk_rays_cpu.py
+# asserts that they are the constructors' own.
+# name: (scene, rays) — scene: ("hand", shape, options) | ("fixture", ref_* name) | ("lanes", lights) | ("chain",);
+# rays: "random" — WALK_RANDOM of walk_rays.random_set's rays, both walks on the same — | "edges" — the scene's edge classes |
+# "inside" — walk_rays.inside_all_rays
+WALK_RANDOM = 1024
+WALK_CASES = {
+    "hand_leaf1": (("hand", "leaf1", {"degenerate": True, "signed_zeros": True}), "random"),         # 2 nodes
+    "hand_chain300": (("hand", "chain300", {"degenerate": True, "signed_zeros": True}), "random"),   # 603 nodes
+    "suzanne_shadow": (("fixture", "ref_suzanne_sa_shadow"), "random"),                              # its orb light
+    "inside_wide7": (("hand", "wide7", {"degenerate": True, "signed_zeros": True, "loose": True}), "inside"),   # every ray starts inside every box
+    "lanes": (("lanes", False), "edges"),
+    "lanes_lit": (("lanes", True), "edges"),
+    "chain": (("chain",), "edges"),
+}
+WALK_SIZE_CAP = 256 * 1024
+
+
+def walk_scene(name):
+    """The scene of a walk case as a refit_scenes.Scene (desc, cfg, arrays), shared."""
+    key = ("walk_scene", name)
+    if key not in _inputs:
+        import hand_scenes
+        import refit_scenes
+        import walk_rays
+        pbr = _host()
+        where = WALK_CASES[name][0]
+        if where[0] == "hand":
+            sc = hand_scenes.scene(pbr, where[1], **where[2])
+        elif where[0] == "fixture":
+            sc = refit_scenes.load(pbr, where[1])
+        elif where[0] == "lanes":
+            sc = walk_rays.lanes_scene(pbr, where[1])
+        else:
+            sc = walk_rays.chain_scene(pbr)
+        _inputs[key] = sc
+    return _inputs[key]
+
+
+def walk_rays_of(name):
+    """{c_rays, c_t0, s_rays, s_tlight} of a walk case, from tests/walk_rays.py."""
+    import walk_rays
+    sc, (where, kind) = walk_scene(name), WALK_CASES[name]
+    if kind == "random":
+        rays, t_light = walk_rays.random_set(sc)
+        rays, t_light = rays[:WALK_RANDOM], t_light[:WALK_RANDOM]
+        return {"c_rays": rays, "c_t0": np.full(rays.shape[0], np.inf, np.float32), "s_rays": rays, "s_tlight": t_light}
+    if kind == "inside":
+        closest, shadow = walk_rays.inside_all_rays(sc, False), walk_rays.inside_all_rays(sc, True)
+        return {"c_rays": closest.rays, "c_t0": closest.t0, "s_rays": shadow.rays, "s_tlight": shadow.t0}
+    closest, shadow = (walk_rays.lanes_rays(False, where[1]), walk_rays.lanes_rays(True, where[1])) if where[0] == "lanes" else \
+        (walk_rays.chain_rays(False), walk_rays.chain_rays(True))
+    return {"c_rays": closest.rays, "c_t0": closest.t0, "s_rays": shadow.rays, "s_tlight": shadow.t0}
+
+
+def walk_values_of(name):
+    sc = walk_scene(name)
+    data = {"config": np.array([float(getattr(sc.cfg, f)) for f in CONFIG_FIELDS], np.float64), "sky_light": np.array(list(sc.cfg.sky_light), np.float32),
+            "bvh": sc.arrays["bvh"], "lights": sc.arrays["lights"]}
+    return values_of(data)
+
+
+def walk_reference_outputs(name, scratch):
+    """What the compiled reference's traverse and traverseShadows make of a walk case's rays: the arrays a recording stores."""
+    from oracle import refkernel
+    sc, rays = walk_scene(name), walk_rays_of(name)
+    values = walk_values_of(name)
+    out = refkernel.run(values, sc.arrays, np.zeros(0, np.float32), 0, float(sc.px), bytes(sc.cam), rays["c_rays"], scratch,
+                        t0=rays["c_t0"], shadow_rays=np.concatenate([rays["s_rays"], rays["s_tlight"][:, None]], axis=1))
+    keys = sorted(values)
+    return dict(rays, c_t=out["ray_t"], c_face=out["ray_face"], c_counts=out["ray_counts"], s_t=out["shadow_t"], s_face=out["shadow_face"],
+                s_tests=out["shadow_tests"], values_keys=np.array(keys, dtype=str), values_values=np.array([values[k] for k in keys], dtype=str))
+
+
+def recorded_walk(name):
+    return _golden("refkernel_walk_" + name)
+
+
 def focus_w(name, out):
     x, y = CASES[name]["focus"]
     return float(out["image"][y, x, 3])
@@ -288,6 +371,18 @@ if __name__ == "__main__":
 
     if not refkernel.available():
         sys.exit("the reference's sources are not on this machine")
+    # the walk recordings (python tests/golden/make_refkernel.py --walk writes these alone and leaves refkernel_<case>.npz as they are)
+    refkernel.build_many([walk_values_of(n) for n in WALK_CASES])
+    with tempfile.TemporaryDirectory() as scratch:
+        for name in WALK_CASES:
+            out = walk_reference_outputs(name, scratch)
+            path = os.path.join(HERE, "refkernel_walk_%s.npz" % name)
+            np.savez_compressed(path, **out)
+            assert os.path.getsize(path) < WALK_SIZE_CAP, path
+            print("%-36s %6d bytes  %d closest-hit rays, %d hits; %d shadow rays, %d blocked" % (
+                "walk_" + name, os.path.getsize(path), out["c_t"].size, np.isfinite(out["c_t"]).sum(), out["s_t"].size, (out["s_t"] < out["s_tlight"]).sum()))
+    if "--walk" in sys.argv:
+        sys.exit(0)
     t0 = time.time()
     refkernel.build_many([values_of(case_inputs(n)) for n in CASES], force=True)
     t1 = time.time()
