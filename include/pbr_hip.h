@@ -37,10 +37,10 @@ extern "C" {
  * version 13 pbr_refit_ordered_walk, version 14 pbr_update_geometry, version 15 pbr_set_parts, pbr_update_transforms and
  * pbr_read_geometry, version 16 pbr_set_skin and pbr_update_skin,
  * version 17 pbr_set_morph, pbr_update_morph and pbr_update_pose, version 18 pbr_update_skin_dq, pbr_update_pose_dq and
- * pbr_dual_quats_from_matrices).  A caller that loads the library at run time — or
+ * pbr_dual_quats_from_matrices, version 19 pbr_display and pbr_display_reset).  A caller that loads the library at run time — or
  * links a libpbrhip.so it did not build — compares pbr_abi_version() with the PBR_ABI_VERSION it was compiled against
  * BEFORE it hands the library a struct: pbr_configure reads sizeof( pbr_config ) bytes of ITS version. */
-#define PBR_ABI_VERSION 18
+#define PBR_ABI_VERSION 19
 uint32_t pbr_abi_version( void );
 
 #define PBR_OK 0
@@ -879,6 +879,95 @@ int pbr_set_focus_depth( pbr_ctx* ctx, float t );
  * alpha 255, converted on the device (4 B instead of 16 B per pixel over PCIe).  top_row_first = 0: row 0 is the
  * bottom of the image, as pbr_read_output and GL have it; 1: top row first, as image files want it. */
 int pbr_read_display( pbr_ctx* ctx, uint8_t* rgba8, int top_row_first );
+
+/* EXPOSURE, TONE CURVE AND sRGB ON THE DEVICE (ABI version 19).  pbr_read_display above is the reference's pass-through shader:
+ * no exposure, no transfer function, everything above 1 burns out.  pbr_display turns an HDR image — the accumulated one, or
+ * one the caller hands in, such as a denoise call's result — into RGBA8 with an exposure that is given or found from the
+ * image's luminance histogram, a tone curve with a shoulder, and linear or sRGB codes.  pbr_read_display stays exactly as it is;
+ * { manual, exposure 1, curve 0, transfer 0 } gives its bytes.
+ *
+ * THE SOURCE.  rgba == NULL reads the accumulated image (imageOut), as pbr_read_display does.  Otherwise rgba is a host image of
+ * width x height x 4 floats, row 0 = bottom — what pbr_read_output, pbr_read_full and the three denoise calls return; it is
+ * borrowed for the call and copied to a device staging buffer.  Nothing is allocated per call: the buffers are made by the
+ * first pbr_display after pbr_configure (the staging buffer by the first one that hands an image in) and freed with the
+ * configuration.  The accumulation, the moments and the temporal history are never modified.
+ *
+ * THE DEFINITION.  Each operation is in binary32 unless it says double, none is fused, `/` is correctly rounded; fmaxf and fminf
+ * return the other operand when one is NaN — a signalling NaN too — and fmaxf( -0, 0 ) is +0 (the library writes them as
+ * compare-and-select, so this does not depend on a libm).
+ *  1 Luminance.  r' = fminf( fmaxf( r, 0 ), FLT_MAX ), likewise g and b: a NaN becomes 0, an infinity FLT_MAX.
+ *    Y = ( 0.2126f*r' + 0.7152f*g' ) + 0.0722f*b' (pbr_read_variance's weights).
+ *  2 Bin.  Y == 0 counts in `dark`.  Otherwise bin = clamp( (int) ( bits( Y ) >> 20 ) - 888, 0, 255 ): eight bins per octave
+ *    over [2^-16, 2^16), everything below in bin 0, everything above — +inf included — in bin 255, Y = 1.0f in bin 128.  Integer
+ *    arithmetic on the bit pattern: the histogram is exact and does not depend on the order of the additions.
+ *  3 Target, on the host, in double, from the 256 counts n[b].  N = sum n[b]; lo = (double) low_fraction * N;
+ *    hi = N - (double) high_fraction * N; with c_b = sum_{i<b} n[i]: kept_b = max( 0, min( c_b + n_b, hi ) - max( c_b, lo ) );
+ *    m = ( sum kept_b * ( ( b + 0.5 ) / 8 - 16 ) ) / sum kept_b, both sums in ascending b; log2_target = m clamped to
+ *    [min_log2, max_log2].  If N == 0 the target is the remembered value if there is one, else 0.
+ *  4 Adaptation.  With no remembered value, or adapt == 1: log2_used = log2_target.  Otherwise
+ *    log2_used = prev + (double) adapt * ( log2_target - prev ).  A successful auto call remembers log2_used; pbr_display_reset
+ *    and pbr_configure forget it; manual calls neither read nor write it.
+ *    exposure = (float) ( (double) key * exp2( -log2_used ) ).  In manual mode exposure is the parameter, and both log2 values
+ *    of `info` are 0.
+ *  5 Map, per channel c of r, g, b.  x = fminf( fmaxf( c * exposure, 0 ), 65504.0f ).
+ *    curve 0: y = x.   curve 1: y = ( x * ( 1.0f + x / ( white * white ) ) ) / ( 1.0f + x ).
+ *    curve 2: y = ( x * ( 2.51f * x + 0.03f ) ) / ( x * ( 2.43f * x + 0.59f ) + 0.14f ).
+ *    Then y = fminf( fmaxf( y, 0 ), 1 ).  Every curve maps 0 to 0; curve 1 maps x == white to 1.
+ *  6 Encode.  transfer 0: (int) floorf( y * 255.0f + 0.5f ), pbr_read_display's arithmetic.  transfer 1: the code is the number
+ *    of k in 1 .. 255 with y >= T[k], where T[k] is the smallest binary32 not below x_k, and x_k is the inverse sRGB OETF of
+ *    ( k - 0.5 ) / 255 in double: ( ( c + 0.055 ) / 1.055 )^2.4 above 0.04045, c / 12.92 below.  T is a table of constants
+ *    (csrc/pt_display_host.hpp): no pow runs per pixel, the encoding is monotone and exact by construction.  Alpha is 255.
+ *    Rows are bottom-first, or top-first, as in pbr_read_display.
+ * `info` (may be NULL) receives the exposure the map used, the two log2 values, the histogram, counted = N and dark.  Manual
+ * mode launches the histogram kernel only when info is given.
+ *
+ * SHARDED CONTEXTS (tile_world > 1).  With rgba == NULL and manual exposure the call behaves like pbr_read_display: other
+ * ranks' tiles read 0 and encode to 0 (and count as dark in `info`).  With rgba == NULL and auto exposure the call returns
+ * PBR_ESTATE — a shard's histogram is not the image's; the message says to pass the gathered image (pbr_read_full) as rgba.
+ * A host image is always the whole frame.
+ *
+ * REFUSALS.  Each leaves the context and the remembered exposure unchanged.
+ *   PBR_EINVAL  a null context;
+ *   PBR_ESTATE  before pbr_configure;
+ *   PBR_EINVAL  null params or a null destination; a mode, curve or transfer out of range; a parameter of the ACTIVE mode outside
+ *               the ranges its field states, or not finite (the inactive mode's parameters are not looked at; `white` only for
+ *               curve 1); the message names the field;
+ *   PBR_ESTATE  the sharded auto case above.
+ * pbr_last_kernel_ms reports the device time of the histogram and map kernels (not of the copies, not of the host's wait
+ * between them).  OUT OF SCOPE: pbr_multi.h, dithering, a luminance-preserving (not per-channel) curve, using the previous
+ * call's histogram to avoid the read-back, colour grading. */
+#define PBR_DISPLAY_EXPOSURE_MANUAL 0
+#define PBR_DISPLAY_EXPOSURE_AUTO 1
+#define PBR_DISPLAY_CURVE_CLAMP 0
+#define PBR_DISPLAY_CURVE_REINHARD 1
+#define PBR_DISPLAY_CURVE_ACES 2
+#define PBR_DISPLAY_TRANSFER_LINEAR 0
+#define PBR_DISPLAY_TRANSFER_SRGB 1
+
+typedef struct pbr_display_params {
+    uint32_t exposure_mode;   /* 0 manual, 1 auto */
+    float    exposure;        /* manual: the multiplier, finite and > 0 */
+    float    key;             /* auto: the value the scene's trimmed log-mean luminance is mapped to (0.18 is usual); finite, > 0 */
+    float    low_fraction;    /* auto: share of the counted pixels dropped at the dark end, >= 0 */
+    float    high_fraction;   /* auto: ... at the bright end, >= 0; low + high < 1 */
+    float    min_log2, max_log2; /* auto: the log2 mean is clamped to this range; -16 <= min <= max <= 16 */
+    float    adapt;           /* auto: in (0, 1]; 1 = jump to the target, less = move that share of the way per call */
+    uint32_t curve;           /* 0 clamp, 1 extended Reinhard, 2 ACES fit */
+    float    white;           /* curve 1: the input that maps to 1; finite, > 0 */
+    uint32_t transfer;        /* 0 linear, 1 sRGB */
+} pbr_display_params;
+
+typedef struct pbr_display_info {
+    float    exposure;            /* the multiplier the map used */
+    double   log2_target;         /* auto: this image's clamped trimmed mean; manual: 0 */
+    double   log2_used;           /* auto: after adaptation */
+    uint64_t counted, dark;       /* pixels in the histogram / pixels with Y == 0 */
+    uint32_t histogram[256];
+} pbr_display_info;
+
+int pbr_display( pbr_ctx* ctx, const pbr_display_params* params, const float* rgba /* NULL: the accumulated image */,
+                 uint8_t* rgba8, int top_row_first, pbr_display_info* info /* may be NULL */ );
+int pbr_display_reset( pbr_ctx* ctx );   /* forget the adapted exposure */
 
 int pbr_get_counters( pbr_ctx* ctx, pbr_counters* out );
 /* CL::getKernelTimes (source/CL.cpp:480-488): device time of the last launch, HIP events. */

@@ -273,6 +273,8 @@ int pbr_diag_launch_fit( pbr_ctx* ctx, double* fixed_ms, double* per_frame_ms );
  *   "tune_log"      1 = the schedule tuner logs its launches to stderr
  *   "deal_order"    the queue's dealing order: 0 always spatial, 1 always cost classes, 2 always expensive last (once learnt), -1 by the render call's size
  *   "chain_layout"  the focus chain's table (pbr_render_dof): 0 frame-major planes (default), 1 a pixel slot's frames side by side
+ *   "display_merge" pbr_display's histogram kernel: merge rounds per wave and group of 64 pixels ahead of the LDS adds, 0, 1, 2 or 4
+ *                   (any other value: the default; csrc/pt_display.hpp).  The counts do not depend on it (tested)
  * Setting a knob rebuilds the plans and restarts the schedule tuner. */
 int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value );
 
@@ -333,6 +335,10 @@ int pbr_diag_raw_counters( pbr_ctx* ctx, uint64_t out[16] );
 /* Loop-bound trips of the LAST render, recorded by a PBR_GUARD build ([0] unused since round 3, [1] path loop,
  * [2] traversal); all zero in a normal build.  A render in which a bounded loop gave up returns PBR_EDEVICE. */
 int pbr_diag_guard_trips( pbr_ctx* ctx, uint32_t out[3] );
+
+/* The last pbr_display: the device time of its histogram kernel (0 when it launched none) and of its map kernel;
+ * pbr_last_kernel_ms is their sum.  PBR_EINVAL for a null argument. */
+int pbr_diag_display_info( pbr_ctx* ctx, double* histogram_ms, double* map_ms );
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,26 @@ class AdaptiveParams(ctypes.Structure):
                 ("threshold", ctypes.c_float)]
 
 
+class DisplayParams(ctypes.Structure):
+    """pbr_display_params.  exposure_mode 0 manual (exposure) / 1 auto (key, the two trim fractions, the clamp of the log2 mean,
+    adapt); curve 0 clamp / 1 extended Reinhard (white) / 2 ACES fit; transfer 0 linear / 1 sRGB.  The defaults: auto exposure to
+    a key of 0.18 over the middle 90 % of the lit pixels, jumping to the target, ACES, sRGB."""
+    _fields_ = [("exposure_mode", ctypes.c_uint32), ("exposure", ctypes.c_float), ("key", ctypes.c_float),
+                ("low_fraction", ctypes.c_float), ("high_fraction", ctypes.c_float), ("min_log2", ctypes.c_float),
+                ("max_log2", ctypes.c_float), ("adapt", ctypes.c_float), ("curve", ctypes.c_uint32), ("white", ctypes.c_float),
+                ("transfer", ctypes.c_uint32)]
+
+    def __init__(self, exposure_mode=1, exposure=1.0, key=0.18, low_fraction=0.05, high_fraction=0.05, min_log2=-16.0, max_log2=16.0,
+                 adapt=1.0, curve=2, white=4.0, transfer=1):
+        super().__init__(exposure_mode, exposure, key, low_fraction, high_fraction, min_log2, max_log2, adapt, curve, white, transfer)
+
+
+class DisplayInfo(ctypes.Structure):
+    """pbr_display_info"""
+    _fields_ = [("exposure", ctypes.c_float), ("log2_target", ctypes.c_double), ("log2_used", ctypes.c_double),
+                ("counted", ctypes.c_uint64), ("dark", ctypes.c_uint64), ("histogram", ctypes.c_uint32 * 256)]
+
+
 class Counters(ctypes.Structure):
     _fields_ = [("nodes", ctypes.c_uint64), ("tris", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("paths", ctypes.c_uint64)]
 
@@ -122,7 +142,7 @@ _vp = ctypes.c_void_p
 
 # the struct mirrors below are written against this version of include/pbr_hip.h (pbr_config: 68 bytes since version 5).
 # A library of another ABI version must not be handed them; lab runs that load an older build on purpose (PBR_HIP_LIB) say so.
-ABI_VERSION = 18
+ABI_VERSION = 19
 if hasattr(hip, "pbr_abi_version"):
     hip.pbr_abi_version.restype = ctypes.c_uint32
     if hip.pbr_abi_version() != ABI_VERSION and not _lab:
@@ -218,6 +238,9 @@ for _name, _args in (
         ("pbr_update_pose_dq", [_vp, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
         ("pbr_dual_quats_from_matrices", [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
         ("pbr_diag_skin_dq_info", [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+        ("pbr_display", [_vp, ctypes.POINTER(DisplayParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(DisplayInfo)]),   # ABI version 19
+        ("pbr_display_reset", [_vp]),
+        ("pbr_diag_display_info", [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
         ("pbr_diag_solve_cubic", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_phong_face", [_vp, _fp, ctypes.c_int, _fp]),
         ("pbr_diag_camera_ray", [_vp, ctypes.c_float, ctypes.POINTER(Camera), _fp, ctypes.c_int, _fp]),
@@ -815,6 +838,34 @@ class Device:
         out = np.empty((self.height, self.width, 4), np.uint8)
         self._check(hip.pbr_read_display(self._ctx, out.ctypes.data, 1 if top_row_first else 0))
         return out
+
+    def display(self, params=None, rgba=None, top_row_first=False, info=False):
+        """pbr_display: the accumulated image — or `rgba`, an (H, W, 4) float32 image with row 0 at the bottom, as read_output,
+        read_full and the denoise calls return it — through exposure, tone curve and transfer function (DisplayParams) to
+        (H, W, 4) uint8.  With info=True also a dict: exposure, log2_target, log2_used, counted, dark, histogram (256 uint32)."""
+        params = params if params is not None else DisplayParams()
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        if rgba is not None:
+            rgba = np.ascontiguousarray(rgba, np.float32)
+            if rgba.shape != (self.height, self.width, 4):
+                raise PbrError("display: rgba is %r, the configured image (%d, %d, 4)" % (rgba.shape, self.height, self.width))
+        record = DisplayInfo() if info else None
+        self._check(hip.pbr_display(self._ctx, ctypes.byref(params), None if rgba is None else rgba.ctypes.data, out.ctypes.data,
+                                    1 if top_row_first else 0, ctypes.byref(record) if info else None))
+        if not info:
+            return out
+        return out, {"exposure": float(record.exposure), "log2_target": float(record.log2_target), "log2_used": float(record.log2_used),
+                     "counted": int(record.counted), "dark": int(record.dark), "histogram": np.array(record.histogram, np.uint32)}
+
+    def display_reset(self):
+        """pbr_display_reset: forgets the adapted exposure; the next auto display jumps to its target."""
+        self._check(hip.pbr_display_reset(self._ctx))
+
+    def display_info(self):
+        """pbr_diag_display_info: (histogram kernel ms, map kernel ms) of the last display."""
+        hist, mapped = ctypes.c_double(), ctypes.c_double()
+        self._check(hip.pbr_diag_display_info(self._ctx, ctypes.byref(hist), ctypes.byref(mapped)))
+        return float(hist.value), float(mapped.value)
 
     def denoise(self, px_dim, cam, params=None, features=False):
         """pbr_denoise: the accumulated image after the edge-avoiding a-trous filter, (H, W, 4) float32 (the accumulation

@@ -40,6 +40,7 @@
 #include "pt_skin_dq.hpp"
 #include "pt_update_host.hpp"
 #include "pt_device_memory.hpp"
+#include "pt_display.hpp"
 
 using ptk::DevParams;
 using ptmem::Owned;
@@ -76,6 +77,7 @@ struct Knobs {
 	int tuneLog = -1;       // 1 = the schedule tuner logs its launches to stderr
 	int dealOrder = -1;     // the queue's dealing order: 0 always spatial, 1 always cost-ordered (once learnt), -1 by the launch's size
 	int chainLayout = -1;   // the focus chain's table (pbr_render_dof): 0 frame-major planes (the built-in choice), 1 a pixel slot's frames side by side
+	int displayMerge = -1;  // pbr_display's histogram kernel: merge rounds per wave and group before the LDS adds, 0, 1, 2 or 4 (pt_display.hpp)
 };
 
 // One dealing order's table: band b's stretch is [ first[b], first[b + 1] ) of host / dev.
@@ -279,6 +281,12 @@ struct Images {
 	Owned<unsigned> dAdaptiveOrder;
 	// pbr_denoise_temporal (pt_temporal.hpp): the history's planes, allocated by the first temporal call after pbr_configure
 	TemporalPlanes planes;
+	// pbr_display (pt_display.hpp): the histogram's 257 counters with their pinned host twin and the sRGB table, made by the
+	// first display call after pbr_configure; the staging buffer of a host image, W x H row-major, by the first call that hands one in
+	Owned<unsigned> dDisplayCounts;
+	Owned<unsigned, Pinned> hDisplayCounts;
+	Owned<float> dDisplayTable;
+	Owned<float4> dDisplaySource;
 };
 
 // The context's stream and events: declared ahead of every buffer, so that they go after the buffers when the context does.
@@ -309,6 +317,7 @@ struct pbr_ctx {
 	// the events of the step that computes V' and N' on the device; shared: one update is one kind of move
 	Event evXfStart, evXfStop, evXfNormalsStart, evXfNormalsStop;
 	Event evFoldStart, evFoldStop;
+	Event evHistogramStart, evHistogramStop;   // pbr_display: the histogram kernel (the map kernel: evStart, evStop)
 	std::string error;
 	double lastKernelMs = 0.0;
 	int numCUs = 0;
@@ -379,6 +388,10 @@ struct pbr_ctx {
 	bool temporalFresh = false;          // a pbr_render_adaptive succeeded since the last successful temporal call
 	pbr_camera temporalCam = {};         // the history's camera and pixel size
 	float temporalPxDim = 0.0f;
+	// pbr_display: the adapted exposure a successful auto call left, as a log2; forgotten by pbr_display_reset and pbr_configure
+	bool displayAdapted = false;
+	double displayLog2 = 0.0;
+	double lastHistogramMs = 0.0, lastMapMs = 0.0;   // of the last pbr_display (pbr_diag_display_info)
 };
 
 // pt_device_memory.hpp's four primitives over the HIP runtime
@@ -462,6 +475,7 @@ void freeImages( pbr_ctx* ctx ) {
 	ctx->varianceCurrent = false;
 	ctx->temporal.configure();
 	ctx->temporalFresh = false;
+	ctx->displayAdapted = false;
 	ctx->costLearnt = false;
 	ctx->orderPinned = false;
 	ctx->configured = false;
@@ -1459,7 +1473,8 @@ int pbr_create( int device, pbr_ctx** out ) {
 	HIP_TRY( ctx, hipStreamCreateWithFlags( &ctx->stream.s, hipStreamNonBlocking ) );
 
 	for( Event* event : { &ctx->evStart, &ctx->evTraceStart, &ctx->evTraceStop, &ctx->evStop, &ctx->evChainStart, &ctx->evFoldStart, &ctx->evFoldStop,
-	                      &ctx->evRelinkStart, &ctx->evRelinkStop, &ctx->evXfStart, &ctx->evXfStop, &ctx->evXfNormalsStart, &ctx->evXfNormalsStop } ) {
+	                      &ctx->evRelinkStart, &ctx->evRelinkStop, &ctx->evXfStart, &ctx->evXfStop, &ctx->evXfNormalsStart, &ctx->evXfNormalsStop,
+	                      &ctx->evHistogramStart, &ctx->evHistogramStop } ) {
 		HIP_TRY( ctx, hipEventCreate( &event->e ) );
 	}
 
@@ -2796,6 +2811,188 @@ int pbr_read_display( pbr_ctx* ctx, uint8_t* rgba8, int top_row_first ) {
 	HIP_TRY( ctx, hipGetLastError() );
 	HIP_TRY( ctx, hipMemcpyAsync( rgba8, ctx->images.dRows, (size_t) 4 * ctx->cfg.width * ctx->cfg.height, hipMemcpyDeviceToHost, ctx->stream ) );
 	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	return PBR_OK;
+}
+
+// ---- pbr_display: exposure, tone curve and transfer function on the device (pt_display_host.hpp, pt_display.hpp) ----
+
+namespace {
+
+// merge rounds of the histogram kernel without the "display_merge" knob: DESIGN.md 5.5e has the measurement
+const int kDisplayMerge = 2;
+
+void launchDisplayHistogram( pbr_ctx* ctx, const float4* pixels, size_t groups ) {
+	const dim3 grid( ptv::histogramBlocks( groups ) ), block( ptv::kHistogramBlock );
+	unsigned* counts = ctx->images.dDisplayCounts;
+	const int knob = ctx->knobs.displayMerge;
+
+	switch( ( knob == 0 || knob == 1 || knob == 2 || knob == 4 ) ? knob : kDisplayMerge ) {
+		case 0: hipLaunchKernelGGL( ptv::displayHistogram<0>, grid, block, 0, ctx->stream, pixels, (unsigned) groups, counts ); break;
+		case 1: hipLaunchKernelGGL( ptv::displayHistogram<1>, grid, block, 0, ctx->stream, pixels, (unsigned) groups, counts ); break;
+		case 4: hipLaunchKernelGGL( ptv::displayHistogram<4>, grid, block, 0, ctx->stream, pixels, (unsigned) groups, counts ); break;
+		default: hipLaunchKernelGGL( ptv::displayHistogram<2>, grid, block, 0, ctx->stream, pixels, (unsigned) groups, counts ); break;
+	}
+}
+
+// The counters, their pinned twin and the table: all of them or none, and the table uploaded — or none of them.
+int displayBuffers( pbr_ctx* ctx ) {
+	Images& I = ctx->images;
+
+	if( !I.dDisplayCounts.empty() ) {
+		return PBR_OK;
+	}
+
+	HIP_TRY( ctx, allocAll( { want( I.dDisplayCounts, (size_t) ptv::kCountSlots ), want( I.hDisplayCounts, (size_t) ptv::kCountSlots ), want( I.dDisplayTable, (size_t) 256 ) } ) );
+	const hipError_t err = hipMemcpy( I.dDisplayTable, ptv::kSrgbThreshold, sizeof( ptv::kSrgbThreshold ), hipMemcpyHostToDevice );
+
+	if( err != hipSuccess ) {
+		I.dDisplayCounts.reset();
+		I.hDisplayCounts.reset();
+		I.dDisplayTable.reset();
+		return fail( ctx, PBR_EDEVICE, "pbr_display: uploading the sRGB table: %s", hipGetErrorString( err ) );
+	}
+
+	return PBR_OK;
+}
+
+}  // namespace
+
+int pbr_display( pbr_ctx* ctx, const pbr_display_params* params, const float* rgba, uint8_t* rgba8, int top_row_first, pbr_display_info* info ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+	if( ctx->stream == nullptr ) {
+		return fail( ctx, PBR_ESTATE, "context is not usable" );
+	}
+	if( !ctx->configured ) {
+		return fail( ctx, PBR_ESTATE, "pbr_display before pbr_configure" );
+	}
+	if( rgba8 == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_display: null destination" );
+	}
+
+	std::string why;
+	const int admitted = checkDisplayParams( params, &why );
+
+	if( admitted != PBR_OK ) {
+		return fail( ctx, admitted, "%s", why.c_str() );
+	}
+
+	const bool automatic = ( params->exposure_mode == PBR_DISPLAY_EXPOSURE_AUTO );
+	const bool sharded = ( ctx->cfg.tile_world > 1 );
+
+	if( automatic && rgba == nullptr && sharded ) {
+		return fail( ctx, PBR_ESTATE, "pbr_display: auto exposure over a shard's tiles (tile_world %u): its histogram is not the image's — gather the frame (pbr_import_tiles, pbr_read_full) and pass it as rgba", ctx->cfg.tile_world );
+	}
+
+	HIP_TRY( ctx, hipSetDevice( ctx->device ) );
+	PBR_TRY( displayBuffers( ctx ) );
+	Images& I = ctx->images;
+	const size_t pixels = (size_t) ctx->cfg.width * ctx->cfg.height;
+	const float4* source = I.dImgOut;
+	size_t groups = (size_t) ctx->numLocalTiles;
+
+	if( rgba != nullptr ) {
+		HIP_TRY( ctx, I.dDisplaySource.grow( pixels ) );
+		HIP_TRY( ctx, hipMemcpyAsync( I.dDisplaySource, rgba, sizeof( float4 ) * pixels, hipMemcpyHostToDevice, ctx->stream ) );
+		source = I.dDisplaySource;
+		groups = pixels / 64;   // width and height are multiples of 8
+	}
+
+	const bool counts = automatic || info != nullptr;
+	const uint32_t* n = I.hDisplayCounts;
+
+	if( counts ) {
+		HIP_TRY( ctx, hipMemsetAsync( I.dDisplayCounts, 0, sizeof( unsigned ) * ptv::kCountSlots, ctx->stream ) );
+		HIP_TRY( ctx, hipEventRecord( ctx->evHistogramStart, ctx->stream ) );
+		launchDisplayHistogram( ctx, source, groups );
+		HIP_TRY( ctx, hipGetLastError() );
+		HIP_TRY( ctx, hipEventRecord( ctx->evHistogramStop, ctx->stream ) );
+		HIP_TRY( ctx, hipMemcpyAsync( I.hDisplayCounts, I.dDisplayCounts, sizeof( unsigned ) * ptv::kCountSlots, hipMemcpyDeviceToHost, ctx->stream ) );
+	}
+
+	// auto: the host reads the counts between the two kernels
+	float exposure = params->exposure;
+	double target = 0.0, used = 0.0;
+	uint64_t counted = 0;
+
+	if( automatic ) {
+		HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+		target = displayTarget( n, *params, ctx->displayAdapted, ctx->displayLog2, &counted );
+		used = displayAdapt( target, *params, ctx->displayAdapted, ctx->displayLog2 );
+		exposure = displayExposure( *params, used );
+	}
+
+	ptv::MapArgs A;
+	A.exposure = exposure;
+	A.white = params->white;
+	A.curve = params->curve;
+	A.transfer = params->transfer;
+	A.width = (int) ctx->cfg.width;
+	A.height = (int) ctx->cfg.height;
+	A.rowMajor = ( rgba != nullptr ) ? 1 : 0;
+	A.tilesX = ctx->tilesX;
+	A.tileWorld = (int) ctx->cfg.tile_world;
+	A.tileRank = (int) ctx->cfg.tile_rank;
+	A.topRowFirst = top_row_first ? 1 : 0;
+	HIP_TRY( ctx, hipEventRecord( ctx->evStart, ctx->stream ) );
+	// dRows (16 B per pixel) doubles as the 4-B-per-pixel staging buffer, as in pbr_read_display
+	hipLaunchKernelGGL( ptv::displayMap, imageGrid( A.width, A.height ), kImageBlock, 0, ctx->stream, source, (const float*) I.dDisplayTable, (uchar4*) I.dRows.get(), A );
+	HIP_TRY( ctx, hipGetLastError() );
+	HIP_TRY( ctx, hipEventRecord( ctx->evStop, ctx->stream ) );
+	HIP_TRY( ctx, hipMemcpyAsync( rgba8, I.dRows, 4 * pixels, hipMemcpyDeviceToHost, ctx->stream ) );
+	HIP_TRY( ctx, hipStreamSynchronize( ctx->stream ) );
+	float histogramMs = 0.0f, mapMs = 0.0f;
+
+	if( counts ) {
+		HIP_TRY( ctx, hipEventElapsedTime( &histogramMs, ctx->evHistogramStart, ctx->evHistogramStop ) );
+	}
+
+	HIP_TRY( ctx, hipEventElapsedTime( &mapMs, ctx->evStart, ctx->evStop ) );
+	ctx->lastHistogramMs = (double) histogramMs;
+	ctx->lastMapMs = (double) mapMs;
+	ctx->lastKernelMs = (double) histogramMs + (double) mapMs;
+
+	if( info != nullptr ) {
+		counted = 0;
+
+		for( int b = 0; b < ptv::kBins; b++ ) {
+			info->histogram[b] = n[b];
+			counted += n[b];
+		}
+
+		info->exposure = exposure;
+		info->log2_target = target;
+		info->log2_used = used;
+		info->counted = counted;
+		// the tiles of other ranks read 0, as the map sees them
+		info->dark = (uint64_t) n[ptv::kDarkSlot] + ( ( rgba == nullptr ) ? 64u * (uint64_t) ( ctx->numTiles - ctx->numLocalTiles ) : 0u );
+	}
+
+	if( automatic ) {
+		ctx->displayAdapted = true;
+		ctx->displayLog2 = used;
+	}
+
+	return PBR_OK;
+}
+
+int pbr_display_reset( pbr_ctx* ctx ) {
+	if( ctx == nullptr ) {
+		return PBR_EINVAL;
+	}
+
+	ctx->displayAdapted = false;
+	return PBR_OK;
+}
+
+int pbr_diag_display_info( pbr_ctx* ctx, double* histogram_ms, double* map_ms ) {
+	if( ctx == nullptr || histogram_ms == nullptr || map_ms == nullptr ) {
+		return fail( ctx, PBR_EINVAL, "pbr_diag_display_info: null argument" );
+	}
+
+	*histogram_ms = ctx->lastHistogramMs;
+	*map_ms = ctx->lastMapMs;
 	return PBR_OK;
 }
 
@@ -4318,6 +4515,7 @@ int pbr_diag_set_knob( pbr_ctx* ctx, const char* name, int value ) {
 		{ "park_eighths", &k.parkEighths }, { "drain_mode", &k.drainMode }, { "refill_batch", &k.refillBatch },
 		{ "chunk_frames", &k.chunkFrames }, { "face_normals", &k.faceNormals }, { "bvh_builder", &k.bvhBuilder },
 		{ "ploc_radius", &k.plocRadius }, { "tune_log", &k.tuneLog }, { "deal_order", &k.dealOrder }, { "chain_layout", &k.chainLayout },
+		{ "display_merge", &k.displayMerge },
 	};
 
 	for( const auto& entry : table ) {
